@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the render() hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--fp parity|fast]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--fp parity|fast] [--full] [--dump-outputs DIR]
 
 A "step" is one full frame of the workload rendered through the C-ABI (init* once, then runRenderer
-per step; scene and camera already resident in HBM).
+per step; scene and camera already resident in HBM).  A plain run sets up, warms up, times the K steps and
+prints the headline line (value, ms_per_step, frame_ms_kernel).  --full adds everything else below: the
+untimed counted run with the roofline, the other configs, the N > 1 gather check and the CPU baseline.
+--dump-outputs DIR writes the framebuffer of the last timed step (dump_outputs below).
 
   N = 1   headline = BASELINE.json configs[1] (C2): random-spheres (488 spheres), 1200x800, 100 spp,
-          maxDepth 50.  The other single-GPU configs of BASELINE.json ride in the same JSON line under
+          maxDepth 50.  With --full the other single-GPU configs of BASELINE.json ride in the same JSON line under
           "other_configs": C3 (1200x800x1000), C4 (staircase mesh 1920x1080x256 through initRenderer,
           NEE + RR, with its own BVH-form roofline) and C5's workload (3840x2160x4096) on this one GPU.
   N > 1   STRONG scaling of a FIXED image: BASELINE.json configs[4] (C5), random-spheres 3840x2160 at
@@ -16,14 +19,14 @@ per step; scene and camera already resident in HBM).
           path — and the stripes are gathered on the host: the ranks share one framebuffer in /dev/shm,
           page-locked by every rank, and each rank's finished pixels (stored by the kernel itself, over
           the bus) land in it directly.  The barrier and the max / sum of the timing go through /dev/shm
-          too (multigpu.ShmComm): no RCCL anywhere.  The line carries "gather_ok": the shared framebuffer
+          too (multigpu.ShmComm): no RCCL anywhere.  With --full the line carries "gather_ok": the shared framebuffer
           equals rank 0's single-GPU render of the same frame bit for bit.  The same partitioned job on C2 (1200x800x100: 2 ms
           of kernel per GPU at N = 8, i.e. launch + D2H) is recorded under "other_configs" for the
           north star's "1200x800x100 at 1/2/4/8 GPUs", and rank 0 renders the whole C5 frame alone
           once ("single_gpu_same_workload") so the line carries its own strong-scaling denominator.
           Launched by the driver as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it carries `roofline` and `cpu_baseline` too.
 
 run_job() below is THE partitioned job: stripe partition, shared host framebuffer, barrier-bracketed
 timing, max/sum over ranks.  tests/test_multigpu_gloo.py drives this same function on CPU (world sizes
@@ -158,11 +161,13 @@ class HipBackend:
 # THE job: partition -> (shared framebuffer) -> warm-up -> K timed steps between barriers -> max over ranks
 # ------------------------------------------------------------------------------------------------------
 
-def run_job(backend, comm, w, steps, warmup, tag="job", count_spp=None, warmup_spp=None, keep_image=False):
+def run_job(backend, comm, w, steps, warmup, tag="job", count_spp=None, warmup_spp=None, keep_image=False, count=True):
     """Renders workload `w` `steps` times on comm.world ranks (interleaved 8-row stripes, host gather into one shared
     framebuffer, no collective on the data path) and returns, on every rank, the whole-job figures:
     elapsed = MAX over ranks of the barrier-bracketed wall time of the K steps, kernel_ms = MAX over ranks of the mean
-    HIP-event kernel time, counters = SUM over ranks, scaled from `count_spp` to the workload's spp."""
+    HIP-event kernel time, counters = SUM over ranks, scaled from `count_spp` to the workload's spp.
+    count=False skips the untimed counting run: counters, counted_spp and exec_tests_per_ray are then None.
+    keep_image=True returns the frame of the last timed step (the whole gathered image at N > 1) as `image`."""
     from cuda_raytracing_optimized_amd import multigpu
     rank, world = comm.rank, comm.world
     shared = None
@@ -170,7 +175,7 @@ def run_job(backend, comm, w, steps, warmup, tag="job", count_spp=None, warmup_s
         shared = multigpu.SharedFramebuffer(tag, w["nx"], w["ny"], rank, comm.barrier)
     try:
         backend.open(w, rank, world, shared.array if shared else None)
-        cnt = backend.counted(count_spp or w["spp"])
+        cnt = backend.counted(count_spp or w["spp"]) if count else None
         for _ in range(warmup):
             backend.step(warmup_spp)
         comm.barrier(); backend.device_sync()
@@ -188,15 +193,18 @@ def run_job(backend, comm, w, steps, warmup, tag="job", count_spp=None, warmup_s
     finally:
         if shared:
             shared.close(comm.barrier)
-    scale = w["spp"] / float(cnt["spp"])
-    keys = ("rays", "exec_tests", "node_visits", "prim_tests", "box_tests", "shadow_rays")
     mx = comm.reduce([elapsed, float(np.mean(kernel_ms))], "max")
-    sm = comm.reduce([cnt[k] * scale for k in keys] + [cnt["rays"], cnt["exec_tests"]], "sum")
     samples = w["nx"] * w["ny"] * w["spp"]
     out = dict(elapsed=mx[0], kernel_ms=mx[1], samples=samples, steps=steps, nx=w["nx"], ny=w["ny"], spp=w["spp"],
                value=samples * steps / mx[0] / 1e6, ms_per_step=mx[0] / steps * 1e3,
-               counters={k: sm[i] for i, k in enumerate(keys)}, counted_spp=cnt["spp"],
-               exec_tests_per_ray=(sm[-1] / sm[-2]) if sm[-2] else None, image=image)
+               counters=None, counted_spp=None, exec_tests_per_ray=None, image=image)
+    if cnt is None:
+        return out
+    scale = w["spp"] / float(cnt["spp"])
+    keys = ("rays", "exec_tests", "node_visits", "prim_tests", "box_tests", "shadow_rays")
+    sm = comm.reduce([cnt[k] * scale for k in keys] + [cnt["rays"], cnt["exec_tests"]], "sum")
+    out.update(counters={k: sm[i] for i, k in enumerate(keys)}, counted_spp=cnt["spp"],
+               exec_tests_per_ray=(sm[-1] / sm[-2]) if sm[-2] else None)
     return out
 
 
@@ -337,6 +345,25 @@ def brief(job, extra=None):
     return d
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6       # all files of --dump-outputs together
+
+
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the framebuffer the last timed step delivered ((ny, nx, 3) float32, what runRenderer's caller reads) as
+    framebuffer.npy.  A frame above DUMP_LIMIT_BYTES (3840x2160 is 99.5 MB) is cut to the rows of a fixed seeded sample instead:
+    framebuffer_rows.npy (their indices, float64) and framebuffer_sample.npy (those rows, float32)."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes + 1024 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "framebuffer.npy"), img)
+        return
+    row_bytes = img[0].nbytes
+    k = (DUMP_LIMIT_BYTES - 2048) // (row_bytes + 8)
+    rows = np.sort(np.random.default_rng(0).choice(img.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, "framebuffer_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "framebuffer_sample.npy"), img[rows])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -347,8 +374,12 @@ def main():
     ap.add_argument("--rng", choices=["reference", "counter"], default="reference",
                     help="reference = the reference's per-pixel xorshift stream (the contract workload); counter = per-sample "
                          "stream, samples split over lanes (a different, equally valid estimate of the same image)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the counted run and roofline, the other configs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the framebuffer of the last timed step to DIR as float32 .npy (a seeded row sample above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: headline only (profiling runs)")
     ap.add_argument("--spp", type=int, default=0, help="experiments only: overrides the headline workload's spp")
     ap.add_argument("--max-depth", type=int, default=0, help="experiments only: overrides the headline workload's maxDepth")
     args = ap.parse_args()
@@ -397,14 +428,17 @@ def main():
 
     others = {}
     gather = None
+    roof = None
+    full, dump = args.full, bool(args.dump_outputs)
     if world == 1:
         w = with_overrides(WORKLOADS["C2"])
-        job = run_job(hip, comm, w, args.steps, args.warmup, tag)
+        job = run_job(hip, comm, w, args.steps, args.warmup, tag, keep_image=dump, count=full)
         metric = "Msamples/s (pixels x spp / s), random-spheres 1200x800x100spp"
         scaling = "weak"                     # one GPU: nothing is partitioned (the N > 1 lines say "strong")
         partition = "single GPU"
-        roof = sphere_roofline(job, 1, committed_traffic("C2", w["nx"] * w["ny"] * 12) if default_mode else None)
-        if not args.no_other_configs:
+        if full:
+            roof = sphere_roofline(job, 1, committed_traffic("C2", w["nx"] * w["ny"] * 12) if default_mode else None)
+        if full and not args.no_other_configs:
             # C3: the same frame at 1000 spp
             j3 = run_job(hip, comm, WORKLOADS["C3"], 2, 1, tag, count_spp=8, warmup_spp=16)
             others["C3"] = brief(j3, {"workload": WORKLOADS["C3"]["name"] + ", " + mode,
@@ -422,12 +456,14 @@ def main():
                                                            if k in ("bound", "achieved", "peak", "unit", "frac", "effective_frac", "executed_per_ray", "traffic", "traffic_over_algorithmic", "traffic_source")}})
     else:
         w = with_overrides(WORKLOADS["C5"])
-        job = run_job(hip, comm, w, args.steps, args.warmup, tag, count_spp=4, warmup_spp=16, keep_image=True)
+        job = run_job(hip, comm, w, args.steps, args.warmup, tag, count_spp=4, warmup_spp=16,
+                      keep_image=dump or (full and not args.no_other_configs), count=full)
         metric = f"Msamples/s (pixels x spp / s), random-spheres 3840x2160x{w['spp']}spp split over {world} GPUs (BASELINE.json configs[4])"
         scaling = "strong"
         partition = f"{world} x interleaved 8-row stripes of the fixed 3840x2160 image, host gather into one shared pinned framebuffer, no collective"
-        roof = sphere_roofline(job, world)
-        if not args.no_other_configs:
+        if full:
+            roof = sphere_roofline(job, world)
+        if full and not args.no_other_configs:
             # the north star's "1200x800x100 at 1/2/4/8 GPUs": same partitioned job on C2
             j2 = run_job(hip, comm, WORKLOADS["C2"], max(args.steps, 5), 1, tag + "_c2")
             others["C2_partitioned"] = brief(j2, {"workload": WORKLOADS["C2"]["name"] + ", " + mode + f"; the fixed 1200x800 image over {world} GPUs",
@@ -454,16 +490,20 @@ def main():
             "config": {"workload": w["name"] + ", " + mode, "image": [w["nx"], w["ny"]], "spp": w["spp"], "max_depth": w["depth"],
                        "spheres": N_SPHERES, "partition": partition, "fp_mode": args.fp, "rng": args.rng, "kernel_variant": args.variant},
             "frame_ms_kernel": job["kernel_ms"],
-            "rays_per_sample": job["counters"]["rays"] / job["samples"],
-            "executed_sphere_tests_per_ray": job["exec_tests_per_ray"],
-            "roofline": roof,
         }
+        if full:
+            out.update({"rays_per_sample": job["counters"]["rays"] / job["samples"],
+                        "executed_sphere_tests_per_ray": job["exec_tests_per_ray"],
+                        "roofline": roof})
         if world > 1:
-            out.update(gather if gather else {"gather_ok": None, "gather_check": "not run (--no-other-configs: no single-GPU render to compare with)"})
+            out.update(gather if gather else {"gather_ok": None, "gather_check": "not run (needs --full without --no-other-configs: "
+                                                                                 "no single-GPU render to compare with)"})
         if others:
             out["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w)
+        if dump:
+            dump_outputs(args.dump_outputs, job["image"])
         print(json.dumps(out), flush=True)
 
     if world > 1:

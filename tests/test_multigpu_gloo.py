@@ -209,3 +209,24 @@ def test_bench_workloads_are_the_baseline_configs():
     assert "1000spp" in cfg[2] and bench.WORKLOADS["C3"]["spp"] == 1000
     assert "1920" in cfg[3] and (bench.WORKLOADS["C4"]["nx"], bench.WORKLOADS["C4"]["ny"], bench.WORKLOADS["C4"]["spp"]) == (1920, 1080, 256)
     assert "3840" in cfg[4] and (bench.WORKLOADS["C5"]["nx"], bench.WORKLOADS["C5"]["ny"], bench.WORKLOADS["C5"]["spp"]) == (3840, 2160, 4096)
+
+
+def test_bench_dump_outputs_whole_frame_or_seeded_row_sample(tmp_path):
+    """bench.py --dump-outputs: the C2 frame is written whole; the 3840x2160 frame of the N > 1 job (99.5 MB) is cut to the same
+    seeded sample of rows on every run, float32 rows plus float64 row indices, all files together within 64 MB."""
+    import bench
+    img = np.random.default_rng(3).random((2160, 3840, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "c2"), img[:800, :1200])
+    assert os.listdir(tmp_path / "c2") == ["framebuffer.npy"]
+    assert np.load(tmp_path / "c2" / "framebuffer.npy").tobytes() == img[:800, :1200].tobytes()
+    rows = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), img)
+        assert sorted(os.listdir(d)) == ["framebuffer_rows.npy", "framebuffer_sample.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= bench.DUMP_LIMIT_BYTES == 64 * 10**6
+        r, s = np.load(d / "framebuffer_rows.npy"), np.load(d / "framebuffer_sample.npy")
+        assert r.dtype == np.float64 and s.dtype == np.float32 and len(r) > 1000 and np.all(np.diff(r) > 0)
+        assert s.tobytes() == img[r.astype(np.int64)].tobytes()
+        rows.append(r)
+    assert np.array_equal(rows[0], rows[1])

@@ -1,14 +1,45 @@
-"""CPU: our restatement (oracle/liboracle.so) against the reference's own header-only code compiled from
-/root/reference (oracle/_ref/libref.so), function by function and on whole frames, on FRESH random inputs
-(the committed golden vectors are the same comparison frozen).  Skipped where the shim was never built."""
+"""CPU: our restatement (oracle/liboracle.so) against the reference's own header-only code, function by function and on whole
+frames.  The reference side comes from the reference compiled where its sources exist (oracle/_ref/libref.so, libref_main.so);
+elsewhere from tests/golden/vs_ref.npz: the same reference calls on the same seeded inputs, frozen.  Where the shims exist the live
+outputs must also equal the frozen ones, so the file cannot go stale.  To re-mint it where the shims exist:
+RT_MINT_VS_REF=tests/golden/vs_ref.npz python -m pytest tests/test_oracle_vs_ref.py"""
 import ctypes as C
+import hashlib
+import os
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
 
-pytestmark = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref/libref.so absent (built only where /root/reference exists)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vs_ref.npz")
+MINT = os.environ.get("RT_MINT_VS_REF")
+_minted = {}
+_golden = None
+
+
+def _reference(key, live, have=O.have_ref):
+    """The reference's outputs for `key` as a dict of arrays: live() where the shim was built (checked against the frozen copy,
+    or recorded into RT_MINT_VS_REF), else the frozen copy."""
+    global _golden
+    if _golden is None and os.path.exists(GOLDEN):
+        with np.load(GOLDEN) as z:
+            _golden = {k: z[k] for k in z.files}
+    frozen = {k[len(key) + 1:]: v for k, v in (_golden or {}).items() if k.startswith(key + "/")}
+    if not have():
+        assert frozen, f"{key}: no reference shim and no frozen outputs in {GOLDEN}"
+        return frozen
+    out = {k: np.asarray(v) for k, v in live().items()}
+    if MINT:
+        _minted.update({f"{key}/{k}": v for k, v in out.items()})
+        np.savez_compressed(MINT, **_minted)
+    else:
+        assert set(out) == set(frozen) and all(out[k].tobytes() == frozen[k].tobytes() for k in out), f"{key}: {GOLDEN} is stale"
+    return out
+
+
+def _sha(b):
+    return np.frombuffer(hashlib.sha256(bytes(b)).digest(), np.uint8)
 
 
 def _bits(a):
@@ -20,12 +51,14 @@ def f3(v):
 
 
 def test_struct_layouts_match_reference(rt):
-    ref = O.load_ref()
-    sizes = (C.c_int * 32)()
-    n = ref.ref_struct_sizes(sizes, 32)
+    def live():
+        sizes = (C.c_int * 32)()
+        n = O.load_ref().ref_struct_sizes(sizes, 32)
+        return {"sizes": np.array(sizes[:n], np.int32)}
+    sizes = _reference("struct_sizes", live)["sizes"]
     names = ["vec3", "ray", "camera", "sphere", "plane", "bbox", "triangle", "bvh_node", "material", "stexture", "mesh", "scene",
              "kernel_scene", "intersection", "scatter_info", "path", "tri_hit"]
-    got = dict(zip(names, sizes[:n]))
+    got = dict(zip(names, sizes.tolist()))
     # SURVEY.md §8b table
     assert got == {"vec3": 12, "ray": 24, "camera": 88, "sphere": 16, "plane": 24, "bbox": 24, "triangle": 64, "bvh_node": 24,
                    "material": 24, "stexture": 16, "mesh": 56, "scene": 96, "kernel_scene": 64, "intersection": 56,
@@ -34,46 +67,67 @@ def test_struct_layouts_match_reference(rt):
         assert C.sizeof(getattr(rt, nm)) == got[nm], nm
 
 
-def test_functions_random(rt):
-    ref = O.load_ref(); orc = O.load_oracle()
+def _function_cases(rt):
+    """The seeded inputs of test_functions_random: rng seed, a ray, a sphere, a box (some ray directions with a zero
+    component), a triangle with a ray towards a point inside it, a floor plane."""
     rng = np.random.default_rng(99)
-    N = 1500
-    o1 = (C.c_float * 3)(); o2 = (C.c_float * 3)()
-    for k in range(N):
-        s = int(rng.integers(1, 2 ** 32)) | 1
-        a = C.c_uint32(s); b = C.c_uint32(s)
-        orc.orc_random_in_unit_sphere(C.byref(a), o1); ref.ref_random_in_unit_sphere(C.byref(b), o2)
-        assert o1[:] == o2[:] and a.value == b.value
-        org = rng.uniform(-3, 3, 3); d = rng.normal(size=3)
+    cases = []
+    for k in range(1500):
+        c = {"seed": int(rng.integers(1, 2 ** 32)) | 1}
+        c["org"] = rng.uniform(-3, 3, 3); c["d"] = rng.normal(size=3)
         sp = rt.sphere(); sp.center.e[:] = rng.uniform(-2, 2, 3); sp.radius = rng.uniform(0.1, 2.5)
-        t1 = orc.orc_sphere_hit(C.byref(sp), f3(org), f3(d), 0.001, 3.0e38); t2 = ref.ref_sphere_hit(C.byref(sp), f3(org), f3(d), 0.001, 3.0e38)
-        assert np.float32(t1).view(np.uint32) == np.float32(t2).view(np.uint32)
-        lo = rng.uniform(-2, 1, 3); hi = lo + rng.uniform(0, 2, 3)
+        c["sphere"] = sp
+        c["lo"] = rng.uniform(-2, 1, 3); c["hi"] = c["lo"] + rng.uniform(0, 2, 3)
+        c["d_box"] = c["d"].copy()
         if k % 7 == 0:
-            d[k % 3] = 0.0
-        assert np.float32(orc.orc_hit_bbox_dist(f3(lo), f3(hi), f3(org), f3(d), 10.0)).view(np.uint32) == \
-            np.float32(ref.ref_hit_bbox_dist(f3(lo), f3(hi), f3(org), f3(d), 10.0)).view(np.uint32)
-        assert orc.orc_hit_bbox(f3(lo), f3(hi), f3(org), f3(d), 10.0) == ref.ref_hit_bbox(f3(lo), f3(hi), f3(org), f3(d), 10.0)
+            c["d_box"][k % 3] = 0.0
         tri = rt.triangle()
         for q in range(3):
             tri.v[q].e[:] = rng.uniform(-2, 2, 3)
         target = sum(np.array(tri.v[q].e[:]) * w for q, w in enumerate(rng.dirichlet([1, 1, 1])))
-        dd = target - org
-        u1 = C.c_float(); v1 = C.c_float(); u2 = C.c_float(); v2 = C.c_float()
-        t1 = orc.orc_triangle_hit(C.byref(tri), f3(org), f3(dd), 0.01, 3.0e38, C.byref(u1), C.byref(v1))
-        t2 = ref.ref_triangle_hit(C.byref(tri), f3(org), f3(dd), 0.01, 3.0e38, C.byref(u2), C.byref(v2))
-        assert np.float32(t1).view(np.uint32) == np.float32(t2).view(np.uint32)
-        if t1 < 1e30:
-            assert u1.value == u2.value and v1.value == v2.value
+        c["tri"], c["dd"] = tri, target - c["org"]
         pl = rt.plane(); pl.norm.e[:] = (0.0, 1.0, 0.0); pl.point.e[:] = (0.0, float(rng.uniform(-1, 1)), 0.0)
-        assert np.float32(orc.orc_plane_hit(C.byref(pl), f3(org), f3(d), 0.01, 3.0e38)).view(np.uint32) == \
-            np.float32(ref.ref_plane_hit(C.byref(pl), f3(org), f3(d), 0.01, 3.0e38)).view(np.uint32)
+        c["plane"] = pl
+        cases.append(c)
+    return cases
+
+
+def _functions(lib, p, cases):
+    """Every function of test_functions_random on every case through `lib` (prefix `p`: "orc_" or "ref_")."""
+    n = len(cases)
+    r = {k: np.zeros(n, np.float32) for k in ("sphere_t", "box_dist", "tri_t", "tri_u", "tri_v", "plane_t")}
+    r["unit_sphere"] = np.zeros((n, 3), np.float32); r["rng_after"] = np.zeros(n, np.uint32); r["box_hit"] = np.zeros(n, np.int32)
+    o = (C.c_float * 3)()
+    for k, c in enumerate(cases):
+        s = C.c_uint32(c["seed"])
+        getattr(lib, p + "random_in_unit_sphere")(C.byref(s), o)
+        r["unit_sphere"][k], r["rng_after"][k] = o[:], s.value
+        org, d, db = f3(c["org"]), f3(c["d"]), f3(c["d_box"])
+        r["sphere_t"][k] = getattr(lib, p + "sphere_hit")(C.byref(c["sphere"]), org, d, 0.001, 3.0e38)
+        r["box_dist"][k] = getattr(lib, p + "hit_bbox_dist")(f3(c["lo"]), f3(c["hi"]), org, db, 10.0)
+        r["box_hit"][k] = getattr(lib, p + "hit_bbox")(f3(c["lo"]), f3(c["hi"]), org, db, 10.0)
+        u = C.c_float(); v = C.c_float()
+        r["tri_t"][k] = getattr(lib, p + "triangle_hit")(C.byref(c["tri"]), org, f3(c["dd"]), 0.01, 3.0e38, C.byref(u), C.byref(v))
+        r["tri_u"][k], r["tri_v"][k] = u.value, v.value
+        r["plane_t"][k] = getattr(lib, p + "plane_hit")(C.byref(c["plane"]), org, db, 0.01, 3.0e38)
+    return r
+
+
+def test_functions_random(rt):
+    cases = _function_cases(rt)
+    ref = _reference("functions", lambda: _functions(O.load_ref(), "ref_", cases))
+    orc = _functions(O.load_oracle(), "orc_", cases)
+    assert np.array_equal(orc["unit_sphere"], ref["unit_sphere"]) and np.array_equal(orc["rng_after"], ref["rng_after"])
+    for k in ("sphere_t", "box_dist", "tri_t", "plane_t"):
+        assert np.array_equal(_bits(orc[k]), _bits(ref[k])), k
+    assert np.array_equal(orc["box_hit"], ref["box_hit"])
+    hit = orc["tri_t"] < 1e30
+    assert np.array_equal(orc["tri_u"][hit], ref["tri_u"][hit]) and np.array_equal(orc["tri_v"][hit], ref["tri_v"][hit])
 
 
 def test_light_sampling_expressions(rt):
     """kernels.cu:378-387: the two vec3 expressions of generateShadowRay, restated in rt_oracle.c, against the
     same expressions evaluated with the reference's own vec3 operators (tests/golden/light.npz)."""
-    import os
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "light.npz"))
     f = np.float32
     for k in range(len(g["eps2"])):
@@ -98,9 +152,13 @@ def test_frames_random_configs(rt, scene, nx, ny, ns, kw):
     for k, v in kw.items():
         setattr(opt, k, v)
     a, ca = O.render(O.sphere_scene(sp, mt), cam, opt, nx, ny, ns, 50, counters=True)
-    b, cb = O.ref_render_spheres(sp, mt, cam, opt, nx, ny, ns, 50, counters=True)
-    assert np.array_equal(_bits(a), _bits(b))
-    assert (ca.rays, ca.prim_tests, ca.hits) == (cb.rays, cb.prim_tests, cb.hits)
+
+    def live():
+        b, cb = O.ref_render_spheres(sp, mt, cam, opt, nx, ny, ns, 50, counters=True)
+        return {"frame": b, "counters": np.array([cb.rays, cb.prim_tests, cb.hits], np.int64)}
+    ref = _reference(f"frames_{scene}_{nx}x{ny}x{ns}_" + "_".join(f"{k}{v}" for k, v in kw.items()), live)
+    assert np.array_equal(_bits(a), _bits(ref["frame"]))
+    assert [ca.rays, ca.prim_tests, ca.hits] == ref["counters"].tolist()
 
 
 # ---- the MESH path: oracle restatement vs the reference-arithmetic twin (oracle/ref_driver.cpp ref_render_mesh) ------------
@@ -119,9 +177,13 @@ def _triangle_soup(rt, rng, n, n_mats=6):
     return tris, mats
 
 
-def _same_counters(a, b):
-    return (a.samples, a.rays, a.shadow_rays, a.prim_tests, a.node_visits, a.hits) == \
-           (b.samples, b.rays, b.shadow_rays, b.prim_tests, b.node_visits, b.hits) and list(a.ref_stats) == list(b.ref_stats)
+def _counters(c):
+    return np.array([c.samples, c.rays, c.shadow_rays, c.prim_tests, c.node_visits, c.hits] + list(c.ref_stats), np.int64)
+
+
+def _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, depth):
+    b, cb = O.ref_render_mesh(sc, cam, opt, nx, ny, ns, depth, counters=True)
+    return {"frame": b, "counters": _counters(cb)}
 
 
 @pytest.mark.parametrize("kw", [{}, {"nee": 0}, {"nee": 0, "rr": 0}, {"sky": 1}, {"floor": 1}, {"floor": 1, "nee": 0}, {"rng": 1},
@@ -134,6 +196,7 @@ def test_mesh_frames_oracle_equals_reference_twin_staircase(rt, kw):
     nx, ny, ns = 64, 80, 2
     cam = rt.staircase_camera(nx, ny)
     opt = O.default_options(False)
+    key = "mesh_staircase_" + "_".join(f"{k}{v}" for k, v in kw.items())
     kw = dict(kw)
     if "light_radius" in kw:
         opt.light.radius = kw.pop("light_radius")
@@ -143,9 +206,9 @@ def test_mesh_frames_oracle_equals_reference_twin_staircase(rt, kw):
     floor = (0.0, 1.0, 0.0, 0.0, float(lo[1]) - 5.0, 0.0)                 # plane(point, norm): norm first (helper_structs.h:165-171)
     sc = O.mesh_scene(hm, mats, floor=floor)
     a, ca = O.render(sc, cam, opt, nx, ny, ns, 64, counters=True)
-    b, cb = O.ref_render_mesh(sc, cam, opt, nx, ny, ns, 64, counters=True)
-    assert np.array_equal(_bits(a), _bits(b)), np.count_nonzero(_bits(a) != _bits(b))
-    assert _same_counters(ca, cb)
+    ref = _reference(key, lambda: _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, 64))
+    assert np.array_equal(_bits(a), _bits(ref["frame"])), np.count_nonzero(_bits(a) != _bits(ref["frame"]))
+    assert np.array_equal(_counters(ca), ref["counters"])
     assert ca.ref_stats[rt.RT_STAT_PRIMARY] == nx * ny * ns and ca.ref_stats[rt.RT_STAT_PRIMARY] + ca.ref_stats[rt.RT_STAT_SECONDARY] == ca.rays
     if opt.nee:
         assert ca.ref_stats[rt.RT_STAT_SHADOWS] == ca.shadow_rays > 0
@@ -166,13 +229,24 @@ def test_mesh_frames_oracle_equals_reference_twin_soups(rt, n, nppl, nee, floor)
     opt.floor = floor
     sc = O.mesh_scene(hm, mats, tex, floor=(0.0, 1.0, 0.0, 0.0, -3.0, 0.0))   # plane {norm, point} (helper_structs.h:165-171)
     a, ca = O.render(sc, cam, opt, nx, ny, ns, 12, counters=True)
-    b, cb = O.ref_render_mesh(sc, cam, opt, nx, ny, ns, 12, counters=True)
-    assert np.array_equal(_bits(a), _bits(b)), np.count_nonzero(_bits(a) != _bits(b))
-    assert _same_counters(ca, cb)
+    ref = _reference(f"mesh_soup_{n}_{nppl}_{nee}_{floor}", lambda: _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, 12))
+    assert np.array_equal(_bits(a), _bits(ref["frame"])), np.count_nonzero(_bits(a) != _bits(ref["frame"]))
+    assert np.array_equal(_counters(ca), ref["counters"])
     if floor:       # primary rays that hit only the floor count as "primary nohit" (kernels.cu:430); paths leaving the floor into the sky as "secondary no hit"
         assert ca.ref_stats[rt.RT_STAT_SECONDARY_NOHIT] > 0 and ca.ref_stats[rt.RT_STAT_PRIMARY_NOHITS] > 0
     else:
         assert ca.ref_stats[rt.RT_STAT_SECONDARY_NOHIT] == 0
+
+
+def _shadow_rays(opt, cases, which):
+    n = len(cases)
+    r = {"generated": np.zeros(n, np.int32), "draws": np.zeros(n, np.int32), "rng_after": np.zeros(n, np.uint32),
+         "dir": np.zeros((n, 3), np.float32), "contribution": np.zeros((n, 3), np.float32), "dist": np.zeros(n, np.float32),
+         "cos_a_max": np.zeros(n, np.float32)}
+    for k, (org, att, nrm, seed) in enumerate(cases):
+        g = O.generate_shadow_ray(opt, org, att, nrm, seed, which)
+        r["generated"][k], r["dir"][k], r["contribution"][k], r["dist"][k], r["cos_a_max"][k], r["draws"][k], r["rng_after"][k] = g
+    return r
 
 
 def test_generate_shadow_ray_oracle_equals_reference_twin(rt):
@@ -180,7 +254,7 @@ def test_generate_shadow_ray_oracle_equals_reference_twin(rt):
     incl. the NaN early-out before any draw and the dotl <= 0 rejection after two draws."""
     rng = np.random.default_rng(5)
     opt = O.default_options(False)
-    n_gen = n_nan = n_rej = 0
+    cases = []
     for k in range(3000):
         if k % 10 == 9:                                   # inside the light's sphere: cosAMax = NaN
             org = np.array(opt.light.center.e[:]) + rng.normal(size=3) * 20.0
@@ -190,20 +264,23 @@ def test_generate_shadow_ray_oracle_equals_reference_twin(rt):
         nrm = rng.normal(size=3); nrm /= np.linalg.norm(nrm)
         if k % 3 == 0:                                    # facing the light more often than not
             nrm = np.array(opt.light.center.e[:]) - org; nrm /= np.linalg.norm(nrm)
-        seed = int(rng.integers(1, 2 ** 32)) | 1
-        ra = O.generate_shadow_ray(opt, org, att, nrm, seed, "orc")
-        rb = O.generate_shadow_ray(opt, org, att, nrm, seed, "ref")
-        assert ra[0] == rb[0] and ra[5] == rb[5] and ra[6] == rb[6], k
-        assert np.array_equal(_bits(ra[4]), _bits(rb[4]))                                     # cosAMax (NaN included: same bits)
-        if ra[0]:
+        cases.append((org, att, nrm, int(rng.integers(1, 2 ** 32)) | 1))
+    ra = _shadow_rays(opt, cases, "orc")
+    rb = _reference("shadow_rays", lambda: _shadow_rays(opt, cases, "ref"))
+    n_gen = n_nan = n_rej = 0
+    for k in range(len(cases)):
+        assert ra["generated"][k] == rb["generated"][k] and ra["draws"][k] == rb["draws"][k] and ra["rng_after"][k] == rb["rng_after"][k], k
+        assert _bits(ra["cos_a_max"][k]) == _bits(rb["cos_a_max"][k])                                   # cosAMax (NaN included: same bits)
+        if ra["generated"][k]:
             n_gen += 1
-            assert np.array_equal(_bits(ra[1]), _bits(rb[1])) and np.array_equal(_bits(ra[2]), _bits(rb[2])) and _bits(ra[3]) == _bits(rb[3]), k
-        elif ra[5] == 0:
+            assert np.array_equal(_bits(ra["dir"][k]), _bits(rb["dir"][k])) and np.array_equal(_bits(ra["contribution"][k]), _bits(rb["contribution"][k])) \
+                and _bits(ra["dist"][k]) == _bits(rb["dist"][k]), k
+        elif ra["draws"][k] == 0:
             n_nan += 1
-            assert np.isnan(ra[4])
+            assert np.isnan(ra["cos_a_max"][k])
         else:
             n_rej += 1
-            assert ra[5] == 2
+            assert ra["draws"][k] == 2
     assert n_gen > 500 and n_nan > 100 and n_rej > 100
 
 
@@ -211,75 +288,101 @@ def test_generate_shadow_ray_oracle_equals_reference_twin(rt):
 
 def test_bvh_file_written_here_loads_through_the_reference_loader(rt, tmp_path):
     """rtSaveBvhFile -> the reference's loadBVH (staircase_scene.h:75-101): triangles, nodes, bounds and the leaf size come back byte for byte;
-    rtLoadBvhFile of the same file returns what loadBVH returns; both refuse a wrong header and a missing file."""
+    rtLoadBvhFile of the same file returns what loadBVH returns; both refuse a wrong header and a missing file.
+    (Frozen: the sha256 of the file loadBVH read and of the arrays it returned.)"""
     cases = [(rt.scene_staircase_procedural(1)[0], 5, None), (rt.scene_staircase_procedural(1)[0][:333], 3, 2)]
     rng = np.random.default_rng(9)
     soup = np.zeros(57, rt.triangle_dtype)
     soup["v"] = rng.uniform(-3, 3, (57, 3, 3)).astype(np.float32)
     soup["meshID"] = rng.integers(0, 20, 57)
     cases.append((soup, 1, None))
+    meshes, paths = [], []
     for k, (tris, nppl, levels) in enumerate(cases):
         hm = rt.HostMesh.build(tris, nppl, levels)
         path = str(tmp_path / f"m{k}.bvh")
         assert hm.save(path) == 0
-        got = O.ref_load_bvh(path)
-        assert got is not None
-        rtris, rbvh, rbounds, rnppl = got
-        assert rnppl == nppl == hm.nppl
-        assert rtris.tobytes() == hm.tris.tobytes() and rbvh.tobytes() == hm.bvh.tobytes()
-        assert rbounds.tobytes() == bytes(hm.view.bounds)
-        hm2 = rt.HostMesh.load(path)                                   # our reader on the same file: what the reference's reader returned
-        assert hm2.nppl == rnppl and hm2.tris.tobytes() == rtris.tobytes() and hm2.bvh.tobytes() == rbvh.tobytes()
-        assert bytes(hm2.view.bounds) == rbounds.tobytes()
-        if k == 0:
-            raw = open(path, "rb").read()
-            bad = str(tmp_path / "bad.bvh")
-            open(bad, "wb").write(b"BVH_00.03\x00" + raw[10:])
-            assert O.ref_load_bvh(bad) is None
-            with pytest.raises(ValueError):
-                rt.HostMesh.load(bad)
+        meshes.append(hm); paths.append(path)
+    bad = str(tmp_path / "bad.bvh")
+    open(bad, "wb").write(b"BVH_00.03\x00" + open(paths[0], "rb").read()[10:])
+
+    def live():
+        out = {"bad_refused": np.int32(O.ref_load_bvh(bad) is None), "missing_refused": np.int32(O.ref_load_bvh(str(tmp_path / "missing.bvh")) is None)}
+        for k, path in enumerate(paths):
+            got = O.ref_load_bvh(path)
+            assert got is not None
+            rtris, rbvh, rbounds, rnppl = got
+            out.update({f"file_sha{k}": _sha(open(path, "rb").read()), f"tris_sha{k}": _sha(rtris.tobytes()), f"bvh_sha{k}": _sha(rbvh.tobytes()),
+                        f"bounds{k}": np.frombuffer(rbounds.tobytes(), np.uint8), f"nppl{k}": np.int32(rnppl)})
+        return out
+    ref = _reference("bvh_loader", live)
+    for k, hm in enumerate(meshes):
+        assert np.array_equal(_sha(open(paths[k], "rb").read()), ref[f"file_sha{k}"])        # the very file the reference's loader read
+        assert int(ref[f"nppl{k}"]) == cases[k][1] == hm.nppl
+        assert np.array_equal(_sha(hm.tris.tobytes()), ref[f"tris_sha{k}"]) and np.array_equal(_sha(hm.bvh.tobytes()), ref[f"bvh_sha{k}"])
+        assert bytes(hm.view.bounds) == ref[f"bounds{k}"].tobytes()
+        hm2 = rt.HostMesh.load(paths[k])                               # our reader on the same file: what the reference's reader returned
+        assert hm2.nppl == int(ref[f"nppl{k}"]) and np.array_equal(_sha(hm2.tris.tobytes()), ref[f"tris_sha{k}"])
+        assert np.array_equal(_sha(hm2.bvh.tobytes()), ref[f"bvh_sha{k}"]) and bytes(hm2.view.bounds) == ref[f"bounds{k}"].tobytes()
         hm.close(); hm2.close()
-    assert O.ref_load_bvh(str(tmp_path / "missing.bvh")) is None
+    assert int(ref["bad_refused"]) == 1 and int(ref["missing_refused"]) == 1
+    with pytest.raises(ValueError):
+        rt.HostMesh.load(bad)
 
 
 def test_ppm_bytes_equal_the_reference_writer(rt, tmp_path):
     """rtWritePPM's file = the bytes the reference's writePPM (staircase_scene.h:32-43) sends to std::cout: header, row order (top row first), sRGB
     quantisation of every channel, separators - on random frames incl. negative, > 1, NaN-free extremes."""
     rng = np.random.default_rng(11)
+    fbs = []
     for (ny, nx) in ((1, 1), (7, 5), (33, 64)):
         fb = rng.uniform(-0.2, 1.4, (ny, nx, 3)).astype(np.float32)
         fb[0, 0] = (0.0, 1.0, 0.5)
         if ny > 1:
             fb[1, 0] = (1e-9, 1e9, 0.0031308)
+        fbs.append(fb)
+    ref = _reference("ppm", lambda: {f"ppm{k}": np.frombuffer(O.ref_write_ppm(fb), np.uint8) for k, fb in enumerate(fbs)})
+    for k, fb in enumerate(fbs):
         path = str(tmp_path / "o.ppm")
         assert rt.write_ppm(path, fb) == 0
-        assert open(path, "rb").read() == O.ref_write_ppm(fb)
+        assert open(path, "rb").read() == ref[f"ppm{k}"].tobytes()
 
 
 def test_staircase_camera_equals_the_reference_setup_camera(rt):
     """rtStaircaseCamera = setup_camera (staircase_scene.h:62-73), every one of the 22 floats, for several image sizes."""
-    for (nx, ny) in ((640, 800), (1920, 1080), (160, 200), (48, 60), (1, 1), (1234, 567)):
-        assert bytes(rt.staircase_camera(nx, ny)) == bytes(O.ref_setup_camera(nx, ny)), (nx, ny)
+    sizes = ((640, 800), (1920, 1080), (160, 200), (48, 60), (1, 1), (1234, 567))
+    ref = _reference("camera", lambda: {f"{nx}x{ny}": np.frombuffer(bytes(O.ref_setup_camera(nx, ny)), np.uint8) for nx, ny in sizes})
+    for (nx, ny) in sizes:
+        assert bytes(rt.staircase_camera(nx, ny)) == ref[f"{nx}x{ny}"].tobytes(), (nx, ny)
 
 
-@pytest.mark.skipif(not O.have_ref_main(), reason="oracle/_ref/libref_main.so absent (built only where /root/reference exists)")
 def test_ref_files_against_the_reference_main_cpp(rt, tmp_path):
     """REF_00.01 images (main.cpp:25-60): a file rtSaveReference writes loads through the reference's loadReference into the same floats, the file the
     reference's saveReference writes is byte-identical to ours and loads through rtLoadReference; a size mismatch and a missing file are refused by both."""
-    rm = O.load_ref_main()
     rng = np.random.default_rng(13)
     nx, ny = 9, 6
     fb = rng.uniform(0, 1.3, (ny, nx, 3)).astype(np.float32)
     ours, theirs = str(tmp_path / "ours.ref"), str(tmp_path / "theirs.ref")
     assert rt.save_reference(ours, fb) == 0
-    rm.ref_save_reference(theirs.encode(), nx, ny, fb.ctypes.data)
-    assert open(ours, "rb").read() == open(theirs, "rb").read()
-    back = np.zeros_like(fb)
-    assert rm.ref_load_reference(ours.encode(), back.ctypes.data, nx, ny) == 0 and back.tobytes() == fb.tobytes()
-    rc, back2 = rt.load_reference(theirs, nx, ny)
-    assert rc == 0 and back2.tobytes() == fb.tobytes()
-    assert rm.ref_load_reference(ours.encode(), back.ctypes.data, ny, nx) != 0 and rt.load_reference(ours, ny, nx)[0] != 0
-    assert rm.ref_load_reference(str(tmp_path / "none.ref").encode(), back.ctypes.data, nx, ny) != 0
     bad = str(tmp_path / "bad.ref")
     open(bad, "wb").write(b"REF_00.02\x00" + open(ours, "rb").read()[10:])
-    assert rm.ref_load_reference(bad.encode(), back.ctypes.data, nx, ny) != 0 and rt.load_reference(bad, nx, ny)[0] != 0
+
+    def live():
+        rm = O.load_ref_main()
+        rm.ref_save_reference(theirs.encode(), nx, ny, fb.ctypes.data)
+        back = np.zeros_like(fb)
+        rc = rm.ref_load_reference(ours.encode(), back.ctypes.data, nx, ny)
+        return {"theirs": np.frombuffer(open(theirs, "rb").read(), np.uint8), "ours_sha": _sha(open(ours, "rb").read()),
+                "load_rc": np.int32(rc), "loaded": back.copy(),
+                "transposed_rc": np.int32(rm.ref_load_reference(ours.encode(), back.ctypes.data, ny, nx)),
+                "missing_rc": np.int32(rm.ref_load_reference(str(tmp_path / "none.ref").encode(), back.ctypes.data, nx, ny)),
+                "bad_rc": np.int32(rm.ref_load_reference(bad.encode(), back.ctypes.data, nx, ny))}
+    ref = _reference("ref_files", live, O.have_ref_main)
+    assert np.array_equal(_sha(open(ours, "rb").read()), ref["ours_sha"])          # the very file the reference's loader read
+    assert open(ours, "rb").read() == ref["theirs"].tobytes()
+    assert int(ref["load_rc"]) == 0 and ref["loaded"].tobytes() == fb.tobytes()
+    open(theirs, "wb").write(ref["theirs"].tobytes())
+    rc, back2 = rt.load_reference(theirs, nx, ny)
+    assert rc == 0 and back2.tobytes() == fb.tobytes()
+    assert int(ref["transposed_rc"]) != 0 and rt.load_reference(ours, ny, nx)[0] != 0
+    assert int(ref["missing_rc"]) != 0
+    assert int(ref["bad_rc"]) != 0 and rt.load_reference(bad, nx, ny)[0] != 0

@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $REPO
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline $*"
 PROG=bench.py
 if [ -n "${PROF_PROG:-}" ]; then PROG=$PROF_PROG; ARGS="$*"; fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $PROG $ARGS > $OUT/trace.log 2>&1
