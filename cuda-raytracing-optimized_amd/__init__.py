@@ -129,7 +129,7 @@ assert triangle_dtype.itemsize == 64 and bvh_node_dtype.itemsize == 24
 # symbols every library must export (tests check the .so against the headers with these)
 RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRendererSpheres",
                     "getDefaultRenderOptions", "setRenderOptions", "setExternalFramebuffer", "getRenderStats",
-                    "rtDeviceCount", "rtApiVersion", "rtStructSizes"]
+                    "rtDeviceCount", "rtApiVersion", "rtStructSizes", "rtLastLaunches"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
@@ -241,6 +241,8 @@ def load_renderer():
         r.rtDeviceCount.restype = C.c_int
         r.rtApiVersion.argtypes = []
         r.rtApiVersion.restype = C.c_int
+        r.rtLastLaunches.argtypes = [C.POINTER(C.c_int32), C.c_int]
+        r.rtLastLaunches.restype = C.c_int
         _renderer = r
     return _renderer
 
@@ -454,6 +456,20 @@ def getRenderStats():
 
 def device_count():
     return load_renderer().rtDeviceCount()
+
+
+# rtLastLaunches (include/rt_api.h): kernel families and the words of a launch record
+RT_KERNEL_SPHERE_QUEUE, RT_KERNEL_SPHERE_TILES, RT_KERNEL_MESH_QUEUE, RT_KERNEL_MESH_TILES = 1, 2, 3, 4
+LAUNCH_FIELDS = ("family", "phase", "cls", "chunked", "dbg", "scene", "lean", "threads", "blocks", "device", "fp")
+
+
+def last_launches():
+    """The render-kernel launches of the last runRenderer, in launch order: one dict per launch with the LAUNCH_FIELDS of its record."""
+    lib = load_renderer()
+    n = lib.rtLastLaunches(None, 0)
+    buf = (C.c_int32 * (n * len(LAUNCH_FIELDS)))()
+    n = min(n, lib.rtLastLaunches(buf, n))
+    return [dict(zip(LAUNCH_FIELDS, buf[k * len(LAUNCH_FIELDS):(k + 1) * len(LAUNCH_FIELDS)])) for k in range(n)]
 
 
 # ---------------------------------------------------------------------------------------------

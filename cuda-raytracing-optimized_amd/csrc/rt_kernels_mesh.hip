@@ -412,6 +412,7 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
         // the frame is less than ~16 fills of the machine (C4: 7.9; 3840x2160: 31.6 - chain waves measured -3 % there, +12 % on C4; profiles/r04_mesh_chain_scenes.txt)
         if (((leaf_thr >> 24) & 0xF) != 0 && (uint32_t)P.part.local_rows * (uint32_t)P.nx > 16u * gridDim.x * blockDim.x) E = 0u;      // list 0 is not "a few pixels" in this scene (its threshold is absolute): no chain waves
         const uint32_t max_waves = grid_x * (blockDim.x >> 6) >> 3;
+        if (max_waves == 0u) E = 0u;          // fewer than 8 waves serve this queue (a frame of < 16 workgroups): no chain waves, as the cap below gave before
         if (E > max_waves * chain_lanes) chain_lanes = min(64u, (E + max_waves - 1u) / max_waves);      // (a long list: more of its pixels per wave, not fewer of them in chain waves)
         if (E > max_waves * chain_lanes) E = max_waves * chain_lanes;
         const uint32_t N = pixels - E;
@@ -1050,6 +1051,13 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
 
 }  // namespace
 
+// Every launch of the persistent kernel: launch and note its template arguments for the launch report (rtLastLaunches)
+template <int TRAV, bool DBG, bool STATS, bool LEAN = false, int PHASE = 0>
+static void launch_mesh_queue(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const RtMeshParams& p, uint32_t stride, int min_traversing, int leaf_thr) {
+    hipLaunchKernelGGL((k_render_mesh_queue<TRAV, DBG, STATS, LEAN, PHASE>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+    rt_note_launch(RT_KERNEL_MESH_QUEUE, PHASE, TRAV, 0, (DBG ? 1 : 0) | (STATS ? 2 : 0), 0, LEAN ? 1 : 0, (int)block.x, grid.x);
+}
+
 // variant: bits 0..7  0 = persistent state-machine kernel (default), 1 = first kernel (one tile per wave);
 //          bits 8..15 workgroups per CU of the persistent kernel (0 = default 4);
 //          bits 16..23 keep traversing while at least this many lanes have nodes left (0 = default: 24, classic 40);
@@ -1059,6 +1067,7 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
     if ((variant & 0xFF) == 1) {
         const dim3 grid((p.nx + 8 * kWavesPerWg - 1) / (8 * kWavesPerWg), (p.part.local_rows + 7) / 8);
         hipLaunchKernelGGL(k_render_mesh<0>, grid, dim3(kThreads), 0, stream, p);
+        rt_note_launch(RT_KERNEL_MESH_TILES, 0, 0, 0, 0, 0, 0, kThreads, grid.x * grid.y);
         return hipGetLastError();
     }
     if (!p.queue) return hipErrorInvalidValue;
@@ -1115,8 +1124,8 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
             stride1 = (uint32_t)(cand % segs);
             mt1 |= 256;
         }
-        if (lean) hipLaunchKernelGGL((k_render_mesh_queue<0, false, false, true, 1>), grid, block, lds, stream, q, stride1, mt1, leaf_thr);
-        else hipLaunchKernelGGL((k_render_mesh_queue<0, false, false, false, 1>), grid, block, lds, stream, q, stride1, mt1, leaf_thr);
+        if (lean) launch_mesh_queue<0, false, false, true, 1>(grid, block, lds, stream, q, stride1, mt1, leaf_thr);
+        else launch_mesh_queue<0, false, false, false, 1>(grid, block, lds, stream, q, stride1, mt1, leaf_thr);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
         e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords, stream);
@@ -1141,8 +1150,8 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
         if (!d_items) { (void)hipMalloc(&d_items, n_px * 8); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_diag_items), &d_items, sizeof d_items); }
         { const unsigned long long init[4] = { ~0ull, ~0ull, 0ull, 0ull }; (void)hipMemcpyAsync(p.queue + 48, init, sizeof init, hipMemcpyHostToDevice, stream); (void)hipStreamSynchronize(stream); }
 #endif
-        if (lean) hipLaunchKernelGGL((k_render_mesh_queue<0, false, false, true, 2>), grid, block, lds, stream, q, stride2, min_traversing, lt2);
-        else hipLaunchKernelGGL((k_render_mesh_queue<0, false, false, false, 2>), grid, block, lds, stream, q, stride2, min_traversing, lt2);
+        if (lean) launch_mesh_queue<0, false, false, true, 2>(grid, block, lds, stream, q, stride2, min_traversing, lt2);
+        else launch_mesh_queue<0, false, false, false, 2>(grid, block, lds, stream, q, stride2, min_traversing, lt2);
 #if RT_MESH_TAIL_DIAG
         { unsigned long long r[4]; (void)hipStreamSynchronize(stream); (void)hipMemcpy(r, p.queue + 48, sizeof r, hipMemcpyDeviceToHost);
           unsigned q4[2]; (void)hipMemcpy(q4, p.queue + 4, 4, hipMemcpyDeviceToHost); fprintf(stderr, "list 0: %u pixels; ", q4[0]);
@@ -1154,14 +1163,14 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
         return hipGetLastError();
     }
     if (classic) {
-        if (p.dbg) hipLaunchKernelGGL((k_render_mesh_queue<1, true, false>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else if (p.counters) hipLaunchKernelGGL((k_render_mesh_queue<1, false, true>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else hipLaunchKernelGGL((k_render_mesh_queue<1, false, false>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+        if (p.dbg) launch_mesh_queue<1, true, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+        else if (p.counters) launch_mesh_queue<1, false, true>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+        else launch_mesh_queue<1, false, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
     } else {
-        if (lean) hipLaunchKernelGGL((k_render_mesh_queue<0, false, false, true>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else if (p.dbg) hipLaunchKernelGGL((k_render_mesh_queue<0, true, false>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else if (p.counters) hipLaunchKernelGGL((k_render_mesh_queue<0, false, true>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else hipLaunchKernelGGL((k_render_mesh_queue<0, false, false>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+        if (lean) launch_mesh_queue<0, false, false, true>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+        else if (p.dbg) launch_mesh_queue<0, true, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+        else if (p.counters) launch_mesh_queue<0, false, true>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+        else launch_mesh_queue<0, false, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
     }
     return hipGetLastError();
 }

@@ -1817,13 +1817,30 @@ size_t rt_sphere_kernel_lds_bytes(int n_padded, int n) {                       /
 //          bits 24..25 work order of the persistent kernel: 0 = two-phase, cost-ordered (reference stream; otherwise as 3),
 //                      1 = tile-major, 2 = scattered only, 3 = one launch ordered by the centre-ray pre-pass
 //                      (glass-crossing pixels first, sky last).
+// One instantiation of k_render_spheres_queue, named by its template arguments: launch_sphere_queue launches it and notes those arguments for the
+// launch report (rtLastLaunches).  Every launch of the persistent kernel goes through it.
+template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN = 0> struct SphereQueueForm {};
+
+template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN>
+static hipError_t launch_sphere_queue(SphereQueueForm<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>, const RtSphereParams& q, unsigned blocks, int threads, size_t lds,
+                                      hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps, bool set_lds_attr) {
+    const auto kern = k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>;
+    // the attribute goes on the function that is launched
+    if (set_lds_attr && lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, stream, q, stride, cfg, chain_cfg, caps);
+    rt_note_launch(RT_KERNEL_SPHERE_QUEUE, PHASE, CLS, CHUNKED, DBG, SCENE, LEAN, threads, blocks);
+    return hipGetLastError();
+}
+
 template <bool CHUNKED>
 static hipError_t launch_queue_kernel_global(const RtSphereParams& q, unsigned blocks, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg) {
     const size_t lds = (size_t)kWavesPerWg * kWaveScratch;          // only the per-wave scratch: the scene stays in global memory
     // (counters - and with them the reference's ray statistics - live in the diagnostic instantiation only)
-    if (q.counters != nullptr || q.wave_dbg != nullptr) hipLaunchKernelGGL((k_render_spheres_queue<0, 0, CHUNKED, true, 1>), dim3(blocks), dim3(kThreads), lds, stream, q, stride, cfg, chain_cfg, 0x4444);
-    else hipLaunchKernelGGL((k_render_spheres_queue<0, 0, CHUNKED, false, 1>), dim3(blocks), dim3(kThreads), lds, stream, q, stride, cfg, chain_cfg, 0x4444);
-    return hipGetLastError();
+    if (q.counters != nullptr || q.wave_dbg != nullptr) return launch_sphere_queue(SphereQueueForm<0, 0, CHUNKED, true, 1>{}, q, blocks, kThreads, lds, stream, stride, cfg, chain_cfg, 0x4444, false);
+    return launch_sphere_queue(SphereQueueForm<0, 0, CHUNKED, false, 1>{}, q, blocks, kThreads, lds, stream, stride, cfg, chain_cfg, 0x4444, false);
 }
 
 static int g_queue_threads = kThreads;      // workgroup size of the persistent kernel for the scene being launched (launch_spheres: 16 waves, or 8 when only that fits)
@@ -1835,49 +1852,41 @@ template <int PHASE, int CLS, bool CHUNKED, int SCENE>
 static hipError_t launch_queue_kernel_scene(const RtSphereParams& q, unsigned blocks, size_t lds, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps) {
     // (the diagnostic instantiation - counters, the reference's ray statistics, time stamps - is the general kernel: launch_spheres leaves g_lean at 0 for it)
     const bool counting = q.wave_dbg != nullptr || q.counters != nullptr;
-    auto go = [&](auto kern) -> hipError_t {
-        // the attribute goes on the function that is launched
-        if (lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(g_queue_threads), lds, stream, q, stride, cfg, chain_cfg, caps);
-        return hipGetLastError();
-    };
+    auto go = [&](auto form) -> hipError_t { return launch_sphere_queue(form, q, blocks, g_queue_threads, lds, stream, stride, cfg, chain_cfg, caps, true); };
     // (time lines of the PRODUCTION kernel of the benchmark scene - RT_WAVE_DEBUG with RT_WAVE_DEBUG_LIGHT=1, no counters: the lean kind 3 with the stamps)
-    if (counting && q.counters == nullptr && SCENE == 0 && !CHUNKED && PHASE != 0 && g_lean_dbg == 3) return go(k_render_spheres_queue<PHASE, CLS, false, true, 0, 3>);
-    if (counting) return go(k_render_spheres_queue<PHASE, CLS, CHUNKED, true, SCENE>);
+    if (counting && q.counters == nullptr && SCENE == 0 && !CHUNKED && PHASE != 0 && g_lean_dbg == 3) return go(SphereQueueForm<PHASE, CLS, false, true, 0, 3>{});
+    if (counting) return go(SphereQueueForm<PHASE, CLS, CHUNKED, true, SCENE>{});
     if (SCENE == 0 && CHUNKED) {                                     // the sample chunks of the counter stream: the kinds of the benchmark's shape
         switch (g_lean) {
-        case 1:  return go(k_render_spheres_queue<PHASE, CLS, true, false, 0, 1>);
-        case 3:  return go(k_render_spheres_queue<PHASE, CLS, true, false, 0, 3>);
-        case 7:  return go(k_render_spheres_queue<PHASE, CLS, true, false, 0, 7>);
+        case 1:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 1>{});
+        case 3:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 3>{});
+        case 7:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 7>{});
         default: break;
         }
     }
     if (SCENE == 0 && !CHUNKED) {
         switch (g_lean) {
-        case 1:  return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 1>);
-        case 3:  return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 3>);
-        case 7:  return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 7>);
-        case 11: return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 11>);
-        case 15: return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 15>);
-        case 19: return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 19>);
-        case 27: return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 27>);
-        case 35: return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 35>);
-        case 43: return go(k_render_spheres_queue<PHASE, CLS, false, false, 0, 43>);
+        case 1:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 1>{});
+        case 3:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 3>{});
+        case 7:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 7>{});
+        case 11: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 11>{});
+        case 15: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 15>{});
+        case 19: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 19>{});
+        case 27: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 27>{});
+        case 35: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 35>{});
+        case 43: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 43>{});
         default: break;
         }
     }
     if (SCENE == 2 && !CHUNKED) {                                    // the hybrid scene copy (hit data in global memory: ~1500-3400 spheres)
         switch (g_lean) {
-        case 1:  return go(k_render_spheres_queue<PHASE, CLS, false, false, 2, 1>);
-        case 35: return go(k_render_spheres_queue<PHASE, CLS, false, false, 2, 35>);
-        case 43: return go(k_render_spheres_queue<PHASE, CLS, false, false, 2, 43>);
+        case 1:  return go(SphereQueueForm<PHASE, CLS, false, false, 2, 1>{});
+        case 35: return go(SphereQueueForm<PHASE, CLS, false, false, 2, 35>{});
+        case 43: return go(SphereQueueForm<PHASE, CLS, false, false, 2, 43>{});
         default: break;
         }
     }
-    return go(k_render_spheres_queue<PHASE, CLS, CHUNKED, false, SCENE>);
+    return go(SphereQueueForm<PHASE, CLS, CHUNKED, false, SCENE>{});
 }
 
 // `hybrid`: stage_scene's form 2 (test data in the LDS, hit data in global memory)
@@ -1985,6 +1994,7 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
         { const hipError_t ew = wait_fb(); if (ew != hipSuccess) return ew; }
         if (legacy) hipLaunchKernelGGL(k_render_spheres_tiles<true>, grid, dim3(kThreads), lds, stream, p, coop_below, cull);
         else hipLaunchKernelGGL(k_render_spheres_tiles<false>, grid, dim3(kThreads), lds, stream, p, coop_below, cull);
+        rt_note_launch(RT_KERNEL_SPHERE_TILES, 0, legacy ? 1 : 0, 0, 0, 0, 0, kThreads, grid.x * grid.y);
         return hipGetLastError();
     }
     if (!p.queue) return hipErrorInvalidValue;

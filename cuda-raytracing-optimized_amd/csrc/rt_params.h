@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rt_types.h"
+#include "../../include/rt_api.h"
 
 // Row partition of the image over devices / processes: the image is cut into
 // stripes of `stripe_rows` rows; stripe k belongs to part (k % world).  A device renders its
@@ -185,3 +186,6 @@ hipError_t rt_launch_spheres_parity(const RtSphereParams& p, int variant, hipStr
 hipError_t rt_launch_spheres_fast(const RtSphereParams& p, int variant, hipStream_t stream);
 hipError_t rt_launch_mesh_parity(const RtMeshParams& p, int variant, hipStream_t stream);
 hipError_t rt_launch_mesh_fast(const RtMeshParams& p, int variant, hipStream_t stream);
+// The launch report (rtLastLaunches, rt_api.h): the launchers note every render-kernel launch with the template arguments of the instantiation they launched
+// (RT_KERNEL_* family and the RT_LAUNCH_* words up to RT_LAUNCH_BLOCKS); the renderer adds the device and the fp mode of the frame.  Host bookkeeping only.
+void rt_note_launch(int family, int phase, int cls, int chunked, int dbg, int scene, int lean, int threads, unsigned blocks);

@@ -140,6 +140,10 @@ struct RenderContext {
 
 RenderContext g_ctx;     // kernels.cu:145: one global context per process
 
+// rtLastLaunches: the records of the last runRenderer (RT_LAUNCH_WORDS each) and the device / fp mode of the launcher being called
+std::vector<int32_t> g_launches;
+int g_launch_device = 0, g_launch_fp = 0;
+
 void default_options(rt_render_options* o, int spheres) {
     memset(o, 0, sizeof *o);
     o->sky = spheres ? RT_SKY_GRADIENT : RT_SKY_CONST_GREY;     // kernels.cu:419-424
@@ -495,6 +499,11 @@ void cleanup_impl() {
 
 }  // namespace
 
+void rt_note_launch(int family, int phase, int cls, int chunked, int dbg, int scene, int lean, int threads, unsigned blocks) {
+    const int32_t rec[RT_LAUNCH_WORDS] = { family, phase, cls, chunked, dbg, scene, lean, threads, (int32_t)blocks, g_launch_device, g_launch_fp };
+    g_launches.insert(g_launches.end(), rec, rec + RT_LAUNCH_WORDS);
+}
+
 extern "C" {
 
 int rtApiVersion(void) { return RT_API_VERSION; }
@@ -509,6 +518,13 @@ int rtStructSizes(int32_t* out, int n) {
         (int32_t)sizeof(rt_kernel_scene), (int32_t)sizeof(rt_stexture), (int32_t)sizeof(rt_plane), (int32_t)sizeof(rt_bbox), (int32_t)sizeof(rt_vec3) };
     for (int k = 0; k < n && k < RT_SIZEOF_COUNT; k++) out[k] = sizes[k];
     return RT_SIZEOF_COUNT;
+}
+
+int rtLastLaunches(int32_t* out, int cap) {
+    const int count = (int)(g_launches.size() / RT_LAUNCH_WORDS);
+    const int n = std::min(count, std::max(cap, 0));
+    if (out && n > 0) memcpy(out, g_launches.data(), (size_t)n * RT_LAUNCH_WORDS * sizeof(int32_t));
+    return count;
 }
 
 int rtDeviceCount(void) {
@@ -653,11 +669,14 @@ void runRenderer(int ns, int tx, int ty) {
     const size_t row_bytes = (size_t)c.nx * sizeof(rt_vec3);
     int64_t samples = 0;
     int launches = 0;
+    g_launches.clear();
+    g_launch_fp = c.opt.fp;
 
     for (int k = 0; k < nd; k++) {
         DeviceState& d = c.devs[k];
         if (d.fb_rows == 0) continue;
         HIP_CHECK(hipSetDevice(d.device));
+        g_launch_device = d.device;
         RtPartition part;
         part.stripe_rows = c.opt.stripe_rows;
         part.rank = c.opt.part_rank * nd + k;

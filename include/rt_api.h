@@ -79,6 +79,23 @@ enum { RT_SIZEOF_RENDER_OPTIONS = 0, RT_SIZEOF_RENDER_STATS, RT_SIZEOF_CAMERA, R
        RT_SIZEOF_COUNT };
 int rtStructSizes(int32_t* out, int n);
 
+/* Launch report of the last runRenderer: one record of RT_LAUNCH_WORDS int32 per render-kernel launch, in launch order, over all
+ * in-process devices.  The helper kernels of a frame (cost ordering, centre-ray classification, framebuffer poison, chunk sums) are not
+ * listed.  Writes min(cap, count) records to out (out may be NULL when cap is 0) and returns count.  Host-side bookkeeping only.
+ * Each record names the template instantiation that was LAUNCHED:
+ *   [RT_LAUNCH_FAMILY]  RT_KERNEL_SPHERE_QUEUE  k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>
+ *                       RT_KERNEL_SPHERE_TILES  k_render_spheres_tiles<LEGACY>          (LEGACY in the CLS word, the rest 0)
+ *                       RT_KERNEL_MESH_QUEUE    k_render_mesh_queue<TRAV, DBG, STATS, LEAN, PHASE>
+ *                                               (TRAV in the CLS word: 1 = classic while-while; DBG | STATS << 1 in the DBG word; LEAN 0 / 1)
+ *                       RT_KERNEL_MESH_TILES    k_render_mesh<VARIANT>                  (VARIANT in the CLS word, the rest 0)
+ *   [RT_LAUNCH_PHASE] .. [RT_LAUNCH_LEAN]  the template arguments above (bools as 0 / 1)
+ *   [RT_LAUNCH_THREADS] threads per workgroup   [RT_LAUNCH_BLOCKS] workgroups launched
+ *   [RT_LAUNCH_DEVICE]  HIP device ordinal      [RT_LAUNCH_FP]     rt_render_options.fp of the frame (RT_FP_PARITY / RT_FP_FAST) */
+enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
+enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
+       RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };
+int rtLastLaunches(int32_t* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif
