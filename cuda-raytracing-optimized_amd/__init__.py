@@ -129,7 +129,8 @@ assert triangle_dtype.itemsize == 64 and bvh_node_dtype.itemsize == 24
 # symbols every library must export (tests check the .so against the headers with these)
 RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRendererSpheres",
                     "getDefaultRenderOptions", "setRenderOptions", "setExternalFramebuffer", "getRenderStats",
-                    "rtDeviceCount", "rtApiVersion", "rtStructSizes", "rtLastLaunches"]
+                    "rtDeviceCount", "rtApiVersion", "rtStructSizes", "rtLastLaunches",
+                    "runRendererProgressive", "rtProgressiveSamples", "rtResetProgressive", "setCamera"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
@@ -243,6 +244,14 @@ def load_renderer():
         r.rtApiVersion.restype = C.c_int
         r.rtLastLaunches.argtypes = [C.POINTER(C.c_int32), C.c_int]
         r.rtLastLaunches.restype = C.c_int
+        r.runRendererProgressive.argtypes = [C.c_int, C.c_int, C.c_int]
+        r.runRendererProgressive.restype = None
+        r.rtProgressiveSamples.argtypes = []
+        r.rtProgressiveSamples.restype = C.c_int
+        r.rtResetProgressive.argtypes = []
+        r.rtResetProgressive.restype = None
+        r.setCamera.argtypes = [C.POINTER(camera)]
+        r.setCamera.restype = None
         _renderer = r
     return _renderer
 
@@ -408,6 +417,26 @@ def initRendererSpheres(spheres, materials, cam, nx, ny, maxDepth):
 def runRenderer(ns, tx=8, ty=8):
     """extern "C" runRenderer (/root/reference/kernels.h:7); blocking."""
     load_renderer().runRenderer(ns, tx, ty)
+
+
+def runRendererProgressive(ns, tx=8, ty=8):
+    """Adds ns samples per pixel to the progressive frame; the framebuffer holds the mean of all samples since the last reset (include/rt_api.h)."""
+    load_renderer().runRendererProgressive(ns, tx, ty)
+
+
+def progressive_samples():
+    """Samples per pixel accumulated by runRendererProgressive since init / the last reset."""
+    return load_renderer().rtProgressiveSamples()
+
+
+def resetProgressive():
+    """The next runRendererProgressive starts again at sample 0."""
+    load_renderer().rtResetProgressive()
+
+
+def setCamera(cam):
+    """Replaces the camera for the following frames (no re-upload of the scene); resets the progressive frame."""
+    load_renderer().setCamera(C.byref(cam))
 
 
 def cleanupRenderer():

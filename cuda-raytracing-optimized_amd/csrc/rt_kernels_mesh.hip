@@ -660,6 +660,8 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
                     const f3 out = col / (float)P.ns;                // kernels.cu:568
                     // one 12-byte store (global_store_dwordx3): a lane finishes its pixel on its own, three dword stores are three partial-sector writes
                     *reinterpret_cast<float3*>(fbf + ((size_t)lr * P.nx + pi) * 3) = make_float3(out.x, out.y, out.z);
+                    float4* const acc = rt_cold_arg<float4*>(offsetof(RtMeshParams, acc_state));
+                    if (acc) acc[(size_t)lr * P.nx + pi] = make_float4(col.x, col.y, col.z, __uint_as_float(rng));      // a progressive pass: state for the next
                     have_pixel = false;
 #if RT_MESH_TAIL_DIAG
                     if (PHASE == 2) g_diag_items[((size_t)lr * P.nx + pi) * 2 + 1] = (uint32_t)(__builtin_amdgcn_s_memrealtime() / 100ull);
@@ -722,9 +724,17 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
                 if (i < P.nx && lr < P.part.local_rows) {
                     pi = i; pj = global_row(P.part, lr);
                     pixelId = (uint32_t)(pj * P.nx + pi);
-                    rng = pixel_seed(pixelId);
-                    col = F3(0, 0, 0);
-                    s = 0;
+                    const int acc_first = PHASE == 0 ? rt_cold_arg<int32_t>(offsetof(RtMeshParams, acc_first)) : 0;
+                    if (acc_first > 0) {                             // a progressive pass: the pixel's stream continues where the last pass left it
+                        const float4 st4 = rt_cold_arg<const float4*>(offsetof(RtMeshParams, acc_state))[(size_t)lr * P.nx + pi];
+                        rng = __float_as_uint(st4.w);
+                        col = F3(st4.x, st4.y, st4.z);
+                        s = acc_first;
+                    } else {
+                        rng = pixel_seed(pixelId);
+                        col = F3(0, 0, 0);
+                        s = 0;
+                    }
                     pix_jobs = 0;
                     have_pixel = true;
                     need_sample = true;
@@ -1109,8 +1119,9 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
     static const bool two_env = !(getenv("RT_MESH_TWO") && getenv("RT_MESH_TWO")[0] == '0');
     static const int split_env = getenv("RT_MESH_SPLIT") ? atoi(getenv("RT_MESH_SPLIT")) : 2;      // (1: 903, 2: 911, 4: 893, 8: 866 Msamples/s on C4, profiles/r04_ab_mesh_two_b.txt)
     const int split = split_env < 1 ? 1 : split_env;
+    // (a continuation pass of a progressive frame, p.acc_first > 0, takes the single dispatch: PHASE 0 resumes every pixel from p.acc_state)
     if (two_env && !classic && !p.dbg && !p.counters && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.px_state && p.px_rays && p.order && p.ord_state && p.ord_rays &&
-        p.ns >= 4 * split && p.nx <= 65535 && p.part.local_rows <= 65535) {
+        p.acc_first == 0 && p.ns >= 4 * split && p.nx <= 65535 && p.part.local_rows <= 65535) {
         RtMeshParams q = p;
         q.s_split = split;
         // (p.p1_segments: the first dispatch scatters row segments of 8 pixels - `stride` coprime with total / 8, flag in bit 8 of min_traversing)

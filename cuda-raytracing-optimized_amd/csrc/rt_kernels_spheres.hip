@@ -1242,6 +1242,9 @@ constexpr int kChainClasses = 4;      // lists 0..3: >= 12 rays per sample, the 
                                       // that hold ONE pixel (kernel parameter `caps`) and trace it in the single-ray form (scan_single)
 constexpr int kHeavyClasses = 3;      // lists 4..6: 6..12 rays per sample -> spread over the first fill of the normal waves
 
+// A progressive pass orders its pixels by the rays of ALL their samples so far (s_split = samples accumulated): at most 255 rays per sample (max_depth),
+// so the window sum x 16 below stays within 32 bits up to the largest total runRendererProgressive accepts.
+static_assert(9ull * 16ull * 255ull * RT_PROGRESSIVE_MAX_SAMPLES <= 0xFFFFFFFFull, "cost_class: window sum of a progressive total overflows 32 bits");
 __device__ __forceinline__ int cost_class(const RtSphereParams& P, int i, int lr) {
     uint32_t sum = 0, cnt = 0;
     for (int dy = -1; dy <= 1; dy++) {
@@ -1531,6 +1534,12 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                     // one 12-byte store (global_store_dwordx3): a lane finishes its pixel on its own, so three dword
                     // stores would be three partial-sector writes
                     *reinterpret_cast<float3*>(fbf + ((size_t)(P.fb_global_rows ? L.j : lr) * P.nx + L.i) * 3) = make_float3(out.x, out.y, out.z);
+                    float4* const acc = rt_cold_arg<float4*>(offsetof(RtSphereParams, acc_state));
+                    if (acc) {                                       // a progressive pass: the stream position and running sum for the next pass
+                        const size_t px = (size_t)lr * P.nx + L.i;
+                        acc[px] = make_float4(L.col.x, L.col.y, L.col.z, __uint_as_float(L.rng));
+                        rt_cold_arg<uint32_t*>(offsetof(RtSphereParams, acc_rays))[px] = pix_rays;
+                    }
                 } else {                                             // partial sum of this chunk; k_sum_chunks adds them in order
                     float* dst = reinterpret_cast<float*>(P.partial) + (((size_t)lr * P.nx + L.i) * (uint32_t)P.chunks + (uint32_t)chunk) * 3;
                     dst[0] = L.col.x; dst[1] = L.col.y; dst[2] = L.col.z;
@@ -1674,7 +1683,17 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                     lr = ty * 8 + (int)(within >> 3);
                 }
                 if (i < P.nx && lr < P.part.local_rows) {            // pixels of partial edge tiles are skipped
-                    if (PHASE == 0) {
+                    const int acc_first = (PHASE == 0 && !CHUNKED) ? rt_cold_arg<int32_t>(offsetof(RtSphereParams, acc_first)) : 0;
+                    if (acc_first > 0) {                             // a progressive pass: the pixel's stream continues where the last pass left it
+                        const size_t px = (size_t)lr * P.nx + i;
+                        const float4 st4 = rt_cold_arg<const float4*>(offsetof(RtSphereParams, acc_state))[px];
+                        L.i = i; L.j = global_row(P.part, lr);
+                        L.pixelId = (uint32_t)(L.j * P.nx + i);
+                        L.rng = __float_as_uint(st4.w);
+                        L.col = F3(st4.x, st4.y, st4.z);
+                        L.s = acc_first;
+                        pix_rays = rt_cold_arg<const uint32_t*>(offsetof(RtSphereParams, acc_rays))[px];
+                    } else if (PHASE == 0) {
                         s_end_lane = min(P.ns, (chunk + 1) * P.spw);
                         init_pixel(P, L, i, global_row(P.part, lr), chunk * P.spw);
                         pix_rays = 0;
@@ -2081,25 +2100,35 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
     // samples, then resume all pixels longest-first (see k_order_by_cost).  Otherwise: one launch, optionally ordered
     // by the centre-ray pre-pass (k_classify_spheres: order_mode 3) or plainly scattered (2) / tile-major (1).
     const int split = 2;                                             // measured: 1 -> 15.5 ms, 2 -> 15.0, 3 -> 15.1 (round 2); 2 -> 24.5, 4 -> 24.8, 6 -> 25.4 (round 1)
-    if (order_mode == 0 && p.order && p.px_state && p.px_rays && p.chunks == 1 && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.ns >= 8 &&
+    // A continuation pass of a progressive frame (p.acc_first > 0) is the second dispatch of a two-dispatch frame whose first dispatch ran in earlier passes:
+    // the ordering pass reads the accumulated state and rays over p.acc_first samples, PHASE 2 resumes [acc_first, ns).  It has no first dispatch to poison
+    // the host framebuffer: k_poison_fb runs in front of it.
+    const bool resume = p.acc_first > 0 && p.acc_state && p.acc_rays;
+    if (order_mode == 0 && p.order && p.px_state && p.px_rays && p.chunks == 1 && p.rng_mode == RT_RNG_REFERENCE_STREAM && (p.ns >= 8 || resume) &&
         p.nx <= 65535 && p.part.local_rows <= 65535) {                                   // list entries pack (row << 16 | column)
         RtSphereParams q = p;
-        q.phase = 1; q.s_split = split;
-        // (q.p1_tile_major 1: the two-sample items in tile-major order - a wave parks two adjacent 8x8 tiles, whole lines of px_state; 2: scattered as row
-        // segments of 8 pixels - a line of px_state per 8 lanes, the scattering kept)
-        uint32_t stride1 = stride;
-        int cfg1 = cfg;
-        if (q.p1_tile_major == 1) stride1 = 1u;
-        if (q.p1_tile_major == 2 && total_px > 512) {
-            auto gcd = [](unsigned long long a, unsigned long long b) { while (b) { const unsigned long long t = a % b; a = b; b = t; } return a; };
-            const unsigned long long segs = (unsigned long long)total_px >> 3;
-            unsigned long long cand = (unsigned long long)((double)segs * 0.6180339887) | 1ull;
-            while (gcd(cand, segs) != 1ull) cand += 2;
-            stride1 = (uint32_t)(cand % segs);
-            cfg1 |= 1 << 30;
+        if (resume) {
+            q.px_state = p.acc_state; q.px_rays = p.acc_rays; q.s_split = p.acc_first;
+            e = wait_fb();
+            if (e != hipSuccess) return e;
+        } else {
+            q.phase = 1; q.s_split = split;
+            // (q.p1_tile_major 1: the two-sample items in tile-major order - a wave parks two adjacent 8x8 tiles, whole lines of px_state; 2: scattered as row
+            // segments of 8 pixels - a line of px_state per 8 lanes, the scattering kept)
+            uint32_t stride1 = stride;
+            int cfg1 = cfg;
+            if (q.p1_tile_major == 1) stride1 = 1u;
+            if (q.p1_tile_major == 2 && total_px > 512) {
+                auto gcd = [](unsigned long long a, unsigned long long b) { while (b) { const unsigned long long t = a % b; a = b; b = t; } return a; };
+                const unsigned long long segs = (unsigned long long)total_px >> 3;
+                unsigned long long cand = (unsigned long long)((double)segs * 0.6180339887) | 1ull;
+                while (gcd(cand, segs) != 1ull) cand += 2;
+                stride1 = (uint32_t)(cand % segs);
+                cfg1 |= 1 << 30;
+            }
+            e = launch_queue_kernel<1, 0, false>(q, nb, lds, hybrid, stream, stride1, cfg1, chain_cfg);
+            if (e != hipSuccess) return e;
         }
-        e = launch_queue_kernel<1, 0, false>(q, nb, lds, hybrid, stream, stride1, cfg1, chain_cfg);
-        if (e != hipSuccess) return e;
         e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords, stream);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_order_by_cost<0>, dim3(kOrderBlocks), dim3(kThreads), 0, stream, q);

@@ -110,6 +110,13 @@ struct RtSphereParams {
                                 // L2, which merges their 12-byte stores into whole lines (`fb` in device memory).  0 / 1: one queue for the machine
     int32_t p1_tile_major;      // 1: the first dispatch hands out its two-sample items in tile-major order (a wave parks the pixels of two adjacent 8x8 tiles: its 16-byte
                                 // states fill whole lines) instead of scattered
+    // Progressive rendering (runRendererProgressive, rt_api.h): a pass adds samples [acc_first, ns) to every pixel.  acc_state / acc_rays (local_rows * nx,
+    // nullptr = not a progressive pass) hold (col.xyz, rng bits) and the rays traced since sample 0 of every pixel, written by the PHASE 0 and PHASE 2 kernels
+    // when a pixel is finished.  acc_first > 0: the pass continues them - PHASE 0 loads the parked state at fetch instead of starting the pixel; the
+    // two-dispatch frame skips its first dispatch and orders the pixels by acc_rays over acc_first samples (launch_spheres).
+    float4* acc_state;
+    uint32_t* acc_rays;
+    int32_t acc_first;
 };
 constexpr int kXcdQueueWords = 64;      // words per queue block: [0] general counter [1] chain counter [2] middle-tier counter [3] first position of this XCD's lists in
                                         // `order` [4 .. 4 + 18) list lengths [22 .. 22 + 18) fill cursors
@@ -171,7 +178,21 @@ struct RtMeshParams {
     float4* ord_rec;
     int32_t xcd_queues;
     int32_t p1_segments;
+    // Progressive rendering, as in RtSphereParams: (col.xyz, rng bits) of every pixel after the samples so far (written by PHASE 0 and PHASE 2 when a pixel
+    // is finished; nullptr = not a progressive pass); acc_first > 0: PHASE 0 resumes them at sample acc_first (a continuation takes no two-dispatch frame)
+    float4* acc_state;
+    int32_t acc_first;
 };
+
+// A field of a render kernel's parameter block (its first argument: offset 0 of the kernarg segment), loaded where it is used.  The base is opaque to the
+// optimiser, so it cannot hoist the load to the kernel's head and hold the value in SGPRs for the life of the wave: the progressive-pass fields are read
+// once per pixel, and held they cost the persistent kernels SGPR and VGPR spills (the six-wave kernel 6 -> 17 spilled VGPRs).
+template <typename T>
+__device__ __forceinline__ T rt_cold_arg(size_t offset) {
+    unsigned long long base = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(base));
+    return *reinterpret_cast<const __attribute__((address_space(4))) T*>(base + offset);
+}
 
 // LDS the sphere kernel needs for a scene of n spheres (n_padded slots).
 size_t rt_sphere_kernel_lds_bytes(int n_padded, int n);

@@ -93,6 +93,8 @@ struct DeviceState {
     float4* d_ord_state = nullptr;      // ... and their copies in queue order (RtSphereParams::ord_state / ord_rays)
     uint32_t* d_ord_rays = nullptr;
     float4* d_ord_rec = nullptr;        // ... or as one 32-byte record per queue position (RtSphereParams::ord_rec)
+    float4* d_acc_state = nullptr;      // progressive frame (runRendererProgressive): per local pixel (col, rng) after the samples so far, and (sphere scenes)
+    uint32_t* d_acc_rays = nullptr;     // the rays they took; allocated by the first pass on this device
 };
 
 struct RenderContext {
@@ -136,6 +138,7 @@ struct RenderContext {
     std::vector<int32_t> h_tex_w, h_tex_h;
     std::vector<DeviceState> devs;
     rt_render_stats stats;
+    int prog_samples = 0;               // samples per pixel of the progressive frame so far (rtProgressiveSamples)
 };
 
 RenderContext g_ctx;     // kernels.cu:145: one global context per process
@@ -172,6 +175,7 @@ void free_device(DeviceState& d) {
     for (float* t : d.d_tex) fr(t);
     fr(d.d_tex_data); fr(d.d_tex_width); fr(d.d_tex_height);
     fr(d.d_fb); fr(d.d_counters); fr(d.d_queue); fr(d.d_wave_dbg); fr(d.d_order); fr(d.d_partial); fr(d.d_px_state); fr(d.d_px_rays); fr(d.d_ord_state); fr(d.d_ord_rays); fr(d.d_ord_rec);
+    fr(d.d_acc_state); fr(d.d_acc_rays);
     fr(d.d_params);
     if (d.h_params) HIP_CHECK(hipHostFree(d.h_params));
     if (d.ev_start) HIP_CHECK(hipEventDestroy(d.ev_start));
@@ -286,6 +290,7 @@ void common_init(const rt_camera& cam, rt_vec3** fb, int nx, int ny, int maxDept
     memset(c.h_fb, 0, (size_t)nx * ny * sizeof(rt_vec3));
     *fb = c.h_fb;
     memset(&c.stats, 0, sizeof c.stats);
+    c.prog_samples = 0;
     setup_devices();
     c.initialised = true;
 }
@@ -654,13 +659,17 @@ void setRenderOptions(const rt_render_options* opt) {
                     old.part_world != opt->part_world || old.num_devices != opt->num_devices;
     for (int k = 0; k < RT_MAX_DEVICES && !relayout; k++) relayout = old.devices[k] != opt->devices[k];
     if (relayout) setup_devices();
+    c.prog_samples = 0;                                     // (any call: the options of the accumulated samples may differ)
 }
 
-void runRenderer(int ns, int tx, int ty) {
-    (void)tx; (void)ty;     // CUDA block shape of the reference (main.cpp:69-70); the wave64 tile is fixed
+}  // extern "C"
+
+namespace {
+
+// One frame of ns samples per pixel (runRenderer), or one pass of a progressive frame (progressive): samples [first, ns) of every pixel, continued from
+// and parked into the device's accumulation buffers, the framebuffer = sum / ns.
+void render_frame(int ns, int first, bool progressive) {
     RenderContext& c = g_ctx;
-    if (!c.initialised) rt_fail("runRenderer before init");
-    if (ns <= 0) rt_fail("runRenderer: ns must be positive");
     const auto t0 = std::chrono::steady_clock::now();
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
@@ -732,6 +741,7 @@ void runRenderer(int ns, int tx, int ty) {
             // with the per-sample counter stream the samples are independent and a pixel is split into chunks
             p.spw = spw; p.chunks = chunks; p.partial = nullptr;
             p.phase = 0; p.s_split = 0; p.px_state = d.d_px_state; p.px_rays = d.d_px_rays; p.ord_state = d.d_ord_state; p.ord_rays = d.d_ord_rays;
+            if (progressive) { p.acc_state = d.d_acc_state; p.acc_rays = d.d_acc_rays; p.acc_first = first; }
             static const int top_thr_env = getenv("RT_TOP_THR") ? atoi(getenv("RT_TOP_THR")) : 0;      // experiments
             p.chain_top_thr = top_thr_env >= 320 ? top_thr_env : 384;                                 // 24 rays per sample
             // Traffic forms of the two-dispatch frame (RtSphereParams::ord_rec / xcd_queues / p1_tile_major; A/B switches read per frame, defaults = what measured best)
@@ -752,7 +762,7 @@ void runRenderer(int ns, int tx, int ty) {
             }
             static const char* dbg_path = getenv("RT_WAVE_DEBUG");      // diagnostics: per-wave time stamps -> file
             const size_t dbg_bytes = (size_t)65536 * 8 * sizeof(unsigned long long);
-            if (dbg_path) {
+            if (dbg_path && !progressive) {       // (PHASE 2's per-pixel time line would overwrite the parked state)
                 if (!d.d_wave_dbg) HIP_CHECK(hipMalloc((void**)&d.d_wave_dbg, dbg_bytes));
                 HIP_CHECK(hipMemsetAsync(d.d_wave_dbg, 0, dbg_bytes, d.stream));
                 p.wave_dbg = d.d_wave_dbg;
@@ -797,6 +807,7 @@ void runRenderer(int ns, int tx, int ty) {
             p.counters = c.opt.counters ? d.d_counters : nullptr;
             p.queue = d.d_queue;
             p.s_split = 0; p.px_state = d.d_px_state; p.px_rays = d.d_px_rays; p.order = d.d_order; p.ord_state = d.d_ord_state; p.ord_rays = d.d_ord_rays;
+            if (progressive) { p.acc_state = d.d_acc_state; p.acc_first = first; }
             // the traffic forms of the two-dispatch frame, as for sphere scenes (the same switches; the mesh frame always renders into the device framebuffer)
             p.ord_rec = env_flag("RT_ORD_PACKED", kDefaultOrdPacked) ? d.d_ord_rec : nullptr;
             p.xcd_queues = env_flag("RT_XCD_QUEUES", kDefaultXcdQueues) ? kXcdQueues : 0;
@@ -827,7 +838,7 @@ void runRenderer(int ns, int tx, int ty) {
         if (world != 1 && rem > 0 && !fb_direct)
             HIP_CHECK(hipMemcpyAsync(dst0 + full * (size_t)world * stripe_bytes, src0 + full * stripe_bytes, rem * row_bytes,
                                      hipMemcpyDeviceToHost, d.stream));
-        samples += (int64_t)d.fb_rows * c.nx * ns;
+        samples += (int64_t)d.fb_rows * c.nx * (ns - first);
     }
 
     double kernel_ms = 0.0;
@@ -867,6 +878,52 @@ void runRenderer(int ns, int tx, int ty) {
     st.samples = samples;
     st.num_launches = launches;
     c.stats = st;
+}
+
+}  // namespace
+
+extern "C" {
+
+void runRenderer(int ns, int tx, int ty) {
+    (void)tx; (void)ty;     // CUDA block shape of the reference (main.cpp:69-70); the wave64 tile is fixed
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("runRenderer before init");
+    if (ns <= 0) rt_fail("runRenderer: ns must be positive");
+    render_frame(ns, 0, false);
+}
+
+void runRendererProgressive(int ns, int tx, int ty) {
+    (void)tx; (void)ty;
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("runRendererProgressive before init");
+    if (ns <= 0) rt_fail("runRendererProgressive: ns must be positive");
+    if (c.opt.rng != RT_RNG_REFERENCE_STREAM) rt_fail("runRendererProgressive: only the reference RNG stream accumulates (RT_RNG_COUNTER sums sample chunks)");
+    if (c.opt.variant != 0) rt_fail("runRendererProgressive: only the default kernels (variant 0) continue a frame");
+    if (ns > RT_PROGRESSIVE_MAX_SAMPLES - c.prog_samples) rt_fail("runRendererProgressive: total samples per pixel above RT_PROGRESSIVE_MAX_SAMPLES");
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    for (DeviceState& d : c.devs) {                     // the accumulation buffers: on the first pass of this device state
+        if (d.fb_rows == 0 || d.d_acc_state) continue;
+        HIP_CHECK(hipSetDevice(d.device));
+        HIP_CHECK(hipMalloc((void**)&d.d_acc_state, d.fb_rows * c.nx * sizeof(float4)));
+        if (c.is_spheres) HIP_CHECK(hipMalloc((void**)&d.d_acc_rays, d.fb_rows * c.nx * sizeof(uint32_t)));
+    }
+    HIP_CHECK(hipSetDevice(current));
+    const int first = c.prog_samples;
+    render_frame(first + ns, first, true);
+    c.prog_samples = first + ns;
+}
+
+int rtProgressiveSamples(void) { return g_ctx.prog_samples; }
+
+void rtResetProgressive(void) { g_ctx.prog_samples = 0; }
+
+void setCamera(const rt_camera* cam) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("setCamera before init");
+    if (!cam) rt_fail("setCamera: null");
+    c.cam = *cam;                                           // read by every frame's parameter block; nothing of the scene depends on it
+    c.prog_samples = 0;
 }
 
 void setExternalFramebuffer(rt_vec3* fb) {

@@ -31,7 +31,8 @@ void initRenderer(const rt_kernel_scene sc, const rt_camera cam, rt_vec3** fb, i
 
 /* replaces kernels.cu:652-664.  Renders ns samples per pixel into the framebuffer; blocking.
  * tx,ty are the reference's CUDA block shape (main.cpp:69-70); accepted and ignored — the
- * wave64 tile shape is fixed by the kernel. May be called repeatedly: same image every time. */
+ * wave64 tile shape is fixed by the kernel. May be called repeatedly: same image every time.
+ * Leaves the progressive frame (runRendererProgressive) as it was. */
 void runRenderer(int ns, int tx, int ty);
 
 /* replaces kernels.cu:666-680.  Frees everything, the framebuffer included. */
@@ -91,6 +92,32 @@ int rtStructSizes(int32_t* out, int n);
  *   [RT_LAUNCH_PHASE] .. [RT_LAUNCH_LEAN]  the template arguments above (bools as 0 / 1)
  *   [RT_LAUNCH_THREADS] threads per workgroup   [RT_LAUNCH_BLOCKS] workgroups launched
  *   [RT_LAUNCH_DEVICE]  HIP device ordinal      [RT_LAUNCH_FP]     rt_render_options.fp of the frame (RT_FP_PARITY / RT_FP_FAST) */
+/* --- progressive rendering ------------------------------------------------------------------------------------------------
+ * A progressive frame adds samples to every pixel across calls.  Each pixel's samples are one sequential RNG stream (kernels.cu:541-548): a pass
+ * continues every pixel's stream and running colour sum where the previous pass left them (kept on the device, per device over its local rows) and
+ * stores their mean.  Reference RNG stream only (RT_RNG_REFERENCE_STREAM, variant 0), PARITY and FAST, sphere and mesh scenes, every row partition and
+ * device list, direct and copy-engine delivery, counters on or off.  RT_RNG_COUNTER is refused: runRenderer adds that stream's sample chunks in chunk
+ * order (not one sequential sum), so a progressive total could not match it bit for bit.
+ *
+ * The accumulation is reset (the next pass starts at sample 0) by every init*, cleanupRenderer, setRenderOptions (any call), setCamera and
+ * rtResetProgressive.  setExternalFramebuffer does not reset it: the next pass delivers the whole image to the new target.  runRenderer neither reads nor
+ * changes it: a pass after a runRenderer continues where the previous pass stopped.  The accumulation buffers (16 + 4 bytes per local pixel) are
+ * allocated by the first pass on each device and freed by cleanupRenderer (or a setRenderOptions that changes the device layout).
+ * getRenderStats / rtLastLaunches after a pass describe THAT pass: samples = pixels x ns, its launches, kernel time, rays and counters. */
+
+/* Adds ns samples per pixel to the progressive frame and leaves in the framebuffer (library-owned or external) the mean of ALL samples accumulated
+ * since the last reset.  Blocking, like runRenderer; tx, ty ignored.  PARITY fp mode: after calls with ns_1 .. ns_k the framebuffer is bit-identical to
+ * runRenderer(ns_1 + .. + ns_k).  Misuse (rt error, exit 99): before init, ns <= 0, RT_RNG_COUNTER, variant != 0, a total above
+ * RT_PROGRESSIVE_MAX_SAMPLES (the cost ordering of a pass sums the rays of a pixel's 3x3 window over all its samples in 32 bits). */
+#define RT_PROGRESSIVE_MAX_SAMPLES 65536
+void runRendererProgressive(int ns, int tx, int ty);
+/* Samples per pixel accumulated so far; 0 after init / reset. */
+int rtProgressiveSamples(void);
+/* The next runRendererProgressive starts again at sample 0. */
+void rtResetProgressive(void);
+/* Replaces the camera for the following frames (runRenderer and passes) without re-uploading the scene; resets the progressive frame. */
+void setCamera(const rt_camera* cam);
+
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };
