@@ -323,17 +323,7 @@ __device__ __forceinline__ void job_start(const RtMeshParams& P, Job& J, f3 org,
 // LEAN (the launcher's promise: every material is RT_DIFFUSE / RT_METAL / RT_GLASS without a texture - what scene_materials.h:13-20 at HEAD can produce -, no
 // floor plane, pair rounds available): PROCESS without the preset tables, textures and the plane, no (u, v) carried through the traversal - fewer registers,
 // so more waves per SIMD (RT_MESH_LEAN_WAVES) to hide the dependent node loads behind.
-#ifndef RT_MESH_HEAVY_CLS
-#define RT_MESH_HEAVY_CLS 5         // PHASE 2: cost classes counted as expensive (>= 1.6 x the mean pixel) and spread over the first fills (0 = off) ...
-#define RT_MESH_SPREAD_ROUNDS 2     // ... of this many times the lanes in flight.  C4, A/B in one call (profiles/r04_sweep_mesh_spread*.txt): lists as they lie 907, 5 classes over
-                                    // 1 / 2 / 3 / 5 fills 972 / 937-987 / 954 / 938, 4 classes 969 / 967, 6 classes 903 / 945, 7 classes 905-919 Msamples/s
-#endif
-#ifndef RT_MESH_CHAIN_THR
-#define RT_MESH_CHAIN_THR 448       // PHASE 2: list 0 = pixels from 16 x this many cost units per sample (the mean pixel of C4 has ~100): the chains, see "Chain waves"
-#endif
-#ifndef RT_MESH_CHAIN_LANES
-#define RT_MESH_CHAIN_LANES 6       // pixels of list 0 per chain wave (0 = no chain waves)
-#endif
+// (the second dispatch's scheduling constants - expensive classes and their spread, the list-0 threshold, chain lanes - are RtSwitches fields, rt_params.h)
 #ifndef RT_MESH_TAIL_DIAG
 #define RT_MESH_TAIL_DIAG 0
 #endif
@@ -1073,7 +1063,7 @@ static void launch_mesh_queue(dim3 grid, dim3 block, size_t lds, hipStream_t str
 //          bits 16..23 keep traversing while at least this many lanes have nodes left (0 = default: 24, classic 40);
 //          bits 24..25 traversal of the persistent kernel: 0 = thresholded while-while (default), 1 = classic while-while;
 //          bits 26..31 leaf threshold of the former (0 = default 16).
-hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream) {
+hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
     if ((variant & 0xFF) == 1) {
         const dim3 grid((p.nx + 8 * kWavesPerWg - 1) / (8 * kWavesPerWg), (p.part.local_rows + 7) / 8);
         hipLaunchKernelGGL(k_render_mesh<0>, grid, dim3(kThreads), 0, stream, p);
@@ -1087,8 +1077,7 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     int wg_per_cu = (variant >> 8) & 0xFF;
     const bool classic0 = ((variant >> 24) & 3) == 1;
-    static const bool lean_env = !(getenv("RT_MESH_LEAN") && getenv("RT_MESH_LEAN")[0] == '0');          // A/B: RT_MESH_LEAN=0 keeps the general kernel
-    const bool lean = lean_env && !classic0 && !p.dbg && !p.counters && p.lean_ok && !p.floor_on && p.leaf_sentinels_trailing && p.leaf_ofs && p.leaf_tri &&
+    const bool lean = sw.mesh_lean && !classic0 && !p.dbg && !p.counters && p.lean_ok && !p.floor_on && p.leaf_sentinels_trailing && p.leaf_ofs && p.leaf_tri &&
                       p.nppl >= 1u && p.nppl <= 16u && p.first_leaf <= kLeafCntLds;
     if (wg_per_cu == 0) wg_per_cu = lean ? RT_MESH_LEAN_WAVES : (classic0 ? 5 : 4);   // = the launch bounds (96 / 128 VGPRs); the pair rounds spill at 96      // launch bound: 5 waves per SIMD (96 VGPRs); 6 gave the same rate, 8 spills
     const long long total_px = (long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64;
@@ -1097,13 +1086,7 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
     if (blocks > useful) blocks = useful;
     if (blocks < 1) blocks = 1;
     uint32_t stride = 1;
-    static const bool tile_order = getenv("RT_MESH_ORDER") && getenv("RT_MESH_ORDER")[0] == 't';       // A/B: tile-major pixel order (stride 1)
-    if (total_px > 64 && !tile_order) {
-        auto gcd = [](unsigned long long a, unsigned long long b) { while (b) { const unsigned long long t = a % b; a = b; b = t; } return a; };
-        unsigned long long cand = (unsigned long long)((double)total_px * 0.6180339887) | 1ull;
-        while (gcd(cand, (unsigned long long)total_px) != 1ull) cand += 2;
-        stride = (uint32_t)(cand % (unsigned long long)total_px);
-    }
+    if (total_px > 64 && !sw.mesh_tile_order) stride = rt_coprime_stride((unsigned long long)total_px);
     const bool classic = ((variant >> 24) & 3) == 1;
     int min_traversing = (variant >> 16) & 0xFF;
     if (min_traversing == 0) min_traversing = classic ? kMinTraversing : 24;    // measured: 16 -> 409, 20 -> 435, 24 -> 446, 32 -> 429 Msamples/s
@@ -1116,23 +1099,17 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
     // the counting instantiation (STATS: the reference's ray statistics as device atomics) runs only when counters are asked for
     // The cost-ordered frame in two dispatches (template parameter PHASE): reference RNG stream, no diagnostics, enough samples for the first few to be a small part.
     // RT_MESH_TWO=0: the single scattered dispatch (A/B); RT_MESH_SPLIT=<n>: samples of the first dispatch.
-    static const bool two_env = !(getenv("RT_MESH_TWO") && getenv("RT_MESH_TWO")[0] == '0');
-    static const int split_env = getenv("RT_MESH_SPLIT") ? atoi(getenv("RT_MESH_SPLIT")) : 2;      // (1: 903, 2: 911, 4: 893, 8: 866 Msamples/s on C4, profiles/r04_ab_mesh_two_b.txt)
-    const int split = split_env < 1 ? 1 : split_env;
+    const int split = sw.mesh_split;
     // (a continuation pass of a progressive frame, p.acc_first > 0, takes the single dispatch: PHASE 0 resumes every pixel from p.acc_state)
-    if (two_env && !classic && !p.dbg && !p.counters && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.px_state && p.px_rays && p.order && p.ord_state && p.ord_rays &&
+    if (sw.mesh_two && !classic && !p.dbg && !p.counters && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.px_state && p.px_rays && p.order && p.ord_state && p.ord_rays &&
         p.acc_first == 0 && p.ns >= 4 * split && p.nx <= 65535 && p.part.local_rows <= 65535) {
         RtMeshParams q = p;
         q.s_split = split;
         // (p.p1_segments: the first dispatch scatters row segments of 8 pixels - `stride` coprime with total / 8, flag in bit 8 of min_traversing)
         uint32_t stride1 = stride;
         int mt1 = min_traversing;
-        if (p.p1_segments && total_px > 512 && !tile_order) {
-            auto gcd = [](unsigned long long a, unsigned long long b) { while (b) { const unsigned long long t = a % b; a = b; b = t; } return a; };
-            const unsigned long long segs = (unsigned long long)total_px >> 3;
-            unsigned long long cand = (unsigned long long)((double)segs * 0.6180339887) | 1ull;
-            while (gcd(cand, segs) != 1ull) cand += 2;
-            stride1 = (uint32_t)(cand % segs);
+        if (p.p1_segments && total_px > 512 && !sw.mesh_tile_order) {
+            stride1 = rt_coprime_stride((unsigned long long)total_px >> 3);
             mt1 |= 256;
         }
         if (lean) launch_mesh_queue<0, false, false, true, 1>(grid, block, lds, stream, q, stride1, mt1, leaf_thr);
@@ -1143,19 +1120,13 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
         if (e != hipSuccess) return e;
         RtSphereParams o;                                            // what the ordering pass reads (rt_params.h: rt_order_pixels_by_cost)
         memset(&o, 0, sizeof o);
-        const int chain_thr_env = getenv("RT_MESH_CHAIN_THR") ? atoi(getenv("RT_MESH_CHAIN_THR")) : RT_MESH_CHAIN_THR;
-        const int chain_lanes_env = getenv("RT_MESH_CHAIN_LANES") ? atoi(getenv("RT_MESH_CHAIN_LANES")) : RT_MESH_CHAIN_LANES;
-        o.nx = p.nx; o.ny = p.ny; o.part = p.part; o.s_split = split; o.chain_top_thr = chain_thr_env < 17 ? 17 : chain_thr_env;
+        o.nx = p.nx; o.ny = p.ny; o.part = p.part; o.s_split = split; o.chain_top_thr = sw.mesh_chain_thr;
         o.px_rays = p.px_rays; o.px_state = p.px_state; o.order = p.order; o.ord_state = p.ord_state; o.ord_rays = p.ord_rays; o.queue = p.queue;
         o.ord_rec = p.ord_rec; o.xcd_queues = p.xcd_queues;
         e = rt_order_pixels_by_cost(o, stream);
         if (e != hipSuccess) return e;
-        static const bool rev_env = getenv("RT_MESH_REV") && getenv("RT_MESH_REV")[0] == '1';       // experiment: cheapest pixels first
-        static const int heavy_env = getenv("RT_MESH_HEAVY") ? atoi(getenv("RT_MESH_HEAVY")) : RT_MESH_HEAVY_CLS;       // expensive classes spread over the first fills
-        static const int rounds_env = getenv("RT_MESH_ROUNDS") ? atoi(getenv("RT_MESH_ROUNDS")) : RT_MESH_SPREAD_ROUNDS;
-        const uint32_t stride2 = rev_env ? 0xFFFFFFFFu : stride;
-        const int chain_frac = getenv("RT_MESH_CHAIN_FRAC") ? (atoi(getenv("RT_MESH_CHAIN_FRAC")) & 0xF) : 8;     // chain waves only while list 0 is below pixels >> this (tests: 0)
-        const int lt2 = leaf_thr | ((heavy_env & 0xF) << 8) | ((rounds_env & 0xF) << 12) | ((chain_lanes_env < 0 ? 0 : chain_lanes_env > 64 ? 64 : chain_lanes_env) << 16) | (chain_frac << 24);
+        const uint32_t stride2 = sw.mesh_rev ? 0xFFFFFFFFu : stride;
+        const int lt2 = leaf_thr | ((sw.mesh_heavy & 0xF) << 8) | ((sw.mesh_rounds & 0xF) << 12) | (sw.mesh_chain_lanes << 16) | (sw.mesh_chain_frac << 24);
 #if RT_MESH_TAIL_DIAG
         static uint32_t* d_items = nullptr; const size_t n_px = (size_t)p.part.local_rows * p.nx;
         if (!d_items) { (void)hipMalloc(&d_items, n_px * 8); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_diag_items), &d_items, sizeof d_items); }
@@ -1168,8 +1139,8 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, hipStream_t stream
           unsigned q4[2]; (void)hipMemcpy(q4, p.queue + 4, 4, hipMemcpyDeviceToHost); fprintf(stderr, "list 0: %u pixels; ", q4[0]);
           fprintf(stderr, "mesh tail diag: queue empty at %.1f ms, last wave ends at %.1f ms, mean wave life %.1f ms (%u waves)\n", (double)(r[0] - r[1]) * 1e-5, (double)(r[2] - r[1]) * 1e-5,
                   (double)r[3] * 1e-5 / ((double)grid.x * (block.x / 64)), grid.x * (block.x / 64));
-          if (const char* f = getenv("RT_MESH_DIAG_FILE")) { std::vector<uint32_t> h(n_px * 3); (void)hipMemcpy(h.data(), d_items, n_px * 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(h.data() + n_px * 2, p.px_rays, n_px * 4, hipMemcpyDeviceToHost); if (FILE* o = fopen(f, "wb")) { fwrite(h.data(), 4, h.size(), o); fclose(o); } } }
+          if (sw.mesh_diag_file) { std::vector<uint32_t> h(n_px * 3); (void)hipMemcpy(h.data(), d_items, n_px * 8, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(h.data() + n_px * 2, p.px_rays, n_px * 4, hipMemcpyDeviceToHost); if (FILE* o = fopen(sw.mesh_diag_file->c_str(), "wb")) { fwrite(h.data(), 4, h.size(), o); fclose(o); } } }
 #endif
         return hipGetLastError();
     }

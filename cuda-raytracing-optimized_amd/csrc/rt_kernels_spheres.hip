@@ -61,10 +61,6 @@ using namespace rtd;
 
 namespace {
 
-#ifndef RT_MID_WAVES
-#define RT_MID_WAVES 0      // middle tier: waves per workgroup (0 = off) and pixels per such wave
-#define RT_MID_CAP 16
-#endif
 #ifndef RT_BOX_CUT
 #define RT_BOX_CUT 12       // group_needs_cells: the per-lane box loop stops when fewer lanes than this still have candidates (A/B on C5 at 256 spp, profiles/r04_ab_basic_c5.txt:
                             // 1 (never): 10870, 8: 10930, 12: 10945, 20: 10945 Msamples/s)
@@ -1862,21 +1858,23 @@ static hipError_t launch_queue_kernel_global(const RtSphereParams& q, unsigned b
     return launch_sphere_queue(SphereQueueForm<0, 0, CHUNKED, false, 1>{}, q, blocks, kThreads, lds, stream, stride, cfg, chain_cfg, 0x4444, false);
 }
 
-static int g_queue_threads = kThreads;      // workgroup size of the persistent kernel for the scene being launched (launch_spheres: 16 waves, or 8 when only that fits)
-
-static int g_lean_dbg = 0;                  // the kind the scene would take without the diagnostics (time lines of the production kernel)
-static int g_lean = 0;                      // LEAN bits of the instantiation launch_spheres chose for the scene being launched (0 = the general kernel)
+// The persistent kernel's form for the scene being launched, as launch_spheres chose it.
+struct QueueShape {
+    int lean;           // LEAN bits of the instantiation (0 = the general kernel)
+    int lean_dbg;       // the kind the scene would take without the diagnostics (time lines of the production kernel)
+    int threads;        // workgroup size (16 waves, 12 for the six-wave kinds, or 8 when only that fits)
+};
 
 template <int PHASE, int CLS, bool CHUNKED, int SCENE>
-static hipError_t launch_queue_kernel_scene(const RtSphereParams& q, unsigned blocks, size_t lds, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps) {
-    // (the diagnostic instantiation - counters, the reference's ray statistics, time stamps - is the general kernel: launch_spheres leaves g_lean at 0 for it)
+static hipError_t launch_queue_kernel_scene(const RtSphereParams& q, QueueShape shape, unsigned blocks, size_t lds, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps) {
+    // (the diagnostic instantiation - counters, the reference's ray statistics, time stamps - is the general kernel: launch_spheres leaves lean at 0 for it)
     const bool counting = q.wave_dbg != nullptr || q.counters != nullptr;
-    auto go = [&](auto form) -> hipError_t { return launch_sphere_queue(form, q, blocks, g_queue_threads, lds, stream, stride, cfg, chain_cfg, caps, true); };
+    auto go = [&](auto form) -> hipError_t { return launch_sphere_queue(form, q, blocks, shape.threads, lds, stream, stride, cfg, chain_cfg, caps, true); };
     // (time lines of the PRODUCTION kernel of the benchmark scene - RT_WAVE_DEBUG with RT_WAVE_DEBUG_LIGHT=1, no counters: the lean kind 3 with the stamps)
-    if (counting && q.counters == nullptr && SCENE == 0 && !CHUNKED && PHASE != 0 && g_lean_dbg == 3) return go(SphereQueueForm<PHASE, CLS, false, true, 0, 3>{});
+    if (counting && q.counters == nullptr && SCENE == 0 && !CHUNKED && PHASE != 0 && shape.lean_dbg == 3) return go(SphereQueueForm<PHASE, CLS, false, true, 0, 3>{});
     if (counting) return go(SphereQueueForm<PHASE, CLS, CHUNKED, true, SCENE>{});
     if (SCENE == 0 && CHUNKED) {                                     // the sample chunks of the counter stream: the kinds of the benchmark's shape
-        switch (g_lean) {
+        switch (shape.lean) {
         case 1:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 1>{});
         case 3:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 3>{});
         case 7:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 7>{});
@@ -1884,7 +1882,7 @@ static hipError_t launch_queue_kernel_scene(const RtSphereParams& q, unsigned bl
         }
     }
     if (SCENE == 0 && !CHUNKED) {
-        switch (g_lean) {
+        switch (shape.lean) {
         case 1:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 1>{});
         case 3:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 3>{});
         case 7:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 7>{});
@@ -1898,7 +1896,7 @@ static hipError_t launch_queue_kernel_scene(const RtSphereParams& q, unsigned bl
         }
     }
     if (SCENE == 2 && !CHUNKED) {                                    // the hybrid scene copy (hit data in global memory: ~1500-3400 spheres)
-        switch (g_lean) {
+        switch (shape.lean) {
         case 1:  return go(SphereQueueForm<PHASE, CLS, false, false, 2, 1>{});
         case 35: return go(SphereQueueForm<PHASE, CLS, false, false, 2, 35>{});
         case 43: return go(SphereQueueForm<PHASE, CLS, false, false, 2, 43>{});
@@ -1910,22 +1908,22 @@ static hipError_t launch_queue_kernel_scene(const RtSphereParams& q, unsigned bl
 
 // `hybrid`: stage_scene's form 2 (test data in the LDS, hit data in global memory)
 template <int PHASE, int CLS, bool CHUNKED>
-static hipError_t launch_queue_kernel(const RtSphereParams& q, unsigned blocks, size_t lds, bool hybrid, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps = 0x4444) {
-    return hybrid ? launch_queue_kernel_scene<PHASE, CLS, CHUNKED, 2>(q, blocks, lds, stream, stride, cfg, chain_cfg, caps)
-                  : launch_queue_kernel_scene<PHASE, CLS, CHUNKED, 0>(q, blocks, lds, stream, stride, cfg, chain_cfg, caps);
+static hipError_t launch_queue_kernel(const RtSphereParams& q, QueueShape shape, unsigned blocks, size_t lds, bool hybrid, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps = 0x4444) {
+    return hybrid ? launch_queue_kernel_scene<PHASE, CLS, CHUNKED, 2>(q, shape, blocks, lds, stream, stride, cfg, chain_cfg, caps)
+                  : launch_queue_kernel_scene<PHASE, CLS, CHUNKED, 0>(q, shape, blocks, lds, stream, stride, cfg, chain_cfg, caps);
 }
 
-static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream_t stream);
+static hipError_t launch_spheres(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream);
 
-hipError_t RT_LAUNCH_NAME(const RtSphereParams& p, int variant, hipStream_t stream) {
+hipError_t RT_LAUNCH_NAME(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
     // p.self: the device copy of the parameter block, owned and refreshed by the renderer (one per device state and frame).  Only fields that are
     // the same for the whole frame of that device state (camera, image size, RNG mode) are read through it.  (Reading the per-pixel fields -
     // framebuffer, parked state, partition - this way too took the kernel from 61 to 43 spilled SGPRs and gained nothing more: 7030 against 7025 Msamples/s.)
     if (!p.self) return hipErrorInvalidValue;
-    return launch_spheres(p, variant, stream);
+    return launch_spheres(p, variant, sw, stream);
 }
 
-static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream_t stream) {
+static hipError_t launch_spheres(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
     // p.poison_fb: a single-dispatch frame is preceded by k_poison_fb on the same stream; the two-dispatch frame lets its first dispatch do it
     auto wait_fb = [&]() -> hipError_t {
         if (!p.poison_fb) return hipSuccess;
@@ -1950,30 +1948,26 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
     // throughput or its slowest pixels allow, whichever is longer, and the slowest pixels (6-12 rays per sample in dense waves, one ray per iteration) get
     // slower with every wave that shares the SIMD; both scale with spp, so the pixel count decides: 1920x1080 -4 %, 2560x1440 +9 %, 3200x1800 +10 %
     // (profiles/r04_ab_lean6_sizes.txt).  RT_BASIC=0 / RT_ONEPASS=0 / RT_LEAN6_PIXELS=<n> (0 = never): A/B.
-    static const bool basic_env = !(getenv("RT_BASIC") && getenv("RT_BASIC")[0] == '0');
-    static const bool onepass_env = !(getenv("RT_ONEPASS") && getenv("RT_ONEPASS")[0] == '0');
-    static const long long lean6_pixels = getenv("RT_LEAN6_PIXELS") ? atoll(getenv("RT_LEAN6_PIXELS")) : 2600000ll;
     const bool counting = p.wave_dbg != nullptr || p.counters != nullptr;
-    g_lean = 0;
+    int lean = 0;
     int lean_wgs = 1;
-    g_lean_dbg = 0;
-    if (kind == 0 && !p.global_scene && p.basic_materials && basic_env) {
+    int lean_dbg = 0;
+    if (kind == 0 && !p.global_scene && p.basic_materials && sw.basic) {
         const int n_small_groups = p.n_groups - p.n_big_groups;
-        g_lean = 1;
-        if (cull && p.cell_on != 0 && n_small_groups >= 1 && n_small_groups <= 128 && onepass_env) {
-            g_lean |= 2;                                                         // one list per ray batch
-            if (n_small_groups > 64) g_lean |= 32;                               // ... of four words
-            else if (n_small_groups > 32) g_lean |= 16;                          // ... of two
-            if (p.box_shared_axis != 2) g_lean |= 8;                             // no shared vertical extent: the 3-axis prefilter
+        lean = 1;
+        if (cull && p.cell_on != 0 && n_small_groups >= 1 && n_small_groups <= 128 && sw.onepass) {
+            lean |= 2;                                                           // one list per ray batch
+            if (n_small_groups > 64) lean |= 32;                                 // ... of four words
+            else if (n_small_groups > 32) lean |= 16;                            // ... of two
+            if (p.box_shared_axis != 2) lean |= 8;                               // no shared vertical extent: the 3-axis prefilter
         }
     }
-    if (p.chunks > 1 && g_lean != 1 && g_lean != 3) g_lean &= 1;             // (sample chunks: kinds 1, 3 and 7 are built)
-    static const bool dbg_light_env = getenv("RT_WAVE_DEBUG_LIGHT") && getenv("RT_WAVE_DEBUG_LIGHT")[0] == '1';
+    if (p.chunks > 1 && lean != 1 && lean != 3) lean &= 1;                       // (sample chunks: kinds 1, 3 and 7 are built)
     // (only a frame that takes the two cost-ordered dispatches: its two kernels are the ones instantiated with the stamps)
     const bool two_phase_frame = ((variant >> 24) & 3) == 0 && p.order && p.px_state && p.px_rays && p.chunks == 1 && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.ns >= 8 &&
                                  p.nx <= 65535 && p.part.local_rows <= 65535;
-    if (counting) { g_lean_dbg = (g_lean == 3 && p.counters == nullptr && dbg_light_env && two_phase_frame) ? 3 : 0; g_lean = g_lean_dbg == 3 ? 3 : 0; }
-    const bool lean_list = (g_lean & 2) != 0;                                    // (the smaller per-wave scratch)
+    if (counting) { lean_dbg = (lean == 3 && p.counters == nullptr && sw.wave_debug_light && two_phase_frame) ? 3 : 0; lean = lean_dbg == 3 ? 3 : 0; }
+    const bool lean_list = (lean & 2) != 0;                                      // (the smaller per-wave scratch)
     // The persistent kernel's workgroup is a whole CU's worth of waves (16: the launch bound's 4 per SIMD) around ONE scene copy - 88 KB of per-wave scratch (68
     // in the one-list kernels) leave 72 (92) KB for the scene: the full copy up to ~1200 (1500) spheres (60 bytes per sphere), the hybrid one (what a sphere TEST
     // reads in the LDS, what only a HIT reads in global memory: 21 bytes per sphere) up to ~3400; an 8-wave workgroup (44 KB of scratch, 2 waves per SIMD) keeps
@@ -1984,15 +1978,15 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
         if (lds_bytes(p.n_padded, p.n, false, 0, 16, lean_list) <= kLdsPerCu) { hybrid = false; waves = 16; }
         else {                                                                   // hybrid: the lean kinds built for it are 1 and the four-word lists
             hybrid = true;
-            if (g_lean != 1 && (g_lean & 32) == 0) g_lean &= 1;
-            if (lds_bytes(p.n_padded, p.n, false, 2, 16, (g_lean & 2) != 0) <= kLdsPerCu) waves = 16;
+            if (lean != 1 && (lean & 32) == 0) lean &= 1;
+            if (lds_bytes(p.n_padded, p.n, false, 2, 16, (lean & 2) != 0) <= kLdsPerCu) waves = 16;
             else { waves = 8; }
         }
     }
-    if ((g_lean & 0x32) == 2 && lean6_pixels > 0 && (long long)p.nx * p.part.local_rows >= lean6_pixels &&
-        2 * (lds_bytes(p.n_padded, p.n, false, 0, 12, true) + kStaticLds) <= (size_t)160 * 1024) { g_lean |= 4; waves = 12; lean_wgs = 2; }
-    g_queue_threads = 64 * waves;
-    const size_t lds = kind == 1 ? lds_bytes(p.n_padded, p.n, true, 0, kWavesPerWg) : lds_bytes(p.n_padded, p.n, false, hybrid ? 2 : 0, waves, (g_lean & 2) != 0);
+    if ((lean & 0x32) == 2 && sw.lean6_pixels > 0 && (long long)p.nx * p.part.local_rows >= sw.lean6_pixels &&
+        2 * (lds_bytes(p.n_padded, p.n, false, 0, 12, true) + kStaticLds) <= (size_t)160 * 1024) { lean |= 4; waves = 12; lean_wgs = 2; }
+    const QueueShape shape = { lean, lean_dbg, 64 * waves };
+    const size_t lds = kind == 1 ? lds_bytes(p.n_padded, p.n, true, 0, kWavesPerWg) : lds_bytes(p.n_padded, p.n, false, hybrid ? 2 : 0, waves, (lean & 2) != 0);
     // bits 27..29: extra sparse-form rays per iteration for lanes on a long chain (0 = default 2, 7 = off)
     const int pb = (variant >> 27) & 7;
     // bits 30..31: a wave switches to the sparse form at <= 4 / 8 / 12 / 16 live rays (0 = default)
@@ -2025,7 +2019,7 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
     if (wg_per_cu == 0) wg_per_cu = lean_wgs;   // one workgroup = the residency the kernel's launch bound (4 waves/SIMD, 128 VGPRs) and the LDS allow; the lean kernel: two of 10 waves
     const long long total_px = (long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64;
     long long blocks = (long long)cus * wg_per_cu;
-    const long long useful = (total_px + g_queue_threads - 1) / g_queue_threads;      // never more lanes than pixels
+    const long long useful = (total_px + shape.threads - 1) / shape.threads;          // never more lanes than pixels
     if (blocks > useful) blocks = useful;
     if (blocks < 1) blocks = 1;
     // scattered order: stride ~ 0.618 * total, coprime with total
@@ -2033,14 +2027,8 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
     int order_mode = (variant >> 24) & 3;
     // Scenes whose hit data (hybrid copy) or whole scene (global) is read from global memory: the scattered single dispatch beats the cost-ordered two
     // dispatches (tools/sweep_scene_sizes.py, 1200x800x50, 16-wave workgroups: 1500 spheres 2819 against 2751, 2000: 2113 / 1696, 2600: 1812 / 1149).
-    static const bool hybrid_two = getenv("RT_HYBRID_TWO") && getenv("RT_HYBRID_TWO")[0] == '1';      // A/B: the cost-ordered two dispatches for the hybrid copy too
-    if (order_mode == 0 && ((hybrid && !hybrid_two) || p.global_scene)) order_mode = 2;
-    if (order_mode != 1 && total_px > 64) {
-        auto gcd = [](unsigned long long a, unsigned long long b) { while (b) { const unsigned long long t = a % b; a = b; b = t; } return a; };
-        unsigned long long cand = (unsigned long long)((double)total_px * 0.6180339887) | 1ull;
-        while (gcd(cand, (unsigned long long)total_px) != 1ull) cand += 2;
-        stride = (uint32_t)(cand % (unsigned long long)total_px);
-    }
+    if (order_mode == 0 && ((hybrid && !sw.hybrid_two) || p.global_scene)) order_mode = 2;
+    if (order_mode != 1 && total_px > 64) stride = rt_coprime_stride((unsigned long long)total_px);
     // chain waves: wave 0 of every workgroup (512 waves) serves the chain lists, kSparseRays pixels to a wave; lanes of
     // normal waves above 10 rays per sample are boosted.  Measured on C2 (flat basin) with the multi-ray sparse form:
     // 512 waves x 4 pixels 5780, x 3: 5740, x 2: 5720; 1024 waves x 2: 5610 Msamples/s (before it: 256 x 4: 5040, 512 x 2: 5540).
@@ -2051,36 +2039,31 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
     // basin: 768 waves, list 0 from 20..26 rays per sample, 2..4 pixels for the other lists all within 0.5 %; 1024 waves -2 %, list 0 from 30: -6 %).
     int chain_cfg = 1 | ((waves == 16 ? 3 : (waves >= 10 ? 2 : 1)) << 8) | (kSparseRays << 12) | (8 << 16) | (kChainClasses << 24);
     int caps = 1 | (4 << 4) | (4 << 8) | (4 << 12);     // pixels a chain wave holds while one of them comes from chain list 0 / 1 / 2 / 3
-    static const char* mid_env = getenv("RT_MID");       // "waves per workgroup,pixels per wave" of the middle tier (k_render_spheres_queue, role 1); 0 = off
-    int mid_waves = RT_MID_WAVES, mid_cap = RT_MID_CAP;
-    if (mid_env) sscanf(mid_env, "%d,%d", &mid_waves, &mid_cap);
-    if (mid_waves < 0 || mid_waves > 12 || mid_cap < 1 || mid_cap > 64) return hipErrorInvalidValue;
-    const int caps_mid = (mid_waves << 16) | (mid_cap << 20);
+    if (sw.mid_waves < 0 || sw.mid_waves > 12 || sw.mid_cap < 1 || sw.mid_cap > 64) return hipErrorInvalidValue;        // (the middle tier, RT_MID)
+    const int caps_mid = (sw.mid_waves << 16) | (sw.mid_cap << 20);
     caps |= caps_mid;
     int cfg = cull | (boost << 8) | (sparse_max << 16);
-    static const bool chain_single = !(getenv("RT_CHAIN_SINGLE") && getenv("RT_CHAIN_SINGLE")[0] == '0');  // chain waves grab one pixel at a time
-    static const bool single_ray = !(getenv("RT_SINGLE_RAY") && getenv("RT_SINGLE_RAY")[0] == '0');          // scan_single for waves with one live ray
     // phase 2: a normal wave reserves at least 8 queue positions per grab (one atomic round trip per ~6 finished pixels instead of per ~1: +1.3 % on C2;
     // 16 and more hoard pixels at the end of the frame and lose: 8 -> 7144, 16 -> 6616, 32 -> 6019 Msamples/s, profiles/r03_sweep_pool.txt)
-    static const int pool_env = getenv("RT_POOL") ? atoi(getenv("RT_POOL")) : 4;      // (round 4, lean kernel: 4 -> 8517, 8 -> 8420, 16 -> 8110 Msamples/s, profiles/r04_sweep_tune_c2.txt)
-    if (chain_single) cfg |= 2;
-    if (single_ray) cfg |= 4;
-    cfg |= ((pool_env / 4) & 0x1F) << 3;
-    static const bool dbg_light = getenv("RT_WAVE_DEBUG_LIGHT") && getenv("RT_WAVE_DEBUG_LIGHT")[0] == '1';
-    if (dbg_light) cfg |= 1 << 29;
-    if (const char* t = getenv("RT_TUNE")) {        // experiments: "chain_every,chain_waves,heavy_thr,n_chain,boost,chain_pixels,chain_pixels of list 0,1,2"
-        int a = 1, b = waves == 16 ? 3 : 1, c = 8, d = kChainClasses, e2 = boost, f = kSparseRays, g = 1, g1 = 4, g2 = 4;
-        sscanf(t, "%d,%d,%d,%d,%d,%d,%d,%d,%d", &a, &b, &c, &d, &e2, &f, &g, &g1, &g2);
+    // (RT_POOL, round 4, lean kernel: 4 -> 8517, 8 -> 8420, 16 -> 8110 Msamples/s, profiles/r04_sweep_tune_c2.txt)
+    if (sw.chain_single) cfg |= 2;
+    if (sw.single_ray) cfg |= 4;
+    cfg |= ((sw.pool / 4) & 0x1F) << 3;
+    if (sw.wave_debug_light) cfg |= 1 << 29;
+    if (sw.tune) {        // experiments: "chain_every,chain_waves,heavy_thr,n_chain,boost,chain_pixels,chain_pixels of list 0,1,2"
+        int v[9] = { 1, waves == 16 ? 3 : 1, 8, kChainClasses, boost, kSparseRays, 1, 4, 4 };      // the fields not given
+        for (int i = 0; i < sw.tune->n; i++) v[i] = sw.tune->v[i];
+        const int a = v[0], b = v[1], c = v[2], d = v[3], e2 = v[4], f = v[5], g = v[6], g1 = v[7], g2 = v[8];
         // every field is a bit-field of chain_cfg / cfg and some are divisors or loop bounds in the kernel: refuse what does not fit
         if (a < 1 || a > 255 || b < 0 || b > waves || c < 1 || c > 255 || d < 0 || d > 15 || e2 < 0 || e2 > 255 ||
             f < 1 || f > 15 || g < 1 || g > 15 || g1 < 1 || g1 > 15 || g2 < 1 || g2 > 15) {
             fprintf(stderr, "rt error: RT_TUNE=%s out of range (chain_every 1..255, chain_waves 0..%d, heavy_thr 1..255, n_chain 0..15, boost 0..255, "
-                            "chain_pixels 1..15, chain_pixels of list 0 / 1 / 2 1..15)\n", t, kWavesPerWg);
+                            "chain_pixels 1..15, chain_pixels of list 0 / 1 / 2 1..15)\n", sw.tune->text.c_str(), kWavesPerWg);
             return hipErrorInvalidValue;
         }
         chain_cfg = a | (b << 8) | (f << 12) | (c << 16) | (d << 24);
         caps = g | (g1 << 4) | (g2 << 8) | (f << 12) | caps_mid;
-        cfg = cull | (e2 << 8) | (sparse_max << 16) | (chain_single ? 2 : 0) | (single_ray ? 4 : 0) | (((pool_env / 4) & 0x1F) << 3) | (dbg_light ? (1 << 29) : 0);
+        cfg = cull | (e2 << 8) | (sparse_max << 16) | (sw.chain_single ? 2 : 0) | (sw.single_ray ? 4 : 0) | (((sw.pool / 4) & 0x1F) << 3) | (sw.wave_debug_light ? (1 << 29) : 0);
     }
     const unsigned nb = (unsigned)blocks;
     const unsigned cls_blocks = (unsigned)((total_px + kThreads - 1) / kThreads);
@@ -2119,14 +2102,10 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
             int cfg1 = cfg;
             if (q.p1_tile_major == 1) stride1 = 1u;
             if (q.p1_tile_major == 2 && total_px > 512) {
-                auto gcd = [](unsigned long long a, unsigned long long b) { while (b) { const unsigned long long t = a % b; a = b; b = t; } return a; };
-                const unsigned long long segs = (unsigned long long)total_px >> 3;
-                unsigned long long cand = (unsigned long long)((double)segs * 0.6180339887) | 1ull;
-                while (gcd(cand, segs) != 1ull) cand += 2;
-                stride1 = (uint32_t)(cand % segs);
+                stride1 = rt_coprime_stride((unsigned long long)total_px >> 3);
                 cfg1 |= 1 << 30;
             }
-            e = launch_queue_kernel<1, 0, false>(q, nb, lds, hybrid, stream, stride1, cfg1, chain_cfg);
+            e = launch_queue_kernel<1, 0, false>(q, shape, nb, lds, hybrid, stream, stride1, cfg1, chain_cfg);
             if (e != hipSuccess) return e;
         }
         e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords, stream);
@@ -2136,9 +2115,8 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
         e = hipGetLastError();
         if (e != hipSuccess) return e;
         q.phase = 2;
-        static const bool dbg_phase1 = getenv("RT_WAVE_DEBUG_PHASE") && getenv("RT_WAVE_DEBUG_PHASE")[0] == '1';      // diagnostics: the time line of the FIRST dispatch
-        if (dbg_phase1) q.wave_dbg = nullptr;
-        return launch_queue_kernel<2, 2, false>(q, nb, lds, hybrid, stream, stride, cfg, chain_cfg, caps);
+        if (sw.wave_debug_phase) q.wave_dbg = nullptr;                  // diagnostics: the time line of the FIRST dispatch
+        return launch_queue_kernel<2, 2, false>(q, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg, caps);
     }
     bool classified = false;
     if ((order_mode == 0 || order_mode == 3) && p.order != nullptr) {
@@ -2156,8 +2134,8 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, hipStream
     const bool chunked = p.chunks > 1;
     e = wait_fb();
     if (e != hipSuccess) return e;
-    if (classified) e = chunked ? launch_queue_kernel<0, 1, true>(p, nb, lds, hybrid, stream, stride, cfg, chain_cfg) : launch_queue_kernel<0, 1, false>(p, nb, lds, hybrid, stream, stride, cfg, chain_cfg);
-    else e = chunked ? launch_queue_kernel<0, 0, true>(p, nb, lds, hybrid, stream, stride, cfg, chain_cfg) : launch_queue_kernel<0, 0, false>(p, nb, lds, hybrid, stream, stride, cfg, chain_cfg);
+    if (classified) e = chunked ? launch_queue_kernel<0, 1, true>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg) : launch_queue_kernel<0, 1, false>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg);
+    else e = chunked ? launch_queue_kernel<0, 0, true>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg) : launch_queue_kernel<0, 0, false>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg);
     if (e != hipSuccess) return e;
     if (chunked) {
         const size_t npx = (size_t)p.part.local_rows * p.nx;

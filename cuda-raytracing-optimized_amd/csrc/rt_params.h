@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <optional>
+#include <string>
+
 #include "../../include/rt_types.h"
 #include "../../include/rt_api.h"
 
@@ -201,12 +204,77 @@ size_t rt_sphere_kernel_lds_bytes(int n_padded, int n);
 // list lengths into q.queue[4..]; q.queue must have been zeroed on `stream` before.
 hipError_t rt_order_pixels_by_cost(const RtSphereParams& q, hipStream_t stream);
 
-// Each returns the hipError_t of the launch.  `variant` selects a kernel variant (0 = default).
+// RT_TUNE as given: its text (for the error message) and its first n comma-separated fields; the sphere launcher puts them over its defaults and validates.
+struct RtTune {
+    std::string text;
+    int n = 0;
+    int v[9] = {};
+};
+
+// The library's environment switches (A/B measurements and diagnostics), host only.  rt_read_switches() (rt_renderer.hip) is the one
+// reader: render_frame (a frame of runRenderer, a pass of runRendererProgressive) reads them once at its start and hands that copy to the launchers, so a
+// switch holds for a whole frame or pass and a change takes effect from the next one; initRendererSpheres, setExternalFramebuffer and cleanupRenderer read the fields they use the same way.  The initialisers are the
+// defaults (DESIGN.md names the measurement behind each); the reader applies the clamps.
+struct RtSwitches {
+    // the two-dispatch frames of both kernels
+    bool xcd_queues = true;             // RT_XCD_QUEUES=0: one set of cost lists and queue counters for the machine instead of one per XCD
+    bool ord_packed = true;             // RT_ORD_PACKED=0: the parked state in three arrays instead of one 32-byte record per queue position
+    int p1_tile = 2;                    // RT_P1_TILE: first dispatch 0 scattered, 1 tile-major (spheres only), 2 scattered row segments (out of 0..2: 0)
+    std::optional<std::string> wave_debug;      // RT_WAVE_DEBUG=<file>: the diagnostic instantiation, per-wave time stamps / phase counters -> file
+    // the renderer
+    bool fb_direct = false;             // RT_FB_DIRECT: sphere scenes deliver finished pixels straight into the pinned host framebuffer
+    bool fb_poison = true;              // RT_FB_POISON=0: ... without NaN-poisoning it first
+    bool box_cells = true;              // RT_BOX_CELLS=0: no cell-table prefilter (initRendererSpheres)
+    bool compact_leaves = true;         // RT_COMPACT_LEAVES=0: the mesh leaf tests read the caller's triangles
+    bool ext_fb_no_register = false;    // RT_EXT_FB_NO_REGISTER=1: setExternalFramebuffer takes its cannot-page-lock fallback
+    bool cleanup_device_reset = false;  // RT_CLEANUP_DEVICE_RESET=1: cleanupRenderer ends with hipDeviceReset
+    // the sphere launcher
+    int top_thr = 384;                  // RT_TOP_THR: 16 x rays per sample from which a pixel goes to chain list 0 (24; below 320: the default)
+    bool basic = true;                  // RT_BASIC=0 / RT_ONEPASS=0: keep the general shading code / pass loop where the lean kinds would do
+    bool onepass = true;
+    long long lean6_pixels = 2600000;   // RT_LEAN6_PIXELS: pixels per device from which the lean kernel runs six waves per SIMD (0 = never)
+    bool hybrid_two = false;            // RT_HYBRID_TWO=1: the cost-ordered two dispatches for the hybrid copy too
+    int mid_waves = 0, mid_cap = 16;    // RT_MID=waves,pixels: the middle tier (k_render_spheres_queue, role 1; 0 waves = off); the launcher validates
+    bool chain_single = true;           // RT_CHAIN_SINGLE=0: chain waves grab more than one pixel at a time
+    bool single_ray = true;             // RT_SINGLE_RAY=0: no scan_single for waves with one live ray
+    int pool = 4;                       // RT_POOL: queue positions a normal wave reserves per grab (second dispatch)
+    bool wave_debug_light = false;      // RT_WAVE_DEBUG_LIGHT=1: time stamps only (the production kernel of the benchmark scene)
+    bool wave_debug_phase = false;      // RT_WAVE_DEBUG_PHASE=1: the time line of the first dispatch instead of the second
+    std::optional<RtTune> tune;         // RT_TUNE: the chain tier's scheduling constants (experiments)
+    // the mesh launcher
+    bool mesh_lean = true;              // RT_MESH_LEAN=0: keep the general kernel
+    bool mesh_tile_order = false;       // RT_MESH_ORDER=t: tile-major pixel order (stride 1)
+    bool mesh_two = true;               // RT_MESH_TWO=0: the single scattered dispatch
+    int mesh_split = 2;                 // RT_MESH_SPLIT: samples of the first dispatch (at least 1; 1: 903, 2: 911, 4: 893, 8: 866 Msamples/s on C4,
+                                        // profiles/r04_ab_mesh_two_b.txt)
+    int mesh_heavy = 5;                 // RT_MESH_HEAVY: PHASE 2: cost classes counted as expensive (>= 1.6 x the mean pixel) and spread over the first fills
+                                        // (0 = off) ...
+    int mesh_rounds = 2;                // RT_MESH_ROUNDS: ... of this many times the lanes in flight.  C4, A/B in one call (profiles/r04_sweep_mesh_spread*.txt):
+                                        // lists as they lie 907, 5 classes over 1 / 2 / 3 / 5 fills 972 / 937-987 / 954 / 938, 4 classes 969 / 967, 6 classes
+                                        // 903 / 945, 7 classes 905-919 Msamples/s
+    bool mesh_rev = false;              // RT_MESH_REV=1: cheapest pixels first (experiment)
+    int mesh_chain_thr = 448;           // RT_MESH_CHAIN_THR: PHASE 2: list 0 = pixels from 16 x this many cost units per sample (the mean pixel of C4 has ~100):
+                                        // the chains, see "Chain waves" (at least 17)
+    int mesh_chain_lanes = 6;           // RT_MESH_CHAIN_LANES: pixels of list 0 per chain wave (0 = no chain waves; at most 64)
+    int mesh_chain_frac = 8;            // RT_MESH_CHAIN_FRAC: chain waves only while list 0 is below pixels >> this (& 0xF; tests: 0)
+    std::optional<std::string> mesh_diag_file;  // RT_MESH_DIAG_FILE=<file>: per-pixel items of the second dispatch (RT_MESH_TAIL_DIAG builds only)
+};
+RtSwitches rt_read_switches();
+
+// The golden-ratio stride of n items: ~0.618 n, coprime with n, so that i -> i * stride mod n scatters neighbouring items over different waves.
+inline uint32_t rt_coprime_stride(unsigned long long n) {
+    auto gcd = [](unsigned long long a, unsigned long long b) { while (b) { const unsigned long long t = a % b; a = b; b = t; } return a; };
+    unsigned long long cand = (unsigned long long)((double)n * 0.6180339887) | 1ull;
+    while (gcd(cand, n) != 1ull) cand += 2;
+    return (uint32_t)(cand % n);
+}
+
+// Each returns the hipError_t of the launch.  `variant` selects a kernel variant (0 = default); `sw`: the frame's switches.
 // Sphere launchers: p.self must point to a device copy of `p` that is complete on `stream` before the launch (the renderer owns it).
-hipError_t rt_launch_spheres_parity(const RtSphereParams& p, int variant, hipStream_t stream);
-hipError_t rt_launch_spheres_fast(const RtSphereParams& p, int variant, hipStream_t stream);
-hipError_t rt_launch_mesh_parity(const RtMeshParams& p, int variant, hipStream_t stream);
-hipError_t rt_launch_mesh_fast(const RtMeshParams& p, int variant, hipStream_t stream);
+hipError_t rt_launch_spheres_parity(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream);
+hipError_t rt_launch_spheres_fast(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream);
+hipError_t rt_launch_mesh_parity(const RtMeshParams& p, int variant, const RtSwitches& sw, hipStream_t stream);
+hipError_t rt_launch_mesh_fast(const RtMeshParams& p, int variant, const RtSwitches& sw, hipStream_t stream);
 // The launch report (rtLastLaunches, rt_api.h): the launchers note every render-kernel launch with the template arguments of the instantiation they launched
 // (RT_KERNEL_* family and the RT_LAUNCH_* words up to RT_LAUNCH_BLOCKS); the renderer adds the device and the fp mode of the frame.  Host bookkeeping only.
 void rt_note_launch(int family, int phase, int cls, int chunked, int dbg, int scene, int lean, int threads, unsigned blocks);

@@ -44,16 +44,6 @@ void hip_check(hipError_t result, const char* func, const char* file, int line) 
     exit(99);
 }
 
-// Defaults of the traffic forms of the sphere kernel's two-dispatch frame (see runRenderer; each has an environment switch of the same meaning for A/B runs)
-constexpr bool kDefaultOrdPacked = true;
-constexpr bool kDefaultXcdQueues = true;
-constexpr int kDefaultP1Tile = 2;
-constexpr bool kDefaultFbDirect = false;
-static bool env_flag(const char* name, bool dflt) {     // "0" = off, any other value = on, unset = dflt
-    const char* v = getenv(name);
-    return v ? v[0] != '0' : dflt;
-}
-
 struct DeviceState {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -467,8 +457,7 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
                 }
             }
         }
-        const bool cells_off = getenv("RT_BOX_CELLS") && getenv("RT_BOX_CELLS")[0] == '0';     // (read at every init: the tests render with and without)
-        c.cell_on = (ok && !cells_off) ? 1 : 0;
+        c.cell_on = (ok && rt_read_switches().box_cells) ? 1 : 0;
     }
     // per-ray margin constants
     double cc[3] = { 0, 0, 0 }, rad = 0.0;
@@ -680,6 +669,7 @@ void render_frame(int ns, int first, bool progressive) {
     int launches = 0;
     g_launches.clear();
     g_launch_fp = c.opt.fp;
+    const RtSwitches sw = rt_read_switches();           // the environment switches of this frame
 
     for (int k = 0; k < nd; k++) {
         DeviceState& d = c.devs[k];
@@ -692,9 +682,6 @@ void render_frame(int ns, int first, bool progressive) {
         part.world = world;
         part.local_rows = (int)d.fb_rows;
         if (c.opt.counters) HIP_CHECK(hipMemsetAsync(d.d_counters, 0, sizeof(RtCounters), d.stream));
-        // Finished pixels of the default sphere kernel go straight to the pinned host framebuffer (12 bytes each, spread over the whole frame time):
-        // no device-to-host copy after the kernel.  RT_FB_DIRECT=0 keeps the compact device buffer + copy (every other kernel always does).
-        const bool fb_direct_env = env_flag("RT_FB_DIRECT", kDefaultFbDirect);
         int spw = ns, chunks = 1;               // sphere path, RT_RNG_COUNTER: samples per work item, work items per pixel
         if (c.is_spheres && c.opt.rng == RT_RNG_COUNTER && (c.opt.variant & 0xFF) == 0) {
             // default: 4 samples per item, but no more items than fill and balance the machine (~32 M): a 3840x2160x4096spp frame cut into 4-sample items
@@ -708,8 +695,10 @@ void render_frame(int ns, int first, bool progressive) {
             if (want < ns) { spw = want; chunks = (ns + want - 1) / want; }
         }
         const int vk = c.opt.variant & 0xFF, vcb = (c.opt.variant >> 16) & 0xFF;
-        // (an external framebuffer that could not be page-locked is reached by the copy path only: see setExternalFramebuffer)
-        const bool fb_direct = c.is_spheres && c.max_depth > 0 && fb_direct_env && vk == 0 && (vcb == 0 || vcb == 255) && chunks == 1 &&
+        // Every kernel renders into the compact device framebuffer, which the copy engine delivers behind it (below).  RT_FB_DIRECT=1 (A/B): the default
+        // sphere kernel stores finished pixels straight into the pinned host framebuffer instead (12 bytes each, spread over the whole frame time), with
+        // no copy after the kernel.  (An external framebuffer that could not be page-locked is reached by the copy path only: see setExternalFramebuffer.)
+        const bool fb_direct = c.is_spheres && c.max_depth > 0 && sw.fb_direct && vk == 0 && (vcb == 0 || vcb == 255) && chunks == 1 &&
                                (!c.h_ext || c.ext_registered);
         rt_vec3* const h_target = c.h_ext ? c.h_ext : c.h_fb;
         // Poison the framebuffer the kernel WRITES (all-ones = NaN): every pixel is written exactly once per frame, so a pixel the work
@@ -742,15 +731,11 @@ void render_frame(int ns, int first, bool progressive) {
             p.spw = spw; p.chunks = chunks; p.partial = nullptr;
             p.phase = 0; p.s_split = 0; p.px_state = d.d_px_state; p.px_rays = d.d_px_rays; p.ord_state = d.d_ord_state; p.ord_rays = d.d_ord_rays;
             if (progressive) { p.acc_state = d.d_acc_state; p.acc_rays = d.d_acc_rays; p.acc_first = first; }
-            static const int top_thr_env = getenv("RT_TOP_THR") ? atoi(getenv("RT_TOP_THR")) : 0;      // experiments
-            p.chain_top_thr = top_thr_env >= 320 ? top_thr_env : 384;                                 // 24 rays per sample
-            // Traffic forms of the two-dispatch frame (RtSphereParams::ord_rec / xcd_queues / p1_tile_major; A/B switches read per frame, defaults = what measured best)
-            const bool ord_packed_env = env_flag("RT_ORD_PACKED", kDefaultOrdPacked);
-            const bool xcd_queues_env = env_flag("RT_XCD_QUEUES", kDefaultXcdQueues);
-            const int p1_tile_env = getenv("RT_P1_TILE") ? atoi(getenv("RT_P1_TILE")) : kDefaultP1Tile;     // 0 scattered, 1 tile-major, 2 scattered row segments
-            p.ord_rec = ord_packed_env ? d.d_ord_rec : nullptr;
-            p.xcd_queues = xcd_queues_env ? kXcdQueues : 0;
-            p.p1_tile_major = (p1_tile_env >= 0 && p1_tile_env <= 2) ? p1_tile_env : 0;
+            p.chain_top_thr = sw.top_thr;
+            // traffic forms of the two-dispatch frame (RtSphereParams::ord_rec / xcd_queues / p1_tile_major)
+            p.ord_rec = sw.ord_packed ? d.d_ord_rec : nullptr;
+            p.xcd_queues = sw.xcd_queues ? kXcdQueues : 0;
+            p.p1_tile_major = sw.p1_tile;
             if (chunks > 1) {
                 const size_t need = d.fb_rows * c.nx * (size_t)p.chunks * sizeof(rt_vec3);
                 if (need > d.partial_bytes) {
@@ -760,9 +745,9 @@ void render_frame(int ns, int first, bool progressive) {
                 }
                 p.partial = d.d_partial;
             }
-            static const char* dbg_path = getenv("RT_WAVE_DEBUG");      // diagnostics: per-wave time stamps -> file
             const size_t dbg_bytes = (size_t)65536 * 8 * sizeof(unsigned long long);
-            if (dbg_path && !progressive) {       // (PHASE 2's per-pixel time line would overwrite the parked state)
+            if (sw.wave_debug && !progressive) {       // diagnostics: per-wave time stamps -> file (not in a progressive pass: PHASE 2's per-pixel
+                                                       // time line would overwrite the parked state)
                 if (!d.d_wave_dbg) HIP_CHECK(hipMalloc((void**)&d.d_wave_dbg, dbg_bytes));
                 HIP_CHECK(hipMemsetAsync(d.d_wave_dbg, 0, dbg_bytes, d.stream));
                 p.wave_dbg = d.d_wave_dbg;
@@ -774,24 +759,22 @@ void render_frame(int ns, int first, bool progressive) {
                 HIP_CHECK(hipHostGetDevicePointer(&dp, (void*)h_target, 0));
                 p.fb = reinterpret_cast<rt_vec3*>(dp);
                 p.fb_global_rows = 1;
-                static const bool poison_env = !(getenv("RT_FB_POISON") && getenv("RT_FB_POISON")[0] == '0');      // (experiment switch)
-                p.poison_fb = poison_env ? 1 : 0;
+                p.poison_fb = sw.fb_poison ? 1 : 0;
             }
             // the device copy of the parameter block (RtSphereParams::self): owned by this DeviceState, refreshed by every frame from a pinned
             // staging copy (runRenderer is synchronous: the previous frame's upload has completed)
             p.self = d.d_params;
             *d.h_params = p;
             HIP_CHECK(hipMemcpyAsync(d.d_params, d.h_params, sizeof(RtSphereParams), hipMemcpyHostToDevice, d.stream));
-            HIP_CHECK(c.opt.fp == RT_FP_FAST ? rt_launch_spheres_fast(p, c.opt.variant, d.stream)
-                                             : rt_launch_spheres_parity(p, c.opt.variant, d.stream));
+            HIP_CHECK(c.opt.fp == RT_FP_FAST ? rt_launch_spheres_fast(p, c.opt.variant, sw, d.stream)
+                                             : rt_launch_spheres_parity(p, c.opt.variant, sw, d.stream));
             launches++;
         } else {
             RtMeshParams p;
             memset(&p, 0, sizeof p);
             p.cam = c.cam; p.nx = c.nx; p.ny = c.ny; p.ns = ns; p.max_depth = c.max_depth;
             p.tris = d.d_tris; p.bvh4 = d.d_bvh; p.bvh_axis = d.d_bvh_axis;
-            static const bool compact_leaves = !(getenv("RT_COMPACT_LEAVES") && getenv("RT_COMPACT_LEAVES")[0] == '0');        // A/B
-            p.leaf_tri = compact_leaves ? d.d_leaf_tri : nullptr; p.leaf_ofs = compact_leaves ? d.d_leaf_ofs : nullptr;
+            p.leaf_tri = sw.compact_leaves ? d.d_leaf_tri : nullptr; p.leaf_ofs = sw.compact_leaves ? d.d_leaf_ofs : nullptr;
             p.first_leaf = (uint32_t)c.num_bvh_nodes / 2; p.nppl = (uint32_t)c.nppl; p.bounds = c.bounds;
             p.leaf_sentinels_trailing = c.leaf_sentinels_trailing;
             p.lean_ok = 1;
@@ -809,17 +792,17 @@ void render_frame(int ns, int first, bool progressive) {
             p.s_split = 0; p.px_state = d.d_px_state; p.px_rays = d.d_px_rays; p.order = d.d_order; p.ord_state = d.d_ord_state; p.ord_rays = d.d_ord_rays;
             if (progressive) { p.acc_state = d.d_acc_state; p.acc_first = first; }
             // the traffic forms of the two-dispatch frame, as for sphere scenes (the same switches; the mesh frame always renders into the device framebuffer)
-            p.ord_rec = env_flag("RT_ORD_PACKED", kDefaultOrdPacked) ? d.d_ord_rec : nullptr;
-            p.xcd_queues = env_flag("RT_XCD_QUEUES", kDefaultXcdQueues) ? kXcdQueues : 0;
-            p.p1_segments = (getenv("RT_P1_TILE") ? atoi(getenv("RT_P1_TILE")) : kDefaultP1Tile) == 2 ? 1 : 0;
-            if (getenv("RT_WAVE_DEBUG")) {                           // diagnostics: phase cycle / lane counters -> file
+            p.ord_rec = sw.ord_packed ? d.d_ord_rec : nullptr;
+            p.xcd_queues = sw.xcd_queues ? kXcdQueues : 0;
+            p.p1_segments = sw.p1_tile == 2 ? 1 : 0;
+            if (sw.wave_debug) {                                     // diagnostics: phase cycle / lane counters -> file
                 const size_t dbg_bytes = (size_t)65536 * 8 * sizeof(unsigned long long);
                 if (!d.d_wave_dbg) HIP_CHECK(hipMalloc((void**)&d.d_wave_dbg, dbg_bytes));
                 HIP_CHECK(hipMemsetAsync(d.d_wave_dbg, 0, dbg_bytes, d.stream));
                 p.dbg = d.d_wave_dbg;
             }
-            HIP_CHECK(c.opt.fp == RT_FP_FAST ? rt_launch_mesh_fast(p, c.opt.variant, d.stream)
-                                             : rt_launch_mesh_parity(p, c.opt.variant, d.stream));
+            HIP_CHECK(c.opt.fp == RT_FP_FAST ? rt_launch_mesh_fast(p, c.opt.variant, sw, d.stream)
+                                             : rt_launch_mesh_parity(p, c.opt.variant, sw, d.stream));
             launches++;
         }
         HIP_CHECK(hipEventRecord(d.ev_stop, d.stream));
@@ -852,14 +835,14 @@ void render_frame(int ns, int first, bool progressive) {
         float ms = 0.0f;
         HIP_CHECK(hipEventElapsedTime(&ms, d.ev_start, d.ev_stop));
         kernel_ms = std::max(kernel_ms, (double)ms);
-        if (d.d_wave_dbg && getenv("RT_WAVE_DEBUG")) {
+        if (d.d_wave_dbg && sw.wave_debug) {
             std::vector<unsigned long long> h((size_t)65536 * 8);
             HIP_CHECK(hipMemcpy(h.data(), d.d_wave_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            if (FILE* f = fopen(getenv("RT_WAVE_DEBUG"), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
+            if (FILE* f = fopen(sw.wave_debug->c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
             if (d.d_px_state && c.is_spheres) {                      // per-pixel time line of the second phase (see finish())
                 std::vector<float> px((size_t)d.fb_rows * c.nx * 4);
                 HIP_CHECK(hipMemcpy(px.data(), d.d_px_state, px.size() * sizeof(float), hipMemcpyDeviceToHost));
-                const std::string path = std::string(getenv("RT_WAVE_DEBUG")) + ".px";
+                const std::string path = *sw.wave_debug + ".px";
                 if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(px.data(), sizeof(float), px.size(), f); fclose(f); }
             }
         }
@@ -881,6 +864,80 @@ void render_frame(int ns, int first, bool progressive) {
 }
 
 }  // namespace
+
+// The environment switches (rt_params.h: RtSwitches): the library's only reads of the environment.
+namespace {
+
+bool env_flag(const char* name, bool dflt) {            // "0" = off, any other value = on, unset = dflt
+    const char* v = getenv(name);
+    return v ? v[0] != '0' : dflt;
+}
+
+bool env_one(const char* name) {                        // on only as "1"
+    const char* v = getenv(name);
+    return v && v[0] == '1';
+}
+
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+
+std::optional<std::string> env_str(const char* name) {
+    const char* v = getenv(name);
+    if (!v) return std::nullopt;
+    return std::string(v);
+}
+
+}  // namespace
+
+RtSwitches rt_read_switches() {
+    RtSwitches s;
+    s.xcd_queues = env_flag("RT_XCD_QUEUES", s.xcd_queues);
+    s.ord_packed = env_flag("RT_ORD_PACKED", s.ord_packed);
+    const int p1_tile = env_int("RT_P1_TILE", s.p1_tile);
+    s.p1_tile = (p1_tile >= 0 && p1_tile <= 2) ? p1_tile : 0;
+    s.wave_debug = env_str("RT_WAVE_DEBUG");
+
+    s.fb_direct = env_flag("RT_FB_DIRECT", s.fb_direct);
+    s.fb_poison = env_flag("RT_FB_POISON", s.fb_poison);
+    s.box_cells = env_flag("RT_BOX_CELLS", s.box_cells);
+    s.compact_leaves = env_flag("RT_COMPACT_LEAVES", s.compact_leaves);
+    s.ext_fb_no_register = env_one("RT_EXT_FB_NO_REGISTER");
+    s.cleanup_device_reset = env_one("RT_CLEANUP_DEVICE_RESET");
+
+    const int top_thr = env_int("RT_TOP_THR", s.top_thr);
+    if (top_thr >= 320) s.top_thr = top_thr;
+    s.basic = env_flag("RT_BASIC", s.basic);
+    s.onepass = env_flag("RT_ONEPASS", s.onepass);
+    if (const auto v = env_str("RT_LEAN6_PIXELS")) s.lean6_pixels = atoll(v->c_str());
+    s.hybrid_two = env_one("RT_HYBRID_TWO");
+    if (const auto v = env_str("RT_MID")) sscanf(v->c_str(), "%d,%d", &s.mid_waves, &s.mid_cap);
+    s.chain_single = env_flag("RT_CHAIN_SINGLE", s.chain_single);
+    s.single_ray = env_flag("RT_SINGLE_RAY", s.single_ray);
+    s.pool = env_int("RT_POOL", s.pool);
+    s.wave_debug_light = env_one("RT_WAVE_DEBUG_LIGHT");
+    s.wave_debug_phase = env_one("RT_WAVE_DEBUG_PHASE");
+    if (const auto v = env_str("RT_TUNE")) {
+        RtTune& t = s.tune.emplace();
+        t.text = *v;
+        t.n = std::max(0, sscanf(v->c_str(), "%d,%d,%d,%d,%d,%d,%d,%d,%d", &t.v[0], &t.v[1], &t.v[2], &t.v[3], &t.v[4], &t.v[5], &t.v[6], &t.v[7], &t.v[8]));
+    }
+
+    s.mesh_lean = env_flag("RT_MESH_LEAN", s.mesh_lean);
+    const auto order = env_str("RT_MESH_ORDER");
+    s.mesh_tile_order = order && (*order)[0] == 't';
+    s.mesh_two = env_flag("RT_MESH_TWO", s.mesh_two);
+    s.mesh_split = std::max(1, env_int("RT_MESH_SPLIT", s.mesh_split));
+    s.mesh_heavy = env_int("RT_MESH_HEAVY", s.mesh_heavy);
+    s.mesh_rounds = env_int("RT_MESH_ROUNDS", s.mesh_rounds);
+    s.mesh_rev = env_one("RT_MESH_REV");
+    s.mesh_chain_thr = std::max(17, env_int("RT_MESH_CHAIN_THR", s.mesh_chain_thr));
+    s.mesh_chain_lanes = std::min(64, std::max(0, env_int("RT_MESH_CHAIN_LANES", s.mesh_chain_lanes)));
+    s.mesh_chain_frac = env_int("RT_MESH_CHAIN_FRAC", s.mesh_chain_frac) & 0xF;
+    s.mesh_diag_file = env_str("RT_MESH_DIAG_FILE");
+    return s;
+}
 
 extern "C" {
 
@@ -935,9 +992,8 @@ void setExternalFramebuffer(rt_vec3* fb) {
         // straight into it.  If the runtime refuses (locked-memory limit of the account, a mapping it cannot pin) the job must not die on its first
         // multi-GPU node: the renderer falls back to its compact device buffer and plain device-to-host copies of this member's stripes into the
         // (pageable) memory - slower by the copy, same image.  RT_EXT_FB_NO_REGISTER=1 forces that path (tests).
-        const char* no_reg = getenv("RT_EXT_FB_NO_REGISTER");
-        hipError_t e = (no_reg && no_reg[0] == '1') ? hipErrorNotSupported
-                                                    : hipHostRegister(fb, (size_t)c.nx * c.ny * sizeof(rt_vec3), hipHostRegisterDefault);
+        hipError_t e = rt_read_switches().ext_fb_no_register ? hipErrorNotSupported
+                                                             : hipHostRegister(fb, (size_t)c.nx * c.ny * sizeof(rt_vec3), hipHostRegisterDefault);
         if (e != hipSuccess) {
             (void)hipGetLastError();                                 // (clear the sticky error: it has been handled)
             fprintf(stderr, "rt warning: setExternalFramebuffer could not page-lock the caller's framebuffer (%s): stripes are copied into it "
@@ -957,7 +1013,7 @@ void cleanupRenderer(void) {
     cleanup_impl();
     // kernels.cu:679 ends with cudaDeviceReset().  A reset destroys EVERY context of the process on that device - also the one of a
     // host that shares the process (PyTorch in bench.py, a viewer) - so it is opt-in here: RT_CLEANUP_DEVICE_RESET=1 mirrors the reference.
-    if (const char* r = getenv("RT_CLEANUP_DEVICE_RESET")) if (r[0] == '1') (void)hipDeviceReset();
+    if (rt_read_switches().cleanup_device_reset) (void)hipDeviceReset();
 }
 
 }  // extern "C"

@@ -55,9 +55,8 @@ def mesh_one(lean):
 #                                 axis (the group boxes share that extent), "volume": centres and radii spread on all three axes; presets: every
 #                                 seventh small sphere takes a preset material without libm calls (not basic: LEAN 0, still bit-exact)
 #   ("staircase", textured)       the procedural staircase mesh (detail 1, 5 triangles per leaf); textured: albedo textures on the floor and the stairs
-# opts: rt_render_options fields; env: environment of the render (every knob here is read per frame or per init); child: the form needs a knob that
-# the launcher caches in a function static (RT_LEAN6_PIXELS), so it is rendered in a fresh process; tol: the counter stream's sample chunks are
-# added in chunk order - the tolerance of test_counter_rng_sample_chunks instead of bits.
+# opts: rt_render_options fields; env: environment of the render (the renderer reads its switches once per frame); tol: the counter stream's sample
+# chunks are added in chunk order - the tolerance of test_counter_rng_sample_chunks instead of bits.
 _COUNTER = {"rng": 1, "samples_per_item": 2}        # RT_RNG_COUNTER, two samples per work item: ONE_NS = 3 samples in two chunks
 _LEAN6 = {"RT_LEAN6_PIXELS": "1"}
 
@@ -69,14 +68,14 @@ FORMS = [
     dict(name="full_lean1_one", scene=("random",), ns=ONE_NS, env={"RT_BOX_CELLS": "0"}, records=sphere_one(0, 1)),
     dict(name="full_lean3_two", scene=("random",), ns=TWO_NS, records=sphere_two(0, 3)),
     dict(name="full_lean3_one", scene=("random",), ns=ONE_NS, records=sphere_one(0, 3)),
-    dict(name="full_lean7_two", scene=("random",), ns=TWO_NS, env=_LEAN6, child=True, records=sphere_two(0, 7, waves=12)),
-    dict(name="full_lean7_one", scene=("random",), ns=ONE_NS, env=_LEAN6, child=True, records=sphere_one(0, 7, waves=12)),
+    dict(name="full_lean7_two", scene=("random",), ns=TWO_NS, env=_LEAN6, records=sphere_two(0, 7, waves=12)),
+    dict(name="full_lean7_one", scene=("random",), ns=ONE_NS, env=_LEAN6, records=sphere_one(0, 7, waves=12)),
     dict(name="full_lean11_two", scene=("cloud", 488, "volume", False), ns=TWO_NS, records=sphere_two(0, 11)),
     dict(name="full_lean11_one", scene=("cloud", 488, "volume", False), ns=ONE_NS, records=sphere_one(0, 11)),
     dict(name="full_lean11_plane_x", scene=("cloud", 200, "plane_x", False), ns=TWO_NS, records=sphere_two(0, 11)),
     dict(name="full_lean11_plane_z", scene=("cloud", 200, "plane_z", False), ns=ONE_NS, records=sphere_one(0, 11)),
-    dict(name="full_lean15_two", scene=("cloud", 488, "volume", False), ns=TWO_NS, env=_LEAN6, child=True, records=sphere_two(0, 15, waves=12)),
-    dict(name="full_lean15_one", scene=("cloud", 488, "volume", False), ns=ONE_NS, env=_LEAN6, child=True, records=sphere_one(0, 15, waves=12)),
+    dict(name="full_lean15_two", scene=("cloud", 488, "volume", False), ns=TWO_NS, env=_LEAN6, records=sphere_two(0, 15, waves=12)),
+    dict(name="full_lean15_one", scene=("cloud", 488, "volume", False), ns=ONE_NS, env=_LEAN6, records=sphere_one(0, 15, waves=12)),
     dict(name="full_lean19_two", scene=("cloud", 700, "plane_y", False), ns=TWO_NS, records=sphere_two(0, 19)),
     dict(name="full_lean19_one", scene=("cloud", 700, "plane_y", False), ns=ONE_NS, records=sphere_one(0, 19)),
     dict(name="full_lean27_two", scene=("cloud", 700, "volume", False), ns=TWO_NS, records=sphere_two(0, 27)),
@@ -89,7 +88,7 @@ FORMS = [
     dict(name="chunked_general", scene=("cloud", 488, "plane_y", True), ns=ONE_NS, opts=_COUNTER, tol=True, records=sphere_one(0, 0, chunked=True)),
     dict(name="chunked_lean1", scene=("cloud", 488, "volume", False), ns=ONE_NS, opts=_COUNTER, tol=True, records=sphere_one(0, 1, chunked=True)),
     dict(name="chunked_lean3", scene=("random",), ns=ONE_NS, opts=_COUNTER, tol=True, records=sphere_one(0, 3, chunked=True)),
-    dict(name="chunked_lean7", scene=("random",), ns=ONE_NS, opts=_COUNTER, tol=True, env=_LEAN6, child=True,
+    dict(name="chunked_lean7", scene=("random",), ns=ONE_NS, opts=_COUNTER, tol=True, env=_LEAN6,
          records=sphere_one(0, 7, waves=12, chunked=True)),
     # ---- SCENE 2: the hybrid copy (test data in the LDS, hit data in global memory), single scattered dispatch
     dict(name="hybrid16_general", scene=("cloud", 2100, "volume", True), ns=ONE_NS, records=sphere_one(2, 0, cls=0)),

@@ -3,19 +3,12 @@ counting instantiation is the general diagnostic kernel, so a counters-on test n
 name exactly the instantiations the table expects, and the frame must be the oracle's bit for bit (the sample chunks of the counter stream: the
 tolerance of test_counter_rng_sample_chunks).  The same scene with counters on must give the same bits: the production kernel and the diagnostic one
 are held to each other as well as to the oracle."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import kernel_forms as K
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bits(a):
@@ -35,7 +28,7 @@ def _check_records(form, recs):
     assert all(r[len(K.RECORD_FIELDS):] == (0, 0) for r in recs), recs        # device 0, RT_FP_PARITY
 
 
-@pytest.mark.parametrize("form", [f for f in K.FORMS if not f.get("child")], ids=lambda f: f["name"])
+@pytest.mark.parametrize("form", K.FORMS, ids=lambda f: f["name"])
 def test_production_form_is_launched_and_matches_the_oracle(rt, O, form, monkeypatch):
     for k, v in form.get("env", {}).items():
         monkeypatch.setenv(k, v)
@@ -46,31 +39,6 @@ def test_production_form_is_launched_and_matches_the_oracle(rt, O, form, monkeyp
     counted, crecs = K.render_form(rt, form, counters=1)
     assert crecs and all(r[4] != 0 for r in crecs), crecs                     # (the counting instantiation ran)
     assert np.array_equal(_bits(counted), _bits(got)), (form["name"], np.count_nonzero(_bits(counted) != _bits(got)))
-
-
-def test_six_wave_forms_in_a_fresh_process(rt, O, tmp_path):
-    """The six-wave kinds (7, 15 and the chunked 7) are chosen from RT_LEAN6_PIXELS pixels on, a threshold the launcher reads once per process (a
-    function static): one child process renders them all with the threshold at 1 pixel and writes frames and launch records; the oracle runs here."""
-    forms = [f for f in K.FORMS if f.get("child")]
-    env = dict(os.environ)
-    for f in forms:
-        env.update(f["env"])
-    code = ("import sys, json, numpy as np; sys.path[:0] = [%r, %r]; import cuda_raytracing_optimized_amd as rt, kernel_forms as K; out = {}\n"
-            "for f in [f for f in K.FORMS if f.get('child')]:\n"
-            "    for c in (0, 1):\n"
-            "        got, recs = K.render_form(rt, f, counters=c); np.save(%r + '/' + f['name'] + '_%%d.npy' %% c, got); out[f['name'] + '_%%d' %% c] = recs\n"
-            "json.dump(out, open(%r, 'w'))\n") % (ROOT, os.path.join(ROOT, "tests"), str(tmp_path), str(tmp_path / "records.json"))
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    records = json.load(open(tmp_path / "records.json"))
-    for f in forms:
-        ref = K.render_oracle(rt, O, f)
-        got = np.load(tmp_path / (f["name"] + "_0.npy"))
-        _check_records(f, [tuple(x) for x in records[f["name"] + "_0"]])
-        _check_frame(f, got, ref)
-        counted = np.load(tmp_path / (f["name"] + "_1.npy"))
-        assert all(x[4] != 0 for x in records[f["name"] + "_1"])
-        assert np.array_equal(_bits(counted), _bits(got)), f["name"]
 
 
 @pytest.mark.parametrize("lanes", [1, 6])

@@ -1,7 +1,6 @@
 """Progressive rendering (runRendererProgressive, include/rt_api.h): a frame built up in passes continues every pixel's RNG stream and running sum, so
 after passes of ns_1 .. ns_k samples the PARITY framebuffer holds the bits of runRenderer(ns_1 + .. + ns_k) - and of the CPU oracle at that total.
 "Bits" = float32 words compared exactly."""
-import json
 import os
 import subprocess
 import sys
@@ -221,16 +220,11 @@ def test_large_frame(rt, O):
     _same(got[y0:y1, x0:x1], ref[y0:y1, x0:x1], "oracle crop")
 
 
-def test_large_frame_six_wave_kind(rt, O, tmp_path):
-    """The same with the six-wave kind (RT_LEAN6_PIXELS=1, read once per process): in one fresh child process."""
-    env = dict(os.environ, RT_LEAN6_PIXELS="1")
-    code = ("import sys, json, numpy as np; sys.path[:0] = [%r, %r]; import cuda_raytracing_optimized_amd as rt, test_gpu_progressive as T\n"
-            "mono, got, lean = T._large_frame(rt, 1920, 1080); np.save(%r, mono); np.save(%r, got); json.dump(lean, open(%r, 'w'))\n") % (
-        ROOT, os.path.join(ROOT, "tests"), str(tmp_path / "mono.npy"), str(tmp_path / "got.npy"), str(tmp_path / "lean.json"))
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    assert json.load(open(tmp_path / "lean.json")) & 4
-    mono, got = np.load(tmp_path / "mono.npy"), np.load(tmp_path / "got.npy")
+def test_large_frame_six_wave_kind(rt, O, monkeypatch):
+    """The same with the six-wave kind (RT_LEAN6_PIXELS=1)."""
+    monkeypatch.setenv("RT_LEAN6_PIXELS", "1")
+    mono, got, lean = _large_frame(rt, 1920, 1080)
+    assert lean & 4
     _same(got, mono, "six-wave runRenderer(64)")
     sp, mt, cam = rt.scene_random_spheres(1920, 1080)
     x0, y0, x1, y1 = 300, 200, 364, 232

@@ -92,8 +92,8 @@ def test_every_mesh_instantiation_has_a_row_and_every_row_an_instantiation():
 
 
 def test_table_rows_are_complete():
-    """Unique names; every lean kind of the full copy on the two-dispatch path and the single dispatch; the six-wave kinds only in the child process
-    (their threshold is cached per process); the expected records of a frame use the frame's workgroup shape throughout."""
+    """Unique names; every lean kind of the full copy on the two-dispatch path and the single dispatch; the six-wave kinds with their pixel threshold at
+    one pixel and 12-wave workgroups; the expected records of a frame use the frame's workgroup shape throughout."""
     names = [f["name"] for f in K.FORMS]
     assert len(names) == len(set(names))
     full = {}
@@ -103,7 +103,7 @@ def test_table_rows_are_complete():
             if r[0] == SQ and r[5] == 0 and not r[3]:
                 full.setdefault(r[6], set()).add(r[1])
             if r[0] == SQ and r[6] & 4:
-                assert f.get("child") and f["env"].get("RT_LEAN6_PIXELS") == "1" and r[7] == 768, f["name"]
+                assert f["env"]["RT_LEAN6_PIXELS"] == "1" and r[7] == 768, f["name"]
         assert len({r[7:] for r in f["records"]}) == 1, f["name"]
     assert set(full) == {0, 1, 3, 7, 11, 15, 19, 27, 35, 43}
     assert all(phases == {0, 1, 2} for phases in full.values()), full
