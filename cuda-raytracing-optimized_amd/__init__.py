@@ -130,7 +130,8 @@ assert triangle_dtype.itemsize == 64 and bvh_node_dtype.itemsize == 24
 RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRendererSpheres",
                     "getDefaultRenderOptions", "setRenderOptions", "setExternalFramebuffer", "getRenderStats",
                     "rtDeviceCount", "rtApiVersion", "rtStructSizes", "rtLastLaunches",
-                    "runRendererProgressive", "rtProgressiveSamples", "rtResetProgressive", "setCamera"]
+                    "runRendererProgressive", "rtProgressiveSamples", "rtResetProgressive", "setCamera",
+                    "renderGuides", "rtLastGuidesMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
@@ -252,6 +253,11 @@ def load_renderer():
         r.rtResetProgressive.restype = None
         r.setCamera.argtypes = [C.POINTER(camera)]
         r.setCamera.restype = None
+        r.renderGuides.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        r.renderGuides.restype = None
+        r.rtLastGuidesMs.argtypes = []
+        r.rtLastGuidesMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -437,6 +443,41 @@ def resetProgressive():
 def setCamera(cam):
     """Replaces the camera for the following frames (no re-upload of the scene); resets the progressive frame."""
     load_renderer().setCamera(C.byref(cam))
+
+
+# renderGuides (include/rt_api.h): the planes of the mask, the primitive ids of a floor hit and of a miss
+RT_GUIDE_ALBEDO, RT_GUIDE_NORMAL, RT_GUIDE_DEPTH, RT_GUIDE_PRIM, RT_GUIDE_NODES = 1, 2, 4, 8, 16
+RT_GUIDE_PRIM_NONE, RT_GUIDE_PRIM_FLOOR = -1, -2
+GUIDE_PLANES = (("albedo", RT_GUIDE_ALBEDO, np.float32, 3), ("normal", RT_GUIDE_NORMAL, np.float32, 3), ("depth", RT_GUIDE_DEPTH, np.float32, 1),
+                ("prim", RT_GUIDE_PRIM, np.int32, 1), ("nodes", RT_GUIDE_NODES, np.int32, 1))
+
+
+def renderGuides(mask=RT_GUIDE_ALBEDO | RT_GUIDE_NORMAL | RT_GUIDE_DEPTH | RT_GUIDE_PRIM, out=None):
+    """First-hit guide planes of the centre rays (include/rt_api.h).  Returns a dict with the planes of `mask`: albedo, normal (ny, nx, 3) float32;
+    depth (ny, nx) float32; prim, nodes (ny, nx) int32.  `out`: a dict of caller-owned C-contiguous arrays of those shapes and types (e.g. views of shared
+    memory) to fill instead of new ones; only the rows this process owns are written.  Blocking; RT_GUIDE_NODES is defined for mesh scenes only."""
+    nx, ny = _state["nx"], _state["ny"]
+    res, ptrs = {}, []
+    for name, bit, dtype, comps in GUIDE_PLANES:
+        if not (mask & bit):
+            ptrs.append(None)
+            continue
+        shape = (ny, nx, 3) if comps == 3 else (ny, nx)
+        if out is not None and name in out:
+            a = out[name]
+            if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"] and a.shape == shape):
+                raise ValueError(f"renderGuides: out[{name!r}] must be a writable C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        else:
+            a = np.zeros(shape, dtype)
+        res[name] = a
+        ptrs.append(a.ctypes.data_as(C.POINTER(C.c_float if dtype == np.float32 else C.c_int32)))
+    load_renderer().renderGuides(mask, *ptrs)
+    return res
+
+
+def last_guides_ms():
+    """HIP-event time of the guide kernel(s) of the last renderGuides (the largest over the in-process devices), in milliseconds."""
+    return load_renderer().rtLastGuidesMs()
 
 
 def cleanupRenderer():

@@ -218,6 +218,11 @@ __device__ __forceinline__ f3 hex_color(int hexValue) {                    // sc
     return F3(r, g, b) / 255.0f;
 }
 
+// The look presets' constants (scene_materials.h:22-93), shared by material_scatter and guide_albedo below.
+constexpr int kFloorHex = 0x511845, kCheckerHex = 0xff5733;
+constexpr float kCheckerScale = 0.2f;
+constexpr float kModelBaseR = 0.0972942f, kModelBaseG = 0.0482054f, kModelBaseB = 0.000273194f;
+
 // fresnel_layer, material.h:55-60: true = the glossy (reflecting) layer is chosen; draws at most one random number
 __device__ __forceinline__ bool fresnel_layer(f3 normal, bool inside, f3 wo, float ior, uint32_t& rng) {
     const float etai_over_etat = inside ? ior : (1.0f / ior);
@@ -279,16 +284,16 @@ __device__ __forceinline__ void material_scatter(Scatter& out, float hit_t, f3 h
     f3 tint = color;                    // glossy / dielectric tint
     float ior = param, fuzz = 0.0f;
     f3 absorption = F3(0, 0, 0);
-    const f3 model_base = F3(0.0972942f, 0.0482054f, 0.000273194f);
+    const f3 model_base = F3(kModelBaseR, kModelBaseG, kModelBaseB);
     switch (type) {
     case RT_DIFFUSE: bsdf = B_DIFFUSE; break;
     case RT_METAL:   bsdf = B_GLOSSY; fuzz = param; break;
     case RT_GLASS:   bsdf = B_DIELECTRIC; break;                                 // tint = color, absorption 0
-    case RT_FLOOR_COAT:    bsdf = B_COAT; ior = 1.5f; albedo = hex_color(0x511845); tint = F3(1, 1, 1); break;
-    case RT_FLOOR_DIFFUSE: bsdf = B_DIFFUSE; albedo = hex_color(0x511845); break;
+    case RT_FLOOR_COAT:    bsdf = B_COAT; ior = 1.5f; albedo = hex_color(kFloorHex); tint = F3(1, 1, 1); break;
+    case RT_FLOOR_DIFFUSE: bsdf = B_DIFFUSE; albedo = hex_color(kFloorHex); break;
     case RT_FLOOR_CHECKER: {                                                     // checker_layer, material.h:33-36
-        const float sines = rt_checker_sines(0.2f * hp.x, 0.2f * hp.y, 0.2f * hp.z);
-        bsdf = B_DIFFUSE; albedo = (sines < 0) ? hex_color(0x511845) : hex_color(0xff5733);
+        const float sines = rt_checker_sines(kCheckerScale * hp.x, kCheckerScale * hp.y, kCheckerScale * hp.z);
+        bsdf = B_DIFFUSE; albedo = (sines < 0) ? hex_color(kFloorHex) : hex_color(kCheckerHex);
         break;
     }
     case RT_MODEL_COAT:    bsdf = B_COAT; ior = 1.1f; albedo = model_base; tint = F3(1, 1, 1); break;
@@ -351,6 +356,18 @@ __device__ __forceinline__ void material_scatter(Scatter& out, float hit_t, f3 h
     out.specular = specular;
     out.refracted = refracted;
     out.t = t_out;
+}
+
+// The diffuse albedo material_scatter above works with for a hit of material `type` (the RT_GUIDE_ALBEDO plane of renderGuides): `color` (texture lookup
+// or material.color) for the three basic types, the presets' constants above otherwise - (1, 1, 1) for the presets without a diffuse lobe.
+__device__ __forceinline__ f3 guide_albedo(int type, f3 color, f3 hp) {
+    switch (type) {
+    case RT_DIFFUSE: case RT_METAL: case RT_GLASS: return color;
+    case RT_FLOOR_COAT: case RT_FLOOR_DIFFUSE: return hex_color(kFloorHex);
+    case RT_FLOOR_CHECKER: return (rt_checker_sines(kCheckerScale * hp.x, kCheckerScale * hp.y, kCheckerScale * hp.z) < 0) ? hex_color(kFloorHex) : hex_color(kCheckerHex);
+    case RT_MODEL_COAT: case RT_MODEL_DIFFUSE: return F3(kModelBaseR, kModelBaseG, kModelBaseB);
+    default: return F3(1.0f, 1.0f, 1.0f);
+    }
 }
 
 // Sky, kernels.cu:419-421 (gradient) / :424 (constant grey)

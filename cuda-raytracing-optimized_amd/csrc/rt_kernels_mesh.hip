@@ -268,6 +268,71 @@ __global__ void __launch_bounds__(kThreads) k_render_mesh(const RtMeshParams P) 
 }
 
 
+// ---- first-hit guide planes (renderGuides, rt_api.h) ------------------------------------------------------------------
+// One lane per pixel of an 8x8 tile per wave, the grid of the kernel above: the centre ray (no lens offset, no jitter) through hitMesh / hitBvh in the
+// reference's own visiting order with its TravStats, so the node count of the closest-hit query is the oracle's; then the floor (rt_render_options.floor);
+// normal, texture coordinates and texture lookup as bounce 0 above does them.  No atomics, no queue: a lane writes the planes of its own pixel.
+// PARITY objects only: one arithmetic for both fp modes.
+#if defined(RT_MODE_PARITY)
+__global__ void __launch_bounds__(kThreads) k_guides_mesh(const RtMeshParams P, const RtGuidePlanes G) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int i = (blockIdx.x * kWavesPerWg + wave) * 8 + (lane & 7);
+    const int lr = blockIdx.y * 8 + (lane >> 3);
+    if (!(i < P.nx && lr < P.part.local_rows)) return;
+    const int j = global_row(P.part, lr);
+    const float u = ((float)i + 0.5f) / (float)P.nx, v = ((float)j + 0.5f) / (float)P.ny;
+    const f3 org = ld3(P.cam.origin);
+    const f3 dir = unit(ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - org);   // camera.h:8-12, no lens offset
+    const Ray r = make_ray(org, dir);                                // hit(), kernels.cu:325-360: the ray normalises the direction once more
+    uint32_t triId = 0;
+    float hu = 0.0f, hv = 0.0f;
+    TravStats st = { 0, 0 };
+    float t = hit_mesh(P, r, P.t_min, FLT_MAX, false, triId, hu, hv, st);
+    f3 albedo, normal = F3(0, 0, 0);
+    int prim = RT_GUIDE_PRIM_NONE;
+    if (t < FLT_MAX) {
+        const Tri tri = load_tri(P.tris, triId);                     // kernels.cu:334
+        normal = unit(cross(tri.v1 - tri.v0, tri.v2 - tri.v0));
+        const rt_material mat = P.materials[tri.meshID];             // kernels.cu:452-480
+        const bool basic = mat.type == RT_DIFFUSE || mat.type == RT_METAL || mat.type == RT_GLASS;
+        f3 color = ld3(mat.color);
+        if (basic && mat.texId != -1) {
+            const float w0 = 1 - hu - hv;
+            const float tcu = (hu * tri.tc[2] + hv * tri.tc[4] + w0 * tri.tc[0]);
+            const float tcv = (hu * tri.tc[3] + hv * tri.tc[5] + w0 * tri.tc[1]);
+            const int width = P.tex_width[mat.texId];
+            const int height = P.tex_height[mat.texId];
+            float tu = tcu; tu = tu - floorf(tu);
+            float tv = tcv; tv = tv - floorf(tv);
+            const int tx = (int)((float)(width - 1) * tu);
+            const int ty = (int)((float)(height - 1) * tv);
+            const int tIdx = ty * width + tx;
+            const float* d = P.tex_data[mat.texId];
+            color = F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
+        }
+        albedo = guide_albedo(mat.type, color, r.o + t * r.d);
+        prim = (int)triId;
+    } else {
+        if (P.floor_on) t = plane_hit(ld3(P.floor.norm), ld3(P.floor.point), r, P.t_min, FLT_MAX);     // kernels.cu:341-345
+        if (t < FLT_MAX) {
+            normal = ld3(P.floor.norm);
+            albedo = guide_albedo(RT_FLOOR_DIFFUSE, F3(0, 0, 0), F3(0, 0, 0));      // kernels.cu:481-482
+            prim = RT_GUIDE_PRIM_FLOOR;
+        } else {
+            albedo = sky_color(P.sky, dir);                          // kernels.cu:419-425: the path's direction, normalised once
+        }
+    }
+    if (prim != RT_GUIDE_PRIM_NONE && dot(r.d, normal) > 0.0f) normal = -normal;     // kernels.cu:354-355
+    const size_t px = (size_t)lr * P.nx + i;
+    if (G.albedo) { float* o = G.albedo + px * 3; o[0] = albedo.x; o[1] = albedo.y; o[2] = albedo.z; }
+    if (G.normal) { float* o = G.normal + px * 3; o[0] = normal.x; o[1] = normal.y; o[2] = normal.z; }
+    if (G.depth) G.depth[px] = t;
+    if (G.prim) G.prim[px] = prim;
+    if (G.nodes) G.nodes[px] = (int32_t)st.nodes;
+}
+#endif
+
 // ---- variant 0 (default): persistent waves, pixel queue, ray-job state machine ---------------------------------------
 // The first kernel (above) nests two traversals (closest hit, then the shadow ray) inside one loop iteration and lets a
 // lane whose traversal ended wait for the slowest lane of the wave: rocprof showed 17 % of the lanes active per VALU
@@ -1057,6 +1122,14 @@ static void launch_mesh_queue(dim3 grid, dim3 block, size_t lds, hipStream_t str
     hipLaunchKernelGGL((k_render_mesh_queue<TRAV, DBG, STATS, LEAN, PHASE>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
     rt_note_launch(RT_KERNEL_MESH_QUEUE, PHASE, TRAV, 0, (DBG ? 1 : 0) | (STATS ? 2 : 0), 0, LEAN ? 1 : 0, (int)block.x, grid.x);
 }
+
+#if defined(RT_MODE_PARITY)
+hipError_t rt_launch_guides_mesh(const RtMeshParams& p, const RtGuidePlanes& g, hipStream_t stream) {
+    const dim3 grid((p.nx + 8 * kWavesPerWg - 1) / (8 * kWavesPerWg), (p.part.local_rows + 7) / 8);
+    hipLaunchKernelGGL(k_guides_mesh, grid, dim3(kThreads), 0, stream, p, g);
+    return hipGetLastError();
+}
+#endif
 
 // variant: bits 0..7  0 = persistent state-machine kernel (default), 1 = first kernel (one tile per wave);
 //          bits 8..15 workgroups per CU of the persistent kernel (0 = default 4);

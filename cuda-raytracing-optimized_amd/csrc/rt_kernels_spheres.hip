@@ -1218,6 +1218,58 @@ __global__ void __launch_bounds__(kThreads) k_classify_spheres(const RtSpherePar
     }
 }
 
+// ---- first-hit guide planes (renderGuides, rt_api.h) ------------------------------------------------------------------
+// One lane per pixel of an 8x8 tile, like the pre-pass above, but with the literal sphereHit and the (t, caller index) tie rule of accept(): the first
+// hit of the centre ray exactly as bounce 0 of a path finds it (hit(), kernels.cu:325-360: the direction is normalised once by the camera and once more
+// by the ray).  Every lane scans all slots in slot order; the addresses are wave-uniform (LDS broadcasts, or scalar loads from global memory: SCENE 1).
+// No atomics, no queue: a lane writes the planes of its own pixel.  PARITY objects only: one arithmetic for both fp modes.
+#if defined(RT_MODE_PARITY)
+template <int SCENE>
+__global__ void __launch_bounds__(kThreads) k_guides_spheres(const RtSphereParams P, const RtGuidePlanes G) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* unused;
+    const SceneLds S = stage_scene<false, SCENE>(P, smem, &unused);
+    const int tiles_x = (P.nx + 7) >> 3;
+    const int tiles_y = (P.part.local_rows + 7) >> 3;
+    const uint32_t total = (uint32_t)tiles_x * (uint32_t)tiles_y * 64u;
+    const uint32_t p = blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t tile = p >> 6, within = p & 63u;
+    const int ty = (int)(tile / (uint32_t)tiles_x), tx = (int)(tile - (uint32_t)ty * (uint32_t)tiles_x);
+    const int i = tx * 8 + (int)(within & 7u);
+    const int lr = ty * 8 + (int)(within >> 3);
+    if (!(p < total && i < P.nx && lr < P.part.local_rows)) return;
+    const int j = global_row(P.part, lr);
+    const float u = ((float)i + 0.5f) / (float)P.nx, v = ((float)j + 0.5f) / (float)P.ny;
+    const f3 org = ld3(P.cam.origin);
+    const f3 dir = unit(ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - org);   // camera.h:8-12, no lens offset
+    const f3 dn = unit(dir);                                         // ray.h:9, as hit() rebuilds the ray
+    const float a = dot(dn, dn);
+    Hit h = { FLT_MAX, -1, 0x7fffffff };
+    for (int k = 0; k < P.n_padded; k++) {
+        const int orig = S.orig[k];
+        if (orig == 0x7fffffff) continue;                            // pad slot
+        const float t = sphere_hit_exact(S.sph[sidx(k)], org, dn, a, P.t_min, h.closest);
+        if (t < FLT_MAX) accept(h, t, k, orig);
+    }
+    const size_t px = (size_t)lr * P.nx + i;
+    f3 albedo, normal = F3(0, 0, 0);
+    if (h.sid >= 0) {
+        const float4 sc4 = S.sph[sidx(h.sid)];
+        const f3 hp = org + h.closest * dn;                          // ray.h:12
+        normal = (hp - F3(sc4.x, sc4.y, sc4.z)) / S.rad[h.sid];      // intersections.h:95
+        if (dot(dn, normal) > 0.0f) normal = -normal;                // kernels.cu:354-355
+        const float4 m = S.mat[h.sid];
+        albedo = F3(m.x, m.y, m.z);
+    } else {
+        albedo = sky_color(P.sky, dir);                              // kernels.cu:419-425: the path's direction, normalised once
+    }
+    if (G.albedo) { float* o = G.albedo + px * 3; o[0] = albedo.x; o[1] = albedo.y; o[2] = albedo.z; }
+    if (G.normal) { float* o = G.normal + px * 3; o[0] = normal.x; o[1] = normal.y; o[2] = normal.z; }
+    if (G.depth) G.depth[px] = h.closest;
+    if (G.prim) G.prim[px] = h.sid >= 0 ? h.orig : RT_GUIDE_PRIM_NONE;
+}
+#endif
+
 // ---- cost-ordered second phase ---------------------------------------------------------------------------------------
 // In the reference-stream mode the frame is rendered in two launches of the persistent kernel.  Phase 1 traces the first
 // `s_split` samples of every pixel and parks the pixel: RNG state, running colour sum, rays used.  k_order_by_cost then
@@ -1820,6 +1872,24 @@ hipError_t rt_order_pixels_by_cost(const RtSphereParams& q, hipStream_t stream) 
 }
 size_t rt_sphere_kernel_lds_bytes(int n_padded, int n) {                       // of the smallest LDS-resident form: beyond it the scene is read from global memory
     return lds_bytes(n_padded, n, false, 2, 8) + kStaticLds;
+}
+// The guide kernel reads the scene where the render kernels of the same scene read it (full LDS copy, hybrid copy, global memory), without their per-wave scratch.
+hipError_t rt_launch_guides_spheres(const RtSphereParams& p, const RtGuidePlanes& g, hipStream_t stream) {
+    const size_t kLdsPerCu = 160 * 1024 - kStaticLds;
+    const int scene = p.global_scene ? 1 : (lds_bytes(p.n_padded, p.n, false, 0, kWavesPerWg) <= kLdsPerCu ? 0 : 2);
+    const size_t lds = scene == 1 ? 0 : lds_bytes(p.n_padded, p.n, false, scene, 0);
+    const void* kern = scene == 0 ? reinterpret_cast<const void*>(k_guides_spheres<0>)
+                     : scene == 1 ? reinterpret_cast<const void*>(k_guides_spheres<1>) : reinterpret_cast<const void*>(k_guides_spheres<2>);
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const unsigned long long total = (unsigned long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64ull;
+    const dim3 grid((unsigned)((total + kThreads - 1) / kThreads));
+    if (scene == 0) hipLaunchKernelGGL(k_guides_spheres<0>, grid, dim3(kThreads), lds, stream, p, g);
+    else if (scene == 1) hipLaunchKernelGGL(k_guides_spheres<1>, grid, dim3(kThreads), lds, stream, p, g);
+    else hipLaunchKernelGGL(k_guides_spheres<2>, grid, dim3(kThreads), lds, stream, p, g);
+    return hipGetLastError();
 }
 #endif
 

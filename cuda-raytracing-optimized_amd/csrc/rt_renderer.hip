@@ -85,7 +85,11 @@ struct DeviceState {
     float4* d_ord_rec = nullptr;        // ... or as one 32-byte record per queue position (RtSphereParams::ord_rec)
     float4* d_acc_state = nullptr;      // progressive frame (runRendererProgressive): per local pixel (col, rng) after the samples so far, and (sphere scenes)
     uint32_t* d_acc_rays = nullptr;     // the rays they took; allocated by the first pass on this device
+    void* d_guide[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };     // first-hit guide planes (renderGuides), plane k = bit k of the mask: allocated by the
+                                        // first call that asks for the plane on this device
 };
+
+constexpr size_t kGuideBytes[5] = { 12, 12, 4, 4, 4 };      // bytes per pixel of the guide planes: albedo, normal, depth, prim, nodes
 
 struct RenderContext {
     bool initialised = false;
@@ -129,6 +133,7 @@ struct RenderContext {
     std::vector<DeviceState> devs;
     rt_render_stats stats;
     int prog_samples = 0;               // samples per pixel of the progressive frame so far (rtProgressiveSamples)
+    double guides_ms = 0.0;             // rtLastGuidesMs
 };
 
 RenderContext g_ctx;     // kernels.cu:145: one global context per process
@@ -166,6 +171,7 @@ void free_device(DeviceState& d) {
     fr(d.d_tex_data); fr(d.d_tex_width); fr(d.d_tex_height);
     fr(d.d_fb); fr(d.d_counters); fr(d.d_queue); fr(d.d_wave_dbg); fr(d.d_order); fr(d.d_partial); fr(d.d_px_state); fr(d.d_px_rays); fr(d.d_ord_state); fr(d.d_ord_rays); fr(d.d_ord_rec);
     fr(d.d_acc_state); fr(d.d_acc_rays);
+    for (void* g : d.d_guide) fr(g);
     fr(d.d_params);
     if (d.h_params) HIP_CHECK(hipHostFree(d.h_params));
     if (d.ev_start) HIP_CHECK(hipEventDestroy(d.ev_start));
@@ -655,6 +661,24 @@ void setRenderOptions(const rt_render_options* opt) {
 
 namespace {
 
+// gather: local stripe q (rows of a compact device plane of `px_bytes` per pixel) -> global stripe q*world + rank of the host plane `host` (nx*ny pixels), on the
+// device's stream.  The framebuffer and the guide planes are delivered this way.
+void deliver_stripes(const DeviceState& d, const RtPartition& part, char* host, const char* dev, size_t px_bytes) {
+    const RenderContext& c = g_ctx;
+    const size_t row_bytes = (size_t)c.nx * px_bytes;
+    const size_t stripe_bytes = (size_t)part.stripe_rows * row_bytes;
+    const size_t full = d.fb_rows / part.stripe_rows, rem = d.fb_rows % part.stripe_rows;
+    char* dst0 = host + (size_t)part.rank * stripe_bytes;
+    if (part.world == 1) {                                              // the whole image: one linear copy
+        HIP_CHECK(hipMemcpyAsync(dst0, dev, d.fb_rows * row_bytes, hipMemcpyDeviceToHost, d.stream));
+        return;
+    }
+    if (full > 0)
+        HIP_CHECK(hipMemcpy2DAsync(dst0, (size_t)part.world * stripe_bytes, dev, stripe_bytes, stripe_bytes, full, hipMemcpyDeviceToHost, d.stream));
+    if (rem > 0)
+        HIP_CHECK(hipMemcpyAsync(dst0 + full * (size_t)part.world * stripe_bytes, dev + full * stripe_bytes, rem * row_bytes, hipMemcpyDeviceToHost, d.stream));
+}
+
 // One frame of ns samples per pixel (runRenderer), or one pass of a progressive frame (progressive): samples [first, ns) of every pixel, continued from
 // and parked into the device's accumulation buffers, the framebuffer = sum / ns.
 void render_frame(int ns, int first, bool progressive) {
@@ -807,20 +831,7 @@ void render_frame(int ns, int first, bool progressive) {
         }
         HIP_CHECK(hipEventRecord(d.ev_stop, d.stream));
 
-        // gather: local stripe q (rows of the compact buffer) -> global stripe q*world + rank of the pinned framebuffer
-        const int sr = c.opt.stripe_rows;
-        const size_t stripe_bytes = (size_t)sr * row_bytes;
-        const size_t full = d.fb_rows / sr, rem = d.fb_rows % sr;
-        char* dst0 = reinterpret_cast<char*>(c.h_ext ? c.h_ext : c.h_fb) + (size_t)part.rank * stripe_bytes;
-        const char* src0 = reinterpret_cast<const char*>(d.d_fb);
-        if (world == 1) {                                               // the whole image: one linear copy
-            if (!fb_direct) HIP_CHECK(hipMemcpyAsync(dst0, src0, d.fb_rows * row_bytes, hipMemcpyDeviceToHost, d.stream));
-        } else if (full > 0 && !fb_direct)
-            HIP_CHECK(hipMemcpy2DAsync(dst0, (size_t)world * stripe_bytes, src0, stripe_bytes, stripe_bytes, full,
-                                       hipMemcpyDeviceToHost, d.stream));
-        if (world != 1 && rem > 0 && !fb_direct)
-            HIP_CHECK(hipMemcpyAsync(dst0 + full * (size_t)world * stripe_bytes, src0 + full * stripe_bytes, rem * row_bytes,
-                                     hipMemcpyDeviceToHost, d.stream));
+        if (!fb_direct) deliver_stripes(d, part, reinterpret_cast<char*>(c.h_ext ? c.h_ext : c.h_fb), reinterpret_cast<const char*>(d.d_fb), sizeof(rt_vec3));
         samples += (int64_t)d.fb_rows * c.nx * (ns - first);
     }
 
@@ -982,6 +993,81 @@ void setCamera(const rt_camera* cam) {
     c.cam = *cam;                                           // read by every frame's parameter block; nothing of the scene depends on it
     c.prog_samples = 0;
 }
+
+// First-hit guide planes (rt_api.h).  Its own kernels, device planes and timing: nothing of a frame's state (framebuffer, stats, launch report, progressive
+// accumulation, queue words, counters) is read or written.
+void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t* prim, int32_t* nodes) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("renderGuides before init");
+    constexpr int kAll = RT_GUIDE_ALBEDO | RT_GUIDE_NORMAL | RT_GUIDE_DEPTH | RT_GUIDE_PRIM | RT_GUIDE_NODES;
+    if (mask == 0 || (mask & ~kAll) != 0) rt_fail("renderGuides: mask must name at least one RT_GUIDE_* plane and no unknown bit");
+    void* const host[5] = { albedo, normal, depth, prim, nodes };
+    for (int k = 0; k < 5; k++)
+        if ((mask >> k & 1) && !host[k]) rt_fail("renderGuides: a requested plane has a null pointer");
+    if ((mask & RT_GUIDE_NODES) && c.is_spheres) rt_fail("renderGuides: RT_GUIDE_NODES is only defined for mesh scenes");
+    if (c.is_spheres && c.opt.floor) rt_fail("renderGuides: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    const int nd = (int)c.devs.size();
+    const int world = c.opt.part_world * nd;
+    for (int k = 0; k < nd; k++) {
+        DeviceState& d = c.devs[k];
+        if (d.fb_rows == 0) continue;
+        HIP_CHECK(hipSetDevice(d.device));
+        RtPartition part;                                       // exactly as render_frame builds it
+        part.stripe_rows = c.opt.stripe_rows;
+        part.rank = c.opt.part_rank * nd + k;
+        part.world = world;
+        part.local_rows = (int)d.fb_rows;
+        void* plane[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+        for (int q = 0; q < 5; q++) {
+            if (!(mask >> q & 1)) continue;
+            if (!d.d_guide[q]) HIP_CHECK(hipMalloc(&d.d_guide[q], d.fb_rows * c.nx * kGuideBytes[q]));
+            plane[q] = d.d_guide[q];
+        }
+        const RtGuidePlanes g = { static_cast<float*>(plane[0]), static_cast<float*>(plane[1]), static_cast<float*>(plane[2]),
+                                  static_cast<int32_t*>(plane[3]), static_cast<int32_t*>(plane[4]) };
+        HIP_CHECK(hipEventRecord(d.ev_start, d.stream));
+        if (c.is_spheres) {
+            RtSphereParams p;
+            memset(&p, 0, sizeof p);
+            p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
+            p.n = c.n_spheres; p.n_padded = c.n_padded; p.n_groups = c.n_groups; p.n_big_groups = c.n_big_groups; p.n_big = c.n_big;
+            p.spheres = d.d_spheres; p.rad = d.d_rad; p.global_scene = c.global_scene; p.mat_color = d.d_mat_color; p.mat_type = d.d_mat_type;
+            p.groups = d.d_groups; p.orig = d.d_orig; p.slot_of = d.d_slot_of;
+            p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
+            HIP_CHECK(rt_launch_guides_spheres(p, g, d.stream));
+        } else {
+            RtMeshParams p;
+            memset(&p, 0, sizeof p);
+            p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
+            p.tris = d.d_tris; p.bvh4 = d.d_bvh;
+            p.first_leaf = (uint32_t)c.num_bvh_nodes / 2; p.nppl = (uint32_t)c.nppl; p.bounds = c.bounds;
+            p.materials = d.d_materials;
+            p.tex_data = d.d_tex_data; p.tex_width = d.d_tex_width; p.tex_height = d.d_tex_height;
+            p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
+            p.floor_on = c.opt.floor ? 1 : 0; p.floor = c.floor;
+            HIP_CHECK(rt_launch_guides_mesh(p, g, d.stream));
+        }
+        HIP_CHECK(hipEventRecord(d.ev_stop, d.stream));
+        for (int q = 0; q < 5; q++)
+            if (plane[q]) deliver_stripes(d, part, static_cast<char*>(host[q]), static_cast<const char*>(plane[q]), kGuideBytes[q]);
+    }
+    double ms_max = 0.0;
+    for (int k = 0; k < nd; k++) {
+        DeviceState& d = c.devs[k];
+        if (d.fb_rows == 0) continue;
+        HIP_CHECK(hipSetDevice(d.device));
+        HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's arrays are complete on return
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, d.ev_start, d.ev_stop));
+        ms_max = std::max(ms_max, (double)ms);
+    }
+    HIP_CHECK(hipSetDevice(current));
+    c.guides_ms = ms_max;
+}
+
+double rtLastGuidesMs(void) { return g_ctx.guides_ms; }
 
 void setExternalFramebuffer(rt_vec3* fb) {
     RenderContext& c = g_ctx;

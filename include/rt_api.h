@@ -118,6 +118,40 @@ void rtResetProgressive(void);
 /* Replaces the camera for the following frames (runRenderer and passes) without re-uploading the scene; resets the progressive frame. */
 void setCamera(const rt_camera* cam);
 
+/* --- first-hit guide planes ------------------------------------------------------------------------------------------------
+ * Per-pixel features of the scene for a denoiser, a compositor, picking and a traversal-cost view.  For pixel (i, j) (j = global row, row 0 = bottom, like the
+ * framebuffer) the CENTRE RAY is get_ray (camera.h:8-12) without the lens offset and without jitter:
+ *     u = ((float)i + 0.5f) / (float)nx,  v = ((float)j + 0.5f) / (float)ny,  origin = cam.origin,  dir = unit(lower_left_corner + u*horizontal + v*vertical - origin)
+ * and its first hit is found exactly as bounce 0 of a path finds it (hit(), kernels.cu:325-360, which normalises dir once more for the intersection tests,
+ * the hit point and the normal's orientation; t_min = rt_render_options.t_min; the light sphere is never hit; sphere scenes: on equal t the lower caller
+ * index wins; mesh scenes: scene bounds, hitBvh, then kernel_scene.floor with rt_render_options.floor = 1).  All arithmetic fp32 under the PARITY rules, in
+ * both fp modes.  Planes of nx * ny entries, row 0 = bottom:
+ *   RT_GUIDE_ALBEDO  3 x float  hit: the albedo the first bounce's material_scatter works with - texture lookup or material.color for RT_DIFFUSE / RT_METAL /
+ *                               RT_GLASS (sphere scenes: materials[k].color); presets: hex 0x511845 for RT_FLOOR_COAT, RT_FLOOR_DIFFUSE and the floor plane, the
+ *                               checker colour at the hit point for RT_FLOOR_CHECKER, the model's base colour for RT_MODEL_COAT / RT_MODEL_DIFFUSE, (1, 1, 1)
+ *                               for RT_MODEL_GLOSSY / GLASS / TINTEDGLASS / SSS;  miss: the sky colour of dir (rt_render_options.sky)
+ *   RT_GUIDE_NORMAL  3 x float  hit: the shading normal of hit() - (p - center) / radius, unit(cross(v1 - v0, v2 - v0)) or floor.norm, turned against the
+ *                               ray; p = origin + t * direction;  miss: (0, 0, 0)
+ *   RT_GUIDE_DEPTH   float      hit: t, the distance along the unit direction;  miss: FLT_MAX
+ *   RT_GUIDE_PRIM    int32      hit: the caller's sphere index, the triangle's index in mesh.tris, RT_GUIDE_PRIM_FLOOR;  miss: RT_GUIDE_PRIM_NONE
+ *   RT_GUIDE_NODES   int32      mesh scenes only: internal BVH nodes visited by that closest-hit query (the reference's STATS count); 0 for a ray that misses
+ *                               the scene bounds; a ray that misses inside the bounds still carries its count
+ * They depend on scene, camera, nx, ny, t_min, sky, floor and the row partition only.
+ *
+ * renderGuides fills caller-owned host arrays (pageable is fine), one per plane named in `mask`, NULL for the others; blocking.  Like an external framebuffer,
+ * only the rows this process owns (stripe_rows, part_rank / part_world, all in-process devices) are written and the rest is left untouched, so ranks can fill
+ * one shared mapping.  Works after either init*, follows setCamera and setRenderOptions; setExternalFramebuffer has no effect on it.  It changes nothing an
+ * existing call observes: framebuffer, getRenderStats, rtLastLaunches, the progressive frame and rtProgressiveSamples stay as they were.  Misuse (rt error,
+ * exit 99): before init, mask 0 or with unknown bits, a requested plane whose pointer is NULL, RT_GUIDE_NODES on a sphere scene, rt_render_options.floor = 1 on a
+ * sphere scene (as runRenderer refuses it).  The device planes (at most
+ * 36 bytes per local pixel) are allocated by the first call on each device, only for the planes requested, and freed by cleanupRenderer and by a
+ * setRenderOptions that changes the device layout. */
+enum { RT_GUIDE_ALBEDO = 1, RT_GUIDE_NORMAL = 2, RT_GUIDE_DEPTH = 4, RT_GUIDE_PRIM = 8, RT_GUIDE_NODES = 16 };
+enum { RT_GUIDE_PRIM_NONE = -1, RT_GUIDE_PRIM_FLOOR = -2 };
+void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t* prim, int32_t* nodes);
+/* HIP-event time of the guide kernel of the last renderGuides in milliseconds, the largest over the in-process devices; 0 before the first call. */
+double rtLastGuidesMs(void);
+
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };
