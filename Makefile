@@ -37,10 +37,14 @@ $(OBJ)/probe_parity.o: $(CSRC)/rt_probe.hip $(KERNEL_HDRS) include/rt_probe.h | 
 	$(HIPCC) $(HIPFLAGS) -DRT_MODE_PARITY -ffp-contract=off -c $< -o $@
 $(OBJ)/probe_fast.o: $(CSRC)/rt_probe.hip $(KERNEL_HDRS) include/rt_probe.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRT_MODE_FAST -ffp-contract=fast -fno-hip-fp32-correctly-rounded-divide-sqrt -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The denoiser's kernels (denoiseFrame): one arithmetic, defined bit for bit, so one object built like the PARITY ones (no contraction, no vectorisers,
+# the default correctly rounded divide / sqrt and fp32 denormals).  Its own TU and header: the objects above do not depend on it.
+$(OBJ)/denoise.o: $(CSRC)/rt_kernels_denoise.hip $(CSRC)/rt_denoise.h include/rt_types.h include/rt_api.h | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o
+RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o
 
 $(PKG)/librt_mi355x.so: $(RT_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) -o $@

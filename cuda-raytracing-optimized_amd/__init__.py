@@ -131,7 +131,8 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "getDefaultRenderOptions", "setRenderOptions", "setExternalFramebuffer", "getRenderStats",
                     "rtDeviceCount", "rtApiVersion", "rtStructSizes", "rtLastLaunches",
                     "runRendererProgressive", "rtProgressiveSamples", "rtResetProgressive", "setCamera",
-                    "renderGuides", "rtLastGuidesMs"]
+                    "renderGuides", "rtLastGuidesMs",
+                    "rtDefaultDenoiseFlags", "denoiseFrame", "rtLastDenoiseMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
@@ -258,6 +259,12 @@ def load_renderer():
         r.renderGuides.restype = None
         r.rtLastGuidesMs.argtypes = []
         r.rtLastGuidesMs.restype = C.c_double
+        r.rtDefaultDenoiseFlags.argtypes = []
+        r.rtDefaultDenoiseFlags.restype = C.c_int
+        r.denoiseFrame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+        r.denoiseFrame.restype = None
+        r.rtLastDenoiseMs.argtypes = []
+        r.rtLastDenoiseMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -478,6 +485,42 @@ def renderGuides(mask=RT_GUIDE_ALBEDO | RT_GUIDE_NORMAL | RT_GUIDE_DEPTH | RT_GU
 def last_guides_ms():
     """HIP-event time of the guide kernel(s) of the last renderGuides (the largest over the in-process devices), in milliseconds."""
     return load_renderer().rtLastGuidesMs()
+
+
+# denoiseFrame (include/rt_api.h): the flags, the limits and the defaults
+RT_DENOISE_DEMODULATE, RT_DENOISE_SAME_PRIM = 1, 2
+RT_DENOISE_MAX_ITERATIONS, RT_DENOISE_MAX_SQUARINGS, RT_DENOISE_ALBEDO_FLOOR = 8, 7, 0.01
+
+
+def default_denoise_flags():
+    """DEMODULATE | SAME_PRIM for the sphere scene that is initialised, DEMODULATE for a mesh scene."""
+    return load_renderer().rtDefaultDenoiseFlags()
+
+
+def denoiseFrame(fb=None, iterations=5, flags=None, normal_squarings=5, sigma_z=0.01, sigma_c=1.0, out=None):
+    """The guide-driven edge-avoiding a-trous filter on a whole frame (include/rt_api.h).  fb: a (ny, nx, 3) float32 array, row 0 = bottom; None = the
+    framebuffer the renderer currently delivers into.  flags None = the scene kind's default.  Returns the denoised (ny, nx, 3) float32 array: a new one, or
+    `out` (a writable C-contiguous float32 array of that shape; it may be `fb` itself: in place).  Blocking; always the whole image on the first device."""
+    nx, ny = _state["nx"], _state["ny"]
+    r = load_renderer()
+    if flags is None:
+        flags = r.rtDefaultDenoiseFlags()
+    src = None
+    if fb is not None:
+        if not (isinstance(fb, np.ndarray) and fb.dtype == np.float32 and fb.flags["C_CONTIGUOUS"] and fb.shape == (ny, nx, 3)):
+            raise ValueError(f"denoiseFrame: fb must be a C-contiguous float32 array of shape {(ny, nx, 3)}")
+        src = fb.ctypes.data
+    if out is None:
+        out = np.empty((ny, nx, 3), np.float32)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.shape == (ny, nx, 3)):
+        raise ValueError(f"denoiseFrame: out must be a writable C-contiguous float32 array of shape {(ny, nx, 3)}")
+    r.denoiseFrame(src, out.ctypes.data, iterations, flags, normal_squarings, sigma_z, sigma_c)
+    return out
+
+
+def last_denoise_ms():
+    """HIP-event time of the kernels of the last denoiseFrame (prologue + iterations), in milliseconds; 0 before the first call."""
+    return load_renderer().rtLastDenoiseMs()
 
 
 def cleanupRenderer():

@@ -26,6 +26,7 @@
 
 #include "../../include/rt_api.h"
 #include "rt_params.h"
+#include "rt_denoise.h"
 
 namespace {
 
@@ -134,9 +135,24 @@ struct RenderContext {
     rt_render_stats stats;
     int prog_samples = 0;               // samples per pixel of the progressive frame so far (rtProgressiveSamples)
     double guides_ms = 0.0;             // rtLastGuidesMs
+    double denoise_ms = 0.0;            // rtLastDenoiseMs
+};
+
+// The denoiser's own device state (denoiseFrame): whole-image buffers on ONE device, the first in-process device, whatever rows that device renders.  Allocated
+// by the first call, freed by free_denoise (cleanupRenderer, every init*, a setRenderOptions that changes the device layout).
+struct DenoiseState {
+    int device = -1;
+    size_t npix = 0;
+    float* d_guide[4] = { nullptr, nullptr, nullptr, nullptr };     // albedo, normal, depth, prim of the whole image
+    rt_vec3* d_in = nullptr;
+    rt_vec3* d_out = nullptr;
+    float4* d_rec = nullptr;            // RtDenoiseParams::rec
+    float4* d_col[2] = { nullptr, nullptr };
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;               // events of its own: a frame's and the guides' timings stay what they were
 };
 
 RenderContext g_ctx;     // kernels.cu:145: one global context per process
+DenoiseState g_denoise;
 
 // rtLastLaunches: the records of the last runRenderer (RT_LAUNCH_WORDS each) and the device / fp mode of the launcher being called
 std::vector<int32_t> g_launches;
@@ -180,6 +196,22 @@ void free_device(DeviceState& d) {
     d = DeviceState();
 }
 
+void free_denoise() {
+    DenoiseState& n = g_denoise;
+    if (n.device < 0) return;
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(n.device));
+    HIP_CHECK(hipDeviceSynchronize());
+    auto fr = [](void* p) { if (p) HIP_CHECK(hipFree(p)); };
+    for (float* g : n.d_guide) fr(g);
+    fr(n.d_in); fr(n.d_out); fr(n.d_rec); fr(n.d_col[0]); fr(n.d_col[1]);
+    if (n.ev_start) HIP_CHECK(hipEventDestroy(n.ev_start));
+    if (n.ev_stop) HIP_CHECK(hipEventDestroy(n.ev_stop));
+    HIP_CHECK(hipSetDevice(current));
+    n = DenoiseState();
+}
+
 template <typename T>
 T* upload(const std::vector<T>& v) {
     if (v.empty()) return nullptr;
@@ -200,6 +232,7 @@ int local_rows_of(int ny, int sr, int rank, int world) {
 // (Re)creates the per-device state for the device list in g_ctx.opt.
 void setup_devices() {
     RenderContext& c = g_ctx;
+    free_denoise();                                         // (its buffers live on the first device of the list being replaced)
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -490,6 +523,7 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
 
 void cleanup_impl() {
     RenderContext& c = g_ctx;
+    free_denoise();
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -1068,6 +1102,90 @@ void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t*
 }
 
 double rtLastGuidesMs(void) { return g_ctx.guides_ms; }
+
+// Guide-driven preview denoiser (rt_api.h).  The filter needs neighbours across stripe boundaries, so it works on the whole image on the first
+// in-process device (every device holds the whole scene, setup_devices) with buffers, guide planes and events of its own: like renderGuides it reads and
+// writes nothing of a frame's state.
+int rtDefaultDenoiseFlags(void) {
+    if (!g_ctx.initialised) rt_fail("rtDefaultDenoiseFlags before init");
+    return g_ctx.is_spheres ? (RT_DENOISE_DEMODULATE | RT_DENOISE_SAME_PRIM) : RT_DENOISE_DEMODULATE;     // one id = one object / one id = one triangle
+}
+
+void denoiseFrame(const rt_vec3* in, rt_vec3* out, int iterations, int flags, int normal_squarings, float sigma_z, float sigma_c) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("denoiseFrame before init");
+    if (!out) rt_fail("denoiseFrame: out is null");
+    if (iterations < 1 || iterations > RT_DENOISE_MAX_ITERATIONS) rt_fail("denoiseFrame: iterations must be 1 .. RT_DENOISE_MAX_ITERATIONS");
+    if (normal_squarings < 0 || normal_squarings > RT_DENOISE_MAX_SQUARINGS) rt_fail("denoiseFrame: normal_squarings must be 0 .. RT_DENOISE_MAX_SQUARINGS");
+    if ((flags & ~(RT_DENOISE_DEMODULATE | RT_DENOISE_SAME_PRIM)) != 0) rt_fail("denoiseFrame: unknown flag bits");
+    if (!std::isfinite(sigma_z) || !(sigma_z > 0.0f)) rt_fail("denoiseFrame: sigma_z must be finite and positive");
+    if (!std::isfinite(sigma_c)) rt_fail("denoiseFrame: sigma_c must be finite (<= 0 switches the colour weight off)");
+    if (c.is_spheres && c.opt.floor) rt_fail("denoiseFrame: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
+    if (!in) in = c.h_ext ? c.h_ext : c.h_fb;
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    DeviceState& d = c.devs[0];
+    HIP_CHECK(hipSetDevice(d.device));
+    DenoiseState& n = g_denoise;
+    const size_t npix = (size_t)c.nx * c.ny;
+    if (n.device != d.device || n.npix != npix) {
+        free_denoise();
+        HIP_CHECK(hipSetDevice(d.device));
+        n.device = d.device; n.npix = npix;
+        const size_t guide_bytes[4] = { 12, 12, 4, 4 };
+        for (int q = 0; q < 4; q++) HIP_CHECK(hipMalloc((void**)&n.d_guide[q], npix * guide_bytes[q]));
+        HIP_CHECK(hipMalloc((void**)&n.d_in, npix * sizeof(rt_vec3)));
+        HIP_CHECK(hipMalloc((void**)&n.d_out, npix * sizeof(rt_vec3)));
+        HIP_CHECK(hipMalloc((void**)&n.d_rec, 2 * npix * sizeof(float4)));
+        HIP_CHECK(hipMalloc((void**)&n.d_col[0], npix * sizeof(float4)));
+        HIP_CHECK(hipMalloc((void**)&n.d_col[1], npix * sizeof(float4)));
+        HIP_CHECK(hipEventCreate(&n.ev_start));
+        HIP_CHECK(hipEventCreate(&n.ev_stop));
+    }
+    HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));   // before anything is written: out may be in
+    RtPartition part;                                           // the whole image as one member's rows
+    part.stripe_rows = c.opt.stripe_rows; part.rank = 0; part.world = 1; part.local_rows = c.ny;
+    const RtGuidePlanes g = { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr };
+    if (c.is_spheres) {
+        RtSphereParams p;
+        memset(&p, 0, sizeof p);
+        p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
+        p.n = c.n_spheres; p.n_padded = c.n_padded; p.n_groups = c.n_groups; p.n_big_groups = c.n_big_groups; p.n_big = c.n_big;
+        p.spheres = d.d_spheres; p.rad = d.d_rad; p.global_scene = c.global_scene; p.mat_color = d.d_mat_color; p.mat_type = d.d_mat_type;
+        p.groups = d.d_groups; p.orig = d.d_orig; p.slot_of = d.d_slot_of;
+        p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
+        HIP_CHECK(rt_launch_guides_spheres(p, g, d.stream));
+    } else {
+        RtMeshParams p;
+        memset(&p, 0, sizeof p);
+        p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
+        p.tris = d.d_tris; p.bvh4 = d.d_bvh;
+        p.first_leaf = (uint32_t)c.num_bvh_nodes / 2; p.nppl = (uint32_t)c.nppl; p.bounds = c.bounds;
+        p.materials = d.d_materials;
+        p.tex_data = d.d_tex_data; p.tex_width = d.d_tex_width; p.tex_height = d.d_tex_height;
+        p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
+        p.floor_on = c.opt.floor ? 1 : 0; p.floor = c.floor;
+        HIP_CHECK(rt_launch_guides_mesh(p, g, d.stream));
+    }
+    RtDenoiseParams q;
+    memset(&q, 0, sizeof q);
+    q.cam = c.cam; q.nx = c.nx; q.ny = c.ny;
+    q.albedo = n.d_guide[0]; q.normal = n.d_guide[1]; q.depth = n.d_guide[2]; q.prim = reinterpret_cast<const int32_t*>(n.d_guide[3]);
+    q.in = n.d_in; q.out = n.d_out; q.rec = n.d_rec; q.col[0] = n.d_col[0]; q.col[1] = n.d_col[1];
+    q.flags = flags; q.normal_squarings = normal_squarings; q.sigma_z = sigma_z; q.sigma_c = sigma_c;
+    HIP_CHECK(hipEventRecord(n.ev_start, d.stream));
+    HIP_CHECK(rt_launch_denoise_prologue(q, d.stream));
+    for (int it = 0; it < iterations; it++) HIP_CHECK(rt_launch_denoise_iteration(q, it, it == iterations - 1, d.stream));
+    HIP_CHECK(hipEventRecord(n.ev_stop, d.stream));
+    HIP_CHECK(hipMemcpyAsync(out, n.d_out, npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));                  // blocking: out is complete on return
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, n.ev_start, n.ev_stop));
+    c.denoise_ms = (double)ms;
+    HIP_CHECK(hipSetDevice(current));
+}
+
+double rtLastDenoiseMs(void) { return g_ctx.denoise_ms; }
 
 void setExternalFramebuffer(rt_vec3* fb) {
     RenderContext& c = g_ctx;

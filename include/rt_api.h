@@ -152,6 +152,53 @@ void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t*
 /* HIP-event time of the guide kernel of the last renderGuides in milliseconds, the largest over the in-process devices; 0 before the first call. */
 double rtLastGuidesMs(void);
 
+/* --- guide-driven preview denoiser ----------------------------------------------------------------------------------------
+ * Turns a low-sample frame (runRendererProgressive, runRenderer) into a usable preview on the device: an edge-avoiding a-trous wavelet filter (Dammertz et al.
+ * 2010, the spatial half of SVGF) steered by the guide planes above.  All arithmetic is fp32 with + - * / max abs only, every product and sum rounded on its
+ * own (no FMA), operands in the order written, so the result is defined bit for bit (DESIGN.md 3.11 has the reasons for the weights).  Per pixel p = (i, j):
+ * prim, n, a, t are the guide planes; valid(p) = prim(p) != RT_GUIDE_PRIM_NONE (the floor is valid); P(p)[k] = origin[k] + t * d[k] with d the centre ray's
+ * direction normalised once more (the p of RT_GUIDE_NORMAL); rz(p) = 1 / (sigma_z * t(p)); with RT_DENOISE_DEMODULATE m(p)[k] = max(a(p)[k],
+ * RT_DENOISE_ALBEDO_FLOOR) and c0(p)[k] = in(p)[k] / m(p)[k], without it c0 = in (no division, no multiplication at the end).
+ * Iteration it = 0 .. iterations-1: s = 1 << it, K = {0.375, 0.25, 0.0625}, and with sigma_c > 0: sc = sigma_c * 2^-it, rc = 1 / (sc * sc).  For every valid p:
+ *     sum = (0,0,0); wsum = 0
+ *     for dy = -2..2 (outer), dx = -2..2 (inner):
+ *         q = (i + dx*s, j + dy*s);  the tap adds nothing if q is outside the image or !valid(q)
+ *         h = K[|dx|] * K[|dy|]
+ *         if dx == 0 and dy == 0:  w = h
+ *         else:
+ *             dn = n(p).x*n(q).x + n(p).y*n(q).y + n(p).z*n(q).z;  wn = max(dn, 0);  normal_squarings times: wn = wn * wn
+ *             e = P(q) - P(p);  pd = |n(p).x*e.x + n(p).y*e.y + n(p).z*e.z|;  wz = max(1 - pd * rz(p), 0);  wz = wz * wz
+ *             w = h * wn * wz                                                       (left to right)
+ *             if sigma_c > 0:  dc = c(p) - c(q);  d2 = dc.x*dc.x + dc.y*dc.y + dc.z*dc.z;  wc = max(1 - d2 * rc, 0);  wc = wc * wc;  w = w * wc
+ *             if RT_DENOISE_SAME_PRIM and prim(p) != prim(q):  w = 0
+ *         sum[k] += w * c(q)[k];  wsum += w
+ *     c'(p)[k] = sum[k] / wsum                                                      (wsum >= 9/64: the centre tap)
+ * c is the previous iteration's plane, c' the next.  At the end out(p)[k] = c(p)[k] * m(p)[k].  Pixels with !valid(p) copy in(p) to out(p) bit for bit and are
+ * never a tap.  max(x, 0) is x > 0 ? x : 0 (0 for a NaN).  Non-finite input is not treated specially; denormal products are kept.
+ *
+ * denoiseFrame: `in` = nx*ny rt_vec3, row 0 = bottom, any host memory; NULL = the framebuffer the renderer currently delivers into (the external one if set,
+ * else the library's own).  `out` = nx*ny rt_vec3 of caller-owned host memory, never NULL; it may be `in` (the input is uploaded before anything is written).
+ * Blocking.  The filter needs neighbours across stripe boundaries, so it always works on the WHOLE image on ONE device, the first in-process device, whatever
+ * stripe_rows, num_devices, part_rank and part_world are (it computes whole-image guide planes there itself); a multi-rank caller denoises on one rank after
+ * its gather.  Follows setCamera and setRenderOptions (t_min, sky, floor) as the guides do.  Like renderGuides it changes nothing an existing call observes:
+ * framebuffer (unless passed as `out`), getRenderStats, rtLastLaunches, the progressive frame, rtProgressiveSamples and rtLastGuidesMs stay as they were.  Its
+ * device buffers (120 bytes per pixel) are allocated by the first call and freed by cleanupRenderer, every init* and a setRenderOptions that changes the
+ * device layout.  Defaults: iterations 5, normal_squarings 5, sigma_z 0.01f, sigma_c 1.0f, flags = rtDefaultDenoiseFlags: DEMODULATE | SAME_PRIM for sphere
+ * scenes (one id = one object), DEMODULATE for mesh scenes (one id = one triangle).  sigma_c is the noise scale of the demodulated colour and the caller's to
+ * follow, roughly proportional to 1 / sqrt(samples per pixel); sigma_c <= 0 switches the colour weight off.  Misuse (rt error, exit 99): before init,
+ * out NULL, iterations outside 1 .. RT_DENOISE_MAX_ITERATIONS, normal_squarings outside 0 .. RT_DENOISE_MAX_SQUARINGS, unknown flag bits, sigma_z not finite
+ * or <= 0, sigma_c not finite, rt_render_options.floor = 1 on a sphere scene. */
+enum { RT_DENOISE_DEMODULATE = 1, RT_DENOISE_SAME_PRIM = 2 };
+#define RT_DENOISE_MAX_ITERATIONS 8
+#define RT_DENOISE_MAX_SQUARINGS  7
+#define RT_DENOISE_ALBEDO_FLOOR   0.01f
+/* The default flags for the scene that is initialised; rt error before init. */
+int rtDefaultDenoiseFlags(void);
+void denoiseFrame(const rt_vec3* in, rt_vec3* out, int iterations, int flags, int normal_squarings, float sigma_z, float sigma_c);
+/* HIP-event time of the kernels of the last denoiseFrame (prologue + iterations with the fused epilogue; not its guide kernel, not the copies) in milliseconds;
+ * 0 before the first call. */
+double rtLastDenoiseMs(void);
+
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };

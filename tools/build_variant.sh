@@ -8,7 +8,7 @@ cd "$ROOT"
 O=build/ab/obj_$NAME
 mkdir -p $O
 make -s -j8 OBJ=$O HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $*" \
-     $O/renderer.o $O/probe_parity.o $O/probe_fast.o $O/spheres_parity.o $O/spheres_fast.o $O/mesh_parity.o $O/mesh_fast.o
-hipcc --offload-arch=gfx950 -shared -fPIC $O/renderer.o $O/probe_parity.o $O/probe_fast.o $O/spheres_parity.o $O/spheres_fast.o $O/mesh_parity.o $O/mesh_fast.o -o build/ab/$NAME.so
+     $O/renderer.o $O/probe_parity.o $O/probe_fast.o $O/spheres_parity.o $O/spheres_fast.o $O/mesh_parity.o $O/mesh_fast.o $O/denoise.o
+hipcc --offload-arch=gfx950 -shared -fPIC $O/renderer.o $O/probe_parity.o $O/probe_fast.o $O/spheres_parity.o $O/spheres_fast.o $O/mesh_parity.o $O/mesh_fast.o $O/denoise.o -o build/ab/$NAME.so
 rm -rf $O
 echo "built build/ab/$NAME.so"
