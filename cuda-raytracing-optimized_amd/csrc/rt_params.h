@@ -60,7 +60,8 @@ struct RtSphereParams {
     const struct RtSphereParams* self;   // a device copy of this struct (launcher): the kernel re-reads what it needs once per sample / pixel from it
     int32_t basic_materials;    // 1 = every material is RT_DIFFUSE, RT_METAL or RT_GLASS (no look preset): the lean shading instantiation may run (material_scatter<BASIC>)
     int32_t global_scene;       // 1 = the scene does not fit the LDS: the kernels read these arrays from global memory (L2) instead of staging them
-    const float4* groups;       // 2 x n_groups: inflated AABB (lo.xyz, hi.xyz) of each group
+    const float4* groups;       // 3 x n_groups: the tight AABB of each group, one entry per axis (lo, hi, lo, -), then the rt_cell_f4(n_groups) entries of the cell
+                                // tables (below).  The boxes are not inflated: the culling is exact through the per-ray margin of make_box_ray
     // per-ray culling margin (exactness of the culling for ANY ray origin, see make_box_ray): centre and radius of the
     // small spheres' centres, k1 = K eps / (2 r_min), k2 = sqrt(K eps), k3 = slab-test rounding per unit of coordinate,
     // coord_max = largest |coordinate| of any group box

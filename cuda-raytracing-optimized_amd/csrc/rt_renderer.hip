@@ -45,8 +45,41 @@ void hip_check(hipError_t result, const char* func, const char* file, int line) 
     exit(99);
 }
 
+// Device memory: every allocation of a DeviceState / DenoiseState goes through dev_alloc, which notes the pointer in its owner's `owned`, and free_device /
+// free_denoise release what that record holds - a buffer cannot be allocated without being freed.  The record is plain data walked by those two functions
+// only, never by a destructor: exit(99) runs the destructors of the globals below with buffers live, and nothing of HIP may be called then; the states stay copyable.
+template <typename T>
+T* dev_alloc(std::vector<void*>& owned, size_t count) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, count * sizeof(T)));
+    owned.push_back(p);
+    return static_cast<T*>(p);
+}
+
+template <typename T>
+void dev_release(std::vector<void*>& owned, T*& p) {       // one buffer, before it is allocated again with another size
+    if (!p) return;
+    owned.erase(std::find(owned.begin(), owned.end(), static_cast<void*>(p)));
+    HIP_CHECK(hipFree(p));
+    p = nullptr;
+}
+
+void dev_release_all(std::vector<void*>& owned) {
+    for (void* p : owned) HIP_CHECK(hipFree(p));
+    owned.clear();
+}
+
+template <typename T>
+T* upload(std::vector<void*>& owned, const std::vector<T>& v) {
+    if (v.empty()) return nullptr;
+    T* p = dev_alloc<T>(owned, v.size());
+    HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return p;
+}
+
 struct DeviceState {
     int device = 0;
+    std::vector<void*> owned;           // every device allocation of this state (dev_alloc)
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     RtSphereParams* d_params = nullptr; // device copy of the sphere kernel's parameter block (RtSphereParams::self), one per DeviceState
@@ -66,7 +99,6 @@ struct DeviceState {
     float4* d_leaf_tri = nullptr;
     uint32_t* d_leaf_ofs = nullptr;
     rt_material* d_materials = nullptr;
-    std::vector<float*> d_tex;
     float** d_tex_data = nullptr;
     int32_t* d_tex_width = nullptr;
     int32_t* d_tex_height = nullptr;
@@ -101,33 +133,24 @@ struct RenderContext {
     rt_vec3* h_fb = nullptr;            // pinned, nx*ny, handed to the caller
     rt_vec3* h_ext = nullptr;           // caller-owned framebuffer (setExternalFramebuffer), or null
     bool ext_registered = false;        // h_ext is page-locked and device-mapped (hipHostRegister succeeded): the kernels may store into it directly
-    // host copies of the scene (so devices can be (re)configured by setRenderOptions)
+    // The scene's constants in parameter-block form, every pointer null: written once at init (build_sphere_groups / build_mesh_scene), the start of every
+    // parameter block (sphere_params / mesh_params).  Sphere scenes: the slot and group counts, global_scene, basic_materials, the culling constants and the
+    // cell tables' geometry; mesh scenes: first_leaf, nppl, leaf_sentinels_trailing, lean_ok, bounds and floor (kernel_scene.floor, helper_structs.h:219).
+    RtSphereParams sphere_scene = {};
+    RtMeshParams mesh_scene = {};
+    // host copies of the scene's arrays (so devices can be (re)configured by setRenderOptions)
     std::vector<float4> h_spheres;      // the kernel's sphere image (rt_params.h): (n_padded + n_groups) x (cx, cy, cz, r*r)
     std::vector<float> h_rad;           // n_padded radii
-    int global_scene = 0;
-    int basic_materials = 0;            // every material is RT_DIFFUSE / RT_METAL / RT_GLASS (RtSphereParams::basic_materials)
     std::vector<float4> h_mat_color;
     std::vector<int32_t> h_mat_type;
-    std::vector<float4> h_groups;       // three float4 per group of kSphereGroup slots: per axis (lo, hi, lo, -) of the tight AABB
-    float cull_c[3] = { 0, 0, 0 }, cull_radius = 0, cull_k1 = 0, cull_k2 = 0, cull_k3 = 0, cull_coord_max = 0, pair_k0 = 0;
-    int box_shared_axis = 0;
-    int cell_on = 0;
-    float cell_scale[3] = { 0, 0, 0 }, cell_off[3] = { 0, 0, 0 }, ubox[6] = { 0, 0, 0, 0, 0, 0 };
-    int cell_axes = 0;
-    float box_shared_lo = 0, box_shared_hi = 0;
+    std::vector<float4> h_groups;       // three float4 per group of kSphereGroup slots: per axis (lo, hi, lo, -) of the tight AABB; then the cell tables
     std::vector<int32_t> h_orig;        // slot -> caller's sphere index (INT_MAX = pad)
     std::vector<int32_t> h_slot_of;     // caller's sphere index -> slot
-    int n_spheres = 0, n_padded = 0, n_groups = 0, n_big_groups = 0, n_big = 0;
     std::vector<rt_triangle> h_tris;
     std::vector<float4> h_bvh;          // numBvhNodes * 24 B viewed as float4 (padded)
     std::vector<float> h_bvh_axis;      // RtMeshParams::bvh_axis
     std::vector<float4> h_leaf_tri;     // RtMeshParams::leaf_tri (empty = not built: sentinels inside leaves, or more than 16 M triangles)
     std::vector<uint32_t> h_leaf_ofs;   // RtMeshParams::leaf_ofs
-    int num_bvh_nodes = 0;
-    int nppl = 0;
-    int leaf_sentinels_trailing = 1;
-    rt_bbox bounds;
-    rt_plane floor;                     // kernel_scene.floor (helper_structs.h:219): used when rt_render_options.floor = 1
     std::vector<rt_material> h_materials;
     std::vector<std::vector<float>> h_tex;
     std::vector<int32_t> h_tex_w, h_tex_h;
@@ -143,6 +166,7 @@ struct RenderContext {
 struct DenoiseState {
     int device = -1;
     size_t npix = 0;
+    std::vector<void*> owned;           // its device allocations (dev_alloc)
     float* d_guide[4] = { nullptr, nullptr, nullptr, nullptr };     // albedo, normal, depth, prim of the whole image
     rt_vec3* d_in = nullptr;
     rt_vec3* d_out = nullptr;
@@ -180,15 +204,7 @@ void default_options(rt_render_options* o, int spheres) {
 void free_device(DeviceState& d) {
     HIP_CHECK(hipSetDevice(d.device));
     if (d.stream) HIP_CHECK(hipStreamSynchronize(d.stream));
-    auto fr = [](void* p) { if (p) HIP_CHECK(hipFree(p)); };
-    fr(d.d_spheres); fr(d.d_rad); fr(d.d_mat_color); fr(d.d_mat_type); fr(d.d_groups); fr(d.d_orig); fr(d.d_slot_of);
-    fr(d.d_tris); fr(d.d_bvh); fr(d.d_bvh_axis); fr(d.d_leaf_tri); fr(d.d_leaf_ofs); fr(d.d_materials);
-    for (float* t : d.d_tex) fr(t);
-    fr(d.d_tex_data); fr(d.d_tex_width); fr(d.d_tex_height);
-    fr(d.d_fb); fr(d.d_counters); fr(d.d_queue); fr(d.d_wave_dbg); fr(d.d_order); fr(d.d_partial); fr(d.d_px_state); fr(d.d_px_rays); fr(d.d_ord_state); fr(d.d_ord_rays); fr(d.d_ord_rec);
-    fr(d.d_acc_state); fr(d.d_acc_rays);
-    for (void* g : d.d_guide) fr(g);
-    fr(d.d_params);
+    dev_release_all(d.owned);
     if (d.h_params) HIP_CHECK(hipHostFree(d.h_params));
     if (d.ev_start) HIP_CHECK(hipEventDestroy(d.ev_start));
     if (d.ev_stop) HIP_CHECK(hipEventDestroy(d.ev_stop));
@@ -203,22 +219,11 @@ void free_denoise() {
     HIP_CHECK(hipGetDevice(&current));
     HIP_CHECK(hipSetDevice(n.device));
     HIP_CHECK(hipDeviceSynchronize());
-    auto fr = [](void* p) { if (p) HIP_CHECK(hipFree(p)); };
-    for (float* g : n.d_guide) fr(g);
-    fr(n.d_in); fr(n.d_out); fr(n.d_rec); fr(n.d_col[0]); fr(n.d_col[1]);
+    dev_release_all(n.owned);
     if (n.ev_start) HIP_CHECK(hipEventDestroy(n.ev_start));
     if (n.ev_stop) HIP_CHECK(hipEventDestroy(n.ev_stop));
     HIP_CHECK(hipSetDevice(current));
     n = DenoiseState();
-}
-
-template <typename T>
-T* upload(const std::vector<T>& v) {
-    if (v.empty()) return nullptr;
-    T* p = nullptr;
-    HIP_CHECK(hipMalloc((void**)&p, v.size() * sizeof(T)));
-    HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return p;
 }
 
 // Rows of the image owned by partition member `rank` of `world` with stripes of `sr` rows.
@@ -250,48 +255,46 @@ void setup_devices() {
         HIP_CHECK(hipEventCreate(&d.ev_start));
         HIP_CHECK(hipEventCreate(&d.ev_stop));
         if (c.is_spheres) {
-            HIP_CHECK(hipMalloc((void**)&d.d_params, sizeof(RtSphereParams)));
+            d.d_params = dev_alloc<RtSphereParams>(d.owned, 1);
             HIP_CHECK(hipHostMalloc((void**)&d.h_params, sizeof(RtSphereParams), hipHostMallocDefault));
-            d.d_spheres = upload(c.h_spheres);
-            d.d_rad = upload(c.h_rad);
-            d.d_mat_color = upload(c.h_mat_color);
-            d.d_mat_type = upload(c.h_mat_type);
-            d.d_groups = upload(c.h_groups);
-            d.d_orig = upload(c.h_orig);
-            d.d_slot_of = upload(c.h_slot_of);
+            d.d_spheres = upload(d.owned, c.h_spheres);
+            d.d_rad = upload(d.owned, c.h_rad);
+            d.d_mat_color = upload(d.owned, c.h_mat_color);
+            d.d_mat_type = upload(d.owned, c.h_mat_type);
+            d.d_groups = upload(d.owned, c.h_groups);
+            d.d_orig = upload(d.owned, c.h_orig);
+            d.d_slot_of = upload(d.owned, c.h_slot_of);
         } else {
-            d.d_tris = upload(c.h_tris);
-            d.d_bvh = upload(c.h_bvh);
-            d.d_bvh_axis = upload(c.h_bvh_axis);
-            d.d_leaf_tri = upload(c.h_leaf_tri);
-            d.d_leaf_ofs = upload(c.h_leaf_ofs);
-            d.d_materials = upload(c.h_materials);
-            const int nt = (int)c.h_tex.size();
-            if (nt > 0) {
-                for (int t = 0; t < nt; t++) d.d_tex.push_back(upload(c.h_tex[t]));
-                std::vector<float*> ptrs(d.d_tex.begin(), d.d_tex.end());
-                d.d_tex_data = upload(ptrs);
-                d.d_tex_width = upload(c.h_tex_w);
-                d.d_tex_height = upload(c.h_tex_h);
+            d.d_tris = upload(d.owned, c.h_tris);
+            d.d_bvh = upload(d.owned, c.h_bvh);
+            d.d_bvh_axis = upload(d.owned, c.h_bvh_axis);
+            d.d_leaf_tri = upload(d.owned, c.h_leaf_tri);
+            d.d_leaf_ofs = upload(d.owned, c.h_leaf_ofs);
+            d.d_materials = upload(d.owned, c.h_materials);
+            if (!c.h_tex.empty()) {
+                std::vector<float*> ptrs;
+                for (const std::vector<float>& t : c.h_tex) ptrs.push_back(upload(d.owned, t));
+                d.d_tex_data = upload(d.owned, ptrs);
+                d.d_tex_width = upload(d.owned, c.h_tex_w);
+                d.d_tex_height = upload(d.owned, c.h_tex_h);
             }
         }
         const int world = c.opt.part_world * nd, rank = c.opt.part_rank * nd + k;
         d.fb_rows = (size_t)local_rows_of(c.ny, c.opt.stripe_rows, rank, world);
-        if (d.fb_rows > 0) HIP_CHECK(hipMalloc((void**)&d.d_fb, d.fb_rows * c.nx * sizeof(rt_vec3)));
-        if (d.fb_rows > 0) {        // work-order lists of the persistent kernels: 3 x (pixels padded to 8x8 tiles)
+        if (d.fb_rows > 0) {
+            const size_t pixels = d.fb_rows * c.nx;
             const size_t padded = (size_t)((c.nx + 7) / 8) * ((d.fb_rows + 7) / 8) * 64;
-            HIP_CHECK(hipMalloc((void**)&d.d_order, 3 * padded * sizeof(uint32_t)));
-            {                                                       // the two-dispatch frames of both kernels: parked state + its copy in queue order
-                HIP_CHECK(hipMalloc((void**)&d.d_px_state, d.fb_rows * c.nx * sizeof(float4)));
-                HIP_CHECK(hipMalloc((void**)&d.d_px_rays, d.fb_rows * c.nx * sizeof(uint32_t)));
-                HIP_CHECK(hipMalloc((void**)&d.d_ord_state, padded * sizeof(float4)));
-                HIP_CHECK(hipMalloc((void**)&d.d_ord_rays, padded * sizeof(uint32_t)));
-                HIP_CHECK(hipMalloc((void**)&d.d_ord_rec, padded * 2 * sizeof(float4)));
-            }
+            d.d_fb = dev_alloc<rt_vec3>(d.owned, pixels);
+            d.d_order = dev_alloc<uint32_t>(d.owned, 3 * padded);       // work-order lists of the persistent kernels: 3 x (pixels padded to 8x8 tiles)
+            d.d_px_state = dev_alloc<float4>(d.owned, pixels);          // the two-dispatch frames of both kernels: parked state + its copy in queue order
+            d.d_px_rays = dev_alloc<uint32_t>(d.owned, pixels);
+            d.d_ord_state = dev_alloc<float4>(d.owned, padded);
+            d.d_ord_rays = dev_alloc<uint32_t>(d.owned, padded);
+            d.d_ord_rec = dev_alloc<float4>(d.owned, padded * 2);
         }
-        HIP_CHECK(hipMalloc((void**)&d.d_counters, sizeof(RtCounters)));
+        d.d_counters = dev_alloc<RtCounters>(d.owned, 1);
         HIP_CHECK(hipMemset(d.d_counters, 0, sizeof(RtCounters)));
-        HIP_CHECK(hipMalloc((void**)&d.d_queue, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords));          // one block of queue words per XCD (rt_params.h)
+        d.d_queue = dev_alloc<uint32_t>(d.owned, (size_t)kXcdQueues * kXcdQueueWords);     // one block of queue words per XCD (rt_params.h)
         HIP_CHECK(hipMemset(d.d_queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords));
         c.devs.push_back(d);
     }
@@ -329,8 +332,9 @@ void common_init(const rt_camera& cam, rt_vec3** fb, int nx, int ny, int maxDept
 //   * "big" spheres (radius > 4 x the median radius: the ground and the three unit spheres of the benchmark scene)
 //     come first; their groups are always scanned, by every lane, and give each ray a first `closest`;
 //   * "small" spheres are split recursively at medians so that the G slots of a group are neighbours in space; each
-//     group of G gets an axis-aligned bounding box, inflated well beyond fp32 rounding (1 % + 1e-4 of the scene
-//     extent), which the kernel uses to skip the group for rays that cannot reach it before their current hit;
+//     group of G gets its tight axis-aligned bounding box, three entries (lo, hi, lo, -), one per axis, with the cell
+//     tables behind them; the kernel uses it to skip the group for rays that cannot reach it before their current hit,
+//     and the culling is exact through the margin every ray adds for itself (make_box_ray), not through an inflation;
 //   * pad slots fill the last group of each class and the tail up to a multiple of 64 slots; they carry
 //     orig = INT_MAX and are never accepted.
 // Scanning in slot order instead of the caller's order cannot change the result: the kernel resolves equal-t ties
@@ -386,26 +390,25 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
     for (int k : ordered) slots.push_back(k);
     while (slots.size() % 64) slots.push_back(-1);
 
-    double extent = 1.0;
-    for (int a = 0; a < 3; a++) if (hi[a] > lo[a]) extent = std::max(extent, hi[a] - lo[a]);
-    c.n_spheres = n;
-    c.n_padded = (int)slots.size();
-    c.n_groups = c.n_padded / G;
-    c.n_big_groups = n_big_groups;
-    c.n_big = (int)big.size();
+    RtSphereParams& sp = c.sphere_scene;                         // the scene's constants go straight into the parameter-block template
+    sp.n = n;
+    sp.n_padded = (int)slots.size();
+    sp.n_groups = sp.n_padded / G;
+    sp.n_big_groups = n_big_groups;
+    sp.n_big = (int)big.size();
     const auto sidx = [](int slot) { return slot + slot / kSphereGroup; };
-    c.h_spheres.assign(c.n_padded + c.n_groups, make_float4(0.0f, 3.0e18f, 0.0f, 0.0f));      // pad: radius 0, far away
-    c.h_rad.assign(c.n_padded, 0.0f);
-    c.h_mat_color.assign(c.n_padded, make_float4(0, 0, 0, 0));
-    c.h_mat_type.assign(c.n_padded, RT_DIFFUSE);
-    c.h_orig.assign(c.n_padded, INT_MAX);
+    c.h_spheres.assign(sp.n_padded + sp.n_groups, make_float4(0.0f, 3.0e18f, 0.0f, 0.0f));      // pad: radius 0, far away
+    c.h_rad.assign(sp.n_padded, 0.0f);
+    c.h_mat_color.assign(sp.n_padded, make_float4(0, 0, 0, 0));
+    c.h_mat_type.assign(sp.n_padded, RT_DIFFUSE);
+    c.h_orig.assign(sp.n_padded, INT_MAX);
     c.h_slot_of.assign(n, 0);
     // bounds: 3 float4 per group, one per AXIS: (lo, hi, lo, -) - a ray reads two consecutive floats, at 0 or at 1 by the sign of its direction,
     // and has (near plane, far plane).  Empty group: lo > hi on every axis (never reachable).
-    c.h_groups.assign((size_t)c.n_groups * 3, make_float4(3.0e38f, -3.0e38f, 3.0e38f, 0.0f));
-    c.basic_materials = 1;
-    for (int k = 0; k < n; k++) if (materials[k].type != RT_DIFFUSE && materials[k].type != RT_METAL && materials[k].type != RT_GLASS) c.basic_materials = 0;
-    for (int s = 0; s < c.n_padded; s++) {
+    c.h_groups.assign((size_t)sp.n_groups * 3, make_float4(3.0e38f, -3.0e38f, 3.0e38f, 0.0f));
+    sp.basic_materials = 1;
+    for (int k = 0; k < n; k++) if (materials[k].type != RT_DIFFUSE && materials[k].type != RT_METAL && materials[k].type != RT_GLASS) sp.basic_materials = 0;
+    for (int s = 0; s < sp.n_padded; s++) {
         const int k = slots[s];
         if (k < 0) continue;
         const float r = spheres[k].radius;
@@ -426,7 +429,7 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
     float shared_lo[3] = { 0, 0, 0 }, shared_hi[3] = { 0, 0, 0 };
     bool shared_ok[3] = { true, true, true };
     int n_boxes = 0;
-    for (int g = n_big_groups; g < c.n_groups; g++) {
+    for (int g = n_big_groups; g < sp.n_groups; g++) {
         double blo[3] = { 1e300, 1e300, 1e300 }, bhi[3] = { -1e300, -1e300, -1e300 };
         int cnt = 0;
         for (int s = g * G; s < g * G + G; s++) {
@@ -452,8 +455,8 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
         }
         n_boxes++;
     }
-    c.box_shared_axis = 0;
-    for (int a = 2; a >= 0; a--) if (n_boxes > 0 && shared_ok[a]) { c.box_shared_axis = a + 1; c.box_shared_lo = shared_lo[a]; c.box_shared_hi = shared_hi[a]; }
+    sp.box_shared_axis = 0;
+    for (int a = 2; a >= 0; a--) if (n_boxes > 0 && shared_ok[a]) { sp.box_shared_axis = a + 1; sp.box_shared_lo = shared_lo[a]; sp.box_shared_hi = shared_hi[a]; }
     // Cell tables (rt_params.h, group_needs_cells): for scenes of up to 32 x kCellWordsMax groups, on all three axes.  Bit g of a word = small group g.
     // begins[c] = boxes with lo <= upper edge of cell c, ends[c] = boxes with hi >= lower edge of cell c, both with a slack of kCellSlack cells for
     // the rounding of the device's cell index (x * scale + off in fp32 with |index| <= kCellCount: off by < 2e-5 cells); the last begins-word and the
@@ -461,34 +464,34 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
     // nothing it should not.  An axis on which every box has the same extent (spheres resting on a plane: the vertical one) gets no bit in cell_axes:
     // its table could not reject anything.  ubox = the union of the boxes, to which the kernel clips the ray before it looks anything up.
     constexpr double kCellSlack = 1.0e-3;
-    c.cell_on = 0;
-    c.cell_axes = 0;
-    const int cell_words = rt_cell_words(c.n_groups);
-    c.h_groups.resize((size_t)c.n_groups * 3 + (size_t)rt_cell_f4(c.n_groups), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (int a = 0; a < 3; a++) { c.ubox[a] = 0.0f; c.ubox[3 + a] = 0.0f; c.cell_scale[a] = 0.0f; c.cell_off[a] = 0.0f; }
+    sp.cell_on = 0;
+    sp.cell_axes = 0;
+    const int cell_words = rt_cell_words(sp.n_groups);
+    c.h_groups.resize((size_t)sp.n_groups * 3 + (size_t)rt_cell_f4(sp.n_groups), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (int a = 0; a < 3; a++) { sp.ubox[a] = 0.0f; sp.ubox[3 + a] = 0.0f; sp.cell_scale[a] = 0.0f; sp.cell_off[a] = 0.0f; }
     if (n_boxes > 0 && cell_words > 0) {
         const int W = cell_words;
-        uint32_t* tab = reinterpret_cast<uint32_t*>(c.h_groups.data() + (size_t)c.n_groups * 3);
-        std::vector<char> real(c.n_groups, 0);
-        for (int g = n_big_groups; g < c.n_groups; g++) real[g] = c.h_groups[3 * g].x <= c.h_groups[3 * g].y;
+        uint32_t* tab = reinterpret_cast<uint32_t*>(c.h_groups.data() + (size_t)sp.n_groups * 3);
+        std::vector<char> real(sp.n_groups, 0);
+        for (int g = n_big_groups; g < sp.n_groups; g++) real[g] = c.h_groups[3 * g].x <= c.h_groups[3 * g].y;
         bool ok = true;
         for (int a = 0; a < 3 && ok; a++) {
             double amin = 1e300, amax = -1e300;
-            for (int g = n_big_groups; g < c.n_groups; g++) {
+            for (int g = n_big_groups; g < sp.n_groups; g++) {
                 if (!real[g]) continue;
                 amin = std::min(amin, (double)c.h_groups[3 * g + a].x);
                 amax = std::max(amax, (double)c.h_groups[3 * g + a].y);
             }
-            c.ubox[a] = (float)amin; c.ubox[3 + a] = (float)amax;      // (box coordinates are floats: exact)
+            sp.ubox[a] = (float)amin; sp.ubox[3 + a] = (float)amax;      // (box coordinates are floats: exact)
             const double w = (amax - amin) / kCellCount;
             if (!(w > 1e-30) || !std::isfinite(w) || !std::isfinite(1.0 / w) || !std::isfinite(amin / w)) { ok = false; break; }
-            c.cell_scale[a] = (float)(1.0 / w);
-            c.cell_off[a] = (float)(-amin / w);
-            if (!shared_ok[a]) c.cell_axes |= 1 << a;
+            sp.cell_scale[a] = (float)(1.0 / w);
+            sp.cell_off[a] = (float)(-amin / w);
+            if (!shared_ok[a]) sp.cell_axes |= 1 << a;
             for (int cell = 0; cell < kCellCount; cell++) {
                 uint32_t* begins = tab + ((size_t)(2 * a) * kCellCount + cell) * W;
                 uint32_t* ends = tab + ((size_t)(2 * a + 1) * kCellCount + cell) * W;
-                for (int g = n_big_groups; g < c.n_groups; g++) {
+                for (int g = n_big_groups; g < sp.n_groups; g++) {
                     if (!real[g]) continue;
                     const int k = g - n_big_groups;
                     if (cell == kCellCount - 1 || (double)c.h_groups[3 * g + a].x <= amin + (cell + 1 + kCellSlack) * w) begins[k >> 5] |= 1u << (k & 31);
@@ -496,7 +499,7 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
                 }
             }
         }
-        c.cell_on = (ok && rt_read_switches().box_cells) ? 1 : 0;
+        sp.cell_on = (ok && rt_read_switches().box_cells) ? 1 : 0;
     }
     // per-ray margin constants
     double cc[3] = { 0, 0, 0 }, rad = 0.0;
@@ -509,16 +512,95 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
         }
     } else r_min = 1.0;
     const double K_eps = 96.0 * 5.9604645e-8;            // K x 2^-24, see make_box_ray
-    for (int a = 0; a < 3; a++) c.cull_c[a] = (float)cc[a];
-    c.cull_radius = (float)(rad * 1.000001 + 1e-30);
-    c.cull_k1 = (float)(K_eps / (2.0 * std::max(r_min, 1e-30)));
-    c.cull_k2 = (float)std::sqrt(K_eps);
-    c.cull_k3 = 16.0f * 5.9604645e-8f;
-    c.cull_coord_max = coord_max;
+    sp.cull_cx = (float)cc[0]; sp.cull_cy = (float)cc[1]; sp.cull_cz = (float)cc[2];
+    sp.cull_radius = (float)(rad * 1.000001 + 1e-30);
+    sp.cull_k1 = (float)(K_eps / (2.0 * std::max(r_min, 1e-30)));
+    sp.cull_k2 = (float)std::sqrt(K_eps);
+    sp.cull_k3 = 16.0f * 5.9604645e-8f;
+    sp.cull_coord_max = coord_max;
     double r_max_small = 0.0;
     for (int k : small) r_max_small = std::max(r_max_small, (double)radii[k]);
-    c.pair_k0 = (float)(2.0 * 3.814697265625e-6 * r_max_small * r_max_small * 1.0001);     // 2 x kPairSlack (2^-18) x r_max^2, rounded up
-    (void)extent;
+    sp.pair_k0 = (float)(2.0 * 3.814697265625e-6 * r_max_small * r_max_small * 1.0001);     // 2 x kPairSlack (2^-18) x r_max^2, rounded up
+}
+
+// Device layout of a mesh scene (initRenderer has validated `sc`): the caller's triangles and BVH, the axis-grouped node records, the compact leaf records,
+// materials and textures as host arrays, the scene's constants in the parameter-block template.
+void build_mesh_scene(const rt_kernel_scene& sc) {
+    RenderContext& c = g_ctx;
+    RtMeshParams& mp = c.mesh_scene;
+    const int nppl = sc.numPrimitivesPerLeaf;
+    const uint32_t first_leaf = (uint32_t)sc.m->numBvhNodes / 2;                               // kernels.cu:614
+    mp.first_leaf = first_leaf;
+    mp.nppl = (uint32_t)nppl;                                                                  // kernels.cu:648
+    mp.bounds = sc.m->bounds;
+    mp.floor = sc.floor;
+    c.h_tris.assign(sc.m->tris, sc.m->tris + sc.m->numTris);                                  // kernels.cu:582-583
+    const size_t nfloats = (size_t)sc.m->numBvhNodes * 6;                                      // kernels.cu:587-605
+    c.h_bvh.assign((nfloats + 3) / 4 + 1, make_float4(0, 0, 0, 0));
+    memcpy(c.h_bvh.data(), sc.m->bvh, nfloats * sizeof(float));
+    {   // axis-grouped child-pair records (rt_params.h, bvh_axis): 24 floats per internal node
+        const size_t nrec = (size_t)sc.m->numBvhNodes / 2;
+        c.h_bvh_axis.assign(nrec * 24, 0.0f);
+        const float* nodes = reinterpret_cast<const float*>(sc.m->bvh);
+        for (size_t i = 0; i < nrec; i++) {
+            const float* L = nodes + (2 * i) * 6;
+            const float* R = nodes + (2 * i + 1) * 6;
+            for (int a = 0; a < 3; a++) {
+                float* o = c.h_bvh_axis.data() + i * 24 + a * 8;
+                o[0] = L[a]; o[1] = R[a]; o[2] = L[3 + a]; o[3] = R[3 + a];
+                o[4] = L[3 + a]; o[5] = R[3 + a]; o[6] = L[a]; o[7] = R[a];
+            }
+        }
+    }
+    // The leaf loop of kernels.cu:196-214 stops at the first sentinel (inf) triangle of a leaf.  The pair rounds of the mesh
+    // kernel test a leaf's triangles in parallel and rely on sentinels being TRAILING (true for every builder that pads
+    // leaves at the end); a leaf with a real triangle behind a sentinel sends the kernel to its sequential leaf loop.
+    mp.leaf_sentinels_trailing = 1;
+    for (uint32_t leaf = 0; leaf < first_leaf && mp.leaf_sentinels_trailing; leaf++) {
+        bool seen = false;
+        for (int k = 0; k < nppl; k++) {
+            const bool sent = std::isinf(c.h_tris[(size_t)leaf * nppl + k].v[0].e[0]);
+            if (seen && !sent) mp.leaf_sentinels_trailing = 0;
+            seen = seen || sent;
+        }
+    }
+    // Compact leaf records for the pair rounds (rt_params.h, leaf_tri / leaf_ofs): what triangleHit reads of a triangle and nothing else - v0 and the
+    // two edges, e1 = v1 - v0 and e2 = v2 - v0 computed here with the same single fp32 subtraction per component as intersections.h:56-57 (same bits) -
+    // for the REAL triangles only.  The caller's 64-byte array stays the ABI of this boundary (helper_structs.h:81-96) and is what a closest hit re-reads.
+    c.h_leaf_tri.clear(); c.h_leaf_ofs.clear();
+    if (mp.leaf_sentinels_trailing && nppl <= 255) {
+        c.h_leaf_tri.assign((size_t)first_leaf * nppl * 3, make_float4(0, 0, 0, 0));
+        c.h_leaf_ofs.assign(((size_t)first_leaf + 3) / 4, 0u);
+        for (uint32_t leaf = 0; leaf < first_leaf; leaf++) {
+            uint32_t cnt = 0;
+            for (int k = 0; k < nppl; k++) {
+                const rt_triangle& t = c.h_tris[(size_t)leaf * nppl + k];
+                if (std::isinf(t.v[0].e[0])) break;
+                volatile float e1[3], e2[3];                         // (volatile: one rounded fp32 subtraction each, never a contracted or widened form)
+                for (int a = 0; a < 3; a++) { e1[a] = t.v[1].e[a] - t.v[0].e[a]; e2[a] = t.v[2].e[a] - t.v[0].e[a]; }
+                float4* rec = c.h_leaf_tri.data() + ((size_t)leaf * nppl + k) * 3;
+                rec[0] = make_float4(t.v[0].e[0], t.v[0].e[1], t.v[0].e[2], e1[0]);
+                rec[1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
+                uint32_t mesh_bits = (uint32_t)t.meshID;
+                float mesh_f;
+                memcpy(&mesh_f, &mesh_bits, 4);
+                rec[2] = make_float4(e2[2], mesh_f, 0.0f, 0.0f);       // (.y: meshID as an integer bit pattern - a closest hit reads its record again for the normal and the material)
+                cnt++;
+            }
+            c.h_leaf_ofs[leaf >> 2] |= cnt << (8 * (leaf & 3));
+        }
+    }
+    c.h_materials.assign(sc.materials, sc.materials + sc.numMaterials);                        // kernels.cu:617-618
+    mp.lean_ok = 1;                                         // every material is RT_DIFFUSE / RT_METAL / RT_GLASS and untextured
+    for (const rt_material& m : c.h_materials)
+        if ((m.type != RT_DIFFUSE && m.type != RT_METAL && m.type != RT_GLASS) || m.texId != -1) mp.lean_ok = 0;
+    c.h_tex.clear(); c.h_tex_w.clear(); c.h_tex_h.clear();
+    for (int t = 0; t < sc.numTextures; t++) {                                                 // kernels.cu:620-645
+        const rt_stexture& tx = sc.textures[t];
+        c.h_tex.emplace_back(tx.data, tx.data + (size_t)tx.width * tx.height * 3);
+        c.h_tex_w.push_back(tx.width);
+        c.h_tex_h.push_back(tx.height);
+    }
 }
 
 void cleanup_impl() {
@@ -584,79 +666,13 @@ void initRenderer(const rt_kernel_scene sc, const rt_camera cam, rt_vec3** fb, i
     if (first_leaf > (1u << 30)) rt_fail("initRenderer: BVH deeper than the 32-bit traversal bit-stack");
     c.is_spheres = false;
     default_options(&c.opt, 0);
-    c.h_tris.assign(sc.m->tris, sc.m->tris + sc.m->numTris);                                  // kernels.cu:582-583
-    for (const rt_triangle& t : c.h_tris)
-        if (t.meshID >= sc.numMaterials && !std::isinf(t.v[0].e[0])) rt_fail("initRenderer: triangle meshID out of range");
-    c.num_bvh_nodes = sc.m->numBvhNodes;                                                       // kernels.cu:587-605
-    const size_t nfloats = (size_t)c.num_bvh_nodes * 6;
-    c.h_bvh.assign((nfloats + 3) / 4 + 1, make_float4(0, 0, 0, 0));
-    memcpy(c.h_bvh.data(), sc.m->bvh, nfloats * sizeof(float));
-    {   // axis-grouped child-pair records (rt_params.h, bvh_axis): 24 floats per internal node
-        const size_t nrec = (size_t)c.num_bvh_nodes / 2;
-        c.h_bvh_axis.assign(nrec * 24, 0.0f);
-        const float* nodes = reinterpret_cast<const float*>(sc.m->bvh);
-        for (size_t i = 0; i < nrec; i++) {
-            const float* L = nodes + (2 * i) * 6;
-            const float* R = nodes + (2 * i + 1) * 6;
-            for (int a = 0; a < 3; a++) {
-                float* o = c.h_bvh_axis.data() + i * 24 + a * 8;
-                o[0] = L[a]; o[1] = R[a]; o[2] = L[3 + a]; o[3] = R[3 + a];
-                o[4] = L[3 + a]; o[5] = R[3 + a]; o[6] = L[a]; o[7] = R[a];
-            }
-        }
-    }
-    c.nppl = sc.numPrimitivesPerLeaf;                                                          // kernels.cu:648
-    // The leaf loop of kernels.cu:196-214 stops at the first sentinel (inf) triangle of a leaf.  The pair rounds of the mesh
-    // kernel test a leaf's triangles in parallel and rely on sentinels being TRAILING (true for every builder that pads
-    // leaves at the end); a leaf with a real triangle behind a sentinel sends the kernel to its sequential leaf loop.
-    c.leaf_sentinels_trailing = 1;
-    for (uint32_t leaf = 0; leaf < first_leaf && c.leaf_sentinels_trailing; leaf++) {
-        bool seen = false;
-        for (int k = 0; k < c.nppl; k++) {
-            const bool sent = std::isinf(c.h_tris[(size_t)leaf * c.nppl + k].v[0].e[0]);
-            if (seen && !sent) c.leaf_sentinels_trailing = 0;
-            seen = seen || sent;
-        }
-    }
-    // Compact leaf records for the pair rounds (rt_params.h, leaf_tri / leaf_ofs): what triangleHit reads of a triangle and nothing else - v0 and the
-    // two edges, e1 = v1 - v0 and e2 = v2 - v0 computed here with the same single fp32 subtraction per component as intersections.h:56-57 (same bits) -
-    // for the REAL triangles only.  The caller's 64-byte array stays the ABI of this boundary (helper_structs.h:81-96) and is what a closest hit re-reads.
-    c.h_leaf_tri.clear(); c.h_leaf_ofs.clear();
-    if (c.leaf_sentinels_trailing && c.nppl <= 255) {
-        c.h_leaf_tri.assign((size_t)first_leaf * c.nppl * 3, make_float4(0, 0, 0, 0));
-        c.h_leaf_ofs.assign(((size_t)first_leaf + 3) / 4, 0u);
-        for (uint32_t leaf = 0; leaf < first_leaf; leaf++) {
-            uint32_t cnt = 0;
-            for (int k = 0; k < c.nppl; k++) {
-                const rt_triangle& t = c.h_tris[(size_t)leaf * c.nppl + k];
-                if (std::isinf(t.v[0].e[0])) break;
-                volatile float e1[3], e2[3];                         // (volatile: one rounded fp32 subtraction each, never a contracted or widened form)
-                for (int a = 0; a < 3; a++) { e1[a] = t.v[1].e[a] - t.v[0].e[a]; e2[a] = t.v[2].e[a] - t.v[0].e[a]; }
-                float4* rec = c.h_leaf_tri.data() + ((size_t)leaf * c.nppl + k) * 3;
-                rec[0] = make_float4(t.v[0].e[0], t.v[0].e[1], t.v[0].e[2], e1[0]);
-                rec[1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-                uint32_t mesh_bits = (uint32_t)t.meshID;
-                float mesh_f;
-                memcpy(&mesh_f, &mesh_bits, 4);
-                rec[2] = make_float4(e2[2], mesh_f, 0.0f, 0.0f);       // (.y: meshID as an integer bit pattern - a closest hit reads its record again for the normal and the material)
-                cnt++;
-            }
-            c.h_leaf_ofs[leaf >> 2] |= cnt << (8 * (leaf & 3));
-        }
-    }
-    c.bounds = sc.m->bounds;
-    c.floor = sc.floor;
-    c.h_materials.assign(sc.materials, sc.materials + sc.numMaterials);                        // kernels.cu:617-618
-    c.h_tex.clear(); c.h_tex_w.clear(); c.h_tex_h.clear();
-    for (int t = 0; t < sc.numTextures; t++) {                                                 // kernels.cu:620-645
-        const rt_stexture& tx = sc.textures[t];
-        if (!tx.data || tx.width <= 0 || tx.height <= 0) rt_fail("initRenderer: bad texture");
-        c.h_tex.emplace_back(tx.data, tx.data + (size_t)tx.width * tx.height * 3);
-        c.h_tex_w.push_back(tx.width);
-        c.h_tex_h.push_back(tx.height);
-    }
-    for (const rt_material& m : c.h_materials)
-        if (m.texId != -1 && (m.texId < 0 || m.texId >= sc.numTextures)) rt_fail("initRenderer: material texId out of range");
+    for (size_t k = 0; k < sc.m->numTris; k++)
+        if (sc.m->tris[k].meshID >= sc.numMaterials && !std::isinf(sc.m->tris[k].v[0].e[0])) rt_fail("initRenderer: triangle meshID out of range");
+    for (int t = 0; t < sc.numTextures; t++)
+        if (!sc.textures[t].data || sc.textures[t].width <= 0 || sc.textures[t].height <= 0) rt_fail("initRenderer: bad texture");
+    for (int k = 0; k < sc.numMaterials; k++)
+        if (sc.materials[k].texId != -1 && (sc.materials[k].texId < 0 || sc.materials[k].texId >= sc.numTextures)) rt_fail("initRenderer: material texId out of range");
+    build_mesh_scene(sc);
     common_init(cam, fb, nx, ny, maxDepth);
 }
 
@@ -672,8 +688,8 @@ void initRendererSpheres(const rt_sphere* spheres, const rt_material* materials,
     build_sphere_groups(spheres, materials, n);
     // Scenes up to ~2100 spheres live in the LDS of every workgroup; larger ones are read from global memory (they stay in L2) by the
     // same kernel (no cost-ordered second phase, no sparse form beyond 4096 groups: slower per ray, same image).
-    c.global_scene = rt_sphere_kernel_lds_bytes(c.n_padded, n) > 160 * 1024 ? 1 : 0;
-    if (c.n_padded > (1 << 24)) rt_fail("initRendererSpheres: more than 16 M sphere slots");
+    c.sphere_scene.global_scene = rt_sphere_kernel_lds_bytes(c.sphere_scene.n_padded, n) > 160 * 1024 ? 1 : 0;
+    if (c.sphere_scene.n_padded > (1 << 24)) rt_fail("initRendererSpheres: more than 16 M sphere slots");
     common_init(cam, fb, nx, ny, maxDepth);
 }
 
@@ -694,6 +710,56 @@ void setRenderOptions(const rt_render_options* opt) {
 }  // extern "C"
 
 namespace {
+
+// The rows of in-process device k: member part_rank * devices + k of part_world * devices.
+RtPartition partition_of(int k) {
+    const RenderContext& c = g_ctx;
+    const int nd = (int)c.devs.size();
+    RtPartition part;
+    part.stripe_rows = c.opt.stripe_rows;
+    part.rank = c.opt.part_rank * nd + k;
+    part.world = c.opt.part_world * nd;
+    part.local_rows = (int)c.devs[k].fb_rows;
+    return part;
+}
+
+// The parameter block of a kernel that works on rows `part` of the scene on device state `d`: the scene template, that device's scene arrays and what every
+// kernel is given alike (camera, image size, partition, sky, t_min; meshes: the floor switch).  The only place a parameter block gets its scene pointers:
+// a frame (render_frame) adds what belongs to a frame, the guide kernels (launch_guides) take it as it is.
+RtSphereParams sphere_params(const DeviceState& d, const RtPartition& part) {
+    const RenderContext& c = g_ctx;
+    RtSphereParams p = c.sphere_scene;
+    p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
+    p.spheres = d.d_spheres; p.rad = d.d_rad; p.mat_color = d.d_mat_color; p.mat_type = d.d_mat_type;
+    p.groups = d.d_groups; p.orig = d.d_orig; p.slot_of = d.d_slot_of;
+    p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
+    return p;
+}
+
+RtMeshParams mesh_params(const DeviceState& d, const RtPartition& part) {
+    const RenderContext& c = g_ctx;
+    RtMeshParams p = c.mesh_scene;
+    p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
+    p.tris = d.d_tris; p.bvh4 = d.d_bvh; p.bvh_axis = d.d_bvh_axis;
+    p.materials = d.d_materials;
+    p.tex_data = d.d_tex_data; p.tex_width = d.d_tex_width; p.tex_height = d.d_tex_height;
+    p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
+    p.floor_on = c.opt.floor ? 1 : 0;
+    return p;
+}
+
+// The first-hit guide kernel of the scene kind over rows `part`, into the compact planes `g` (renderGuides, denoiseFrame).
+void launch_guides(const DeviceState& d, const RtPartition& part, const RtGuidePlanes& g) {
+    HIP_CHECK(g_ctx.is_spheres ? rt_launch_guides_spheres(sphere_params(d, part), g, d.stream) : rt_launch_guides_mesh(mesh_params(d, part), g, d.stream));
+}
+
+// The diagnostic buffer of RT_WAVE_DEBUG (8 words per wave, or the mesh kernel's phase counters): allocated on first use, cleared on the stream.
+constexpr size_t kWaveDbgWords = (size_t)65536 * 8;
+unsigned long long* wave_debug_buffer(DeviceState& d) {
+    if (!d.d_wave_dbg) d.d_wave_dbg = dev_alloc<unsigned long long>(d.owned, kWaveDbgWords);
+    HIP_CHECK(hipMemsetAsync(d.d_wave_dbg, 0, kWaveDbgWords * sizeof(unsigned long long), d.stream));
+    return d.d_wave_dbg;
+}
 
 // gather: local stripe q (rows of a compact device plane of `px_bytes` per pixel) -> global stripe q*world + rank of the host plane `host` (nx*ny pixels), on the
 // device's stream.  The framebuffer and the guide planes are delivered this way.
@@ -721,7 +787,6 @@ void render_frame(int ns, int first, bool progressive) {
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
     const int nd = (int)c.devs.size();
-    const int world = c.opt.part_world * nd;
     const size_t row_bytes = (size_t)c.nx * sizeof(rt_vec3);
     int64_t samples = 0;
     int launches = 0;
@@ -734,11 +799,7 @@ void render_frame(int ns, int first, bool progressive) {
         if (d.fb_rows == 0) continue;
         HIP_CHECK(hipSetDevice(d.device));
         g_launch_device = d.device;
-        RtPartition part;
-        part.stripe_rows = c.opt.stripe_rows;
-        part.rank = c.opt.part_rank * nd + k;
-        part.world = world;
-        part.local_rows = (int)d.fb_rows;
+        const RtPartition part = partition_of(k);
         if (c.opt.counters) HIP_CHECK(hipMemsetAsync(d.d_counters, 0, sizeof(RtCounters), d.stream));
         int spw = ns, chunks = 1;               // sphere path, RT_RNG_COUNTER: samples per work item, work items per pixel
         if (c.is_spheres && c.opt.rng == RT_RNG_COUNTER && (c.opt.variant & 0xFF) == 0) {
@@ -769,18 +830,10 @@ void render_frame(int ns, int first, bool progressive) {
         if (c.max_depth <= 0) {
             HIP_CHECK(hipMemsetAsync(d.d_fb, 0, d.fb_rows * row_bytes, d.stream));     // loop of kernels.cu:402 never runs
         } else if (c.is_spheres) {
-            RtSphereParams p;
-            memset(&p, 0, sizeof p);
-            p.cam = c.cam; p.nx = c.nx; p.ny = c.ny; p.ns = ns; p.max_depth = c.max_depth;
-            p.n = c.n_spheres; p.n_padded = c.n_padded; p.n_groups = c.n_groups; p.n_big_groups = c.n_big_groups; p.n_big = c.n_big;
-            p.spheres = d.d_spheres; p.rad = d.d_rad; p.global_scene = c.global_scene; p.basic_materials = c.basic_materials; p.mat_color = d.d_mat_color; p.mat_type = d.d_mat_type;
-            p.groups = d.d_groups; p.orig = d.d_orig; p.slot_of = d.d_slot_of;
-            p.cull_cx = c.cull_c[0]; p.cull_cy = c.cull_c[1]; p.cull_cz = c.cull_c[2]; p.cull_radius = c.cull_radius;
-            p.cull_k1 = c.cull_k1; p.cull_k2 = c.cull_k2; p.cull_k3 = c.cull_k3; p.cull_coord_max = c.cull_coord_max; p.pair_k0 = c.pair_k0; p.box_shared_axis = c.box_shared_axis; p.box_shared_lo = c.box_shared_lo; p.box_shared_hi = c.box_shared_hi;
-            p.cell_on = c.cell_on; p.cell_axes = c.cell_axes;
-            for (int q = 0; q < 3; q++) { p.cell_scale[q] = c.cell_scale[q]; p.cell_off[q] = c.cell_off[q]; p.ubox[q] = c.ubox[q]; p.ubox[3 + q] = c.ubox[3 + q]; }
-            p.fb = d.d_fb; p.part = part;
-            p.sky = c.opt.sky; p.rr = c.opt.rr; p.rng_mode = c.opt.rng; p.t_min = c.opt.t_min;
+            RtSphereParams p = sphere_params(d, part);
+            p.ns = ns; p.max_depth = c.max_depth;
+            p.fb = d.d_fb;
+            p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
             p.counters = c.opt.counters ? d.d_counters : nullptr;
             p.queue = d.d_queue;
             p.order = d.d_order;
@@ -795,21 +848,16 @@ void render_frame(int ns, int first, bool progressive) {
             p.xcd_queues = sw.xcd_queues ? kXcdQueues : 0;
             p.p1_tile_major = sw.p1_tile;
             if (chunks > 1) {
-                const size_t need = d.fb_rows * c.nx * (size_t)p.chunks * sizeof(rt_vec3);
-                if (need > d.partial_bytes) {
-                    if (d.d_partial) HIP_CHECK(hipFree(d.d_partial));
-                    HIP_CHECK(hipMalloc((void**)&d.d_partial, need));
-                    d.partial_bytes = need;
+                const size_t sums = d.fb_rows * c.nx * (size_t)p.chunks;
+                if (sums * sizeof(rt_vec3) > d.partial_bytes) {
+                    dev_release(d.owned, d.d_partial);
+                    d.d_partial = dev_alloc<rt_vec3>(d.owned, sums);
+                    d.partial_bytes = sums * sizeof(rt_vec3);
                 }
                 p.partial = d.d_partial;
             }
-            const size_t dbg_bytes = (size_t)65536 * 8 * sizeof(unsigned long long);
-            if (sw.wave_debug && !progressive) {       // diagnostics: per-wave time stamps -> file (not in a progressive pass: PHASE 2's per-pixel
-                                                       // time line would overwrite the parked state)
-                if (!d.d_wave_dbg) HIP_CHECK(hipMalloc((void**)&d.d_wave_dbg, dbg_bytes));
-                HIP_CHECK(hipMemsetAsync(d.d_wave_dbg, 0, dbg_bytes, d.stream));
-                p.wave_dbg = d.d_wave_dbg;
-            }
+            // diagnostics: per-wave time stamps -> file (not in a progressive pass: PHASE 2's per-pixel time line would overwrite the parked state)
+            if (sw.wave_debug && !progressive) p.wave_dbg = wave_debug_buffer(d);
             if (c.opt.nee) rt_fail("runRenderer: next-event estimation is only defined for mesh scenes");
             if (c.opt.floor) rt_fail("runRenderer: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
             if (fb_direct) {
@@ -828,22 +876,12 @@ void render_frame(int ns, int first, bool progressive) {
                                              : rt_launch_spheres_parity(p, c.opt.variant, sw, d.stream));
             launches++;
         } else {
-            RtMeshParams p;
-            memset(&p, 0, sizeof p);
-            p.cam = c.cam; p.nx = c.nx; p.ny = c.ny; p.ns = ns; p.max_depth = c.max_depth;
-            p.tris = d.d_tris; p.bvh4 = d.d_bvh; p.bvh_axis = d.d_bvh_axis;
+            RtMeshParams p = mesh_params(d, part);
+            p.ns = ns; p.max_depth = c.max_depth;
             p.leaf_tri = sw.compact_leaves ? d.d_leaf_tri : nullptr; p.leaf_ofs = sw.compact_leaves ? d.d_leaf_ofs : nullptr;
-            p.first_leaf = (uint32_t)c.num_bvh_nodes / 2; p.nppl = (uint32_t)c.nppl; p.bounds = c.bounds;
-            p.leaf_sentinels_trailing = c.leaf_sentinels_trailing;
-            p.lean_ok = 1;
-            for (const rt_material& m : c.h_materials)
-                if ((m.type != RT_DIFFUSE && m.type != RT_METAL && m.type != RT_GLASS) || m.texId != -1) p.lean_ok = 0;
-            p.materials = d.d_materials;
-            p.tex_data = d.d_tex_data; p.tex_width = d.d_tex_width; p.tex_height = d.d_tex_height;
-            p.fb = d.d_fb; p.part = part;
-            p.sky = c.opt.sky; p.nee = c.opt.nee; p.rr = c.opt.rr; p.rng_mode = c.opt.rng; p.t_min = c.opt.t_min;
+            p.fb = d.d_fb;
+            p.nee = c.opt.nee; p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
             p.light = c.opt.light; p.lightColor = c.opt.lightColor;
-            p.floor_on = c.opt.floor ? 1 : 0; p.floor = c.floor;
             if (c.opt.floor && (c.opt.variant & 0xFF) == 1) rt_fail("runRenderer: the floor plane is not built into the tile-per-wave A/B kernel (variant 1)");
             p.counters = c.opt.counters ? d.d_counters : nullptr;
             p.queue = d.d_queue;
@@ -853,19 +891,14 @@ void render_frame(int ns, int first, bool progressive) {
             p.ord_rec = sw.ord_packed ? d.d_ord_rec : nullptr;
             p.xcd_queues = sw.xcd_queues ? kXcdQueues : 0;
             p.p1_segments = sw.p1_tile == 2 ? 1 : 0;
-            if (sw.wave_debug) {                                     // diagnostics: phase cycle / lane counters -> file
-                const size_t dbg_bytes = (size_t)65536 * 8 * sizeof(unsigned long long);
-                if (!d.d_wave_dbg) HIP_CHECK(hipMalloc((void**)&d.d_wave_dbg, dbg_bytes));
-                HIP_CHECK(hipMemsetAsync(d.d_wave_dbg, 0, dbg_bytes, d.stream));
-                p.dbg = d.d_wave_dbg;
-            }
+            if (sw.wave_debug) p.dbg = wave_debug_buffer(d);        // diagnostics: phase cycle / lane counters -> file
             HIP_CHECK(c.opt.fp == RT_FP_FAST ? rt_launch_mesh_fast(p, c.opt.variant, sw, d.stream)
                                              : rt_launch_mesh_parity(p, c.opt.variant, sw, d.stream));
             launches++;
         }
         HIP_CHECK(hipEventRecord(d.ev_stop, d.stream));
 
-        if (!fb_direct) deliver_stripes(d, part, reinterpret_cast<char*>(c.h_ext ? c.h_ext : c.h_fb), reinterpret_cast<const char*>(d.d_fb), sizeof(rt_vec3));
+        if (!fb_direct) deliver_stripes(d, part, reinterpret_cast<char*>(h_target), reinterpret_cast<const char*>(d.d_fb), sizeof(rt_vec3));
         samples += (int64_t)d.fb_rows * c.nx * (ns - first);
     }
 
@@ -881,7 +914,7 @@ void render_frame(int ns, int first, bool progressive) {
         HIP_CHECK(hipEventElapsedTime(&ms, d.ev_start, d.ev_stop));
         kernel_ms = std::max(kernel_ms, (double)ms);
         if (d.d_wave_dbg && sw.wave_debug) {
-            std::vector<unsigned long long> h((size_t)65536 * 8);
+            std::vector<unsigned long long> h(kWaveDbgWords);
             HIP_CHECK(hipMemcpy(h.data(), d.d_wave_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             if (FILE* f = fopen(sw.wave_debug->c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
             if (d.d_px_state && c.is_spheres) {                      // per-pixel time line of the second phase (see finish())
@@ -1007,8 +1040,8 @@ void runRendererProgressive(int ns, int tx, int ty) {
     for (DeviceState& d : c.devs) {                     // the accumulation buffers: on the first pass of this device state
         if (d.fb_rows == 0 || d.d_acc_state) continue;
         HIP_CHECK(hipSetDevice(d.device));
-        HIP_CHECK(hipMalloc((void**)&d.d_acc_state, d.fb_rows * c.nx * sizeof(float4)));
-        if (c.is_spheres) HIP_CHECK(hipMalloc((void**)&d.d_acc_rays, d.fb_rows * c.nx * sizeof(uint32_t)));
+        d.d_acc_state = dev_alloc<float4>(d.owned, d.fb_rows * c.nx);
+        if (c.is_spheres) d.d_acc_rays = dev_alloc<uint32_t>(d.owned, d.fb_rows * c.nx);
     }
     HIP_CHECK(hipSetDevice(current));
     const int first = c.prog_samples;
@@ -1043,46 +1076,21 @@ void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t*
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
     const int nd = (int)c.devs.size();
-    const int world = c.opt.part_world * nd;
     for (int k = 0; k < nd; k++) {
         DeviceState& d = c.devs[k];
         if (d.fb_rows == 0) continue;
         HIP_CHECK(hipSetDevice(d.device));
-        RtPartition part;                                       // exactly as render_frame builds it
-        part.stripe_rows = c.opt.stripe_rows;
-        part.rank = c.opt.part_rank * nd + k;
-        part.world = world;
-        part.local_rows = (int)d.fb_rows;
+        const RtPartition part = partition_of(k);
         void* plane[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
         for (int q = 0; q < 5; q++) {
             if (!(mask >> q & 1)) continue;
-            if (!d.d_guide[q]) HIP_CHECK(hipMalloc(&d.d_guide[q], d.fb_rows * c.nx * kGuideBytes[q]));
+            if (!d.d_guide[q]) d.d_guide[q] = dev_alloc<char>(d.owned, d.fb_rows * c.nx * kGuideBytes[q]);
             plane[q] = d.d_guide[q];
         }
         const RtGuidePlanes g = { static_cast<float*>(plane[0]), static_cast<float*>(plane[1]), static_cast<float*>(plane[2]),
                                   static_cast<int32_t*>(plane[3]), static_cast<int32_t*>(plane[4]) };
         HIP_CHECK(hipEventRecord(d.ev_start, d.stream));
-        if (c.is_spheres) {
-            RtSphereParams p;
-            memset(&p, 0, sizeof p);
-            p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
-            p.n = c.n_spheres; p.n_padded = c.n_padded; p.n_groups = c.n_groups; p.n_big_groups = c.n_big_groups; p.n_big = c.n_big;
-            p.spheres = d.d_spheres; p.rad = d.d_rad; p.global_scene = c.global_scene; p.mat_color = d.d_mat_color; p.mat_type = d.d_mat_type;
-            p.groups = d.d_groups; p.orig = d.d_orig; p.slot_of = d.d_slot_of;
-            p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
-            HIP_CHECK(rt_launch_guides_spheres(p, g, d.stream));
-        } else {
-            RtMeshParams p;
-            memset(&p, 0, sizeof p);
-            p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
-            p.tris = d.d_tris; p.bvh4 = d.d_bvh;
-            p.first_leaf = (uint32_t)c.num_bvh_nodes / 2; p.nppl = (uint32_t)c.nppl; p.bounds = c.bounds;
-            p.materials = d.d_materials;
-            p.tex_data = d.d_tex_data; p.tex_width = d.d_tex_width; p.tex_height = d.d_tex_height;
-            p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
-            p.floor_on = c.opt.floor ? 1 : 0; p.floor = c.floor;
-            HIP_CHECK(rt_launch_guides_mesh(p, g, d.stream));
-        }
+        launch_guides(d, part, g);
         HIP_CHECK(hipEventRecord(d.ev_stop, d.stream));
         for (int q = 0; q < 5; q++)
             if (plane[q]) deliver_stripes(d, part, static_cast<char*>(host[q]), static_cast<const char*>(plane[q]), kGuideBytes[q]);
@@ -1132,13 +1140,12 @@ void denoiseFrame(const rt_vec3* in, rt_vec3* out, int iterations, int flags, in
         free_denoise();
         HIP_CHECK(hipSetDevice(d.device));
         n.device = d.device; n.npix = npix;
-        const size_t guide_bytes[4] = { 12, 12, 4, 4 };
-        for (int q = 0; q < 4; q++) HIP_CHECK(hipMalloc((void**)&n.d_guide[q], npix * guide_bytes[q]));
-        HIP_CHECK(hipMalloc((void**)&n.d_in, npix * sizeof(rt_vec3)));
-        HIP_CHECK(hipMalloc((void**)&n.d_out, npix * sizeof(rt_vec3)));
-        HIP_CHECK(hipMalloc((void**)&n.d_rec, 2 * npix * sizeof(float4)));
-        HIP_CHECK(hipMalloc((void**)&n.d_col[0], npix * sizeof(float4)));
-        HIP_CHECK(hipMalloc((void**)&n.d_col[1], npix * sizeof(float4)));
+        for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
+        n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
+        n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
+        n.d_rec = dev_alloc<float4>(n.owned, 2 * npix);
+        n.d_col[0] = dev_alloc<float4>(n.owned, npix);
+        n.d_col[1] = dev_alloc<float4>(n.owned, npix);
         HIP_CHECK(hipEventCreate(&n.ev_start));
         HIP_CHECK(hipEventCreate(&n.ev_stop));
     }
@@ -1146,27 +1153,7 @@ void denoiseFrame(const rt_vec3* in, rt_vec3* out, int iterations, int flags, in
     RtPartition part;                                           // the whole image as one member's rows
     part.stripe_rows = c.opt.stripe_rows; part.rank = 0; part.world = 1; part.local_rows = c.ny;
     const RtGuidePlanes g = { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr };
-    if (c.is_spheres) {
-        RtSphereParams p;
-        memset(&p, 0, sizeof p);
-        p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
-        p.n = c.n_spheres; p.n_padded = c.n_padded; p.n_groups = c.n_groups; p.n_big_groups = c.n_big_groups; p.n_big = c.n_big;
-        p.spheres = d.d_spheres; p.rad = d.d_rad; p.global_scene = c.global_scene; p.mat_color = d.d_mat_color; p.mat_type = d.d_mat_type;
-        p.groups = d.d_groups; p.orig = d.d_orig; p.slot_of = d.d_slot_of;
-        p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
-        HIP_CHECK(rt_launch_guides_spheres(p, g, d.stream));
-    } else {
-        RtMeshParams p;
-        memset(&p, 0, sizeof p);
-        p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
-        p.tris = d.d_tris; p.bvh4 = d.d_bvh;
-        p.first_leaf = (uint32_t)c.num_bvh_nodes / 2; p.nppl = (uint32_t)c.nppl; p.bounds = c.bounds;
-        p.materials = d.d_materials;
-        p.tex_data = d.d_tex_data; p.tex_width = d.d_tex_width; p.tex_height = d.d_tex_height;
-        p.part = part; p.sky = c.opt.sky; p.t_min = c.opt.t_min;
-        p.floor_on = c.opt.floor ? 1 : 0; p.floor = c.floor;
-        HIP_CHECK(rt_launch_guides_mesh(p, g, d.stream));
-    }
+    launch_guides(d, part, g);
     RtDenoiseParams q;
     memset(&q, 0, sizeof q);
     q.cam = c.cam; q.nx = c.nx; q.ny = c.ny;

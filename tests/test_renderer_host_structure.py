@@ -1,0 +1,67 @@
+"""CPU tripwire: the host runtime (rt_renderer.hip) says each thing once.  Device memory is allocated by one function that records the pointer with its
+owner and freed only by the functions that walk that record, so a new buffer cannot be forgotten in a hand-kept list of frees; every scene pointer of a
+kernel parameter block is assigned in exactly one place (sphere_params / mesh_params), so a frame, the guide planes and the denoiser cannot disagree about
+the scene; and RenderContext holds the scene's constants in parameter-block form (sphere_scene / mesh_scene), not as a second set of members that is
+copied across field by field."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RENDERER = os.path.join(ROOT, "cuda-raytracing-optimized_amd", "csrc", "rt_renderer.hip")
+# a function definition at column 0: return type, name, parameters, the opening brace
+FUNC = re.compile(r"^[A-Za-z_][\w:<>,*& ]*?\b(\w+)\s*\([^;{}]*\)\s*(?:const\s*)?\{", re.M)
+
+ALLOCATORS = {"dev_alloc"}
+RELEASERS = {"dev_release", "dev_release_all"}
+SCENE_POINTERS = ["spheres", "rad", "mat_color", "mat_type", "groups", "orig", "slot_of", "tris", "bvh4", "materials", "tex_data"]
+# scalars of RtSphereParams / RtMeshParams (and the names a member-by-member mirror of them would carry): they live in the scene templates only
+MIRRORED = ["n_spheres", "n_padded", "n_groups", "n_big_groups", "n_big", "global_scene", "basic_materials", "cull_c", "cull_radius", "cull_k1", "cull_k2",
+            "cull_k3", "cull_coord_max", "pair_k0", "box_shared_axis", "box_shared_lo", "box_shared_hi", "cell_on", "cell_axes", "cell_scale", "cell_off",
+            "ubox", "num_bvh_nodes", "nppl", "leaf_sentinels_trailing", "bounds", "floor"]
+
+
+def _source():
+    return re.sub(r"//[^\n]*", "", open(RENDERER).read())
+
+
+def _functions(src):
+    """(name, start, end) of every function defined at column 0 (the body ends at the next '}' at column 0)."""
+    out = []
+    for m in FUNC.finditer(src):
+        end = src.find("\n}", m.end())
+        out.append((m.group(1), m.start(), len(src) if end < 0 else end))
+    return out
+
+
+def _enclosing(funcs, pos):
+    inside = [f for f in funcs if f[1] <= pos < f[2]]
+    return inside[-1][0] if inside else None
+
+
+def _callers(src, call):
+    funcs = _functions(src)
+    return [_enclosing(funcs, m.start()) for m in re.finditer(r"\b%s\s*\(" % call, src)]
+
+
+def test_device_memory_is_allocated_and_freed_in_one_place():
+    src = _source()
+    mallocs, frees = _callers(src, "hipMalloc"), _callers(src, "hipFree")
+    assert mallocs and frees
+    assert set(mallocs) <= ALLOCATORS, f"hipMalloc outside the allocation function: {sorted(set(map(str, mallocs)) - ALLOCATORS)}"
+    assert set(frees) <= RELEASERS, f"hipFree outside the release functions: {sorted(set(map(str, frees)) - RELEASERS)}"
+
+
+def test_every_scene_pointer_is_assigned_once():
+    src = _source()
+    for name in SCENE_POINTERS:
+        n = len(re.findall(r"\.%s\s*=(?!=)" % name, src))
+        assert n == 1, f".{name} is assigned {n} times"
+
+
+def test_render_context_does_not_mirror_the_parameter_blocks():
+    m = re.search(r"^struct RenderContext \{(.*?)^\};", _source(), re.M | re.S)
+    assert m, "struct RenderContext not found"
+    body = m.group(1)
+    assert re.search(r"\bRtSphereParams\s+\w+", body) and re.search(r"\bRtMeshParams\s+\w+", body), "no scene template in RenderContext"
+    mirrored = [name for name in MIRRORED if re.search(r"\b%s\b" % name, body)]
+    assert mirrored == [], f"RenderContext mirrors parameter-block fields: {mirrored}"
