@@ -48,6 +48,8 @@
 #include <float.h>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
+#include <utility>
 
 using namespace rtd;
 
@@ -78,7 +80,6 @@ __host__ __device__ constexpr int ws_cand_cap(bool onepass) { return onepass ? 1
 __host__ __device__ constexpr int ws_list_cap(bool onepass) { return onepass ? 64 * 8 + 64 : 64 * kPassGroups + 64; }
 __host__ __device__ constexpr int ws_pairs(bool onepass) { return 64 * 32 + 64 * 8 + ws_list_cap(onepass) * 2; }
 __host__ __device__ constexpr int ws_total(bool onepass) { return ws_pairs(onepass) + ws_cand_cap(onepass) * 4 + 16; }
-constexpr int kWaveScratch = ws_total(false);
 
 __device__ __forceinline__ int global_row(const RtPartition& pt, int lr) {
     const int stripe = lr / pt.stripe_rows;
@@ -146,7 +147,7 @@ struct SceneLds {
     const int*    orig;     // n_padded: the caller's sphere index of each slot (INT_MAX for pad slots)
     const int*    slot_of;  // n: slot of the caller's sphere index
     const float*  rad;      // n_padded: radius (the hit normal divides by it: intersections.h:95)
-    unsigned char* scratch; // kWavesPerWg x kWaveScratch bytes of per-wave work space (pair scan)
+    unsigned char* scratch; // ws_total bytes of work space per wave (pair scan)
 };
 
 // SCENE: 0 = the whole scene copy in the LDS; 1 = nothing staged, every array read from global memory (L2-resident; scenes beyond the LDS);
@@ -1413,6 +1414,28 @@ __global__ void __launch_bounds__(kThreads) k_order_by_cost(const RtSphereParams
 // therefore traces a ray in (almost) every iteration until the queue is empty; which lane renders which pixel is
 // irrelevant to the result because the seed is a function of the global pixel id only.
 
+// The bit-fields of the kernel parameters cfg, chain_cfg and caps: the launcher (plan_spheres) packs them, the kernel reads them, both by these names.
+struct BitField {
+    int shift, mask;
+    constexpr int put(int value) const { return value << shift; }            // (the launcher has checked the range)
+};
+constexpr int kCfgCull = 1 << 0;               // sphere-group culling
+constexpr int kCfgChainSingle = 1 << 1;        // chain waves take ONE pixel per grab
+constexpr int kCfgSingleRay = 1 << 2;          // scan_single for waves with one live ray
+constexpr BitField kCfgPool = { 3, 0x1F };     // x 4 = queue positions a normal wave reserves at least per grab (PHASE 2)
+constexpr BitField kCfgBoost = { 8, 0xFF };    // extra sparse-form rays per iteration for lanes on a long chain
+constexpr BitField kCfgSparseMax = { 16, 0xFF };       // a wave takes the sparse form at <= this many live rays
+constexpr int kCfgDbgLight = 1 << 29;          // RT_WAVE_DEBUG_LIGHT=1: time stamps only
+constexpr int kCfgP1Segments = 1 << 30;        // first dispatch: the permutation moves row segments of 8 pixels
+constexpr BitField kChainEvery = { 0, 0xFF };  // chain_cfg: chain waves live in every N-th workgroup
+constexpr BitField kChainWaves = { 8, 0xF };   // chain waves per such workgroup
+constexpr BitField kChainPixels = { 12, 0xF }; // pixels a chain wave holds
+constexpr BitField kChainHeavyThr = { 16, 0xFF };      // boost threshold (rays per sample)
+constexpr BitField kChainLists = { 24, 0xF };  // number of chain lists
+constexpr BitField caps_list(int c) { return { 4 * c, 0xF }; }         // caps: pixels a chain wave holds while one of them comes from chain list c (0 = the longest chains)
+constexpr BitField kCapsMidWaves = { 16, 0xF };        // the middle tier: its waves per workgroup (0 = off) ...
+constexpr BitField kCapsMidCap = { 20, 0xFF }; // ... and the pixels such a wave holds
+
 // Template parameters (one lean instantiation per job instead of one kernel that carries every mode as run-time state:
 // the all-in-one version kept 98 SGPRs spilled to VGPR lanes):
 //   PHASE    0 = the whole pixel (or sample chunk) in one launch; 1 = first P.s_split samples, then park the pixel;
@@ -1422,24 +1445,21 @@ __global__ void __launch_bounds__(kThreads) k_order_by_cost(const RtSphereParams
 //            (chain lists -> chain waves, heavy lists spread over the first fill, the rest in descending cost)
 //   CHUNKED  RT_RNG_COUNTER: a pixel's samples are independent, P.chunks work items per pixel
 //   DBG      diagnostics (RT_WAVE_DEBUG): time stamps and section timers
-// cfg: bit 0 cull; bits 8..15 extra sparse-form rays per iteration for lanes on a long chain (boost); bits 16..23 a wave takes the
-// sparse form at <= this many live rays.  chain_cfg: bits 0..7 chain waves live in every N-th workgroup; 8..11 chain waves per such
-// workgroup; 12..15 pixels a chain wave holds; 16..23 boost threshold (rays per sample); 24..27 number of chain lists; 28..31 pixels a
-// chain wave holds while one of them comes from list 0 (the longest chains).
+// cfg, chain_cfg, caps: the scheduling constants, packed by the launcher into the bit-fields named above (kCfg*, kChain*, kCaps*).
 //   SCENE    where the scene is read from (stage_scene): 0 = an LDS copy, 1 = global memory, 2 = test data in the LDS, hit data in global memory
 //   LEAN     bit 0: the scene's materials are the three basic ones: lean shading (material_scatter<BASIC>); bit 1: its small groups take ONE list per ray batch
 //            behind the cell-table prefilter (scan_pairs<OP>: at most 32 groups, 64 with bit 4, 128 with bit 5); bit 3: that prefilter is the general 3-axis one (no shared
 //            vertical extent: spheres scattered in space); only with SCENE = 0 (a few kinds also with SCENE = 2) and without DBG.  Bits 0 + 1 need ~100 VGPRs instead of 128; bit 2 (with
-//            both): compiled for SIX waves per SIMD (80 VGPRs, ~20 of them spilled) and launched as two 12-wave workgroups per CU - see launch_spheres for when
+//            both): compiled for SIX waves per SIMD (80 VGPRs, ~20 of them spilled) and launched as two 12-wave workgroups per CU - see plan_spheres for when
 template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE = 0, int LEAN = 0>
 __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres_queue(const RtSphereParams P, uint32_t stride, int cfg, int chain_cfg, int caps) {
     extern __shared__ __align__(16) unsigned char smem[];
     float* unused;
     const SceneLds S = stage_scene<false, SCENE>(P, smem, &unused);
 
-    const bool cull = (cfg & 1) != 0;
-    const int boost = (cfg >> 8) & 0xFF;
-    const int sparse_max = (cfg >> 16) & 0xFF;
+    const bool cull = (cfg & kCfgCull) != 0;
+    const int boost = (cfg >> kCfgBoost.shift) & kCfgBoost.mask;
+    const int sparse_max = (cfg >> kCfgSparseMax.shift) & kCfgSparseMax.mask;
     const int tiles_x = (P.nx + 7) >> 3;
     const int tiles_y = (P.part.local_rows + 7) >> 3;
     const uint32_t padded = (uint32_t)tiles_x * (uint32_t)tiles_y * 64u;
@@ -1462,7 +1482,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
         const uint32_t seg = CLS == 2 ? Q[3] : 0u;
         // CLS = 2 (tiered): lists [0, n_chain) are the chain lists, the lists up to kChainClasses + kHeavyClasses the
         // heavy lists, the remaining ones the rest.  CLS = 1: no chain lists; list 0 is the heavy list.
-        const int n_chain = CLS == 2 ? ((chain_cfg >> 24) & 0xF) : 0;
+        const int n_chain = CLS == 2 ? ((chain_cfg >> kChainLists.shift) & kChainLists.mask) : 0;
         const int n_heavy_end = CLS == 2 ? kChainClasses + kHeavyClasses : 1;
         uint32_t pos = 0, nA = 0, n0 = 0;                            // nA: chain-list pixels; n0: heavy pixels
         for (int c = 0; c < n_cls; c++) {
@@ -1481,15 +1501,15 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
         // lanes that draw from the general queue at t = 0: all (of this XCD), minus the chain waves (which start on the chain lists)
         const uint32_t wgs = xq > 1u ? max(gridDim.x / xq, 1u) : gridDim.x;
         uint32_t spread = wgs * blockDim.x;
-        if (nA > 0u) spread -= min(spread - 64u, ((wgs + (uint32_t)(chain_cfg & 0xFF) - 1u) / (uint32_t)(chain_cfg & 0xFF)) * (uint32_t)((chain_cfg >> 8) & 0xF) * 64u);
+        if (nA > 0u) spread -= min(spread - 64u, ((wgs + (uint32_t)(chain_cfg & kChainEvery.mask) - 1u) / (uint32_t)(chain_cfg & kChainEvery.mask)) * (uint32_t)((chain_cfg >> kChainWaves.shift) & kChainWaves.mask) * 64u);
         uint32_t* const sq = s_q + 8 * x;
         sq[0] = nA; sq[1] = n0; sq[2] = total_px * (CHUNKED ? (uint32_t)P.chunks : 1u); sq[3] = spread;
         sq[4] = (n0 > 0u && n0 <= spread && (spread - n0) <= n_rest) ? 1u : 0u;
-        // Middle tier (caps bits 16..19 = waves per workgroup, 20..27 = pixels such a wave holds; CLS = 2 only): the heavy lists are not spread over the normal
+        // Middle tier (kCapsMidWaves = waves per workgroup, kCapsMidCap = pixels such a wave holds; CLS = 2 only): the heavy lists are not spread over the normal
         // waves but served, from their own counter (queue word [2]), by "middle" waves that hold only a few pixels - see the role comment below.  The general
         // queue is then the rest lists alone.
         sq[5] = 0u;
-        if (CLS == 2 && ((caps >> 16) & 0xF) != 0 && n0 > 0u) { sq[5] = 1u; sq[2] = n_rest; sq[4] = 0u; }
+        if (CLS == 2 && ((caps >> kCapsMidWaves.shift) & kCapsMidWaves.mask) != 0 && n0 > 0u) { sq[5] = 1u; sq[2] = n_rest; sq[4] = 0u; }
         sq[6] = seg;
     }
     __syncthreads();
@@ -1506,9 +1526,9 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
     // holds only `mid_cap` pixels runs the same dense form at about half the iteration time (the per-lane phases cost what they cost, the pair rounds shrink
     // with the rays): such pixels end in half the time for ~2.5x the cost per ray, on a few per cent of the frame's rays.
     int role = 2;
-    if (CLS == 2 && s_q[8 * myx] > 0u && (int)(threadIdx.x >> 6) < ((chain_cfg >> 8) & 0xF) && (blockIdx.x % (uint32_t)(chain_cfg & 0xFF)) == 0u) role = 0;
-    else if (CLS == 2 && s_q[8 * myx + 5] != 0u && (int)(threadIdx.x >> 6) < ((chain_cfg >> 8) & 0xF) + ((caps >> 16) & 0xF)) role = 1;
-    const int mid_cap = (caps >> 20) & 0xFF;
+    if (CLS == 2 && s_q[8 * myx] > 0u && (int)(threadIdx.x >> 6) < ((chain_cfg >> kChainWaves.shift) & kChainWaves.mask) && (blockIdx.x % (uint32_t)(chain_cfg & kChainEvery.mask)) == 0u) role = 0;
+    else if (CLS == 2 && s_q[8 * myx + 5] != 0u && (int)(threadIdx.x >> 6) < ((chain_cfg >> kChainWaves.shift) & kChainWaves.mask) + ((caps >> kCapsMidWaves.shift) & kCapsMidWaves.mask)) role = 1;
+    const int mid_cap = (caps >> kCapsMidCap.shift) & kCapsMidCap.mask;
     // wave-uniform (a queue per XCD only): how far this wave has moved on from its own XCD's queue.  Even: it draws from the general queue of XCD
     // (myx + stolen / 2) mod 8; odd: that general queue is empty and the wave (role 2) takes what is LEFT ON THAT QUEUE'S CHAIN LISTS.  Chain lists are served
     // by the chain waves of their own XCD; but nothing promises that every XCD got a workgroup of this grid (a grid of six workgroups leaves two without), and
@@ -1610,7 +1630,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
     while (true) {
         if (PHASE == 1 && iter_no++ == poison_at) poison_rows(P, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
         // ---- refill idle lanes --------------------------------------------------------------------------------
-        const bool dbg_timers = DBG && wdbg && (cfg & (1 << 29)) == 0;          // RT_WAVE_DEBUG_LIGHT=1: time stamps of waves and pixels only (the section timers
+        const bool dbg_timers = DBG && wdbg && (cfg & kCfgDbgLight) == 0;          // RT_WAVE_DEBUG_LIGHT=1: time stamps of waves and pixels only (the section timers
                                                                                  // stretch a sparse step by 40 %: the light form keeps the frame's real proportions)
         const unsigned long long t_refill = dbg_timers ? __builtin_amdgcn_s_memtime() : 0ull;
         while (!exhausted) {
@@ -1619,10 +1639,10 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
             int cap = 64;
             if (CLS == 2 && (role == 1 || __ballot(have_pixel && ccls == 6) != 0ull)) cap = mid_cap;        // a middle wave, or a wave that still holds a middle-tier pixel
             if (CLS == 2 && (role == 0 || __ballot(have_pixel && ccls < 6) != 0ull)) {
-                cap = (chain_cfg >> 12) & 0xF;
-                if (__ballot(have_pixel && ccls == 2) != 0ull) cap = min(cap, (caps >> 8) & 0xF);
-                if (__ballot(have_pixel && ccls == 1) != 0ull) cap = min(cap, (caps >> 4) & 0xF);
-                if (__ballot(have_pixel && ccls == 0) != 0ull) cap = min(cap, caps & 0xF);
+                cap = (chain_cfg >> kChainPixels.shift) & kChainPixels.mask;
+                if (__ballot(have_pixel && ccls == 2) != 0ull) cap = min(cap, (caps >> caps_list(2).shift) & caps_list(2).mask);
+                if (__ballot(have_pixel && ccls == 1) != 0ull) cap = min(cap, (caps >> caps_list(1).shift) & caps_list(1).mask);
+                if (__ballot(have_pixel && ccls == 0) != 0ull) cap = min(cap, caps & caps_list(0).mask);
             }
             const int allowed = cap - (int)__popcll(live_m);
             if (allowed <= 0) break;
@@ -1633,16 +1653,16 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
             // Whole pixels: reserve exactly as many as there are idle lanes, so nothing is hoarded in a wave while
             // other waves idle.  Sample chunks (counter RNG) and the 960 k two-sample items of phase 1 are small and plentiful,
             // one atomic per idle lane-group would serialise on the counter, so a wave reserves 128 at a time into a wave-local pool.
-            // chain waves take ONE pixel per grab (cfg bit 1): all of them start together, so the grabs interleave and the head of the chain lists - the
+            // chain waves take ONE pixel per grab (kCfgChainSingle): all of them start together, so the grabs interleave and the head of the chain lists - the
             // longest estimates - is dealt one pixel to a wave instead of four neighbours of the list to the first wave that arrives
-            const uint32_t cnt = (role == 0 && (cfg & 2)) ? 1u : (uint32_t)__popcll(need);
+            const uint32_t cnt = (role == 0 && (cfg & kCfgChainSingle)) ? 1u : (uint32_t)__popcll(need);
             const uint32_t qx = xq > 1u ? ((myx + (stolen >> 1)) & (uint32_t)(kXcdQueues - 1)) : 0u;      // the queue this wave draws from now
             const uint32_t* const sq = s_q + 8 * qx;
             const uint32_t total = sq[2];
             if (pool_next >= pool_end) {
-                // (PHASE 2, experiments: cfg bits 3..7 x 4 = positions a normal wave reserves at least per grab)
+                // (PHASE 2, experiments: kCfgPool x 4 = positions a normal wave reserves at least per grab)
                 const bool leftovers = (stolen & 1u) != 0u;             // (role 2 only)
-                const uint32_t grab = leftovers ? 1u : ((CHUNKED || PHASE == 1) ? max(cnt, 128u) : ((PHASE == 2 && role == 2) ? max(cnt, (uint32_t)((cfg >> 3) & 0x1F) * 4u) : cnt));
+                const uint32_t grab = leftovers ? 1u : ((CHUNKED || PHASE == 1) ? max(cnt, 128u) : ((PHASE == 2 && role == 2) ? max(cnt, (uint32_t)((cfg >> kCfgPool.shift) & kCfgPool.mask) * 4u) : cnt));
                 const uint32_t limit = (role == 0 || leftovers) ? sq[0] : (role == 1 ? sq[1] : total);
                 uint32_t b = 0;
                 if ((threadIdx.x & 63) == 0) b = atomicAdd(P.queue + (size_t)qx * kXcdQueueWords + ((role == 0 || leftovers) ? 1 : (role == 1 ? 2 : 0)), grab);
@@ -1673,9 +1693,9 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                     // queue position -> pixel: a multiplicative permutation (stride coprime with total) scatters
                     // neighbouring pixels over different waves, so the few very long pixels (50-bounce paths in the wedge between a sphere and
                     // the ground, clustered along the contact line) never share a wave; stride 1 = tile-major order
-                    // (first dispatch, cfg bit 30: the permutation moves ROW SEGMENTS of a tile - 8 adjacent pixels stay together in 8 adjacent lanes, whose parked
+                    // (first dispatch, kCfgP1Segments: the permutation moves ROW SEGMENTS of a tile - 8 adjacent pixels stay together in 8 adjacent lanes, whose parked
                     // states fill one 128-byte line of px_state; `stride` is then coprime with padded / 8)
-                    if (PHASE == 1 && (cfg & (1 << 30)) != 0) p = ((uint32_t)(((unsigned long long)(pos >> 3) * stride) % (padded >> 3)) << 3) | (pos & 7u);
+                    if (PHASE == 1 && (cfg & kCfgP1Segments) != 0) p = ((uint32_t)(((unsigned long long)(pos >> 3) * stride) % (padded >> 3)) << 3) | (pos & 7u);
                     else p = (uint32_t)(((unsigned long long)pos * stride) % padded);
                 } else {
                     // the n0 pixels of the heavy lists are spread evenly over the first `spread` queue positions (= the lanes in
@@ -1788,7 +1808,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
         for (int x = 0; x < steps; x++) {
             bool sel = have_pixel;
             if (x > 0) {
-                const uint32_t heavy_thr = (uint32_t)((chain_cfg >> 16) & 0xFF);
+                const uint32_t heavy_thr = (uint32_t)((chain_cfg >> kChainHeavyThr.shift) & kChainHeavyThr.mask);
                 const bool heavy = have_pixel && pix_rays > heavy_thr * (uint32_t)(L.s - chunk * P.spw + 2);
                 const unsigned long long hm = __ballot(heavy);
                 if (hm == 0ull) break;
@@ -1804,7 +1824,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
             if (sel) { nrays++; pix_rays++; }
             if (x > 0 || steps == 1) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
             f3 sample;
-            const bool done = trace_rays<false, DBG, (LEAN & 1) != 0, (LEAN & 2) ? ((LEAN & 32) ? 4 : ((LEAN & 16) ? 2 : 1)) : 0, (LEAN & 8) != 0>(P, S, L, sel, -1, cull, groups_done, boxes_done, sample, sparse_max, dbg_timers ? dbg_tm : nullptr, (cfg & 4) != 0);
+            const bool done = trace_rays<false, DBG, (LEAN & 1) != 0, (LEAN & 2) ? ((LEAN & 32) ? 4 : ((LEAN & 16) ? 2 : 1)) : 0, (LEAN & 8) != 0>(P, S, L, sel, -1, cull, groups_done, boxes_done, sample, sparse_max, dbg_timers ? dbg_tm : nullptr, (cfg & kCfgSingleRay) != 0);
             if (dbg_timers) { dbg_tm[x > 0 ? 9 : 8] += 1ull; }
             finish(done && sel, steps > 1, sample);
         }
@@ -1853,6 +1873,7 @@ __global__ void __launch_bounds__(256) k_sum_chunks(const RtSphereParams P) {
 }  // namespace
 
 constexpr size_t kStaticLds = 1024;          // what the kernels declare statically beside the dynamic allocation (the queue words), rounded up
+constexpr size_t kLdsPerCu = 160 * 1024 - kStaticLds;
 static size_t lds_bytes(int n_padded, int n, bool with_fb, int scene = 0, int waves = kWavesPerWg, bool onepass = false) {
     // spheres + group bounds (+ material colour + type / original index / radius per slot + slot_of: scene 0; + original index: scene 2),
     // + fb staging (tile kernel only) + the per-wave scratch
@@ -1864,34 +1885,102 @@ static size_t lds_bytes(int n_padded, int n, bool with_fb, int scene = 0, int wa
            (size_t)((n + 3) & ~3) * 4 + (with_fb ? (size_t)kThreads * 3 * 4 : 0) + scratch;
 }
 
-#if defined(RT_MODE_PARITY)
-hipError_t rt_order_pixels_by_cost(const RtSphereParams& q, hipStream_t stream) {
+// Where a kernel reads the scene from (stage_scene's SCENE): global memory when the renderer says so (p.global_scene), else the full LDS copy if it fits
+// beside the scratch of a 16-wave workgroup (`onepass`: the smaller scratch of the one-list kinds), else the hybrid copy.
+static int scene_form(const RtSphereParams& p, bool onepass) {
+    if (p.global_scene) return 1;
+    return lds_bytes(p.n_padded, p.n, false, 0, kWavesPerWg, onepass) <= kLdsPerCu ? 0 : 2;
+}
+
+// Every launch with dynamic LDS: above 64 KB the attribute goes on the function that is launched.
+template <typename... Params, typename... Args>
+static hipError_t launch_with_lds(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+static hipError_t order_pixels_by_cost(const RtSphereParams& q, hipStream_t stream) {
     hipLaunchKernelGGL(k_order_by_cost<0>, dim3(kOrderBlocks), dim3(kThreads), 0, stream, q);
     hipLaunchKernelGGL(k_order_by_cost<1>, dim3(kOrderBlocks), dim3(kThreads), 0, stream, q);
     return hipGetLastError();
 }
+
+#if defined(RT_MODE_PARITY)
+hipError_t rt_order_pixels_by_cost(const RtSphereParams& q, hipStream_t stream) { return order_pixels_by_cost(q, stream); }
 size_t rt_sphere_kernel_lds_bytes(int n_padded, int n) {                       // of the smallest LDS-resident form: beyond it the scene is read from global memory
     return lds_bytes(n_padded, n, false, 2, 8) + kStaticLds;
 }
-// The guide kernel reads the scene where the render kernels of the same scene read it (full LDS copy, hybrid copy, global memory), without their per-wave scratch.
+// The guide kernel reads the scene from the full LDS copy, the hybrid copy or global memory, without the render kernels' per-wave scratch.  Its choice is
+// scene_form's for the general scratch: a render kernel of a one-list kind, whose scratch is smaller, can still hold the full copy of a scene near the
+// boundary for which the guide kernel already takes the hybrid one.
 hipError_t rt_launch_guides_spheres(const RtSphereParams& p, const RtGuidePlanes& g, hipStream_t stream) {
-    const size_t kLdsPerCu = 160 * 1024 - kStaticLds;
-    const int scene = p.global_scene ? 1 : (lds_bytes(p.n_padded, p.n, false, 0, kWavesPerWg) <= kLdsPerCu ? 0 : 2);
-    const size_t lds = scene == 1 ? 0 : lds_bytes(p.n_padded, p.n, false, scene, 0);
-    const void* kern = scene == 0 ? reinterpret_cast<const void*>(k_guides_spheres<0>)
-                     : scene == 1 ? reinterpret_cast<const void*>(k_guides_spheres<1>) : reinterpret_cast<const void*>(k_guides_spheres<2>);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    const int scene = scene_form(p, false);
+    const auto kern = scene == 0 ? k_guides_spheres<0> : (scene == 1 ? k_guides_spheres<1> : k_guides_spheres<2>);
     const unsigned long long total = (unsigned long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64ull;
     const dim3 grid((unsigned)((total + kThreads - 1) / kThreads));
-    if (scene == 0) hipLaunchKernelGGL(k_guides_spheres<0>, grid, dim3(kThreads), lds, stream, p, g);
-    else if (scene == 1) hipLaunchKernelGGL(k_guides_spheres<1>, grid, dim3(kThreads), lds, stream, p, g);
-    else hipLaunchKernelGGL(k_guides_spheres<2>, grid, dim3(kThreads), lds, stream, p, g);
-    return hipGetLastError();
+    return launch_with_lds(kern, grid, dim3(kThreads), lds_bytes(p.n_padded, p.n, false, scene, 0), stream, p, g);
 }
 #endif
+
+// The LEAN kinds of k_render_spheres_queue that are built beside the general kernel (LEAN 0), by scene form and chunking: the one statement of them.  The
+// launch expands these lists into the instantiations (launch_kind_of), the plan clips a scene's kind to them (clip_lean).
+constexpr int kLeanBasic = 1 << 0, kLeanOneList = 1 << 1, kLeanSixWaves = 1 << 2, kLeanAxes3 = 1 << 3, kLeanWords2 = 1 << 4, kLeanWords4 = 1 << 5;    // the LEAN bits
+using KindsFull = std::integer_sequence<int, 1, 3, 7, 11, 15, 19, 27, 35, 43>;   // SCENE 0, whole pixels
+using KindsChunked = std::integer_sequence<int, 1, 3, 7>;                        // SCENE 0, the sample chunks of the counter stream: the kinds of the benchmark's shape
+using KindsHybrid = std::integer_sequence<int, 1, 35, 43>;                       // SCENE 2 (hit data in global memory: ~1500-3400 spheres), whole pixels: 1 and the four-word lists
+using KindsStamped = std::integer_sequence<int, 3>;                              // SCENE 0, whole pixels, DBG: the production kernel of the benchmark scene with the time stamps
+
+template <int... LEANS>
+constexpr bool in_kinds(std::integer_sequence<int, LEANS...>, int lean) { return ((lean == LEANS) || ...); }
+constexpr bool built(int scene, bool chunked, int lean) {
+    if (lean == 0) return true;                                                  // the general kernel: every scene form, chunked or not
+    if (scene == 0) return chunked ? in_kinds(KindsChunked{}, lean) : in_kinds(KindsFull{}, lean);
+    return scene == 2 && !chunked && in_kinds(KindsHybrid{}, lean);
+}
+// The kind a scene takes of those that are built: its own, else the lean shading alone, else the general kernel.
+constexpr int clip_lean(int scene, bool chunked, int lean) {
+    return built(scene, chunked, lean) ? lean : (built(scene, chunked, lean & kLeanBasic) ? (lean & kLeanBasic) : 0);
+}
+
+enum class SphereFrame {
+    Tiles,              // the tile kernel
+    GlobalSingle,       // the scene in global memory: one scattered dispatch
+    TwoDispatch,        // first samples of every pixel, k_order_by_cost, then the rest longest first
+    TwoDispatchResume,  // a continuation pass of a progressive frame: the ordering pass and the second dispatch alone
+    ClassifiedSingle,   // k_classify_spheres, then one dispatch in its order
+    PlainSingle,        // one dispatch, scattered or tile-major
+};
+enum class SpherePlanError { None, Mid, Tune };
+constexpr int kFirstSamples = 2;    // samples of the first dispatch; measured: 1 -> 15.5 ms, 2 -> 15.0, 3 -> 15.1 (round 2); 2 -> 24.5, 4 -> 24.8, 6 -> 25.4 (round 1)
+
+// What a frame launches, decided by plan_spheres before anything is issued.
+struct SpherePlan {
+    SpherePlanError error = SpherePlanError::None;      // RT_MID / RT_TUNE out of range: nothing but the queue memset is issued
+    SphereFrame frame = SphereFrame::PlainSingle;
+    bool legacy = false;        // tile kernel: the earlier scans (A/B) ...
+    int coop_below = -1;        // ... -1 = pair-compacted scan (+ sparse form), -2 = pair-compacted scan only (A/B)
+    int cull = 1;
+    int scene = 0;              // stage_scene's SCENE
+    bool chunked = false;
+    int lean = 0;               // LEAN bits of the instantiation (0 = the general kernel)
+    int lean_dbg = 0;           // the kind the scene would take without the diagnostics (time lines of the production kernel), if it is built with the stamps
+    int threads = kThreads;     // workgroup size (16 waves, 12 for the six-wave kinds, or 8 when only that fits)
+    size_t lds = 0;
+    unsigned blocks = 1, blocks_y = 1;
+    unsigned cls_blocks = 1;    // k_classify_spheres
+    uint32_t stride = 1;        // scattered order: stride ~ 0.618 * total, coprime with total
+    uint32_t stride1 = 1;       // ... of the first dispatch
+    int cfg = 0, cfg1 = 0, chain_cfg = 0, caps = 0;      // cfg1: the first dispatch; caps: the second dispatch (the others: kCapsNoTiers)
+    bool sum_chunks = false;    // k_sum_chunks follows
+};
+
+// The chain tier's scheduling constants, by name, in the order RT_TUNE gives them (kTuneList0..2: pixels a chain wave holds beside one of chain list 0 / 1 / 2).
+enum { kTuneChainEvery, kTuneChainWaves, kTuneHeavyThr, kTuneChainLists, kTuneBoost, kTuneChainPixels, kTuneList0, kTuneList1, kTuneList2, kTuneFields };
+constexpr int kCapsNoTiers = caps_list(0).put(4) | caps_list(1).put(4) | caps_list(2).put(4) | caps_list(3).put(4);      // every launch but the second dispatch: no middle tier
 
 // variant: bits 0..7   kernel: 0 = persistent waves + pixel queue (default), 1 = one tile per wave;
 //          bits 8..15  workgroups per CU of the persistent kernel (0 = default 2);
@@ -1902,203 +1991,105 @@ hipError_t rt_launch_guides_spheres(const RtSphereParams& p, const RtGuidePlanes
 //          bits 24..25 work order of the persistent kernel: 0 = two-phase, cost-ordered (reference stream; otherwise as 3),
 //                      1 = tile-major, 2 = scattered only, 3 = one launch ordered by the centre-ray pre-pass
 //                      (glass-crossing pixels first, sky last).
-// One instantiation of k_render_spheres_queue, named by its template arguments: launch_sphere_queue launches it and notes those arguments for the
-// launch report (rtLastLaunches).  Every launch of the persistent kernel goes through it.
-template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN = 0> struct SphereQueueForm {};
-
-template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN>
-static hipError_t launch_sphere_queue(SphereQueueForm<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>, const RtSphereParams& q, unsigned blocks, int threads, size_t lds,
-                                      hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps, bool set_lds_attr) {
-    const auto kern = k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>;
-    // the attribute goes on the function that is launched
-    if (set_lds_attr && lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, stream, q, stride, cfg, chain_cfg, caps);
-    rt_note_launch(RT_KERNEL_SPHERE_QUEUE, PHASE, CLS, CHUNKED, DBG, SCENE, LEAN, threads, blocks);
-    return hipGetLastError();
-}
-
-template <bool CHUNKED>
-static hipError_t launch_queue_kernel_global(const RtSphereParams& q, unsigned blocks, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg) {
-    const size_t lds = (size_t)kWavesPerWg * kWaveScratch;          // only the per-wave scratch: the scene stays in global memory
-    // (counters - and with them the reference's ray statistics - live in the diagnostic instantiation only)
-    if (q.counters != nullptr || q.wave_dbg != nullptr) return launch_sphere_queue(SphereQueueForm<0, 0, CHUNKED, true, 1>{}, q, blocks, kThreads, lds, stream, stride, cfg, chain_cfg, 0x4444, false);
-    return launch_sphere_queue(SphereQueueForm<0, 0, CHUNKED, false, 1>{}, q, blocks, kThreads, lds, stream, stride, cfg, chain_cfg, 0x4444, false);
-}
-
-// The persistent kernel's form for the scene being launched, as launch_spheres chose it.
-struct QueueShape {
-    int lean;           // LEAN bits of the instantiation (0 = the general kernel)
-    int lean_dbg;       // the kind the scene would take without the diagnostics (time lines of the production kernel)
-    int threads;        // workgroup size (16 waves, 12 for the six-wave kinds, or 8 when only that fits)
-};
-
-template <int PHASE, int CLS, bool CHUNKED, int SCENE>
-static hipError_t launch_queue_kernel_scene(const RtSphereParams& q, QueueShape shape, unsigned blocks, size_t lds, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps) {
-    // (the diagnostic instantiation - counters, the reference's ray statistics, time stamps - is the general kernel: launch_spheres leaves lean at 0 for it)
-    const bool counting = q.wave_dbg != nullptr || q.counters != nullptr;
-    auto go = [&](auto form) -> hipError_t { return launch_sphere_queue(form, q, blocks, shape.threads, lds, stream, stride, cfg, chain_cfg, caps, true); };
-    // (time lines of the PRODUCTION kernel of the benchmark scene - RT_WAVE_DEBUG with RT_WAVE_DEBUG_LIGHT=1, no counters: the lean kind 3 with the stamps)
-    if (counting && q.counters == nullptr && SCENE == 0 && !CHUNKED && PHASE != 0 && shape.lean_dbg == 3) return go(SphereQueueForm<PHASE, CLS, false, true, 0, 3>{});
-    if (counting) return go(SphereQueueForm<PHASE, CLS, CHUNKED, true, SCENE>{});
-    if (SCENE == 0 && CHUNKED) {                                     // the sample chunks of the counter stream: the kinds of the benchmark's shape
-        switch (shape.lean) {
-        case 1:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 1>{});
-        case 3:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 3>{});
-        case 7:  return go(SphereQueueForm<PHASE, CLS, true, false, 0, 7>{});
-        default: break;
-        }
-    }
-    if (SCENE == 0 && !CHUNKED) {
-        switch (shape.lean) {
-        case 1:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 1>{});
-        case 3:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 3>{});
-        case 7:  return go(SphereQueueForm<PHASE, CLS, false, false, 0, 7>{});
-        case 11: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 11>{});
-        case 15: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 15>{});
-        case 19: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 19>{});
-        case 27: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 27>{});
-        case 35: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 35>{});
-        case 43: return go(SphereQueueForm<PHASE, CLS, false, false, 0, 43>{});
-        default: break;
-        }
-    }
-    if (SCENE == 2 && !CHUNKED) {                                    // the hybrid scene copy (hit data in global memory: ~1500-3400 spheres)
-        switch (shape.lean) {
-        case 1:  return go(SphereQueueForm<PHASE, CLS, false, false, 2, 1>{});
-        case 35: return go(SphereQueueForm<PHASE, CLS, false, false, 2, 35>{});
-        case 43: return go(SphereQueueForm<PHASE, CLS, false, false, 2, 43>{});
-        default: break;
-        }
-    }
-    return go(SphereQueueForm<PHASE, CLS, CHUNKED, false, SCENE>{});
-}
-
-// `hybrid`: stage_scene's form 2 (test data in the LDS, hit data in global memory)
-template <int PHASE, int CLS, bool CHUNKED>
-static hipError_t launch_queue_kernel(const RtSphereParams& q, QueueShape shape, unsigned blocks, size_t lds, bool hybrid, hipStream_t stream, uint32_t stride, int cfg, int chain_cfg, int caps = 0x4444) {
-    return hybrid ? launch_queue_kernel_scene<PHASE, CLS, CHUNKED, 2>(q, shape, blocks, lds, stream, stride, cfg, chain_cfg, caps)
-                  : launch_queue_kernel_scene<PHASE, CLS, CHUNKED, 0>(q, shape, blocks, lds, stream, stride, cfg, chain_cfg, caps);
-}
-
-static hipError_t launch_spheres(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream);
-
-hipError_t RT_LAUNCH_NAME(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
-    // p.self: the device copy of the parameter block, owned and refreshed by the renderer (one per device state and frame).  Only fields that are
-    // the same for the whole frame of that device state (camera, image size, RNG mode) are read through it.  (Reading the per-pixel fields -
-    // framebuffer, parked state, partition - this way too took the kernel from 61 to 43 spilled SGPRs and gained nothing more: 7030 against 7025 Msamples/s.)
-    if (!p.self) return hipErrorInvalidValue;
-    return launch_spheres(p, variant, sw, stream);
-}
-
-static hipError_t launch_spheres(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
-    // p.poison_fb: a single-dispatch frame is preceded by k_poison_fb on the same stream; the two-dispatch frame lets its first dispatch do it
-    auto wait_fb = [&]() -> hipError_t {
-        if (!p.poison_fb) return hipSuccess;
-        hipLaunchKernelGGL(k_poison_fb, dim3(512), dim3(256), 0, stream, p);
-        return hipGetLastError();
-    };
-    int kind = variant & 0xFF;
+static SpherePlan plan_spheres(const RtSphereParams& p, int variant, const RtSwitches& sw, int cus) {
+    SpherePlan pl;
     const int cb_bits = (variant >> 16) & 0xFF;
-    const bool legacy = cb_bits != 0 && cb_bits != 255;
-    if (legacy) kind = 1;                       // the brute-force A/B scans live in the tile kernel only
-    if (p.global_scene) kind = 0;               // scenes beyond the LDS: the persistent kernel only
-    const size_t kLdsPerCu = 160 * 1024 - kStaticLds;
-    if (lds_bytes(p.n_padded, p.n, true, 0, kWavesPerWg) > kLdsPerCu) kind = 0;        // the tile kernel only knows the full copy
-    const int cull = ((variant >> 26) & 1) ? 0 : 1;
-    // Lean instantiations of the persistent kernel (template parameter LEAN), chosen by what the scene is: bit 0 = its materials are the three basic ones,
-    // bit 1 = its small groups (at most 128) take one list per ray batch behind the cell-table prefilter (bits 4 / 5: two / four words of 32 groups; bit 3:
-    // the general 3-axis prefilter, no shared vertical extent).  Bits 0 + 1 need ~100 VGPRs where the general kernel fills its 128 (C5 at 256 spp:
-    // 10530 -> 11515 Msamples/s, C2 7800 -> 8580; profiles/r04_ab_lean_c5.txt), and compiled for 80 (bit 2) they run SIX waves per SIMD as two
+    pl.legacy = cb_bits != 0 && cb_bits != 255;
+    pl.cull = ((variant >> 26) & 1) ? 0 : 1;
+    // The tile kernel: asked for, or the brute-force A/B scans, which live in it only.  It only knows the full copy: a scene beyond it (or beyond the LDS:
+    // p.global_scene) takes the persistent kernel.
+    const size_t tile_lds = lds_bytes(p.n_padded, p.n, true, 0, kWavesPerWg);
+    if (((variant & 0xFF) == 1 || pl.legacy) && !p.global_scene && tile_lds <= kLdsPerCu) {
+        pl.frame = SphereFrame::Tiles;
+        pl.coop_below = cb_bits == 0 ? -1 : (cb_bits == 255 ? -2 : cb_bits);
+        pl.lds = tile_lds;
+        pl.blocks = (p.nx + 8 * kWavesPerWg - 1) / (8 * kWavesPerWg);
+        pl.blocks_y = (p.part.local_rows + 7) / 8;
+        return pl;
+    }
+    pl.chunked = p.chunks > 1;
+    // Lean instantiations of the persistent kernel (template parameter LEAN), chosen by what the scene is: kLeanBasic = its materials are the three basic ones,
+    // kLeanOneList = its small groups (at most 128) take one list per ray batch behind the cell-table prefilter (kLeanWords2 / 4: two / four words of 32 groups;
+    // kLeanAxes3: the general 3-axis prefilter, no shared vertical extent).  Basic + one list need ~100 VGPRs where the general kernel fills its 128 (C5 at 256 spp:
+    // 10530 -> 11515 Msamples/s, C2 7800 -> 8580; profiles/r04_ab_lean_c5.txt), and compiled for 80 (kLeanSixWaves) they run SIX waves per SIMD as two
     // 12-wave workgroups per CU with a scene copy each (the one-list scratch is 1.3 KB per wave smaller: ws_total; workgroups must be a multiple of four
     // waves to pack - a workgroup's waves go round the SIMDs from SIMD 0, two 10-wave workgroups do not fit five per SIMD: tools/mb_occupancy.hip).
     // Six waves buy throughput with latency: +11 % on a 3840x2160 frame, -10 % on a 1200x800 one at 100 AND at 1000 spp - a frame is as long as its
     // throughput or its slowest pixels allow, whichever is longer, and the slowest pixels (6-12 rays per sample in dense waves, one ray per iteration) get
     // slower with every wave that shares the SIMD; both scale with spp, so the pixel count decides: 1920x1080 -4 %, 2560x1440 +9 %, 3200x1800 +10 %
     // (profiles/r04_ab_lean6_sizes.txt).  RT_BASIC=0 / RT_ONEPASS=0 / RT_LEAN6_PIXELS=<n> (0 = never): A/B.
-    const bool counting = p.wave_dbg != nullptr || p.counters != nullptr;
     int lean = 0;
-    int lean_wgs = 1;
-    int lean_dbg = 0;
-    if (kind == 0 && !p.global_scene && p.basic_materials && sw.basic) {
+    if (!p.global_scene && p.basic_materials && sw.basic) {
         const int n_small_groups = p.n_groups - p.n_big_groups;
-        lean = 1;
-        if (cull && p.cell_on != 0 && n_small_groups >= 1 && n_small_groups <= 128 && sw.onepass) {
-            lean |= 2;                                                           // one list per ray batch
-            if (n_small_groups > 64) lean |= 32;                                 // ... of four words
-            else if (n_small_groups > 32) lean |= 16;                            // ... of two
-            if (p.box_shared_axis != 2) lean |= 8;                               // no shared vertical extent: the 3-axis prefilter
+        lean = kLeanBasic;
+        if (pl.cull && p.cell_on != 0 && n_small_groups >= 1 && n_small_groups <= 128 && sw.onepass) {
+            lean |= kLeanOneList;
+            if (n_small_groups > 64) lean |= kLeanWords4;
+            else if (n_small_groups > 32) lean |= kLeanWords2;
+            if (p.box_shared_axis != 2) lean |= kLeanAxes3;
         }
     }
-    if (p.chunks > 1 && lean != 1 && lean != 3) lean &= 1;                       // (sample chunks: kinds 1, 3 and 7 are built)
-    // (only a frame that takes the two cost-ordered dispatches: its two kernels are the ones instantiated with the stamps)
-    const bool two_phase_frame = ((variant >> 24) & 3) == 0 && p.order && p.px_state && p.px_rays && p.chunks == 1 && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.ns >= 8 &&
-                                 p.nx <= 65535 && p.part.local_rows <= 65535;
-    if (counting) { lean_dbg = (lean == 3 && p.counters == nullptr && sw.wave_debug_light && two_phase_frame) ? 3 : 0; lean = lean_dbg == 3 ? 3 : 0; }
-    const bool lean_list = (lean & 2) != 0;                                      // (the smaller per-wave scratch)
+    lean = clip_lean(0, pl.chunked, lean);
+    // The frame takes the two cost-ordered dispatches: asked for, the buffers are there, the reference stream in whole pixels, enough samples, and the list
+    // entries pack (row << 16 | column).  `order`: the work order after the scene form has had its say.
+    auto two_dispatch = [&](int order, bool enough_samples) {
+        return order == 0 && p.order && p.px_state && p.px_rays && p.chunks == 1 && p.rng_mode == RT_RNG_REFERENCE_STREAM && enough_samples &&
+               p.nx <= 65535 && p.part.local_rows <= 65535;
+    };
+    int order_mode = (variant >> 24) & 3;
+    // The diagnostic instantiation (counters, the reference's ray statistics, time stamps) is the general kernel.  Time lines of the PRODUCTION kernel of the
+    // benchmark scene - RT_WAVE_DEBUG with RT_WAVE_DEBUG_LIGHT=1, no counters: a kind of KindsStamped keeps itself, with the stamps, on a frame of at least 8
+    // samples that takes the two dispatches (only their two kernels are instantiated with the stamps; the hybrid copy clips the kind below and launches the
+    // general diagnostic kernel).
+    if (p.wave_dbg != nullptr || p.counters != nullptr) {
+        pl.lean_dbg = (in_kinds(KindsStamped{}, lean) && p.counters == nullptr && sw.wave_debug_light && two_dispatch(order_mode, p.ns >= 8)) ? lean : 0;
+        lean = pl.lean_dbg;
+    }
     // The persistent kernel's workgroup is a whole CU's worth of waves (16: the launch bound's 4 per SIMD) around ONE scene copy - 88 KB of per-wave scratch (68
     // in the one-list kernels) leave 72 (92) KB for the scene: the full copy up to ~1200 (1500) spheres (60 bytes per sphere), the hybrid one (what a sphere TEST
     // reads in the LDS, what only a HIT reads in global memory: 21 bytes per sphere) up to ~3400; an 8-wave workgroup (44 KB of scratch, 2 waves per SIMD) keeps
     // the hybrid copy resident up to ~5500 spheres; beyond that the same kernel reads the scene from global memory (p.global_scene, decided by the renderer).
     int waves = kWavesPerWg;
-    bool hybrid = false;
-    if (kind == 0 && !p.global_scene) {
-        if (lds_bytes(p.n_padded, p.n, false, 0, 16, lean_list) <= kLdsPerCu) { hybrid = false; waves = 16; }
-        else {                                                                   // hybrid: the lean kinds built for it are 1 and the four-word lists
-            hybrid = true;
-            if (lean != 1 && (lean & 32) == 0) lean &= 1;
-            if (lds_bytes(p.n_padded, p.n, false, 2, 16, (lean & 2) != 0) <= kLdsPerCu) waves = 16;
-            else { waves = 8; }
-        }
+    pl.scene = scene_form(p, (lean & kLeanOneList) != 0);
+    if (pl.scene == 2) {
+        lean = clip_lean(2, pl.chunked, lean);
+        if (lds_bytes(p.n_padded, p.n, false, 2, 16, (lean & kLeanOneList) != 0) > kLdsPerCu) waves = 8;
     }
-    if ((lean & 0x32) == 2 && sw.lean6_pixels > 0 && (long long)p.nx * p.part.local_rows >= sw.lean6_pixels &&
-        2 * (lds_bytes(p.n_padded, p.n, false, 0, 12, true) + kStaticLds) <= (size_t)160 * 1024) { lean |= 4; waves = 12; lean_wgs = 2; }
-    const QueueShape shape = { lean, lean_dbg, 64 * waves };
-    const size_t lds = kind == 1 ? lds_bytes(p.n_padded, p.n, true, 0, kWavesPerWg) : lds_bytes(p.n_padded, p.n, false, hybrid ? 2 : 0, waves, (lean & 2) != 0);
+    int default_wgs = 1;
+    if ((lean & (kLeanOneList | kLeanWords2 | kLeanWords4)) == kLeanOneList && sw.lean6_pixels > 0 && (long long)p.nx * p.part.local_rows >= sw.lean6_pixels &&
+        2 * (lds_bytes(p.n_padded, p.n, false, 0, 12, true) + kStaticLds) <= (size_t)160 * 1024) { lean |= kLeanSixWaves; waves = 12; default_wgs = 2; }
+    pl.lean = lean;
+    pl.threads = 64 * waves;
+    pl.lds = lds_bytes(p.n_padded, p.n, false, pl.scene, waves, (lean & kLeanOneList) != 0);      // (global scene: only the per-wave scratch)
+    int wg_per_cu = (variant >> 8) & 0xFF;
+    if (wg_per_cu == 0) wg_per_cu = default_wgs;   // one workgroup = the residency the kernel's launch bound (4 waves/SIMD, 128 VGPRs) and the LDS allow; the lean kernel: two of 12 waves
+    const long long total_px = (long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64;
+    const long long useful = (total_px + pl.threads - 1) / pl.threads;                // never more lanes than pixels
+    pl.blocks = (unsigned)std::max(1ll, std::min((long long)cus * wg_per_cu, useful));
+    pl.cls_blocks = (unsigned)((total_px + kThreads - 1) / kThreads);
+    // Scenes whose hit data (hybrid copy) or whole scene (global) is read from global memory: the scattered single dispatch beats the cost-ordered two
+    // dispatches (tools/sweep_scene_sizes.py, 1200x800x50, 16-wave workgroups: 1500 spheres 2819 against 2751, 2000: 2113 / 1696, 2600: 1812 / 1149).
+    if (order_mode == 0 && ((pl.scene == 2 && !sw.hybrid_two) || pl.scene == 1)) order_mode = 2;
+    if (order_mode != 1 && total_px > 64) pl.stride = rt_coprime_stride((unsigned long long)total_px);
+    // A continuation pass of a progressive frame (p.acc_first > 0) is the second dispatch of a two-dispatch frame whose first dispatch ran in earlier passes:
+    // the ordering pass reads the accumulated state and rays over p.acc_first samples, PHASE 2 resumes [acc_first, ns).  It has no first dispatch to poison
+    // the host framebuffer: k_poison_fb runs in front of it.
+    const bool resume = p.acc_first > 0 && p.acc_state && p.acc_rays;
+    // order_mode 0 (default), reference stream, enough samples: two phases - measure the cost of every pixel on its first
+    // samples, then resume all pixels longest-first (see k_order_by_cost).  Otherwise: one launch, optionally ordered
+    // by the centre-ray pre-pass (k_classify_spheres: order_mode 3) or plainly scattered (2) / tile-major (1).
+    if (pl.scene == 1) pl.frame = SphereFrame::GlobalSingle;
+    else if (two_dispatch(order_mode, p.ns >= 8 || resume)) pl.frame = resume ? SphereFrame::TwoDispatchResume : SphereFrame::TwoDispatch;
+    else if ((order_mode == 0 || order_mode == 3) && p.order != nullptr) pl.frame = SphereFrame::ClassifiedSingle;
+    else pl.frame = SphereFrame::PlainSingle;
+    pl.sum_chunks = pl.chunked;
+
+    if (sw.mid_waves < 0 || sw.mid_waves > 12 || sw.mid_cap < 1 || sw.mid_cap > 64) { pl.error = SpherePlanError::Mid; return pl; }      // (the middle tier, RT_MID)
     // bits 27..29: extra sparse-form rays per iteration for lanes on a long chain (0 = default 2, 7 = off)
     const int pb = (variant >> 27) & 7;
     // bits 30..31: a wave switches to the sparse form at <= 4 / 8 / 12 / 16 live rays (0 = default)
     int sparse_max = 4 + 4 * ((variant >> 30) & 3);
     if (cb_bits == 255) sparse_max = 0;         // pair-compacted scan only (A/B): never the sparse form
-    const int boost = (pb == 7 || cb_bits == 255) ? 0 : (pb == 0 ? 1 : pb);      // measured on C2: round 2 threshold 8, 2 extra steps: 6300 against 6190 with 10 / 4; round 3, after the dense
-                                                                                 // iteration had gained 10 %: 1 extra step 7850, 2: 7650 Msamples/s (profiles/r03_sweep_tail9.txt)
-    if (kind == 1) {
-        int coop_below = cb_bits;
-        if (coop_below == 0) coop_below = -1;      // pair-compacted scan (+ sparse form)
-        if (coop_below == 255) coop_below = -2;    // pair-compacted scan only (A/B)
-        const void* kern = legacy ? reinterpret_cast<const void*>(k_render_spheres_tiles<true>) : reinterpret_cast<const void*>(k_render_spheres_tiles<false>);
-        if (lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        const dim3 grid((p.nx + 8 * kWavesPerWg - 1) / (8 * kWavesPerWg), (p.part.local_rows + 7) / 8);
-        { const hipError_t ew = wait_fb(); if (ew != hipSuccess) return ew; }
-        if (legacy) hipLaunchKernelGGL(k_render_spheres_tiles<true>, grid, dim3(kThreads), lds, stream, p, coop_below, cull);
-        else hipLaunchKernelGGL(k_render_spheres_tiles<false>, grid, dim3(kThreads), lds, stream, p, coop_below, cull);
-        rt_note_launch(RT_KERNEL_SPHERE_TILES, 0, legacy ? 1 : 0, 0, 0, 0, 0, kThreads, grid.x * grid.y);
-        return hipGetLastError();
-    }
-    if (!p.queue) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(p.queue, 0, 256, stream);
-    if (e != hipSuccess) return e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int wg_per_cu = (variant >> 8) & 0xFF;
-    if (wg_per_cu == 0) wg_per_cu = lean_wgs;   // one workgroup = the residency the kernel's launch bound (4 waves/SIMD, 128 VGPRs) and the LDS allow; the lean kernel: two of 10 waves
-    const long long total_px = (long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64;
-    long long blocks = (long long)cus * wg_per_cu;
-    const long long useful = (total_px + shape.threads - 1) / shape.threads;          // never more lanes than pixels
-    if (blocks > useful) blocks = useful;
-    if (blocks < 1) blocks = 1;
-    // scattered order: stride ~ 0.618 * total, coprime with total
-    uint32_t stride = 1;
-    int order_mode = (variant >> 24) & 3;
-    // Scenes whose hit data (hybrid copy) or whole scene (global) is read from global memory: the scattered single dispatch beats the cost-ordered two
-    // dispatches (tools/sweep_scene_sizes.py, 1200x800x50, 16-wave workgroups: 1500 spheres 2819 against 2751, 2000: 2113 / 1696, 2600: 1812 / 1149).
-    if (order_mode == 0 && ((hybrid && !sw.hybrid_two) || p.global_scene)) order_mode = 2;
-    if (order_mode != 1 && total_px > 64) stride = rt_coprime_stride((unsigned long long)total_px);
     // chain waves: wave 0 of every workgroup (512 waves) serves the chain lists, kSparseRays pixels to a wave; lanes of
     // normal waves above 10 rays per sample are boosted.  Measured on C2 (flat basin) with the multi-ray sparse form:
     // 512 waves x 4 pixels 5780, x 3: 5740, x 2: 5720; 1024 waves x 2: 5610 Msamples/s (before it: 256 x 4: 5040, 512 x 2: 5540).
@@ -2107,107 +2098,131 @@ static hipError_t launch_spheres(const RtSphereParams& p, int variant, const RtS
     // among them every pixel above 3000 rays) holds nothing else and traces it in the single-ray form, the others hold up to kSparseRays.  Round 3, after
     // the dense iteration had gained 4 %: 7300 against 7117 Msamples/s with 512 waves x 4 pixels (profiles/r03_sweep_tail5.txt, r03_sweep_tail6.txt; a flat
     // basin: 768 waves, list 0 from 20..26 rays per sample, 2..4 pixels for the other lists all within 0.5 %; 1024 waves -2 %, list 0 from 30: -6 %).
-    int chain_cfg = 1 | ((waves == 16 ? 3 : (waves >= 10 ? 2 : 1)) << 8) | (kSparseRays << 12) | (8 << 16) | (kChainClasses << 24);
-    int caps = 1 | (4 << 4) | (4 << 8) | (4 << 12);     // pixels a chain wave holds while one of them comes from chain list 0 / 1 / 2 / 3
-    if (sw.mid_waves < 0 || sw.mid_waves > 12 || sw.mid_cap < 1 || sw.mid_cap > 64) return hipErrorInvalidValue;        // (the middle tier, RT_MID)
-    const int caps_mid = (sw.mid_waves << 16) | (sw.mid_cap << 20);
-    caps |= caps_mid;
-    int cfg = cull | (boost << 8) | (sparse_max << 16);
-    // phase 2: a normal wave reserves at least 8 queue positions per grab (one atomic round trip per ~6 finished pixels instead of per ~1: +1.3 % on C2;
+    const int boost = (pb == 7 || cb_bits == 255) ? 0 : (pb == 0 ? 1 : pb);      // measured on C2: round 2 threshold 8, 2 extra steps: 6300 against 6190 with 10 / 4; round 3, after the dense
+                                                                                 // iteration had gained 10 %: 1 extra step 7850, 2: 7650 Msamples/s (profiles/r03_sweep_tail9.txt)
+    int t[kTuneFields] = { 1, waves == 16 ? 3 : (waves >= 10 ? 2 : 1), 8, kChainClasses, boost, kSparseRays, 1, 4, 4 };
+    if (sw.tune) {        // experiments: "chain_every,chain_waves,heavy_thr,n_chain,boost,chain_pixels,chain_pixels of list 0,1,2"
+        t[kTuneChainWaves] = waves == 16 ? 3 : 1;                    // (the fields not given keep their defaults, but a 12-wave workgroup one chain wave)
+        for (int i = 0; i < sw.tune->n; i++) t[i] = sw.tune->v[i];
+        // every field is a bit-field of chain_cfg / cfg and some are divisors or loop bounds in the kernel: refuse what does not fit
+        const int lo[kTuneFields] = { 1, 0, 1, 0, 0, 1, 1, 1, 1 }, hi[kTuneFields] = { 255, waves, 255, 15, 255, 15, 15, 15, 15 };
+        for (int i = 0; i < kTuneFields; i++)
+            if (t[i] < lo[i] || t[i] > hi[i]) { pl.error = SpherePlanError::Tune; return pl; }
+    }
+    pl.chain_cfg = kChainEvery.put(t[kTuneChainEvery]) | kChainWaves.put(t[kTuneChainWaves]) | kChainPixels.put(t[kTuneChainPixels]) | kChainHeavyThr.put(t[kTuneHeavyThr]) |
+                   kChainLists.put(t[kTuneChainLists]);
+    pl.caps = caps_list(0).put(t[kTuneList0]) | caps_list(1).put(t[kTuneList1]) | caps_list(2).put(t[kTuneList2]) | caps_list(3).put(t[kTuneChainPixels]) |
+              kCapsMidWaves.put(sw.mid_waves) | kCapsMidCap.put(sw.mid_cap);
+    // kCfgPool: a normal wave of phase 2 reserves at least 8 queue positions per grab (one atomic round trip per ~6 finished pixels instead of per ~1: +1.3 % on C2;
     // 16 and more hoard pixels at the end of the frame and lose: 8 -> 7144, 16 -> 6616, 32 -> 6019 Msamples/s, profiles/r03_sweep_pool.txt)
     // (RT_POOL, round 4, lean kernel: 4 -> 8517, 8 -> 8420, 16 -> 8110 Msamples/s, profiles/r04_sweep_tune_c2.txt)
-    if (sw.chain_single) cfg |= 2;
-    if (sw.single_ray) cfg |= 4;
-    cfg |= ((sw.pool / 4) & 0x1F) << 3;
-    if (sw.wave_debug_light) cfg |= 1 << 29;
-    if (sw.tune) {        // experiments: "chain_every,chain_waves,heavy_thr,n_chain,boost,chain_pixels,chain_pixels of list 0,1,2"
-        int v[9] = { 1, waves == 16 ? 3 : 1, 8, kChainClasses, boost, kSparseRays, 1, 4, 4 };      // the fields not given
-        for (int i = 0; i < sw.tune->n; i++) v[i] = sw.tune->v[i];
-        const int a = v[0], b = v[1], c = v[2], d = v[3], e2 = v[4], f = v[5], g = v[6], g1 = v[7], g2 = v[8];
-        // every field is a bit-field of chain_cfg / cfg and some are divisors or loop bounds in the kernel: refuse what does not fit
-        if (a < 1 || a > 255 || b < 0 || b > waves || c < 1 || c > 255 || d < 0 || d > 15 || e2 < 0 || e2 > 255 ||
-            f < 1 || f > 15 || g < 1 || g > 15 || g1 < 1 || g1 > 15 || g2 < 1 || g2 > 15) {
-            fprintf(stderr, "rt error: RT_TUNE=%s out of range (chain_every 1..255, chain_waves 0..%d, heavy_thr 1..255, n_chain 0..15, boost 0..255, "
-                            "chain_pixels 1..15, chain_pixels of list 0 / 1 / 2 1..15)\n", sw.tune->text.c_str(), kWavesPerWg);
-            return hipErrorInvalidValue;
-        }
-        chain_cfg = a | (b << 8) | (f << 12) | (c << 16) | (d << 24);
-        caps = g | (g1 << 4) | (g2 << 8) | (f << 12) | caps_mid;
-        cfg = cull | (e2 << 8) | (sparse_max << 16) | (sw.chain_single ? 2 : 0) | (sw.single_ray ? 4 : 0) | (((sw.pool / 4) & 0x1F) << 3) | (sw.wave_debug_light ? (1 << 29) : 0);
+    pl.cfg = (pl.cull ? kCfgCull : 0) | (sw.chain_single ? kCfgChainSingle : 0) | (sw.single_ray ? kCfgSingleRay : 0) | kCfgPool.put((sw.pool / 4) & kCfgPool.mask) |
+             kCfgBoost.put(t[kTuneBoost]) | kCfgSparseMax.put(sparse_max) | (sw.wave_debug_light ? kCfgDbgLight : 0);
+    // (p.p1_tile_major 1: the two-sample items of the first dispatch in tile-major order - a wave parks two adjacent 8x8 tiles, whole lines of px_state; 2: scattered
+    // as row segments of 8 pixels - a line of px_state per 8 lanes, the scattering kept)
+    pl.stride1 = p.p1_tile_major == 1 ? 1u : pl.stride;
+    pl.cfg1 = pl.cfg;
+    if (p.p1_tile_major == 2 && total_px > 512) {
+        pl.stride1 = rt_coprime_stride((unsigned long long)total_px >> 3);
+        pl.cfg1 |= kCfgP1Segments;
     }
-    const unsigned nb = (unsigned)blocks;
-    const unsigned cls_blocks = (unsigned)((total_px + kThreads - 1) / kThreads);
-    if (p.global_scene) {                       // single dispatch, scattered order
-        e = wait_fb();
-        if (e != hipSuccess) return e;
-        e = p.chunks > 1 ? launch_queue_kernel_global<true>(p, nb, stream, stride, cfg, chain_cfg) : launch_queue_kernel_global<false>(p, nb, stream, stride, cfg, chain_cfg);
-        if (e != hipSuccess) return e;
-        if (p.chunks > 1) {
-            const size_t npx = (size_t)p.part.local_rows * p.nx;
-            hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, p);
-        }
-        return hipGetLastError();
-    }
+    return pl;
+}
 
-    // order_mode 0 (default), reference stream, enough samples: two phases — measure the cost of every pixel on its first
-    // samples, then resume all pixels longest-first (see k_order_by_cost).  Otherwise: one launch, optionally ordered
-    // by the centre-ray pre-pass (k_classify_spheres: order_mode 3) or plainly scattered (2) / tile-major (1).
-    const int split = 2;                                             // measured: 1 -> 15.5 ms, 2 -> 15.0, 3 -> 15.1 (round 2); 2 -> 24.5, 4 -> 24.8, 6 -> 25.4 (round 1)
-    // A continuation pass of a progressive frame (p.acc_first > 0) is the second dispatch of a two-dispatch frame whose first dispatch ran in earlier passes:
-    // the ordering pass reads the accumulated state and rays over p.acc_first samples, PHASE 2 resumes [acc_first, ns).  It has no first dispatch to poison
-    // the host framebuffer: k_poison_fb runs in front of it.
-    const bool resume = p.acc_first > 0 && p.acc_state && p.acc_rays;
-    if (order_mode == 0 && p.order && p.px_state && p.px_rays && p.chunks == 1 && p.rng_mode == RT_RNG_REFERENCE_STREAM && (p.ns >= 8 || resume) &&
-        p.nx <= 65535 && p.part.local_rows <= 65535) {                                   // list entries pack (row << 16 | column)
+// One instantiation of k_render_spheres_queue, named by its template arguments: launch_sphere_queue launches it and notes those arguments for the
+// launch report (rtLastLaunches).  Every launch of the persistent kernel goes through it.
+template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN = 0> struct SphereQueueForm {};
+
+// (The global scene's launch asks for 86 KB, the per-wave scratch of 16 waves, and used to leave the attribute unset, which the runtime let pass; it now sets it
+// like every other launch above 64 KB.)
+template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN>
+static hipError_t launch_sphere_queue(SphereQueueForm<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>, const RtSphereParams& q, const SpherePlan& pl, hipStream_t stream,
+                                      uint32_t stride, int cfg, int caps) {
+    const hipError_t e = launch_with_lds(k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, q, stride, cfg, pl.chain_cfg, caps);
+    rt_note_launch(RT_KERNEL_SPHERE_QUEUE, PHASE, CLS, CHUNKED, DBG, SCENE, LEAN, pl.threads, pl.blocks);
+    return e;
+}
+
+// Launches the kind `lean` of a list through `go`, if the list has it; says whether it had.
+template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int... LEANS, typename Go>
+static bool launch_kind_of(std::integer_sequence<int, LEANS...>, int lean, Go&& go, hipError_t& e) {
+    return ((lean == LEANS && ((e = go(SphereQueueForm<PHASE, CLS, CHUNKED, DBG, SCENE, LEANS>{})), true)) || ...);
+}
+
+// The planned instantiation of one launch site (PHASE, CLS, CHUNKED): scene form and kind from the plan, the diagnostic one if `q` asks for counters or
+// stamps (they - and with them the reference's ray statistics - live in the diagnostic instantiations only).  A kind that is not built is an error.
+template <int PHASE, int CLS, bool CHUNKED>
+static hipError_t launch_queue_form(const SpherePlan& pl, const RtSphereParams& q, hipStream_t stream, uint32_t stride, int cfg, int caps = kCapsNoTiers) {
+    const bool counting = q.wave_dbg != nullptr || q.counters != nullptr;
+    auto go = [&](auto form) -> hipError_t { return launch_sphere_queue(form, q, pl, stream, stride, cfg, caps); };
+    hipError_t e = hipErrorInvalidValue;
+    if (pl.scene == 1) {
+        if constexpr (PHASE == 0 && CLS == 0) e = counting ? go(SphereQueueForm<0, 0, CHUNKED, true, 1>{}) : go(SphereQueueForm<0, 0, CHUNKED, false, 1>{});
+        return e;
+    }
+    // (time lines of the PRODUCTION kernel, no counters: the plan's lean_dbg with the stamps, on the two dispatches of a frame; else the general diagnostic kernel)
+    if (counting && q.counters == nullptr && pl.scene == 0 && !CHUNKED && PHASE != 0 && launch_kind_of<PHASE, CLS, false, true, 0>(KindsStamped{}, pl.lean_dbg, go, e)) return e;
+    if (counting) return pl.scene == 2 ? go(SphereQueueForm<PHASE, CLS, CHUNKED, true, 2>{}) : go(SphereQueueForm<PHASE, CLS, CHUNKED, true, 0>{});
+    if (pl.lean == 0) return pl.scene == 2 ? go(SphereQueueForm<PHASE, CLS, CHUNKED, false, 2>{}) : go(SphereQueueForm<PHASE, CLS, CHUNKED, false, 0>{});
+    if (pl.scene == 0 && !CHUNKED) launch_kind_of<PHASE, CLS, false, false, 0>(KindsFull{}, pl.lean, go, e);
+    if (pl.scene == 0 && CHUNKED) launch_kind_of<PHASE, CLS, true, false, 0>(KindsChunked{}, pl.lean, go, e);
+    if (pl.scene == 2 && !CHUNKED) launch_kind_of<PHASE, CLS, false, false, 2>(KindsHybrid{}, pl.lean, go, e);
+    return e;
+}
+
+hipError_t RT_LAUNCH_NAME(const RtSphereParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
+    // p.self: the device copy of the parameter block, owned and refreshed by the renderer (one per device state and frame).  Only fields that are
+    // the same for the whole frame of that device state (camera, image size, RNG mode) are read through it.  (Reading the per-pixel fields -
+    // framebuffer, parked state, partition - this way too took the kernel from 61 to 43 spilled SGPRs and gained nothing more: 7030 against 7025 Msamples/s.)
+    if (!p.self) return hipErrorInvalidValue;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const SpherePlan pl = plan_spheres(p, variant, sw, cus);
+    // p.poison_fb: a single-dispatch frame is preceded by k_poison_fb on the same stream; the two-dispatch frame lets its first dispatch do it
+    auto wait_fb = [&]() -> hipError_t {
+        if (!p.poison_fb) return hipSuccess;
+        hipLaunchKernelGGL(k_poison_fb, dim3(512), dim3(256), 0, stream, p);
+        return hipGetLastError();
+    };
+    hipError_t e;
+    if (pl.frame == SphereFrame::Tiles) {
+        if ((e = wait_fb()) != hipSuccess) return e;
+        e = launch_with_lds(pl.legacy ? k_render_spheres_tiles<true> : k_render_spheres_tiles<false>, dim3(pl.blocks, pl.blocks_y), dim3(kThreads), pl.lds, stream, p, pl.coop_below, pl.cull);
+        rt_note_launch(RT_KERNEL_SPHERE_TILES, 0, pl.legacy ? 1 : 0, 0, 0, 0, 0, kThreads, pl.blocks * pl.blocks_y);
+        return e;
+    }
+    if (!p.queue) return hipErrorInvalidValue;
+    if ((e = hipMemsetAsync(p.queue, 0, 256, stream)) != hipSuccess) return e;
+    if (pl.error == SpherePlanError::Tune)
+        fprintf(stderr, "rt error: RT_TUNE=%s out of range (chain_every 1..255, chain_waves 0..%d, heavy_thr 1..255, n_chain 0..15, boost 0..255, "
+                        "chain_pixels 1..15, chain_pixels of list 0 / 1 / 2 1..15)\n", sw.tune->text.c_str(), kWavesPerWg);
+    if (pl.error != SpherePlanError::None) return hipErrorInvalidValue;
+    if (pl.frame == SphereFrame::TwoDispatch || pl.frame == SphereFrame::TwoDispatchResume) {
         RtSphereParams q = p;
-        if (resume) {
+        if (pl.frame == SphereFrame::TwoDispatchResume) {
             q.px_state = p.acc_state; q.px_rays = p.acc_rays; q.s_split = p.acc_first;
             e = wait_fb();
-            if (e != hipSuccess) return e;
         } else {
-            q.phase = 1; q.s_split = split;
-            // (q.p1_tile_major 1: the two-sample items in tile-major order - a wave parks two adjacent 8x8 tiles, whole lines of px_state; 2: scattered as row
-            // segments of 8 pixels - a line of px_state per 8 lanes, the scattering kept)
-            uint32_t stride1 = stride;
-            int cfg1 = cfg;
-            if (q.p1_tile_major == 1) stride1 = 1u;
-            if (q.p1_tile_major == 2 && total_px > 512) {
-                stride1 = rt_coprime_stride((unsigned long long)total_px >> 3);
-                cfg1 |= 1 << 30;
-            }
-            e = launch_queue_kernel<1, 0, false>(q, shape, nb, lds, hybrid, stream, stride1, cfg1, chain_cfg);
-            if (e != hipSuccess) return e;
+            q.phase = 1; q.s_split = kFirstSamples;
+            e = launch_queue_form<1, 0, false>(pl, q, stream, pl.stride1, pl.cfg1);
         }
-        e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords, stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_order_by_cost<0>, dim3(kOrderBlocks), dim3(kThreads), 0, stream, q);
-        hipLaunchKernelGGL(k_order_by_cost<1>, dim3(kOrderBlocks), dim3(kThreads), 0, stream, q);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        if ((e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords, stream)) != hipSuccess) return e;
+        if ((e = order_pixels_by_cost(q, stream)) != hipSuccess) return e;
         q.phase = 2;
         if (sw.wave_debug_phase) q.wave_dbg = nullptr;                  // diagnostics: the time line of the FIRST dispatch
-        return launch_queue_kernel<2, 2, false>(q, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg, caps);
+        return launch_queue_form<2, 2, false>(pl, q, stream, pl.stride, pl.cfg, pl.caps);
     }
-    bool classified = false;
-    if ((order_mode == 0 || order_mode == 3) && p.order != nullptr) {
-        const void* cls_kern = hybrid ? reinterpret_cast<const void*>(k_classify_spheres<2>) : reinterpret_cast<const void*>(k_classify_spheres<0>);
-        if (lds > 64 * 1024) {
-            e = hipFuncSetAttribute(cls_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        if (hybrid) hipLaunchKernelGGL(k_classify_spheres<2>, dim3(cls_blocks), dim3(kThreads), lds, stream, p);
-        else hipLaunchKernelGGL(k_classify_spheres<0>, dim3(cls_blocks), dim3(kThreads), lds, stream, p);
-        e = hipGetLastError();
+    const bool classified = pl.frame == SphereFrame::ClassifiedSingle;
+    if (classified) {
+        e = launch_with_lds(pl.scene == 2 ? k_classify_spheres<2> : k_classify_spheres<0>, dim3(pl.cls_blocks), dim3(kThreads), pl.lds, stream, p);
         if (e != hipSuccess) return e;
-        classified = true;
     }
-    const bool chunked = p.chunks > 1;
-    e = wait_fb();
+    if ((e = wait_fb()) != hipSuccess) return e;
+    if (classified) e = pl.chunked ? launch_queue_form<0, 1, true>(pl, p, stream, pl.stride, pl.cfg) : launch_queue_form<0, 1, false>(pl, p, stream, pl.stride, pl.cfg);
+    else e = pl.chunked ? launch_queue_form<0, 0, true>(pl, p, stream, pl.stride, pl.cfg) : launch_queue_form<0, 0, false>(pl, p, stream, pl.stride, pl.cfg);
     if (e != hipSuccess) return e;
-    if (classified) e = chunked ? launch_queue_kernel<0, 1, true>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg) : launch_queue_kernel<0, 1, false>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg);
-    else e = chunked ? launch_queue_kernel<0, 0, true>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg) : launch_queue_kernel<0, 0, false>(p, shape, nb, lds, hybrid, stream, stride, cfg, chain_cfg);
-    if (e != hipSuccess) return e;
-    if (chunked) {
+    if (pl.sum_chunks) {
         const size_t npx = (size_t)p.part.local_rows * p.nx;
         hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, p);
     }

@@ -117,7 +117,7 @@ struct RtSphereParams {
     // Progressive rendering (runRendererProgressive, rt_api.h): a pass adds samples [acc_first, ns) to every pixel.  acc_state / acc_rays (local_rows * nx,
     // nullptr = not a progressive pass) hold (col.xyz, rng bits) and the rays traced since sample 0 of every pixel, written by the PHASE 0 and PHASE 2 kernels
     // when a pixel is finished.  acc_first > 0: the pass continues them - PHASE 0 loads the parked state at fetch instead of starting the pixel; the
-    // two-dispatch frame skips its first dispatch and orders the pixels by acc_rays over acc_first samples (launch_spheres).
+    // two-dispatch frame skips its first dispatch and orders the pixels by acc_rays over acc_first samples (plan_spheres).
     float4* acc_state;
     uint32_t* acc_rays;
     int32_t acc_first;

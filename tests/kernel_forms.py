@@ -3,14 +3,15 @@ options and environment that select it, and the launch records (rtLastLaunches, 
 the scene builder and the render helpers, read by tests/test_gpu_kernel_forms.py (which renders every form and holds it to the CPU oracle) and by the CPU tripwire in
 tests/test_kernel_forms_table.py (which holds this table to the launch sites in the kernel sources).
 
-How the sphere launcher (launch_spheres, rt_kernels_spheres.hip) picks LEAN for a scene in the LDS:
+How the sphere launcher (plan_spheres, rt_kernels_spheres.hip) picks LEAN for a scene in the LDS:
   bit 0   every material is RT_DIFFUSE / RT_METAL / RT_GLASS
   bit 1   culling on, cell tables on, 1..128 small groups (16 spheres each): one group list per ray batch
   bit 4   ... of two words (33..64 small groups)        bit 5   ... of four words (65..128 small groups)
   bit 3   the group boxes share no extent on y (box_shared_axis != 2): the 3-axis prefilter
   bit 2   one-word lists on a frame of at least RT_LEAN6_PIXELS pixels: six waves per SIMD (12-wave workgroups, two per CU)
 The hybrid copy (scenes past the full LDS copy) keeps 1 and the four-word kinds, the sample chunks (counter RNG) keep 1, 3 and 7; a scene past the
-hybrid copy is read from global memory (SCENE 1, no lean kinds).  Kinds that are not built fall back to LEAN 0 (the general kernel)."""
+hybrid copy is read from global memory (SCENE 1, no lean kinds).  The plan clips a kind that is not built (the lists KindsFull, KindsChunked,
+KindsHybrid) to its basic-materials bit or, failing that, to LEAN 0 (the general kernel); a launch of a kind that is not built is an error."""
 
 # record words compared by the tests (the device and fp words are fixed: device 0, RT_FP_PARITY)
 FAMILY_SPHERE_QUEUE, FAMILY_SPHERE_TILES, FAMILY_MESH_QUEUE, FAMILY_MESH_TILES = 1, 2, 3, 4
@@ -99,7 +100,7 @@ FORMS = [
     dict(name="hybrid8_general", scene=("cloud", 4000, "volume", True), ns=ONE_NS, records=sphere_one(2, 0, waves=8, cls=0)),
     dict(name="hybrid8_lean1", scene=("cloud", 4000, "volume", False), ns=ONE_NS, records=sphere_one(2, 1, waves=8, cls=0)),
     dict(name="hybrid16_chunked", scene=("cloud", 2100, "volume", False), ns=ONE_NS, opts=_COUNTER, tol=True,
-         records=sphere_one(2, 0, cls=0, chunked=True)),                          # (LEAN 1 is chosen, but no chunked hybrid kind is built: the general kernel)
+         records=sphere_one(2, 0, cls=0, chunked=True)),                          # (basic materials, but no chunked hybrid kind is built: the plan takes the general kernel)
     # ---- SCENE 1: the whole scene in global memory, single scattered dispatch
     dict(name="global", scene=("cloud", 6000, "volume", False), ns=ONE_NS, records=sphere_one(1, 0, cls=0)),
     dict(name="global_chunked", scene=("cloud", 6000, "volume", False), ns=ONE_NS, opts=_COUNTER, tol=True, records=sphere_one(1, 0, cls=0, chunked=True)),

@@ -92,7 +92,7 @@ def test_translation_unit_is_built_once_with_contraction_off():
     for name in ("rt_kernels_spheres.hip", "rt_kernels_mesh.hip", "rt_probe.hip", "rt_params.h", "rt_device.h"):
         assert "denoise" not in open(os.path.join(csrc, name)).read().lower(), name
     src = open(os.path.join(csrc, "rt_kernels_denoise.hip")).read()
-    for scanned in ("launch_mesh_queue<", "k_render_mesh<", "k_render_spheres_tiles<", "launch_queue_kernel", "k_render_spheres_queue<", "k_render_mesh_queue<"):
+    for scanned in ("launch_mesh_queue<", "k_render_mesh<", "k_render_spheres_tiles<", "launch_queue_form", "launch_kind_of", "launch_with_lds", "k_render_spheres_queue<", "k_render_mesh_queue<"):
         assert scanned not in src, scanned
     assert "fmaf" not in src and "__fmaf" not in src and "expf" not in src
 

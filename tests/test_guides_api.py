@@ -67,7 +67,7 @@ def test_guide_kernels_are_built_once_and_keep_away_from_the_form_tables():
         src = open(os.path.join(ROOT, "cuda-raytracing-optimized_amd", "csrc", name)).read()
         i = src.index("void __launch_bounds__(kThreads) " + kern)
         assert src.rfind("#if defined(RT_MODE_PARITY)", 0, i) > src.rfind("#endif", 0, i), kern
-        for scanned in ("launch_mesh_queue<", "k_render_mesh<", "k_render_spheres_tiles<", "launch_queue_kernel"):
+        for scanned in ("launch_mesh_queue<", "k_render_mesh<", "k_render_spheres_tiles<", "launch_queue_form", "launch_kind_of"):
             body = src[i:src.index("#endif", i)]
             assert scanned not in body, (kern, scanned)
 

@@ -1,6 +1,7 @@
 """CPU tripwire: the table of production forms (tests/kernel_forms.py, rendered by test_gpu_kernel_forms.py) against the launch sites in the kernel
 sources.  Every instantiation a launcher can launch without diagnostics must have a row, and every row must name an instantiation that is still
-launched: a new `case` in launch_queue_kernel_scene without a test, or a deleted one with a stale row, fails here without a GPU."""
+launched: a new kind in the lists of rt_kernels_spheres.hip (KindsFull, KindsChunked, KindsHybrid) without a test, or a deleted one with a stale row,
+fails here without a GPU.  The sphere launcher's shape is held too: a plan without HIP calls, one place that sets the LDS attribute, one statement of the kinds."""
 import os
 import re
 
@@ -26,26 +27,42 @@ def _function(src, signature):
     return src[i:j]
 
 
+KIND_LISTS = {"KindsFull": (0, 0), "KindsChunked": (0, 1), "KindsHybrid": (2, 0)}     # list -> (scene, chunked) of its instantiations
+
+
+def sphere_kind_lists(src):
+    """The LEAN kinds the source declares: {list name: [kinds]} of every `using Kinds... = std::integer_sequence<int, ...>`."""
+    return {name: [int(v) for v in kinds.split(",")] for name, kinds in re.findall(r"using\s+(Kinds\w+)\s*=\s*std::integer_sequence<int,([^>]*)>;", src)}
+
+
 def sphere_source_forms():
     """(scene, chunked, lean) of every non-diagnostic k_render_spheres_queue launch, (phase, cls, chunked) of the launcher's calls, tile kernels."""
     src = _code("rt_kernels_spheres.hip")
-    scene_fn = _function(src, "static hipError_t launch_queue_kernel_scene(")
+    lists = sphere_kind_lists(src)
+    assert set(lists) == set(KIND_LISTS) | {"KindsStamped"}, sorted(lists)           # (KindsStamped: diagnostic instantiations)
+    form_fn = _function(src, "static hipError_t launch_queue_form(")
     forms = set()
-    for case, args in re.findall(r"case\s+(\d+)\s*:\s*return\s+go\(\s*SphereQueueForm<([^>]*)>\{\}\)", scene_fn):
-        phase, cls, chunked, dbg, scene, lean = [a.strip() for a in args.split(",")]
-        assert (phase, cls) == ("PHASE", "CLS") and dbg == "false" and int(lean) == int(case), args
-        forms.add((int(scene), _bool(chunked), int(lean)))
-    # the fallback: the general kernel of every scene form and chunking the launcher passes in
-    assert re.search(r"return\s+go\(\s*SphereQueueForm<PHASE,\s*CLS,\s*CHUNKED,\s*false,\s*SCENE>\{\}\);", scene_fn)
-    scenes = {int(s) for s in re.findall(r"launch_queue_kernel_scene<PHASE,\s*CLS,\s*CHUNKED,\s*(\d+)>\(", src)}
-    calls = {(int(p), int(c), _bool(ch)) for p, c, ch in re.findall(r"launch_queue_kernel<(\d+),\s*(\d+),\s*(true|false)>\(", src)}
+    for name, (scene, chunked) in KIND_LISTS.items():
+        # the list is expanded into non-diagnostic instantiations of its own scene form and chunking, and of nothing else
+        sites = re.findall(r"launch_kind_of<PHASE,\s*CLS,\s*(true|false),\s*(true|false),\s*(\d+)>\(%s\{\}" % name, form_fn)
+        assert sites == [({0: "false", 1: "true"}[chunked], "false", str(scene))], (name, sites)
+        assert all(v != 0 for v in lists[name]) and len(set(lists[name])) == len(lists[name]), (name, lists[name])
+        forms |= {(scene, chunked, v) for v in lists[name]}
+    assert len(re.findall(r"launch_kind_of<", form_fn)) == len(KIND_LISTS) + 1
+    assert re.findall(r"launch_kind_of<PHASE,\s*CLS,\s*false,\s*true,\s*0>\((\w+)\{\}", form_fn) == ["KindsStamped"]
+    # the general kernel of the two LDS scene forms, for every chunking the launcher passes in
+    scenes = {int(s) for s in re.findall(r"SphereQueueForm<PHASE,\s*CLS,\s*CHUNKED,\s*false,\s*(\d+)>\{\}", form_fn)}
+    calls = {(int(p), int(c), _bool(ch)) for p, c, ch in re.findall(r"launch_queue_form<(\d+),\s*(\d+),\s*(true|false)>\(", src)}
     assert scenes and calls
     forms |= {(s, ch, 0) for s in scenes for ch in {ch for _, _, ch in calls}}
-    # the global scene
-    global_fn = _function(src, "static hipError_t launch_queue_kernel_global(")
-    assert re.search(r"SphereQueueForm<0,\s*0,\s*CHUNKED,\s*false,\s*1>\{\}", global_fn)
-    forms |= {(1, _bool(ch), 0) for ch in re.findall(r"launch_queue_kernel_global<(true|false)>\(", src)}
-    tiles = {_bool(t) for t in re.findall(r"hipLaunchKernelGGL\(k_render_spheres_tiles<(true|false)>", src)}
+    # the global scene: the launch sites of (PHASE 0, CLS 0) alone
+    assert re.search(r"if constexpr \(PHASE == 0 && CLS == 0\)[^\n]*SphereQueueForm<0,\s*0,\s*CHUNKED,\s*false,\s*1>\{\}", form_fn)
+    forms |= {(1, ch, 0) for p, c, ch in calls if (p, c) == (0, 0)}
+    # every instantiation is named in launch_queue_form (through SphereQueueForm) and launched by launch_sphere_queue alone
+    assert len(re.findall(r"k_render_spheres_queue<", src)) == 1 and "k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>" in _function(src, "static hipError_t launch_sphere_queue(")
+    elsewhere = set(re.findall(r"SphereQueueForm<([^>]*)>", src.replace(form_fn, "")))
+    assert elsewhere == {"PHASE, CLS, CHUNKED, DBG, SCENE, LEAN", "PHASE, CLS, CHUNKED, DBG, SCENE, LEANS"}, elsewhere       # launch_sphere_queue, launch_kind_of
+    tiles = {_bool(t) for t in re.findall(r"k_render_spheres_tiles<(true|false)>", _function(src, "hipError_t RT_LAUNCH_NAME("))}
     return forms, calls, tiles
 
 
@@ -107,3 +124,35 @@ def test_table_rows_are_complete():
         assert len({r[7:] for r in f["records"]}) == 1, f["name"]
     assert set(full) == {0, 1, 3, 7, 11, 15, 19, 27, 35, 43}
     assert all(phases == {0, 1, 2} for phases in full.values()), full
+
+
+# ---- the sphere launcher: a pure plan, one attribute site, one statement of the kinds ----------------------------------
+
+def _host_region(src):
+    """The launcher: everything behind the kernels."""
+    return src[src.index("constexpr size_t kStaticLds"):]
+
+
+def test_plan_spheres_makes_no_hip_call():
+    body = _function(_code("rt_kernels_spheres.hip"), "static SpherePlan plan_spheres(")
+    assert len(body) > 2000 and "return pl;" in body
+    assert re.findall(r"hip[A-Z]\w*\(", body) == []
+
+
+def test_lds_attribute_is_set_in_one_function():
+    src = _code("rt_kernels_spheres.hip")
+    assert len(re.findall(r"hipFuncSetAttribute", src)) == 1
+    assert "hipFuncSetAttribute" in _function(src, "static hipError_t launch_with_lds(")
+
+
+def test_lean_literals_of_the_built_kinds_occur_only_in_the_kind_lists():
+    """Outside the kind lists the launcher names no built kind by its number: no `case`, no comparison or assignment of a lean value with such a literal,
+    no template argument list that ends in one.  (The LEAN bits are named constants written as shifts.)"""
+    src = _code("rt_kernels_spheres.hip")
+    built = {v for kinds in sphere_kind_lists(src).values() for v in kinds}
+    assert {1, 3, 7, 35, 43} <= built
+    host = re.sub(r"using\s+Kinds\w+\s*=\s*std::integer_sequence<int,[^>]*>;", "", _host_region(src))
+    found = [(m.group(0), int(m.group(1), 0)) for m in re.finditer(r"\bcase\s+(\d+|0x[0-9a-fA-F]+)\s*:", host)]
+    found += [(m.group(0), int(m.group(1), 0)) for m in re.finditer(r"\blean\w*\s*(?:==|!=|\|=|&=|=|&|\|)\s*(\d+|0x[0-9a-fA-F]+)\b", host)]
+    found += [(m.group(0), int(m.group(1), 0)) for m in re.finditer(r"(?:SphereQueueForm|k_render_spheres_queue)<(?:[^<>,]*,){5}\s*(\d+)\s*>", host)]
+    assert [f for f in found if f[1] in built] == [], found
