@@ -41,10 +41,14 @@ $(OBJ)/probe_fast.o: $(CSRC)/rt_probe.hip $(KERNEL_HDRS) include/rt_probe.h | $(
 # the default correctly rounded divide / sqrt and fp32 denormals).  Its own TU and header: the objects above do not depend on it.
 $(OBJ)/denoise.o: $(CSRC)/rt_kernels_denoise.hip $(CSRC)/rt_denoise.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The temporal accumulation's kernel (accumulateFrame): defined bit for bit as the denoiser is, so one object with the flags of denoise.o; the launcher's
+# host arithmetic (the constants of the previous camera) is compiled under them too.  Its own TU and header: no other kernel object depends on it.
+$(OBJ)/accumulate.o: $(CSRC)/rt_kernels_accumulate.hip $(CSRC)/rt_accumulate.h include/rt_types.h include/rt_api.h | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o
+RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o
 
 $(PKG)/librt_mi355x.so: $(RT_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) -o $@

@@ -132,7 +132,8 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "rtDeviceCount", "rtApiVersion", "rtStructSizes", "rtLastLaunches",
                     "runRendererProgressive", "rtProgressiveSamples", "rtResetProgressive", "setCamera",
                     "renderGuides", "rtLastGuidesMs",
-                    "rtDefaultDenoiseFlags", "denoiseFrame", "rtLastDenoiseMs"]
+                    "rtDefaultDenoiseFlags", "denoiseFrame", "rtLastDenoiseMs",
+                    "accumulateFrame", "rtResetHistory", "rtHistoryFrames", "rtLastAccumulateMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
@@ -265,6 +266,14 @@ def load_renderer():
         r.denoiseFrame.restype = None
         r.rtLastDenoiseMs.argtypes = []
         r.rtLastDenoiseMs.restype = C.c_double
+        r.accumulateFrame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
+        r.accumulateFrame.restype = None
+        r.rtResetHistory.argtypes = []
+        r.rtResetHistory.restype = None
+        r.rtHistoryFrames.argtypes = []
+        r.rtHistoryFrames.restype = C.c_int
+        r.rtLastAccumulateMs.argtypes = []
+        r.rtLastAccumulateMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -521,6 +530,56 @@ def denoiseFrame(fb=None, iterations=5, flags=None, normal_squarings=5, sigma_z=
 def last_denoise_ms():
     """HIP-event time of the kernels of the last denoiseFrame (prologue + iterations), in milliseconds; 0 before the first call."""
     return load_renderer().rtLastDenoiseMs()
+
+
+# accumulateFrame (include/rt_api.h): the largest history length
+RT_ACCUM_MAX_HISTORY = 1024
+
+
+def accumulateFrame(fb=None, out=None, history=False, flags=None, max_history=32, sigma_z=0.01, normal_min=0.9):
+    """Temporal accumulation for a moving camera (include/rt_api.h): blends the frame with the previous call's result, reprojected through the hit points
+    and checked against the previous frame's geometry.  fb: a (ny, nx, 3) float32 array, row 0 = bottom; None = the framebuffer the renderer currently
+    delivers into.  out: a writable C-contiguous float32 array of that shape (it may be `fb` itself: in place), None = a new one.  history: True = also
+    return the per-pixel history length N as a (ny, nx) float32 array, or such an array to fill.  flags None = the scene kind's default.  Returns out, or
+    (out, history).  Blocking; always the whole image on the first device.  The loop of a camera move: setCamera, runRenderer(1), accumulateFrame,
+    denoiseFrame."""
+    nx, ny = _state["nx"], _state["ny"]
+    r = load_renderer()
+    if flags is None:
+        flags = r.rtDefaultDenoiseFlags()
+    src = None
+    if fb is not None:
+        if not (isinstance(fb, np.ndarray) and fb.dtype == np.float32 and fb.flags["C_CONTIGUOUS"] and fb.shape == (ny, nx, 3)):
+            raise ValueError(f"accumulateFrame: fb must be a C-contiguous float32 array of shape {(ny, nx, 3)}")
+        src = fb.ctypes.data
+    if out is None:
+        out = np.empty((ny, nx, 3), np.float32)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.shape == (ny, nx, 3)):
+        raise ValueError(f"accumulateFrame: out must be a writable C-contiguous float32 array of shape {(ny, nx, 3)}")
+    hist = None
+    if history is True:
+        hist = np.empty((ny, nx), np.float32)
+    elif history is not False and history is not None:
+        hist = history
+        if not (isinstance(hist, np.ndarray) and hist.dtype == np.float32 and hist.flags["C_CONTIGUOUS"] and hist.flags["WRITEABLE"] and hist.shape == (ny, nx)):
+            raise ValueError(f"accumulateFrame: history must be True, False or a writable C-contiguous float32 array of shape {(ny, nx)}")
+    r.accumulateFrame(src, out.ctypes.data, None if hist is None else hist.ctypes.data, flags, max_history, sigma_z, normal_min)
+    return out if hist is None else (out, hist)
+
+
+def reset_history():
+    """The next accumulateFrame has no history."""
+    load_renderer().rtResetHistory()
+
+
+def history_frames():
+    """accumulateFrame calls since init / the last reset of the history."""
+    return load_renderer().rtHistoryFrames()
+
+
+def last_accumulate_ms():
+    """HIP-event time of the kernel of the last accumulateFrame, in milliseconds; 0 before the first call."""
+    return load_renderer().rtLastAccumulateMs()
 
 
 def cleanupRenderer():

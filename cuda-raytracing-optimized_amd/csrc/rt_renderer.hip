@@ -27,6 +27,7 @@
 #include "../../include/rt_api.h"
 #include "rt_params.h"
 #include "rt_denoise.h"
+#include "rt_accumulate.h"
 
 namespace {
 
@@ -45,8 +46,8 @@ void hip_check(hipError_t result, const char* func, const char* file, int line) 
     exit(99);
 }
 
-// Device memory: every allocation of a DeviceState / DenoiseState goes through dev_alloc, which notes the pointer in its owner's `owned`, and free_device /
-// free_denoise release what that record holds - a buffer cannot be allocated without being freed.  The record is plain data walked by those two functions
+// Device memory: every allocation of a DeviceState / DenoiseState / AccumulateState goes through dev_alloc, which notes the pointer in its owner's `owned`, and
+// free_device / free_denoise / free_accumulate release what that record holds - a buffer cannot be allocated without being freed.  The record is plain data walked by those functions
 // only, never by a destructor: exit(99) runs the destructors of the globals below with buffers live, and nothing of HIP may be called then; the states stay copyable.
 template <typename T>
 T* dev_alloc(std::vector<void*>& owned, size_t count) {
@@ -159,6 +160,7 @@ struct RenderContext {
     int prog_samples = 0;               // samples per pixel of the progressive frame so far (rtProgressiveSamples)
     double guides_ms = 0.0;             // rtLastGuidesMs
     double denoise_ms = 0.0;            // rtLastDenoiseMs
+    double accumulate_ms = 0.0;         // rtLastAccumulateMs
 };
 
 // The denoiser's own device state (denoiseFrame): whole-image buffers on ONE device, the first in-process device, whatever rows that device renders.  Allocated
@@ -175,8 +177,26 @@ struct DenoiseState {
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;               // events of its own: a frame's and the guides' timings stay what they were
 };
 
+// The temporal accumulation's own device state (accumulateFrame): whole-image buffers on the first in-process device, as the denoiser's, and shared with
+// nothing - neither denoiseFrame nor renderGuides can disturb the history.  Allocated by the first call, freed where the denoiser's buffers are freed.
+struct AccumulateState {
+    int device = -1;
+    size_t npix = 0;
+    std::vector<void*> owned;           // its device allocations (dev_alloc)
+    float* d_guide[4] = { nullptr, nullptr, nullptr, nullptr };     // albedo, normal, depth, prim of the whole image, this call's camera
+    rt_vec3* d_in = nullptr;
+    rt_vec3* d_out = nullptr;
+    float* d_history = nullptr;         // N(p) as a plane for the caller
+    float4* d_rec[2] = { nullptr, nullptr };                        // the two record sets (rt_accumulate.h), 3 * npix each
+    int newest = 0;                     // the set the last call wrote: the next call's history
+    int frames = 0;                     // calls since the last reset (rtHistoryFrames); 0 = the next call has no history
+    rt_camera prev_cam;                 // the camera of the last call
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+};
+
 RenderContext g_ctx;     // kernels.cu:145: one global context per process
 DenoiseState g_denoise;
+AccumulateState g_accumulate;
 
 // rtLastLaunches: the records of the last runRenderer (RT_LAUNCH_WORDS each) and the device / fp mode of the launcher being called
 std::vector<int32_t> g_launches;
@@ -226,6 +246,20 @@ void free_denoise() {
     n = DenoiseState();
 }
 
+void free_accumulate() {
+    AccumulateState& n = g_accumulate;
+    if (n.device < 0) { n = AccumulateState(); return; }
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(n.device));
+    HIP_CHECK(hipDeviceSynchronize());
+    dev_release_all(n.owned);
+    if (n.ev_start) HIP_CHECK(hipEventDestroy(n.ev_start));
+    if (n.ev_stop) HIP_CHECK(hipEventDestroy(n.ev_stop));
+    HIP_CHECK(hipSetDevice(current));
+    n = AccumulateState();
+}
+
 // Rows of the image owned by partition member `rank` of `world` with stripes of `sr` rows.
 int local_rows_of(int ny, int sr, int rank, int world) {
     int rows = 0;
@@ -238,6 +272,7 @@ int local_rows_of(int ny, int sr, int rank, int world) {
 void setup_devices() {
     RenderContext& c = g_ctx;
     free_denoise();                                         // (its buffers live on the first device of the list being replaced)
+    free_accumulate();                                      // (so do the history's)
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -606,6 +641,7 @@ void build_mesh_scene(const rt_kernel_scene& sc) {
 void cleanup_impl() {
     RenderContext& c = g_ctx;
     free_denoise();
+    free_accumulate();
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -705,6 +741,7 @@ void setRenderOptions(const rt_render_options* opt) {
     for (int k = 0; k < RT_MAX_DEVICES && !relayout; k++) relayout = old.devices[k] != opt->devices[k];
     if (relayout) setup_devices();
     c.prog_samples = 0;                                     // (any call: the options of the accumulated samples may differ)
+    g_accumulate.frames = 0;                                // (likewise the history of accumulateFrame)
 }
 
 }  // extern "C"
@@ -1173,6 +1210,77 @@ void denoiseFrame(const rt_vec3* in, rt_vec3* out, int iterations, int flags, in
 }
 
 double rtLastDenoiseMs(void) { return g_ctx.denoise_ms; }
+
+// Temporal accumulation (rt_api.h).  Like the denoiser: the whole image on the first in-process device, guide planes of its own for the
+// camera and options in force, buffers and events of its own.  The history - the last call's camera and the newest record set - stays on the device.
+void accumulateFrame(const rt_vec3* in, rt_vec3* out, float* history, int flags, int max_history, float sigma_z, float normal_min) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("accumulateFrame before init");
+    if (!out) rt_fail("accumulateFrame: out is null");
+    if ((flags & ~(RT_DENOISE_DEMODULATE | RT_DENOISE_SAME_PRIM)) != 0) rt_fail("accumulateFrame: unknown flag bits");
+    if (max_history < 1 || max_history > RT_ACCUM_MAX_HISTORY) rt_fail("accumulateFrame: max_history must be 1 .. RT_ACCUM_MAX_HISTORY");
+    if (!std::isfinite(sigma_z) || !(sigma_z > 0.0f)) rt_fail("accumulateFrame: sigma_z must be finite and positive");
+    if (!std::isfinite(normal_min) || normal_min < -1.0f || normal_min > 1.0f) rt_fail("accumulateFrame: normal_min must be finite and in [-1, 1]");
+    if (c.is_spheres && c.opt.floor) rt_fail("accumulateFrame: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
+    if (!in) in = c.h_ext ? c.h_ext : c.h_fb;
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    DeviceState& d = c.devs[0];
+    HIP_CHECK(hipSetDevice(d.device));
+    AccumulateState& n = g_accumulate;
+    const size_t npix = (size_t)c.nx * c.ny;
+    if (n.device != d.device || n.npix != npix) {
+        free_accumulate();
+        HIP_CHECK(hipSetDevice(d.device));
+        n.device = d.device; n.npix = npix;
+        for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
+        n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
+        n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
+        n.d_history = dev_alloc<float>(n.owned, npix);
+        n.d_rec[0] = dev_alloc<float4>(n.owned, 3 * npix);
+        n.d_rec[1] = dev_alloc<float4>(n.owned, 3 * npix);
+        HIP_CHECK(hipEventCreate(&n.ev_start));
+        HIP_CHECK(hipEventCreate(&n.ev_stop));
+    }
+    HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));   // before anything is written: out may be in
+    RtPartition part;                                           // the whole image as one member's rows
+    part.stripe_rows = c.opt.stripe_rows; part.rank = 0; part.world = 1; part.local_rows = c.ny;
+    const RtGuidePlanes g = { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr };
+    launch_guides(d, part, g);
+    RtAccumulateParams q;
+    memset(&q, 0, sizeof q);
+    q.cam = c.cam; q.nx = c.nx; q.ny = c.ny;
+    q.albedo = n.d_guide[0]; q.normal = n.d_guide[1]; q.depth = n.d_guide[2]; q.prim = reinterpret_cast<const int32_t*>(n.d_guide[3]);
+    q.in = n.d_in; q.out = n.d_out; q.history = history ? n.d_history : nullptr;
+    q.prev = n.d_rec[n.newest]; q.next = n.d_rec[n.newest ^ 1];
+    q.flags = flags; q.has_history = n.frames > 0 ? 1 : 0;
+    q.max_history = (float)max_history; q.sigma_z = sigma_z; q.normal_min = normal_min;
+    HIP_CHECK(hipEventRecord(n.ev_start, d.stream));
+    HIP_CHECK(rt_launch_accumulate(q, n.prev_cam, d.stream));
+    HIP_CHECK(hipEventRecord(n.ev_stop, d.stream));
+    HIP_CHECK(hipMemcpyAsync(out, n.d_out, npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
+    if (history) HIP_CHECK(hipMemcpyAsync(history, n.d_history, npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));                  // blocking: out and history are complete on return
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, n.ev_start, n.ev_stop));
+    c.accumulate_ms = (double)ms;
+    n.newest ^= 1;
+    n.prev_cam = c.cam;
+    if (n.frames < INT_MAX) n.frames++;
+    HIP_CHECK(hipSetDevice(current));
+}
+
+void rtResetHistory(void) {
+    if (!g_ctx.initialised) rt_fail("rtResetHistory before init");
+    g_accumulate.frames = 0;
+}
+
+int rtHistoryFrames(void) {
+    if (!g_ctx.initialised) rt_fail("rtHistoryFrames before init");
+    return g_accumulate.frames;
+}
+
+double rtLastAccumulateMs(void) { return g_ctx.accumulate_ms; }
 
 void setExternalFramebuffer(rt_vec3* fb) {
     RenderContext& c = g_ctx;

@@ -199,6 +199,60 @@ void denoiseFrame(const rt_vec3* in, rt_vec3* out, int iterations, int flags, in
  * 0 before the first call. */
 double rtLastDenoiseMs(void);
 
+/* --- temporal accumulation for a moving camera --------------------------------------------------------------------------------
+ * The temporal half of SVGF, of which denoiseFrame is the spatial half: while the camera moves, every valid pixel of the new 1 spp frame is reprojected into
+ * the previous call's frame through its world-space hit point, the four pixels around that position are checked against the previous frame's geometry, and
+ * what passes is blended into the new sample with a per-pixel history length N.  The loop of a camera move is setCamera, runRenderer(1), accumulateFrame,
+ * denoiseFrame.  All arithmetic is fp32 with + - * / abs floor min only, every operation rounded on its own (no FMA), operands in the order
+ * written, a comparison with a NaN false, dot(a,b) = a.x*b.x + a.y*b.y + a.z*b.z evaluated left to right; min(a,b) is a < b ? a : b.  So the result is
+ * defined bit for bit.  For the current call prim, n, a, t, valid(p), P(p), rz(p) = 1 / (sigma_z * t(p)), m(p) and c0(p) are exactly the denoiser's above.
+ * C' (o', llc', horizontal', vertical', u', v', w') is the camera of the previous call; P', n', prim', c' and N' are the planes the previous call stored.
+ *     L = llc' - o';  Lu = dot(L,u');  Lv = dot(L,v');  Lw = dot(L,w');  Hl = dot(horizontal',u');  Vl = dot(vertical',v')
+ * For every valid p = (i, j):
+ *     e = P(p) - o';  ea = dot(e,u');  eb = dot(e,v');  ec = dot(e,w')
+ *     r = Lw / ec;  s = (ea*r - Lu) / Hl;  tt = (eb*r - Lv) / Vl
+ *     x = s*(float)nx - 0.5f;  y = tt*(float)ny - 0.5f
+ *     candidate = r > 0 && x >= -1 && x < nx && y >= -1 && y < ny
+ *     x0 = floorf(x); fx = x - x0; i0 = (int)x0     (the same for y: y0, fy, j0)
+ *     sum = (0,0,0); nsum = 0; wsum = 0
+ *     for dy = 0,1 (outer), dx = 0,1 (inner):
+ *         q = (i0+dx, j0+dy);  bw = (dx ? fx : 1 - fx) * (dy ? fy : 1 - fy)
+ *         the tap adds nothing unless ALL of these hold:  q inside the image;  N'(q) > 0;  abs(dot(n(p), P'(q) - P(p))) * rz(p) < 1;
+ *             dot(n(p), n'(q)) >= normal_min;  with the SAME_PRIM flag: prim(p) == prim'(q)
+ *         sum[k] += bw * c'(q)[k];  nsum += bw * N'(q);  wsum += bw
+ *     if candidate && wsum > 0:
+ *         h[k] = sum[k]/wsum;  N = min(nsum/wsum + 1, (float)max_history);  al = 1/N;  c(p)[k] = h[k] + al * (c0(p)[k] - h[k])
+ *     else:
+ *         c(p) = c0(p);  N = 1
+ *     out(p)[k] = c(p)[k] * m(p)[k]                                          (no multiplication without the DEMODULATE flag)
+ * Pixels with !valid(p) copy in(p) to out(p) bit for bit and store N = 0, so they are never a tap of the next call.  The first call after a reset takes the
+ * else branch everywhere.  Every call stores P, n, prim, c and N of its frame as the next call's history and its camera as the next C'.  Non-finite input is
+ * not treated specially.  With max_history = M a pixel that keeps its history converges to the mean of its last M frames' worth of samples (al = 1/N).
+ *
+ * A still camera gains nothing: the seed of a pixel's sample stream depends on the pixel alone, so a camera that does not move renders the same noise in every
+ * frame and the blend returns it.  Accumulation pays off when the image moves by about a pixel or more per frame; a still camera is what
+ * runRendererProgressive is for.  Geometry that moves between calls is not followed (the scene is fixed after init).
+ *
+ * accumulateFrame: `in`, `out` as denoiseFrame's - `in` NULL = the framebuffer the renderer currently delivers into, `out` caller-owned and never NULL, `out`
+ * may be `in`; blocking.  `history` = NULL, or nx*ny floats that receive N(p).  flags = the denoiser's bits with the same meaning, default
+ * rtDefaultDenoiseFlags(); the other defaults are max_history 32, sigma_z 0.01f, normal_min 0.9f.  Like the denoiser it works on the WHOLE image on the first
+ * in-process device, whatever the partition is, and computes whole-image guide planes there itself for the camera and options in force.  It changes nothing
+ * an existing call observes: the framebuffer (unless passed as `out`), getRenderStats, rtLastLaunches, the progressive frame, rtProgressiveSamples,
+ * rtLastGuidesMs, rtLastDenoiseMs and the result of a later denoiseFrame stay as they were; and denoiseFrame and renderGuides do not disturb the history.
+ * The history lives on the device (156 bytes per pixel with the call's buffers: two sets of three 16-byte records, guide planes, input, output, N): allocated
+ * by the first call, freed where the denoiser's buffers are.  It is reset - the next call has no history - by every init*, cleanupRenderer, rtResetHistory
+ * and every setRenderOptions call; setCamera, setExternalFramebuffer, runRenderer*, renderGuides and denoiseFrame do not reset it.
+ * Misuse (rt error, exit 99): before init, out NULL, unknown flag bits, max_history outside 1 .. RT_ACCUM_MAX_HISTORY, sigma_z not finite or <= 0,
+ * normal_min not finite or outside [-1, 1], rt_render_options.floor = 1 on a sphere scene; rtResetHistory or rtHistoryFrames before init. */
+#define RT_ACCUM_MAX_HISTORY 1024
+void accumulateFrame(const rt_vec3* in, rt_vec3* out, float* history, int flags, int max_history, float sigma_z, float normal_min);
+/* The next accumulateFrame has no history. */
+void rtResetHistory(void);
+/* accumulateFrame calls since the last reset; 0 after init / reset. */
+int rtHistoryFrames(void);
+/* HIP-event time of the kernel of the last accumulateFrame (not its guide kernel, not the copies) in milliseconds; 0 before the first call. */
+double rtLastAccumulateMs(void);
+
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };
