@@ -506,23 +506,28 @@ def default_denoise_flags():
     return load_renderer().rtDefaultDenoiseFlags()
 
 
+def _frame_in_out(who, fb, out):
+    """The arrays of a whole-image pass, checked against (ny, nx, 3) float32 C-contiguous: (address of the input frame or None, the output array: `out`,
+    which must be writable, or a new one)."""
+    shape = (_state["ny"], _state["nx"], 3)
+    ok = lambda a: isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags["C_CONTIGUOUS"] and a.shape == shape
+    if fb is not None and not ok(fb):
+        raise ValueError(f"{who}: fb must be a C-contiguous float32 array of shape {shape}")
+    if out is None:
+        out = np.empty(shape, np.float32)
+    elif not (ok(out) and out.flags["WRITEABLE"]):
+        raise ValueError(f"{who}: out must be a writable C-contiguous float32 array of shape {shape}")
+    return None if fb is None else fb.ctypes.data, out
+
+
 def denoiseFrame(fb=None, iterations=5, flags=None, normal_squarings=5, sigma_z=0.01, sigma_c=1.0, out=None):
     """The guide-driven edge-avoiding a-trous filter on a whole frame (include/rt_api.h).  fb: a (ny, nx, 3) float32 array, row 0 = bottom; None = the
     framebuffer the renderer currently delivers into.  flags None = the scene kind's default.  Returns the denoised (ny, nx, 3) float32 array: a new one, or
     `out` (a writable C-contiguous float32 array of that shape; it may be `fb` itself: in place).  Blocking; always the whole image on the first device."""
-    nx, ny = _state["nx"], _state["ny"]
     r = load_renderer()
     if flags is None:
         flags = r.rtDefaultDenoiseFlags()
-    src = None
-    if fb is not None:
-        if not (isinstance(fb, np.ndarray) and fb.dtype == np.float32 and fb.flags["C_CONTIGUOUS"] and fb.shape == (ny, nx, 3)):
-            raise ValueError(f"denoiseFrame: fb must be a C-contiguous float32 array of shape {(ny, nx, 3)}")
-        src = fb.ctypes.data
-    if out is None:
-        out = np.empty((ny, nx, 3), np.float32)
-    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.shape == (ny, nx, 3)):
-        raise ValueError(f"denoiseFrame: out must be a writable C-contiguous float32 array of shape {(ny, nx, 3)}")
+    src, out = _frame_in_out("denoiseFrame", fb, out)
     r.denoiseFrame(src, out.ctypes.data, iterations, flags, normal_squarings, sigma_z, sigma_c)
     return out
 
@@ -547,15 +552,7 @@ def accumulateFrame(fb=None, out=None, history=False, flags=None, max_history=32
     r = load_renderer()
     if flags is None:
         flags = r.rtDefaultDenoiseFlags()
-    src = None
-    if fb is not None:
-        if not (isinstance(fb, np.ndarray) and fb.dtype == np.float32 and fb.flags["C_CONTIGUOUS"] and fb.shape == (ny, nx, 3)):
-            raise ValueError(f"accumulateFrame: fb must be a C-contiguous float32 array of shape {(ny, nx, 3)}")
-        src = fb.ctypes.data
-    if out is None:
-        out = np.empty((ny, nx, 3), np.float32)
-    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.shape == (ny, nx, 3)):
-        raise ValueError(f"accumulateFrame: out must be a writable C-contiguous float32 array of shape {(ny, nx, 3)}")
+    src, out = _frame_in_out("accumulateFrame", fb, out)
     hist = None
     if history is True:
         hist = np.empty((ny, nx), np.float32)

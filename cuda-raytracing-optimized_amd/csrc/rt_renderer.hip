@@ -41,13 +41,13 @@ void hip_check(hipError_t result, const char* func, const char* file, int line) 
     }
 }
 
-[[noreturn]] void rt_fail(const char* msg) {
-    fprintf(stderr, "rt error: %s\n", msg);
+[[noreturn]] void rt_fail(const char* msg, const char* who = "") {
+    fprintf(stderr, "rt error: %s%s\n", who, msg);
     exit(99);
 }
 
-// Device memory: every allocation of a DeviceState / DenoiseState / AccumulateState goes through dev_alloc, which notes the pointer in its owner's `owned`, and
-// free_device / free_denoise / free_accumulate release what that record holds - a buffer cannot be allocated without being freed.  The record is plain data walked by those functions
+// Device memory: every allocation of a DeviceState / PassState goes through dev_alloc, which notes the pointer in its owner's `owned`, and
+// free_device / free_pass release what that record holds - a buffer cannot be allocated without being freed.  The record is plain data walked by those functions
 // only, never by a destructor: exit(99) runs the destructors of the globals below with buffers live, and nothing of HIP may be called then; the states stay copyable.
 template <typename T>
 T* dev_alloc(std::vector<void*>& owned, size_t count) {
@@ -163,35 +163,31 @@ struct RenderContext {
     double accumulate_ms = 0.0;         // rtLastAccumulateMs
 };
 
-// The denoiser's own device state (denoiseFrame): whole-image buffers on ONE device, the first in-process device, whatever rows that device renders.  Allocated
-// by the first call, freed by free_denoise (cleanupRenderer, every init*, a setRenderOptions that changes the device layout).
-struct DenoiseState {
-    int device = -1;
-    size_t npix = 0;
-    std::vector<void*> owned;           // its device allocations (dev_alloc)
-    float* d_guide[4] = { nullptr, nullptr, nullptr, nullptr };     // albedo, normal, depth, prim of the whole image
-    rt_vec3* d_in = nullptr;
-    rt_vec3* d_out = nullptr;
-    float4* d_rec = nullptr;            // RtDenoiseParams::rec
-    float4* d_col[2] = { nullptr, nullptr };
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;               // events of its own: a frame's and the guides' timings stay what they were
-};
-
-// The temporal accumulation's own device state (accumulateFrame): whole-image buffers on the first in-process device, as the denoiser's, and shared with
-// nothing - neither denoiseFrame nor renderGuides can disturb the history.  Allocated by the first call, freed where the denoiser's buffers are freed.
-struct AccumulateState {
+// What the whole-image preview passes (denoiseFrame, accumulateFrame) each hold on the device: buffers for the whole image on ONE device, the first in-process
+// device, whatever rows that device renders, with guide planes and events of their own (a frame's and the guides' timings stay what they were).  A pass shares
+// nothing with the other pass or with renderGuides - neither can disturb the history.  Allocated by the pass's first call (begin_pass), freed by free_pass
+// (cleanupRenderer, every init*, a setRenderOptions that changes the device layout).
+struct PassState {
     int device = -1;
     size_t npix = 0;
     std::vector<void*> owned;           // its device allocations (dev_alloc)
     float* d_guide[4] = { nullptr, nullptr, nullptr, nullptr };     // albedo, normal, depth, prim of the whole image, this call's camera
     rt_vec3* d_in = nullptr;
     rt_vec3* d_out = nullptr;
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+};
+
+struct DenoiseState : PassState {
+    float4* d_rec = nullptr;            // RtDenoiseParams::rec
+    float4* d_col[2] = { nullptr, nullptr };
+};
+
+struct AccumulateState : PassState {
     float* d_history = nullptr;         // N(p) as a plane for the caller
     float4* d_rec[2] = { nullptr, nullptr };                        // the two record sets (rt_accumulate.h), 3 * npix each
     int newest = 0;                     // the set the last call wrote: the next call's history
     int frames = 0;                     // calls since the last reset (rtHistoryFrames); 0 = the next call has no history
     rt_camera prev_cam;                 // the camera of the last call
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
 
 RenderContext g_ctx;     // kernels.cu:145: one global context per process
@@ -232,32 +228,20 @@ void free_device(DeviceState& d) {
     d = DeviceState();
 }
 
-void free_denoise() {
-    DenoiseState& n = g_denoise;
-    if (n.device < 0) return;
-    int current = 0;
-    HIP_CHECK(hipGetDevice(&current));
-    HIP_CHECK(hipSetDevice(n.device));
-    HIP_CHECK(hipDeviceSynchronize());
-    dev_release_all(n.owned);
-    if (n.ev_start) HIP_CHECK(hipEventDestroy(n.ev_start));
-    if (n.ev_stop) HIP_CHECK(hipEventDestroy(n.ev_stop));
-    HIP_CHECK(hipSetDevice(current));
-    n = DenoiseState();
-}
-
-void free_accumulate() {
-    AccumulateState& n = g_accumulate;
-    if (n.device < 0) { n = AccumulateState(); return; }
-    int current = 0;
-    HIP_CHECK(hipGetDevice(&current));
-    HIP_CHECK(hipSetDevice(n.device));
-    HIP_CHECK(hipDeviceSynchronize());
-    dev_release_all(n.owned);
-    if (n.ev_start) HIP_CHECK(hipEventDestroy(n.ev_start));
-    if (n.ev_stop) HIP_CHECK(hipEventDestroy(n.ev_stop));
-    HIP_CHECK(hipSetDevice(current));
-    n = AccumulateState();
+// A pass's buffers and events, and the whole state back to its initial values: also without allocations, for the accumulator's frames / newest / prev_cam.
+template <typename State>
+void free_pass(State& n) {
+    if (n.device >= 0) {
+        int current = 0;
+        HIP_CHECK(hipGetDevice(&current));
+        HIP_CHECK(hipSetDevice(n.device));
+        HIP_CHECK(hipDeviceSynchronize());
+        dev_release_all(n.owned);
+        if (n.ev_start) HIP_CHECK(hipEventDestroy(n.ev_start));
+        if (n.ev_stop) HIP_CHECK(hipEventDestroy(n.ev_stop));
+        HIP_CHECK(hipSetDevice(current));
+    }
+    n = State();
 }
 
 // Rows of the image owned by partition member `rank` of `world` with stripes of `sr` rows.
@@ -271,8 +255,8 @@ int local_rows_of(int ny, int sr, int rank, int world) {
 // (Re)creates the per-device state for the device list in g_ctx.opt.
 void setup_devices() {
     RenderContext& c = g_ctx;
-    free_denoise();                                         // (its buffers live on the first device of the list being replaced)
-    free_accumulate();                                      // (so do the history's)
+    free_pass(g_denoise);                                   // (its buffers live on the first device of the list being replaced)
+    free_pass(g_accumulate);                                // (so do the history's)
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -640,8 +624,8 @@ void build_mesh_scene(const rt_kernel_scene& sc) {
 
 void cleanup_impl() {
     RenderContext& c = g_ctx;
-    free_denoise();
-    free_accumulate();
+    free_pass(g_denoise);
+    free_pass(g_accumulate);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -760,6 +744,16 @@ RtPartition partition_of(int k) {
     return part;
 }
 
+// The whole image as one member's rows (the preview passes).
+RtPartition whole_image_partition() {
+    RtPartition part;
+    part.stripe_rows = g_ctx.opt.stripe_rows;
+    part.rank = 0;
+    part.world = 1;
+    part.local_rows = g_ctx.ny;
+    return part;
+}
+
 // The parameter block of a kernel that works on rows `part` of the scene on device state `d`: the scene template, that device's scene arrays and what every
 // kernel is given alike (camera, image size, partition, sky, t_min; meshes: the floor switch).  The only place a parameter block gets its scene pointers:
 // a frame (render_frame) adds what belongs to a frame, the guide kernels (launch_guides) take it as it is.
@@ -785,7 +779,7 @@ RtMeshParams mesh_params(const DeviceState& d, const RtPartition& part) {
     return p;
 }
 
-// The first-hit guide kernel of the scene kind over rows `part`, into the compact planes `g` (renderGuides, denoiseFrame).
+// The first-hit guide kernel of the scene kind over rows `part`, into the compact planes `g` (renderGuides, begin_pass).
 void launch_guides(const DeviceState& d, const RtPartition& part, const RtGuidePlanes& g) {
     HIP_CHECK(g_ctx.is_spheres ? rt_launch_guides_spheres(sphere_params(d, part), g, d.stream) : rt_launch_guides_mesh(mesh_params(d, part), g, d.stream));
 }
@@ -814,6 +808,74 @@ void deliver_stripes(const DeviceState& d, const RtPartition& part, char* host, 
         HIP_CHECK(hipMemcpy2DAsync(dst0, (size_t)part.world * stripe_bytes, dev, stripe_bytes, stripe_bytes, full, hipMemcpyDeviceToHost, d.stream));
     if (rem > 0)
         HIP_CHECK(hipMemcpyAsync(dst0 + full * (size_t)part.world * stripe_bytes, dev + full * stripe_bytes, rem * row_bytes, hipMemcpyDeviceToHost, d.stream));
+}
+
+// The whole-image preview passes (denoiseFrame, accumulateFrame) differ in their own arguments, buffers, parameter block and kernels; the rest is here, once.
+
+// The argument checks both have, under the function's name `fn`.  A pass calls it with one group of `which` at a time, between its own checks: a call with
+// two bad arguments fails on the one that comes first in that function's list.
+enum { kCheckInit = 1, kCheckOut = 2, kCheckFlags = 4, kCheckSigmaZ = 8, kCheckFloor = 16 };
+void check_pass_args(const char* fn, int which, const rt_vec3* out, int flags, float sigma_z) {
+    const RenderContext& c = g_ctx;
+    if ((which & kCheckInit) && !c.initialised) rt_fail(" before init", fn);
+    if ((which & kCheckOut) && !out) rt_fail(": out is null", fn);
+    if ((which & kCheckFlags) && (flags & ~(RT_DENOISE_DEMODULATE | RT_DENOISE_SAME_PRIM)) != 0) rt_fail(": unknown flag bits", fn);
+    if ((which & kCheckSigmaZ) && (!std::isfinite(sigma_z) || !(sigma_z > 0.0f))) rt_fail(": sigma_z must be finite and positive", fn);
+    if ((which & kCheckFloor) && c.is_spheres && c.opt.floor) rt_fail(": the floor plane is only defined for mesh scenes (kernel_scene.floor)", fn);
+}
+
+// Up to a pass's own kernels, on the first in-process device (every device holds the whole scene, setup_devices): in NULL = the framebuffer being delivered
+// into; the buffers every pass has, `alloc_own()` for the pass's own and the events, when the device or the image size is not the state's; the upload of `in`
+// before anything is written (out may be in); the guide planes of the camera and options in force.  Returns the device to restore (end_pass).  The pass
+// records n.ev_start in front of its kernels.
+template <typename State, typename AllocOwn>
+int begin_pass(State& n, const rt_vec3* in, AllocOwn alloc_own) {
+    const RenderContext& c = g_ctx;
+    if (!in) in = c.h_ext ? c.h_ext : c.h_fb;
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    const DeviceState& d = c.devs[0];
+    HIP_CHECK(hipSetDevice(d.device));
+    const size_t npix = (size_t)c.nx * c.ny;
+    if (n.device != d.device || n.npix != npix) {
+        free_pass(n);
+        HIP_CHECK(hipSetDevice(d.device));
+        n.device = d.device; n.npix = npix;
+        for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
+        n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
+        n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
+        alloc_own();
+        HIP_CHECK(hipEventCreate(&n.ev_start));
+        HIP_CHECK(hipEventCreate(&n.ev_stop));
+    }
+    HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));
+    launch_guides(d, whole_image_partition(), { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr });
+    return current;
+}
+
+// The fields every pass's parameter block starts from, the rest zero.
+template <typename Params>
+Params pass_params(const PassState& n) {
+    Params q;
+    memset(&q, 0, sizeof q);
+    q.cam = g_ctx.cam; q.nx = g_ctx.nx; q.ny = g_ctx.ny;
+    q.albedo = n.d_guide[0]; q.normal = n.d_guide[1]; q.depth = n.d_guide[2]; q.prim = reinterpret_cast<const int32_t*>(n.d_guide[3]);
+    q.in = n.d_in; q.out = n.d_out;
+    return q;
+}
+
+// After a pass's kernels: the stop event, out (and accumulateFrame's history plane, `d_history` -> `history`) to the caller, complete on return: blocking.
+// Returns the HIP-event time of the kernels in milliseconds.
+double end_pass(const PassState& n, int current, rt_vec3* out, float* history = nullptr, const float* d_history = nullptr) {
+    const DeviceState& d = g_ctx.devs[0];
+    HIP_CHECK(hipEventRecord(n.ev_stop, d.stream));
+    HIP_CHECK(hipMemcpyAsync(out, n.d_out, n.npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
+    if (history) HIP_CHECK(hipMemcpyAsync(history, d_history, n.npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, n.ev_start, n.ev_stop));
+    HIP_CHECK(hipSetDevice(current));
+    return (double)ms;
 }
 
 // One frame of ns samples per pixel (runRenderer), or one pass of a progressive frame (progressive): samples [first, ns) of every pixel, continued from
@@ -1157,56 +1219,26 @@ int rtDefaultDenoiseFlags(void) {
 }
 
 void denoiseFrame(const rt_vec3* in, rt_vec3* out, int iterations, int flags, int normal_squarings, float sigma_z, float sigma_c) {
-    RenderContext& c = g_ctx;
-    if (!c.initialised) rt_fail("denoiseFrame before init");
-    if (!out) rt_fail("denoiseFrame: out is null");
+    check_pass_args("denoiseFrame", kCheckInit | kCheckOut, out, flags, sigma_z);
     if (iterations < 1 || iterations > RT_DENOISE_MAX_ITERATIONS) rt_fail("denoiseFrame: iterations must be 1 .. RT_DENOISE_MAX_ITERATIONS");
     if (normal_squarings < 0 || normal_squarings > RT_DENOISE_MAX_SQUARINGS) rt_fail("denoiseFrame: normal_squarings must be 0 .. RT_DENOISE_MAX_SQUARINGS");
-    if ((flags & ~(RT_DENOISE_DEMODULATE | RT_DENOISE_SAME_PRIM)) != 0) rt_fail("denoiseFrame: unknown flag bits");
-    if (!std::isfinite(sigma_z) || !(sigma_z > 0.0f)) rt_fail("denoiseFrame: sigma_z must be finite and positive");
+    check_pass_args("denoiseFrame", kCheckFlags | kCheckSigmaZ, out, flags, sigma_z);
     if (!std::isfinite(sigma_c)) rt_fail("denoiseFrame: sigma_c must be finite (<= 0 switches the colour weight off)");
-    if (c.is_spheres && c.opt.floor) rt_fail("denoiseFrame: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
-    if (!in) in = c.h_ext ? c.h_ext : c.h_fb;
-    int current = 0;
-    HIP_CHECK(hipGetDevice(&current));
-    DeviceState& d = c.devs[0];
-    HIP_CHECK(hipSetDevice(d.device));
+    check_pass_args("denoiseFrame", kCheckFloor, out, flags, sigma_z);
     DenoiseState& n = g_denoise;
-    const size_t npix = (size_t)c.nx * c.ny;
-    if (n.device != d.device || n.npix != npix) {
-        free_denoise();
-        HIP_CHECK(hipSetDevice(d.device));
-        n.device = d.device; n.npix = npix;
-        for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
-        n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
-        n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
-        n.d_rec = dev_alloc<float4>(n.owned, 2 * npix);
-        n.d_col[0] = dev_alloc<float4>(n.owned, npix);
-        n.d_col[1] = dev_alloc<float4>(n.owned, npix);
-        HIP_CHECK(hipEventCreate(&n.ev_start));
-        HIP_CHECK(hipEventCreate(&n.ev_stop));
-    }
-    HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));   // before anything is written: out may be in
-    RtPartition part;                                           // the whole image as one member's rows
-    part.stripe_rows = c.opt.stripe_rows; part.rank = 0; part.world = 1; part.local_rows = c.ny;
-    const RtGuidePlanes g = { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr };
-    launch_guides(d, part, g);
-    RtDenoiseParams q;
-    memset(&q, 0, sizeof q);
-    q.cam = c.cam; q.nx = c.nx; q.ny = c.ny;
-    q.albedo = n.d_guide[0]; q.normal = n.d_guide[1]; q.depth = n.d_guide[2]; q.prim = reinterpret_cast<const int32_t*>(n.d_guide[3]);
-    q.in = n.d_in; q.out = n.d_out; q.rec = n.d_rec; q.col[0] = n.d_col[0]; q.col[1] = n.d_col[1];
+    const int current = begin_pass(n, in, [&n] {
+        n.d_rec = dev_alloc<float4>(n.owned, 2 * n.npix);
+        n.d_col[0] = dev_alloc<float4>(n.owned, n.npix);
+        n.d_col[1] = dev_alloc<float4>(n.owned, n.npix);
+    });
+    RtDenoiseParams q = pass_params<RtDenoiseParams>(n);
+    q.rec = n.d_rec; q.col[0] = n.d_col[0]; q.col[1] = n.d_col[1];
     q.flags = flags; q.normal_squarings = normal_squarings; q.sigma_z = sigma_z; q.sigma_c = sigma_c;
-    HIP_CHECK(hipEventRecord(n.ev_start, d.stream));
-    HIP_CHECK(rt_launch_denoise_prologue(q, d.stream));
-    for (int it = 0; it < iterations; it++) HIP_CHECK(rt_launch_denoise_iteration(q, it, it == iterations - 1, d.stream));
-    HIP_CHECK(hipEventRecord(n.ev_stop, d.stream));
-    HIP_CHECK(hipMemcpyAsync(out, n.d_out, npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
-    HIP_CHECK(hipStreamSynchronize(d.stream));                  // blocking: out is complete on return
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, n.ev_start, n.ev_stop));
-    c.denoise_ms = (double)ms;
-    HIP_CHECK(hipSetDevice(current));
+    const hipStream_t stream = g_ctx.devs[0].stream;
+    HIP_CHECK(hipEventRecord(n.ev_start, stream));
+    HIP_CHECK(rt_launch_denoise_prologue(q, stream));
+    for (int it = 0; it < iterations; it++) HIP_CHECK(rt_launch_denoise_iteration(q, it, it == iterations - 1, stream));
+    g_ctx.denoise_ms = end_pass(n, current, out);
 }
 
 double rtLastDenoiseMs(void) { return g_ctx.denoise_ms; }
@@ -1214,60 +1246,29 @@ double rtLastDenoiseMs(void) { return g_ctx.denoise_ms; }
 // Temporal accumulation (rt_api.h).  Like the denoiser: the whole image on the first in-process device, guide planes of its own for the
 // camera and options in force, buffers and events of its own.  The history - the last call's camera and the newest record set - stays on the device.
 void accumulateFrame(const rt_vec3* in, rt_vec3* out, float* history, int flags, int max_history, float sigma_z, float normal_min) {
-    RenderContext& c = g_ctx;
-    if (!c.initialised) rt_fail("accumulateFrame before init");
-    if (!out) rt_fail("accumulateFrame: out is null");
-    if ((flags & ~(RT_DENOISE_DEMODULATE | RT_DENOISE_SAME_PRIM)) != 0) rt_fail("accumulateFrame: unknown flag bits");
+    check_pass_args("accumulateFrame", kCheckInit | kCheckOut | kCheckFlags, out, flags, sigma_z);
     if (max_history < 1 || max_history > RT_ACCUM_MAX_HISTORY) rt_fail("accumulateFrame: max_history must be 1 .. RT_ACCUM_MAX_HISTORY");
-    if (!std::isfinite(sigma_z) || !(sigma_z > 0.0f)) rt_fail("accumulateFrame: sigma_z must be finite and positive");
+    check_pass_args("accumulateFrame", kCheckSigmaZ, out, flags, sigma_z);
     if (!std::isfinite(normal_min) || normal_min < -1.0f || normal_min > 1.0f) rt_fail("accumulateFrame: normal_min must be finite and in [-1, 1]");
-    if (c.is_spheres && c.opt.floor) rt_fail("accumulateFrame: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
-    if (!in) in = c.h_ext ? c.h_ext : c.h_fb;
-    int current = 0;
-    HIP_CHECK(hipGetDevice(&current));
-    DeviceState& d = c.devs[0];
-    HIP_CHECK(hipSetDevice(d.device));
+    check_pass_args("accumulateFrame", kCheckFloor, out, flags, sigma_z);
     AccumulateState& n = g_accumulate;
-    const size_t npix = (size_t)c.nx * c.ny;
-    if (n.device != d.device || n.npix != npix) {
-        free_accumulate();
-        HIP_CHECK(hipSetDevice(d.device));
-        n.device = d.device; n.npix = npix;
-        for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
-        n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
-        n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
-        n.d_history = dev_alloc<float>(n.owned, npix);
-        n.d_rec[0] = dev_alloc<float4>(n.owned, 3 * npix);
-        n.d_rec[1] = dev_alloc<float4>(n.owned, 3 * npix);
-        HIP_CHECK(hipEventCreate(&n.ev_start));
-        HIP_CHECK(hipEventCreate(&n.ev_stop));
-    }
-    HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));   // before anything is written: out may be in
-    RtPartition part;                                           // the whole image as one member's rows
-    part.stripe_rows = c.opt.stripe_rows; part.rank = 0; part.world = 1; part.local_rows = c.ny;
-    const RtGuidePlanes g = { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr };
-    launch_guides(d, part, g);
-    RtAccumulateParams q;
-    memset(&q, 0, sizeof q);
-    q.cam = c.cam; q.nx = c.nx; q.ny = c.ny;
-    q.albedo = n.d_guide[0]; q.normal = n.d_guide[1]; q.depth = n.d_guide[2]; q.prim = reinterpret_cast<const int32_t*>(n.d_guide[3]);
-    q.in = n.d_in; q.out = n.d_out; q.history = history ? n.d_history : nullptr;
+    const int current = begin_pass(n, in, [&n] {
+        n.d_history = dev_alloc<float>(n.owned, n.npix);
+        n.d_rec[0] = dev_alloc<float4>(n.owned, 3 * n.npix);
+        n.d_rec[1] = dev_alloc<float4>(n.owned, 3 * n.npix);
+    });
+    RtAccumulateParams q = pass_params<RtAccumulateParams>(n);
+    q.history = history ? n.d_history : nullptr;
     q.prev = n.d_rec[n.newest]; q.next = n.d_rec[n.newest ^ 1];
     q.flags = flags; q.has_history = n.frames > 0 ? 1 : 0;
     q.max_history = (float)max_history; q.sigma_z = sigma_z; q.normal_min = normal_min;
-    HIP_CHECK(hipEventRecord(n.ev_start, d.stream));
-    HIP_CHECK(rt_launch_accumulate(q, n.prev_cam, d.stream));
-    HIP_CHECK(hipEventRecord(n.ev_stop, d.stream));
-    HIP_CHECK(hipMemcpyAsync(out, n.d_out, npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
-    if (history) HIP_CHECK(hipMemcpyAsync(history, n.d_history, npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
-    HIP_CHECK(hipStreamSynchronize(d.stream));                  // blocking: out and history are complete on return
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, n.ev_start, n.ev_stop));
-    c.accumulate_ms = (double)ms;
+    const hipStream_t stream = g_ctx.devs[0].stream;
+    HIP_CHECK(hipEventRecord(n.ev_start, stream));
+    HIP_CHECK(rt_launch_accumulate(q, n.prev_cam, stream));
+    g_ctx.accumulate_ms = end_pass(n, current, out, history, n.d_history);
     n.newest ^= 1;
-    n.prev_cam = c.cam;
+    n.prev_cam = g_ctx.cam;
     if (n.frames < INT_MAX) n.frames++;
-    HIP_CHECK(hipSetDevice(current));
 }
 
 void rtResetHistory(void) {

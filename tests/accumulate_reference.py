@@ -269,22 +269,3 @@ def sequence_inputs(rt, O, name, k, still=False):
         g = G.sphere_guides(rt, O, sp, mt, cam, nx, ny)
     origin, dn = D.centre_dirs(rt, O, cam, nx, ny)
     return cam, g, origin, dn
-
-
-def oracle_frame(rt, O, name, cam, spp):
-    """The CPU oracle's render of a sequence's scene from `cam` with the default options (and the floor of the *_floor frame)."""
-    nx, ny = _size(rt, O, name)
-    if name in G.MESH_FRAMES:
-        f = G.mesh_frame(rt, O, name)
-        opt = O.default_options(False)
-        if f["floor"] is not None:
-            opt.floor = 1
-        fb, _ = O.render(O.mesh_scene(f["hm"], f["mats"], f["tex"], f["floor"]), cam, opt, nx, ny, spp, 16)
-        return fb
-    sp, mt = G.sphere_frame(rt, name)[:2]
-    fb, _ = O.render(O.sphere_scene(sp, mt), cam, O.default_options(True), nx, ny, spp, 20)
-    return fb
-
-
-def default_flags(name):
-    return D.default_flags(name in G.MESH_FRAMES)

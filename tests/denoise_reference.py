@@ -10,17 +10,13 @@ import functools
 import numpy as np
 
 import guides_reference as G
+from preview_support import DEMODULATE, SAME_PRIM, default_flags, oracle_frame  # noqa: F401  (read as D.default_flags, D.oracle_frame by the tests)
 
 F = np.float32
-DEMODULATE, SAME_PRIM = 1, 2
 ALBEDO_FLOOR = F(0.01)
 K = (F(0.375), F(0.25), F(0.0625))
 DEFAULTS = dict(iterations=5, normal_squarings=5, sigma_z=0.01, sigma_c=1.0)
 COUNTS = ("outside", "invalid", "accepted", "wn_lt1", "wz_lt1", "wc_lt1", "prim_mismatch")
-
-
-def default_flags(mesh):
-    return DEMODULATE if mesh else DEMODULATE | SAME_PRIM
 
 
 def centre_dirs(rt, O, cam, nx, ny):
@@ -225,20 +221,6 @@ def frame_inputs(rt, O, name):
         _, _, cam, nx, ny = G.sphere_frame(rt, name)
     origin, dn = centre_dirs(rt, O, cam, nx, ny)
     return G.reference(rt, O, name), origin, dn, mesh
-
-
-def oracle_frame(rt, O, name, spp):
-    """The CPU oracle's render of a named frame with the default options (and the floor of the *_floor frame)."""
-    if name in G.MESH_FRAMES:
-        f = G.mesh_frame(rt, O, name)
-        opt = O.default_options(False)
-        if f["floor"] is not None:
-            opt.floor = 1
-        fb, _ = O.render(O.mesh_scene(f["hm"], f["mats"], f["tex"], f["floor"]), f["cam"], opt, f["nx"], f["ny"], spp, 16)
-        return fb
-    sp, mt, cam, nx, ny = G.sphere_frame(rt, name)
-    fb, _ = O.render(O.sphere_scene(sp, mt), cam, O.default_options(True), nx, ny, spp, 20)
-    return fb
 
 
 def rmse(a, b):

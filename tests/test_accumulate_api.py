@@ -7,8 +7,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,14 +14,11 @@ import pytest
 import accumulate_reference as A
 import denoise_reference as D
 import guides_reference as R
+from preview_support import bits as _bits, exits_99, oracle_frame
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 API = open(os.path.join(ROOT, "include", "rt_api.h")).read()
 NEW = ("accumulateFrame", "rtResetHistory", "rtHistoryFrames", "rtLastAccumulateMs")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_declared_exported_and_bound(rt):
@@ -69,11 +64,7 @@ def test_abi_unchanged(rt):
                                   "rt.reset_history()", "rt.history_frames()"])
 def test_before_init_exits_99(call):
     """The library's misuse convention in a child process: 'rt error' on stderr and exit status 99.  No GPU: the check precedes any HIP call."""
-    code = ("import sys; sys.path.insert(0, %r); import numpy as np; import cuda_raytracing_optimized_amd as rt\n"
-            "rt._state.update(nx=4, ny=4)\n%s\n") % (ROOT, call)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 99, (r.returncode, r.stderr[-1000:])
-    assert "rt error" in r.stderr
+    exits_99("rt._state.update(nx=4, ny=4)\n%s\n" % call)
 
 
 def test_translation_unit_is_built_once_with_the_denoiser_s_flags():
@@ -107,12 +98,12 @@ def test_translation_unit_is_built_once_with_the_denoiser_s_flags():
 
 def _run_sequence(rt, O, name, calls, spp=1, scalar=False, counts=None, still=False, **kw):
     """`calls` accumulateFrame calls of the reference along a sequence on the oracle's frames; returns the list of (noisy, out, N) and the last camera."""
-    kw = dict(dict(A.DEFAULTS, flags=A.default_flags(name)), **kw)
+    kw = dict(dict(A.DEFAULTS, flags=D.default_flags(name in R.MESH_FRAMES)), **kw)
     acc = A.Accumulator(scalar=scalar)
     res = []
     for k in range(calls):
         cam, g, origin, dn = A.sequence_inputs(rt, O, name, k, still)
-        noisy = A.oracle_frame(rt, O, name, cam, spp)
+        noisy = oracle_frame(rt, O, name, spp, cam)
         out, N = acc.step(noisy, g, cam, origin, dn, counts=counts, **kw)
         res.append((noisy, out, N))
     return res, cam
@@ -167,12 +158,12 @@ def test_accumulation_reduces_the_error_of_a_camera_move(rt, O, name):
     at 256 spp (DESIGN.md 3.12 records the ratios this prints).  The still camera is printed, not asserted: the noise of a pixel depends on the pixel alone, so
     every frame of a camera that does not move is the same and the ratio is 1."""
     res, cam = _run_sequence(rt, O, name, 4)
-    target = A.oracle_frame(rt, O, name, cam, 256)
+    target = oracle_frame(rt, O, name, 256, cam)
     noisy, out, N = res[-1]
     assert np.isfinite(noisy).all() and np.isfinite(target).all() and np.isfinite(out).all()
     ratio = D.rmse(out, target) / D.rmse(noisy, target)
     print(f"{name}: 4 frames at 1 spp, RMSE noisy {D.rmse(noisy, target):.5f}, accumulated {D.rmse(out, target):.5f}, ratio {ratio:.3f}, mean N {float(N[N > 0].mean()):.2f}")
     still, cam0 = _run_sequence(rt, O, name, 4, still=True)
-    target0 = A.oracle_frame(rt, O, name, cam0, 256)
+    target0 = oracle_frame(rt, O, name, 256, cam0)
     print(f"{name}: camera still, ratio {D.rmse(still[-1][1], target0) / D.rmse(still[-1][0], target0):.4f}")
     assert ratio < 1.0

@@ -6,22 +6,17 @@ reduces the error of 4 spp frames."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import denoise_reference as D
 import guides_reference as R
+from preview_support import bits as _bits, exits_99
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 API = open(os.path.join(ROOT, "include", "rt_api.h")).read()
 NEW = ("rtDefaultDenoiseFlags", "denoiseFrame", "rtLastDenoiseMs")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_declared_exported_and_bound(rt):
@@ -69,11 +64,7 @@ def test_abi_unchanged(rt):
                                   "rt.default_denoise_flags()"])
 def test_before_init_exits_99(call):
     """The library's misuse convention in a child process: 'rt error' on stderr and exit status 99.  No GPU: the check precedes any HIP call."""
-    code = ("import sys; sys.path.insert(0, %r); import numpy as np; import cuda_raytracing_optimized_amd as rt\n"
-            "rt._state.update(nx=4, ny=4)\n%s\n") % (ROOT, call)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 99, (r.returncode, r.stderr[-1000:])
-    assert "rt error" in r.stderr
+    exits_99("rt._state.update(nx=4, ny=4)\n%s\n" % call)
 
 
 def test_translation_unit_is_built_once_with_contraction_off():

@@ -2,47 +2,15 @@
 bit for bit (np.array_equal on the raw 32-bit words: no tolerance, nothing left out).  The reference is fed the very framebuffers the GPU rendered (copied
 before the call) and the guide reference's planes, and keeps its own history, so nothing here leans on render parity.  Then synthetic input in place over the
 parameter space, one large frame, the reset rules, the interplay with denoiseFrame and renderGuides, no side effects, partitions and the misuse exits."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import accumulate_reference as A
 import denoise_reference as D
 import guides_reference as R
+from preview_support import bits as _bits, exits_99, init_frame as _init, same as _same, stats_tuple as _stats_tuple
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(got, ref, what):
-    diff = _bits(got) != _bits(ref)
-    print(f"{what}: {int(diff.sum())} of {diff.size} words differ")
-    assert np.array_equal(_bits(got), _bits(ref)), (what, int(diff.sum()), np.argwhere(diff)[:5].tolist())
-
-
-def _init(rt, O, name, **opts):
-    """Initialises the scene of a sequence with its frame-0 camera; returns (framebuffer view, options)."""
-    if name in R.MESH_FRAMES:
-        f = R.mesh_frame(rt, O, name)
-        ks, keep = rt.make_kernel_scene(f["hm"], f["mats"], f["tex"], floor=f["floor"])
-        fb = rt.initRenderer(ks, f["cam"], f["nx"], f["ny"], 16, keepalive=keep)
-        o = rt.getDefaultRenderOptions(False)
-        if f["floor"] is not None:
-            opts = dict(opts, floor=1)
-    else:
-        sp, mt, cam, nx, ny = R.sphere_frame(rt, name)
-        fb = rt.initRendererSpheres(sp, mt, cam, nx, ny, 20)
-        o = rt.getDefaultRenderOptions(True)
-    if opts:
-        rt.setRenderOptions(o, **opts)
-    return fb, o
 
 
 def _synthetic(seed, shape):
@@ -64,7 +32,7 @@ def _call(rt, O, acc, name, k, src=None, fb=None, still=False, counts=None, **kw
         buf = src.copy()
         got, hist = rt.accumulateFrame(buf, out=buf, history=True, **kw)
         assert got is buf
-    ref, N = acc.step(frame, g, cam, origin, dn, counts=counts, **dict(dict(flags=A.default_flags(name)), **kw))
+    ref, N = acc.step(frame, g, cam, origin, dn, counts=counts, **dict(dict(flags=D.default_flags(name in R.MESH_FRAMES)), **kw))
     return frame, got, hist, ref, N
 
 
@@ -74,7 +42,7 @@ def _call(rt, O, acc, name, k, src=None, fb=None, still=False, counts=None, **kw
 def test_rendered_sequences_match_the_reference(rt, O, name, calls):
     """Per step setCamera, runRenderer(1), a copy of the framebuffer, accumulateFrame(NULL, out, history): out and history of every call equal the reference
     fed the same copies."""
-    fb, o = _init(rt, O, name)
+    fb, o, mesh = _init(rt, O, name)
     assert rt.history_frames() == 0
     acc, res = A.Accumulator(), []
     try:
@@ -101,7 +69,7 @@ def test_synthetic_input_in_place(rt, O):
     """random_50x37, seeded random images, uniform in [0, 4), passed explicitly with out == in, three calls along the sequence per parameter set (the third
     shows max_history = 2).  sigma_z = 100 accepts nearly every tap that passes the other tests, 1e-5 nearly none; normal_min = 1 leaves equal normals only."""
     name = "random_50x37"
-    fb, o = _init(rt, O, name)
+    fb, o, mesh = _init(rt, O, name)
     ny, nx = fb.shape[:2]
     try:
         for n, case in enumerate(_CASES):
@@ -125,7 +93,7 @@ def test_camera_turned_away_and_camera_unchanged(rt, O):
     away = rt.make_camera((13, 2, 3), (26, 0, 6), (0, 1, 0), 30.0, nx / ny, 0.1, 10.0)
     g_away = R.sphere_guides(rt, O, sp, mt, away, nx, ny)
     o_away, dn_away = D.centre_dirs(rt, O, away, nx, ny)
-    fb, o = _init(rt, O, name)
+    fb, o, mesh = _init(rt, O, name)
     try:
         acc, cnt = A.Accumulator(), {}
         first = _call(rt, O, acc, name, 0, src=_synthetic(7, (ny, nx)))
@@ -186,7 +154,7 @@ def test_reset_rules(rt, O):
     """rtResetHistory, setRenderOptions and a second init with another size make the next call a first call; setCamera and setExternalFramebuffer do not;
     rtHistoryFrames follows."""
     name = "random_50x37"
-    fb, o = _init(rt, O, name)
+    fb, o, mesh = _init(rt, O, name)
     ny, nx = fb.shape[:2]
     src = [_synthetic(40 + k, (ny, nx)) for k in range(8)]
     try:
@@ -212,7 +180,7 @@ def test_reset_rules(rt, O):
         acc_f = A.Accumulator()
         f = _call(rt, O, acc_f, name, 0, src=src[5])
         assert rt.history_frames() == 1
-        fb2, o2 = _init(rt, O, "three_spheres")                 # 64 x 40 after 50 x 37
+        fb2, o2, mesh2 = _init(rt, O, "three_spheres")                 # 64 x 40 after 50 x 37
         assert rt.history_frames() == 0
         acc_g = A.Accumulator()
         g = _call(rt, O, acc_g, "three_spheres", 1, fb=fb2)
@@ -235,7 +203,7 @@ def test_interplay_with_denoise_and_guides(rt, O):
     """accumulate, denoiseFrame, renderGuides, setCamera, accumulate: the second result is the reference's (neither call disturbed the history), and the denoised
     frame is denoise_reference of its input."""
     name = "random_50x37"
-    fb, o = _init(rt, O, name)
+    fb, o, mesh = _init(rt, O, name)
     try:
         acc = A.Accumulator()
         a = _call(rt, O, acc, name, 0, fb=fb)
@@ -255,18 +223,58 @@ def test_interplay_with_denoise_and_guides(rt, O):
         _same(planes[plane], g0[plane], "renderGuides " + plane)
 
 
+def test_both_passes_live_through_reinit_relayout_and_cleanup(rt, O):
+    """Both passes allocated, then: a second init with another size without cleanupRenderer, a setRenderOptions that replaces the device layout, cleanupRenderer
+    and a third init.  The history is empty after each; every out, history plane and denoised frame equals the references, which start afresh there."""
+    small, large = "random_50x37", "random_96x64"
+    res, den = {}, {}
+    try:
+        fb, o, mesh = _init(rt, O, small)
+        acc = A.Accumulator()
+        res["first 0"] = _call(rt, O, acc, small, 0, fb=fb)
+        res["first 1"] = _call(rt, O, acc, small, 1, fb=fb)
+        den["first"] = (rt.denoiseFrame(res["first 1"][1]), res["first 1"][1], A.sequence_inputs(rt, O, small, 1)[1:])
+        fb, o, mesh = _init(rt, O, large)                       # 96 x 64 after 50 x 37, both passes' buffers live
+        assert rt.history_frames() == 0
+        cam = R.sphere_frame(rt, large)[2]
+        g, origin, dn, _ = D.frame_inputs(rt, O, large)
+        acc = A.Accumulator()
+        rt.runRenderer(1)
+        frame = np.array(fb, copy=True)
+        got, hist = rt.accumulateFrame(history=True)
+        res["second init"] = (frame, got, hist) + acc.step(frame, g, cam, origin, dn, flags=D.default_flags(False))
+        den["second init"] = (rt.denoiseFrame(got), got, (g, origin, dn))
+        rt.setRenderOptions(o, stripe_rows=8, part_rank=1, part_world=2)
+        assert rt.history_frames() == 0
+        acc = A.Accumulator()
+        src = _synthetic(80, fb.shape[:2])
+        got, hist = rt.accumulateFrame(src, history=True)
+        res["new layout"] = (src, got, hist) + acc.step(src, g, cam, origin, dn, flags=D.default_flags(False))
+        src = _synthetic(81, fb.shape[:2])
+        den["new layout"] = (rt.denoiseFrame(src), src, (g, origin, dn))
+        rt.cleanupRenderer()
+        fb, o, mesh = _init(rt, O, small)
+        assert rt.history_frames() == 0
+        res["third init"] = _call(rt, O, A.Accumulator(), small, 0, fb=fb)
+        den["third init"] = (rt.denoiseFrame(res["third init"][1]), res["third init"][1], A.sequence_inputs(rt, O, small, 0)[1:])
+    finally:
+        rt.cleanupRenderer()
+    for what, (frame, got, hist, ref, N) in res.items():
+        _same(got, ref, what + " out"); _same(hist, N, what + " history")
+    for what in ("second init", "new layout", "third init"):
+        assert float(res[what][4].max()) == 1.0                 # a first call
+    assert float(res["first 1"][4].max()) > 1.0
+    for what, (got, src, (g, origin, dn)) in den.items():
+        _same(got, D.denoise(src, g, origin, dn, flags=D.default_flags(False), **D.DEFAULTS), what + " denoised")
+
+
 # ---- 6. no side effects ----------------------------------------------------------------------------------------------
-
-def _stats_tuple(st):
-    return (st.kernel_ms, st.total_ms, st.samples, st.num_launches, st.rays, st.prim_tests, st.node_visits, st.exec_tests, st.shadow_rays, st.box_tests,
-            tuple(st.ref_stats))
-
 
 @pytest.mark.parametrize("name", ["random_50x37", "staircase_a"])
 def test_no_side_effects(rt, O, name):
     """Framebuffer, stats, launch report, guide and denoise timing, a later denoiseFrame and the progressive frame are the same with and without accumulateFrame
     calls in between."""
-    fb, o = _init(rt, O, name)
+    fb, o, mesh = _init(rt, O, name)
     try:
         rt.runRenderer(4)
         four = np.array(fb, copy=True)
@@ -302,7 +310,7 @@ def test_partitioned_renderer_still_accumulates_the_whole_image(rt, O):
     """part_world = 2, part_rank = 1 with stripes of 8 rows, then a partition in which this process owns no row at all: two calls with explicit full inputs
     return the whole-image results of the reference."""
     name = "random_50x37"
-    fb, o = _init(rt, O, name)
+    fb, o, mesh = _init(rt, O, name)
     ny, nx = fb.shape[:2]
     res = {}
     try:
@@ -322,7 +330,7 @@ def test_two_in_process_devices(rt, O):
     if rt.device_count() < 2:
         pytest.skip("needs two HIP devices")
     name = "random_50x37"
-    fb, o = _init(rt, O, name, devices=[0, 1])
+    fb, o, mesh = _init(rt, O, name, devices=[0, 1])
     try:
         acc = A.Accumulator()
         steps = [_call(rt, O, acc, name, k, fb=fb) for k in range(2)]
@@ -361,15 +369,12 @@ _MISUSE = {
 @pytest.mark.parametrize("case", sorted(_MISUSE))
 def test_misuse_exits_99(case):
     """The library's misuse convention, each case in a child process of its own: 'rt error' on stderr and exit status 99 (a clean exit of a host-side check)."""
-    code = ("import sys; sys.path.insert(0, %r); import ctypes as C; import numpy as np; import cuda_raytracing_optimized_amd as rt\n" % ROOT) + _MISUSE[case]
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 99, (r.returncode, r.stderr[-1000:])
-    assert "rt error" in r.stderr
+    exits_99(_MISUSE[case])
 
 
 def test_valid_edge_parameters_are_accepted(rt, O):
     """The other side of the misuse list: max_history 1 and RT_ACCUM_MAX_HISTORY, normal_min -1 and 1, no history plane, every flag combination."""
-    fb, o = _init(rt, O, "tie")
+    fb, o, mesh = _init(rt, O, "tie")
     try:
         rt.runRenderer(1)
         for kw in (dict(max_history=1, normal_min=-1.0, flags=0), dict(max_history=rt.RT_ACCUM_MAX_HISTORY, normal_min=1.0, flags=3), dict(flags=1), dict(flags=2)):

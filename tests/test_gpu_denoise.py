@@ -2,49 +2,15 @@
 the raw 32-bit words: no tolerance, nothing left out).  The reference filters the very framebuffer the GPU rendered (copied before the call) with the guide
 reference's planes, so nothing here leans on render parity.  Then synthetic input in place over the parameter space, one large frame, partitions, setCamera,
 no side effects, progressive use and the misuse exits."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import denoise_reference as D
 import guides_reference as R
+from preview_support import bits as _bits, exits_99, init_frame as _init, same as _same, stats_tuple as _stats_tuple
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FRAMES = ("random_96x64", "random_50x37", "three_spheres", "cloud_hybrid", "tie", "staircase_a", "staircase_b", "tris300", "tris300_floor")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(got, ref, what):
-    diff = _bits(got) != _bits(ref)
-    print(f"{what}: {int(diff.sum())} of {diff.size} words differ")
-    assert np.array_equal(_bits(got), _bits(ref)), (what, int(diff.sum()), np.argwhere(diff)[:5].tolist())
-
-
-def _init(rt, O, name, **opts):
-    """Initialises the named frame; returns (framebuffer view, options, is-mesh)."""
-    if name in R.MESH_FRAMES:
-        f = R.mesh_frame(rt, O, name)
-        ks, keep = rt.make_kernel_scene(f["hm"], f["mats"], f["tex"], floor=f["floor"])
-        fb = rt.initRenderer(ks, f["cam"], f["nx"], f["ny"], 16, keepalive=keep)
-        o = rt.getDefaultRenderOptions(False)
-        if f["floor"] is not None:
-            opts = dict(opts, floor=1)
-        if opts:
-            rt.setRenderOptions(o, **opts)
-        return fb, o, True
-    sp, mt, cam, nx, ny = R.sphere_frame(rt, name)
-    fb = rt.initRendererSpheres(sp, mt, cam, nx, ny, 20)
-    o = rt.getDefaultRenderOptions(True)
-    if opts:
-        rt.setRenderOptions(o, **opts)
-    return fb, o, False
 
 
 def _reference(rt, O, name, frame, **kw):
@@ -206,11 +172,6 @@ def test_follows_t_min_and_reinit_with_another_size(rt, O):
 
 # ---- 6. no side effects, progressive use -----------------------------------------------------------------------------
 
-def _stats_tuple(st):
-    return (st.kernel_ms, st.total_ms, st.samples, st.num_launches, st.rays, st.prim_tests, st.node_visits, st.exec_tests, st.shadow_rays, st.box_tests,
-            tuple(st.ref_stats))
-
-
 @pytest.mark.parametrize("name", ["random_96x64", "staircase_a"])
 def test_no_side_effects(rt, O, name):
     """Framebuffer, stats, launch report, guide timing and the progressive frame are the same with and without a denoiseFrame in between."""
@@ -282,10 +243,7 @@ _MISUSE = {
 @pytest.mark.parametrize("case", sorted(_MISUSE))
 def test_misuse_exits_99(case):
     """The library's misuse convention, each case in a child process of its own: 'rt error' on stderr and exit status 99 (a clean exit of a host-side check)."""
-    code = ("import sys; sys.path.insert(0, %r); import ctypes as C; import numpy as np; import cuda_raytracing_optimized_amd as rt\n" % ROOT) + _MISUSE[case]
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 99, (r.returncode, r.stderr[-1000:])
-    assert "rt error" in r.stderr
+    exits_99(_MISUSE[case])
 
 
 def test_valid_edge_parameters_are_accepted(rt, O):

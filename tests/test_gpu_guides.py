@@ -1,30 +1,20 @@
 """renderGuides (include/rt_api.h) on the GPU against the test reference (tests/guides_reference.py): every plane of every frame, all pixels, bit for bit
 (np.array_equal on the raw 32-bit words: no tolerance, nothing left out); option independence, partitions, subset masks, setCamera, no side effects on
 frames / stats / launch report / progressive accumulation, and the misuse exits."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import guides_reference as R
+from preview_support import bits as _bits, exits_99, init_frame, same, stats_tuple as _stats_tuple
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0x7FC0FFEE                                           # a word no plane produces: a NaN payload as float, a huge id as int
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _same(got, ref, what):
     assert sorted(got) == sorted(ref), (what, sorted(got), sorted(ref))
     for k in ref:
-        diff = _bits(got[k]) != _bits(ref[k])
-        print(f"{what}: plane {k}: {int(diff.sum())} of {diff.size} words differ")
-        assert np.array_equal(_bits(got[k]), _bits(ref[k])), (what, k, int(diff.sum()), np.argwhere(diff)[:5].tolist())
+        same(got[k], ref[k], f"{what}: plane {k}")
 
 
 def _all_mask(rt, mesh):
@@ -33,24 +23,11 @@ def _all_mask(rt, mesh):
 
 
 def _init_spheres(rt, name, **opts):
-    sp, mt, cam, nx, ny = R.sphere_frame(rt, name)
-    fb = rt.initRendererSpheres(sp, mt, cam, nx, ny, 20)
-    o = rt.getDefaultRenderOptions(True)
-    if opts:
-        rt.setRenderOptions(o, **opts)
-    return fb, o, (sp, mt, cam, nx, ny)
+    return init_frame(rt, None, name, **opts)[:2] + (R.sphere_frame(rt, name),)
 
 
 def _init_mesh(rt, O, name, **opts):
-    f = R.mesh_frame(rt, O, name)
-    ks, keep = rt.make_kernel_scene(f["hm"], f["mats"], f["tex"], floor=f["floor"])
-    fb = rt.initRenderer(ks, f["cam"], f["nx"], f["ny"], 16, keepalive=keep)
-    o = rt.getDefaultRenderOptions(False)
-    if f["floor"] is not None:
-        opts = dict(opts, floor=1)
-    if opts:
-        rt.setRenderOptions(o, **opts)
-    return fb, o, f
+    return init_frame(rt, O, name, **opts)[:2] + (R.mesh_frame(rt, O, name),)
 
 
 # ---- 1. sphere scenes ------------------------------------------------------------------------------------------------
@@ -223,11 +200,6 @@ def test_set_camera_spheres(rt, O):
 
 # ---- 7. no side effects ----------------------------------------------------------------------------------------------
 
-def _stats_tuple(st):
-    return (st.kernel_ms, st.total_ms, st.samples, st.num_launches, st.rays, st.prim_tests, st.node_visits, st.exec_tests, st.shadow_rays, st.box_tests,
-            tuple(st.ref_stats))
-
-
 @pytest.mark.parametrize("kind", ["spheres", "mesh"])
 def test_no_side_effects(rt, O, kind):
     """runRenderer(16); framebuffer, stats and launch report are the same after renderGuides.  Progressive 8 + renderGuides + 8 equals runRenderer(16)."""
@@ -270,7 +242,4 @@ _MISUSE = {
 @pytest.mark.parametrize("case", sorted(_MISUSE))
 def test_misuse_exits_99(case):
     """The library's misuse convention, each case in a child process of its own: 'rt error' on stderr and exit status 99 (a clean exit of a host-side check)."""
-    code = ("import sys; sys.path.insert(0, %r); import ctypes as C; import numpy as np; import cuda_raytracing_optimized_amd as rt\n" % ROOT) + _MISUSE[case]
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 99, (r.returncode, r.stderr[-1000:])
-    assert "rt error" in r.stderr
+    exits_99(_MISUSE[case])

@@ -5,13 +5,12 @@ cover - a frame that exercises nothing fails here, without a GPU."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import guides_reference as R
+from preview_support import exits_99
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 API = open(os.path.join(ROOT, "include", "rt_api.h")).read()
@@ -54,11 +53,7 @@ def test_abi_unchanged(rt):
 
 def test_before_init_exits_99():
     """The library's misuse convention in a child process: 'rt error' on stderr and exit status 99.  No GPU: the check precedes any HIP call."""
-    code = ("import sys; sys.path.insert(0, %r); import cuda_raytracing_optimized_amd as rt\n"
-            "rt.renderGuides(rt.RT_GUIDE_DEPTH)\n") % ROOT
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 99, (r.returncode, r.stderr[-1000:])
-    assert "rt error" in r.stderr
+    exits_99("rt.renderGuides(rt.RT_GUIDE_DEPTH)\n")
 
 
 def test_guide_kernels_are_built_once_and_keep_away_from_the_form_tables():

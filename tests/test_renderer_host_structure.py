@@ -1,8 +1,9 @@
 """CPU tripwire: the host runtime (rt_renderer.hip) says each thing once.  Device memory is allocated by one function that records the pointer with its
 owner and freed only by the functions that walk that record, so a new buffer cannot be forgotten in a hand-kept list of frees; every scene pointer of a
 kernel parameter block is assigned in exactly one place (sphere_params / mesh_params), so a frame, the guide planes and the denoiser cannot disagree about
-the scene; and RenderContext holds the scene's constants in parameter-block form (sphere_scene / mesh_scene), not as a second set of members that is
-copied across field by field."""
+the scene; RenderContext holds the scene's constants in parameter-block form (sphere_scene / mesh_scene), not as a second set of members that is
+copied across field by field; and the whole-image preview passes (denoiseFrame, accumulateFrame) share one state struct (PassState), one release (free_pass)
+and one path around their kernels (begin_pass / end_pass), so a third pass is not a third copy of them."""
 import os
 import re
 
@@ -18,6 +19,9 @@ SCENE_POINTERS = ["spheres", "rad", "mat_color", "mat_type", "groups", "orig", "
 MIRRORED = ["n_spheres", "n_padded", "n_groups", "n_big_groups", "n_big", "global_scene", "basic_materials", "cull_c", "cull_radius", "cull_k1", "cull_k2",
             "cull_k3", "cull_coord_max", "pair_k0", "box_shared_axis", "box_shared_lo", "box_shared_hi", "cell_on", "cell_axes", "cell_scale", "cell_off",
             "ubox", "num_bvh_nodes", "nppl", "leaf_sentinels_trailing", "bounds", "floor"]
+# what every whole-image pass holds on the device
+PASS_MEMBERS = ["device", "npix", "owned", "d_guide", "d_in", "d_out"]
+PASSES = {"denoiseFrame", "accumulateFrame"}
 
 
 def _source():
@@ -65,3 +69,29 @@ def test_render_context_does_not_mirror_the_parameter_blocks():
     assert re.search(r"\bRtSphereParams\s+\w+", body) and re.search(r"\bRtMeshParams\s+\w+", body), "no scene template in RenderContext"
     mirrored = [name for name in MIRRORED if re.search(r"\b%s\b" % name, body)]
     assert mirrored == [], f"RenderContext mirrors parameter-block fields: {mirrored}"
+
+
+def test_one_function_builds_the_whole_image_partition():
+    src = _source()
+    funcs = _functions(src)
+    builders = [_enclosing(funcs, m.start()) for m in re.finditer(r"\.world\s*=\s*1\b", src)]
+    assert builders == ["whole_image_partition"], builders
+    assert "RtPartition" not in "".join(src[a:b] for n, a, b in funcs if n in PASSES)
+
+
+def test_the_passes_leave_events_and_the_current_device_to_the_shared_path():
+    src = _source()
+    creators = set(_callers(src, "hipEventCreate"))
+    assert creators == {"setup_devices", "begin_pass"}, sorted(map(str, creators))
+    for call in ("hipEventCreate", "hipGetDevice", "hipSetDevice"):
+        assert not PASSES & set(_callers(src, call)), call
+    assert not re.search(r"\bfree_(denoise|accumulate)\b", src)
+
+
+def test_pass_members_are_declared_in_one_struct():
+    structs = re.findall(r"^struct (\w+)[^{\n]*\{(.*?)^\};", _source(), re.M | re.S)
+    holders = {name: [s for s, body in structs if re.search(r"\b%s\b\s*(?:\[\d+\]\s*)?[=;]" % name, body)] for name in PASS_MEMBERS}
+    whole = [s for s, body in structs if all(s in holders[name] for name in PASS_MEMBERS)]
+    assert len(whole) == 1, holders
+    for name in ("npix", "d_in", "d_out"):                      # (a DeviceState has a device, a record of its allocations and guide planes of its own rows)
+        assert holders[name] == whole, (name, holders[name])
