@@ -45,10 +45,15 @@ $(OBJ)/denoise.o: $(CSRC)/rt_kernels_denoise.hip $(CSRC)/rt_denoise.h include/rt
 # host arithmetic (the constants of the previous camera) is compiled under them too.  Its own TU and header: no other kernel object depends on it.
 $(OBJ)/accumulate.o: $(CSRC)/rt_kernels_accumulate.hip $(CSRC)/rt_accumulate.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The kernels of previewFrame (temporal moments, variance, variance-guided a-trous): defined bit for bit as the two passes it fuses, so one object with the
+# flags of denoise.o; the launcher's host arithmetic is compiled under them too.  Its own TU and header: no other kernel object depends on it.
+$(OBJ)/preview.o: $(CSRC)/rt_kernels_preview.hip $(CSRC)/rt_preview.h include/rt_types.h include/rt_api.h | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o
+RT_OBJS += $(OBJ)/preview.o
 
 $(PKG)/librt_mi355x.so: $(RT_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) -o $@

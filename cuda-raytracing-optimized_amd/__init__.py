@@ -133,7 +133,8 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "runRendererProgressive", "rtProgressiveSamples", "rtResetProgressive", "setCamera",
                     "renderGuides", "rtLastGuidesMs",
                     "rtDefaultDenoiseFlags", "denoiseFrame", "rtLastDenoiseMs",
-                    "accumulateFrame", "rtResetHistory", "rtHistoryFrames", "rtLastAccumulateMs"]
+                    "accumulateFrame", "rtResetHistory", "rtHistoryFrames", "rtLastAccumulateMs",
+                    "previewFrame", "rtResetPreview", "rtPreviewFrames", "rtLastPreviewMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
@@ -274,6 +275,14 @@ def load_renderer():
         r.rtHistoryFrames.restype = C.c_int
         r.rtLastAccumulateMs.argtypes = []
         r.rtLastAccumulateMs.restype = C.c_double
+        r.previewFrame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
+        r.previewFrame.restype = None
+        r.rtResetPreview.argtypes = []
+        r.rtResetPreview.restype = None
+        r.rtPreviewFrames.argtypes = []
+        r.rtPreviewFrames.restype = C.c_int
+        r.rtLastPreviewMs.argtypes = []
+        r.rtLastPreviewMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -577,6 +586,55 @@ def history_frames():
 def last_accumulate_ms():
     """HIP-event time of the kernel of the last accumulateFrame, in milliseconds; 0 before the first call."""
     return load_renderer().rtLastAccumulateMs()
+
+
+# previewFrame (include/rt_api.h): the history length below which the variance is the spatial estimate, and the floor of the luminance width
+RT_PREVIEW_MIN_HISTORY, RT_PREVIEW_LUM_EPS = 4.0, 1e-4
+
+
+def _pixel_plane(who, what, plane):
+    """An optional (ny, nx) float32 plane of a whole-image pass: True = a new array, False / None = none, or a writable C-contiguous array to fill."""
+    shape = (_state["ny"], _state["nx"])
+    if plane is True:
+        return np.empty(shape, np.float32)
+    if plane is False or plane is None:
+        return None
+    if not (isinstance(plane, np.ndarray) and plane.dtype == np.float32 and plane.flags["C_CONTIGUOUS"] and plane.flags["WRITEABLE"] and plane.shape == shape):
+        raise ValueError(f"{who}: {what} must be True, False or a writable C-contiguous float32 array of shape {shape}")
+    return plane
+
+
+def previewFrame(fb=None, out=None, history=False, variance=False, flags=None, max_history=32, iterations=5, normal_squarings=5, sigma_z=0.01, normal_min=0.9,
+                 sigma_l=4.0):
+    """accumulateFrame and denoiseFrame in one device pass, the filter's colour width set pixel by pixel by the variance of the accumulated luminance
+    (include/rt_api.h).  fb, out, history as accumulateFrame's; variance: True = also return the per-pixel variance of stage V as a (ny, nx) float32 array, or
+    such an array to fill.  flags None = the scene kind's default.  Returns out, or a tuple (out, history and / or variance, in that order).  Blocking; always
+    the whole image on the first device; a history of its own.  The loop of a camera move: setCamera, runRenderer(1), previewFrame."""
+    r = load_renderer()
+    if flags is None:
+        flags = r.rtDefaultDenoiseFlags()
+    src, out = _frame_in_out("previewFrame", fb, out)
+    hist = _pixel_plane("previewFrame", "history", history)
+    var = _pixel_plane("previewFrame", "variance", variance)
+    r.previewFrame(src, out.ctypes.data, None if hist is None else hist.ctypes.data, None if var is None else var.ctypes.data, flags, max_history, iterations,
+                   normal_squarings, sigma_z, normal_min, sigma_l)
+    planes = tuple(a for a in (hist, var) if a is not None)
+    return (out,) + planes if planes else out
+
+
+def reset_preview():
+    """The next previewFrame has no history."""
+    load_renderer().rtResetPreview()
+
+
+def preview_frames():
+    """previewFrame calls since init / the last reset of its history."""
+    return load_renderer().rtPreviewFrames()
+
+
+def last_preview_ms():
+    """HIP-event time of the kernels of the last previewFrame (temporal, variance, iterations), in milliseconds; 0 before the first call."""
+    return load_renderer().rtLastPreviewMs()
 
 
 def cleanupRenderer():

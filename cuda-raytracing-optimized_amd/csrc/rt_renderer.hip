@@ -28,6 +28,7 @@
 #include "rt_params.h"
 #include "rt_denoise.h"
 #include "rt_accumulate.h"
+#include "rt_preview.h"
 
 namespace {
 
@@ -161,9 +162,10 @@ struct RenderContext {
     double guides_ms = 0.0;             // rtLastGuidesMs
     double denoise_ms = 0.0;            // rtLastDenoiseMs
     double accumulate_ms = 0.0;         // rtLastAccumulateMs
+    double preview_ms = 0.0;            // rtLastPreviewMs
 };
 
-// What the whole-image preview passes (denoiseFrame, accumulateFrame) each hold on the device: buffers for the whole image on ONE device, the first in-process
+// What the whole-image preview passes (denoiseFrame, accumulateFrame, previewFrame) each hold on the device: buffers for the whole image on ONE device, the first in-process
 // device, whatever rows that device renders, with guide planes and events of their own (a frame's and the guides' timings stay what they were).  A pass shares
 // nothing with the other pass or with renderGuides - neither can disturb the history.  Allocated by the pass's first call (begin_pass), freed by free_pass
 // (cleanupRenderer, every init*, a setRenderOptions that changes the device layout).
@@ -191,8 +193,21 @@ struct AccumulateState : PassState {
 };
 
 RenderContext g_ctx;     // kernels.cu:145: one global context per process
+// previewFrame: a history of its own (the record sets of rt_preview.h with their moment planes), the a-trous pair and the two planes for the caller.
+struct PreviewState : PassState {
+    float* d_history = nullptr;         // N(p) as a plane for the caller
+    float* d_variance = nullptr;        // var(p) of stage V as a plane for the caller
+    float4* d_rec[2] = { nullptr, nullptr };                        // the two record sets, 3 * npix each
+    float2* d_mom[2] = { nullptr, nullptr };                        // their luminance moments
+    float4* d_col[2] = { nullptr, nullptr };                        // RtPreviewParams::col
+    int newest = 0;                     // the set the last call wrote: the next call's history
+    int frames = 0;                     // calls since the last reset (rtPreviewFrames); 0 = the next call has no history
+    rt_camera prev_cam;                 // the camera of the last call
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
+PreviewState g_preview;
 
 // rtLastLaunches: the records of the last runRenderer (RT_LAUNCH_WORDS each) and the device / fp mode of the launcher being called
 std::vector<int32_t> g_launches;
@@ -257,6 +272,7 @@ void setup_devices() {
     RenderContext& c = g_ctx;
     free_pass(g_denoise);                                   // (its buffers live on the first device of the list being replaced)
     free_pass(g_accumulate);                                // (so do the history's)
+    free_pass(g_preview);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -626,6 +642,7 @@ void cleanup_impl() {
     RenderContext& c = g_ctx;
     free_pass(g_denoise);
     free_pass(g_accumulate);
+    free_pass(g_preview);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -726,6 +743,7 @@ void setRenderOptions(const rt_render_options* opt) {
     if (relayout) setup_devices();
     c.prog_samples = 0;                                     // (any call: the options of the accumulated samples may differ)
     g_accumulate.frames = 0;                                // (likewise the history of accumulateFrame)
+    g_preview.frames = 0;                                   // (and previewFrame's)
 }
 
 }  // extern "C"
@@ -810,7 +828,7 @@ void deliver_stripes(const DeviceState& d, const RtPartition& part, char* host, 
         HIP_CHECK(hipMemcpyAsync(dst0 + full * (size_t)part.world * stripe_bytes, dev + full * stripe_bytes, rem * row_bytes, hipMemcpyDeviceToHost, d.stream));
 }
 
-// The whole-image preview passes (denoiseFrame, accumulateFrame) differ in their own arguments, buffers, parameter block and kernels; the rest is here, once.
+// The whole-image preview passes (denoiseFrame, accumulateFrame, previewFrame) differ in their own arguments, buffers, parameter block and kernels; the rest is here, once.
 
 // The argument checks both have, under the function's name `fn`.  A pass calls it with one group of `which` at a time, between its own checks: a call with
 // two bad arguments fails on the one that comes first in that function's list.
@@ -864,13 +882,15 @@ Params pass_params(const PassState& n) {
     return q;
 }
 
-// After a pass's kernels: the stop event, out (and accumulateFrame's history plane, `d_history` -> `history`) to the caller, complete on return: blocking.
-// Returns the HIP-event time of the kernels in milliseconds.
-double end_pass(const PassState& n, int current, rt_vec3* out, float* history = nullptr, const float* d_history = nullptr) {
+// After a pass's kernels: the stop event, out (and the optional per-pixel planes of accumulateFrame and previewFrame, `d_history` -> `history` and
+// `d_variance` -> `variance`) to the caller, complete on return: blocking.  Returns the HIP-event time of the kernels in milliseconds.
+double end_pass(const PassState& n, int current, rt_vec3* out, float* history = nullptr, const float* d_history = nullptr, float* variance = nullptr,
+                const float* d_variance = nullptr) {
     const DeviceState& d = g_ctx.devs[0];
     HIP_CHECK(hipEventRecord(n.ev_stop, d.stream));
     HIP_CHECK(hipMemcpyAsync(out, n.d_out, n.npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
     if (history) HIP_CHECK(hipMemcpyAsync(history, d_history, n.npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+    if (variance) HIP_CHECK(hipMemcpyAsync(variance, d_variance, n.npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
     HIP_CHECK(hipStreamSynchronize(d.stream));
     float ms = 0.0f;
     HIP_CHECK(hipEventElapsedTime(&ms, n.ev_start, n.ev_stop));
@@ -1282,6 +1302,59 @@ int rtHistoryFrames(void) {
 }
 
 double rtLastAccumulateMs(void) { return g_ctx.accumulate_ms; }
+
+// Variance-guided accumulate + filter in one device pass (rt_api.h).  Like the two passes it fuses: the whole image on the first in-process
+// device, guide planes of its own (one guide pass, not two), buffers and events of its own, a history of its own.  The accumulated frame never leaves the device.
+void previewFrame(const rt_vec3* in, rt_vec3* out, float* history, float* variance, int flags, int max_history, int iterations, int normal_squarings,
+                  float sigma_z, float normal_min, float sigma_l) {
+    check_pass_args("previewFrame", kCheckInit | kCheckOut | kCheckFlags, out, flags, sigma_z);
+    if (max_history < 1 || max_history > RT_ACCUM_MAX_HISTORY) rt_fail("previewFrame: max_history must be 1 .. RT_ACCUM_MAX_HISTORY");
+    if (iterations < 1 || iterations > RT_DENOISE_MAX_ITERATIONS) rt_fail("previewFrame: iterations must be 1 .. RT_DENOISE_MAX_ITERATIONS");
+    if (normal_squarings < 0 || normal_squarings > RT_DENOISE_MAX_SQUARINGS) rt_fail("previewFrame: normal_squarings must be 0 .. RT_DENOISE_MAX_SQUARINGS");
+    check_pass_args("previewFrame", kCheckSigmaZ, out, flags, sigma_z);
+    if (!std::isfinite(normal_min) || normal_min < -1.0f || normal_min > 1.0f) rt_fail("previewFrame: normal_min must be finite and in [-1, 1]");
+    if (!std::isfinite(sigma_l) || !(sigma_l > 0.0f)) rt_fail("previewFrame: sigma_l must be finite and positive");
+    check_pass_args("previewFrame", kCheckFloor, out, flags, sigma_z);
+    PreviewState& n = g_preview;
+    const int current = begin_pass(n, in, [&n] {
+        n.d_history = dev_alloc<float>(n.owned, n.npix);
+        n.d_variance = dev_alloc<float>(n.owned, n.npix);
+        for (int k = 0; k < 2; k++) {
+            n.d_rec[k] = dev_alloc<float4>(n.owned, 3 * n.npix);
+            n.d_mom[k] = dev_alloc<float2>(n.owned, n.npix);
+            n.d_col[k] = dev_alloc<float4>(n.owned, n.npix);
+        }
+    });
+    RtPreviewParams q = pass_params<RtPreviewParams>(n);
+    q.history = history ? n.d_history : nullptr;
+    q.variance = variance ? n.d_variance : nullptr;
+    q.prev = n.d_rec[n.newest]; q.next = n.d_rec[n.newest ^ 1];
+    q.prev_mom = n.d_mom[n.newest]; q.next_mom = n.d_mom[n.newest ^ 1];
+    q.col[0] = n.d_col[0]; q.col[1] = n.d_col[1];
+    q.flags = flags; q.has_history = n.frames > 0 ? 1 : 0; q.normal_squarings = normal_squarings;
+    q.max_history = (float)max_history; q.sigma_z = sigma_z; q.normal_min = normal_min; q.sigma_l = sigma_l;
+    const hipStream_t stream = g_ctx.devs[0].stream;
+    HIP_CHECK(hipEventRecord(n.ev_start, stream));
+    HIP_CHECK(rt_launch_preview_temporal(q, n.prev_cam, stream));
+    HIP_CHECK(rt_launch_preview_variance(q, stream));
+    for (int it = 0; it < iterations; it++) HIP_CHECK(rt_launch_preview_iteration(q, it, it == iterations - 1, stream));
+    g_ctx.preview_ms = end_pass(n, current, out, history, n.d_history, variance, n.d_variance);
+    n.newest ^= 1;
+    n.prev_cam = g_ctx.cam;
+    if (n.frames < INT_MAX) n.frames++;
+}
+
+void rtResetPreview(void) {
+    if (!g_ctx.initialised) rt_fail("rtResetPreview before init");
+    g_preview.frames = 0;
+}
+
+int rtPreviewFrames(void) {
+    if (!g_ctx.initialised) rt_fail("rtPreviewFrames before init");
+    return g_preview.frames;
+}
+
+double rtLastPreviewMs(void) { return g_ctx.preview_ms; }
 
 void setExternalFramebuffer(rt_vec3* fb) {
     RenderContext& c = g_ctx;

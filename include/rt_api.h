@@ -253,6 +253,60 @@ int rtHistoryFrames(void);
 /* HIP-event time of the kernel of the last accumulateFrame (not its guide kernel, not the copies) in milliseconds; 0 before the first call. */
 double rtLastAccumulateMs(void);
 
+/* --- variance-guided accumulate + filter, one device pass ----------------------------------------------------------------------
+ * previewFrame is accumulateFrame and denoiseFrame in one call with what SVGF (Schied et al. 2017) puts between them: the first two moments of the luminance
+ * are accumulated with the colour, a per-pixel variance comes from them - from the 7 x 7 neighbourhood where the history is shorter than
+ * RT_PREVIEW_MIN_HISTORY - and that variance, not a caller's sigma_c, sets the colour width of the a-trous filter pixel by pixel and is filtered along with the
+ * colour.  The accumulated frame stays on the device and the guide kernel runs once.  The loop of a camera move is setCamera, runRenderer(1), previewFrame
+ * (INTEGRATION.md 2).  All arithmetic is fp32 with + - * / abs floor min max sqrt only, every operation rounded on its own (no FMA), operands in the order
+ * written, sqrt correctly rounded, max(x, 0) = x > 0 ? x : 0, a comparison with a NaN false, so the result is defined bit for bit.
+ * lum(x) = 0.2126f*x[0] + 0.7152f*x[1] + 0.0722f*x[2], left to right.  valid, P, rz, m, c0, n, prim are the denoiser's above.
+ * Stage T (temporal) is accumulateFrame's definition word for word for c(p) and N(p), with C', P', n', prim', c', N', M1', M2' the camera and the planes the
+ * previous previewFrame stored, and two more accumulated quantities:
+ *     l0 = lum(c0(p));  q0 = l0*l0;  in the tap loop additionally  m1sum += bw * M1'(q);  m2sum += bw * M2'(q)
+ *     if blended:  h1 = m1sum/wsum;  M1 = h1 + al * (l0 - h1);  h2 = m2sum/wsum;  M2 = h2 + al * (q0 - h2)          else:  M1 = l0;  M2 = q0
+ * Every call stores P, n, prim, c, N, M1, M2 of its frame and its camera for the next call; c is the UNFILTERED accumulated colour.
+ * Stage V (variance), for every valid p:
+ *     if N(p) >= RT_PREVIEW_MIN_HISTORY:  var = max(M2 - M1*M1, 0)
+ *     else:
+ *         s1 = s2 = ws = 0
+ *         for dy = -3..3 (outer), dx = -3..3 (inner):
+ *             q = (i + dx, j + dy);  the tap adds nothing if q is outside the image or !valid(q)
+ *             if dx == 0 and dy == 0:  w = 1
+ *             else:  w = wn * wz, wn and wz exactly the denoiser's (normal_squarings, rz(p));  if RT_DENOISE_SAME_PRIM and prim(p) != prim(q):  w = 0
+ *             s1 += w * M1(q);  s2 += w * M2(q);  ws += w
+ *         a1 = s1/ws;  a2 = s2/ws;  var = max(a2 - a1*a1, 0) * (4.0f / N(p))
+ * Stage A (a-trous) on the pair (c, var), it = 0 .. iterations-1, s = 1 << it, K and h the denoiser's.  For every valid p:
+ *     rl = 1 / (sigma_l * sqrt(var(p)) + RT_PREVIEW_LUM_EPS);  lp = lum(c(p));  sum = (0,0,0);  vsum = 0;  wsum = 0
+ *     the 25 taps in the denoiser's order, under its validity rules:
+ *         if dx == 0 and dy == 0:  w = h
+ *         else:
+ *             w = h * wn * wz                                                       (left to right)
+ *             wl = max(1 - abs(lp - lum(c(q))) * rl, 0);  wl = wl * wl;  w = w * wl
+ *             if RT_DENOISE_SAME_PRIM and prim(p) != prim(q):  w = 0
+ *         sum[k] += w * c(q)[k];  vsum += (w*w) * var(q);  wsum += w
+ *     c'(p)[k] = sum[k] / wsum;  var'(p) = vsum / (wsum*wsum)
+ * At the end out(p)[k] = c(p)[k] * m(p)[k] (no multiplication without RT_DENOISE_DEMODULATE).  Pixels with !valid(p) copy in(p) to out(p) bit for bit, store
+ * N = 0, have variance 0 and are never a tap of any stage.  Non-finite input is not treated specially.
+ *
+ * previewFrame: `in`, `out` and `history` exactly as accumulateFrame's - `in` NULL = the framebuffer the renderer currently delivers into, `out` caller-owned
+ * and never NULL, `out` may be `in`, `history` NULL or nx*ny floats that receive N(p); blocking.  `variance` = NULL, or nx*ny floats that receive var(p) of
+ * stage V (0 without a first hit).  Defaults: flags rtDefaultDenoiseFlags(), max_history 32, iterations 5, normal_squarings 5, sigma_z 0.01f, normal_min 0.9f,
+ * sigma_l 4.0f.  It works on the WHOLE image on the first in-process device and keeps a history of its own, independent of accumulateFrame's: neither call
+ * disturbs the other, nor denoiseFrame, renderGuides, the framebuffer (unless passed as `out`), getRenderStats, rtLastLaunches, the progressive frame or the
+ * other rtLast*Ms values.  Its history is reset where accumulateFrame's is - every init*, cleanupRenderer, every setRenderOptions - and by rtResetPreview; its
+ * device buffers (208 bytes per pixel) are allocated by the first call and freed where the other passes' are.  Misuse (rt error, exit 99): before init, out
+ * NULL, unknown flag bits, max_history outside 1 .. RT_ACCUM_MAX_HISTORY, iterations outside 1 .. RT_DENOISE_MAX_ITERATIONS, normal_squarings outside
+ * 0 .. RT_DENOISE_MAX_SQUARINGS, sigma_z not finite or <= 0, normal_min not finite or outside [-1, 1], sigma_l not finite or <= 0, rt_render_options.floor = 1
+ * on a sphere scene; rtResetPreview or rtPreviewFrames before init. */
+#define RT_PREVIEW_MIN_HISTORY 4.0f     /* below it the variance is the spatial estimate */
+#define RT_PREVIEW_LUM_EPS     1e-4f
+void   previewFrame(const rt_vec3* in, rt_vec3* out, float* history, float* variance, int flags, int max_history,
+                    int iterations, int normal_squarings, float sigma_z, float normal_min, float sigma_l);
+void   rtResetPreview(void);      /* the next previewFrame has no history */
+int    rtPreviewFrames(void);     /* calls since the last reset */
+double rtLastPreviewMs(void);     /* HIP-event time of its kernels (not the guide kernel, not the copies); 0 before the first call */
+
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };
