@@ -134,13 +134,15 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "renderGuides", "rtLastGuidesMs",
                     "rtDefaultDenoiseFlags", "denoiseFrame", "rtLastDenoiseMs",
                     "accumulateFrame", "rtResetHistory", "rtHistoryFrames", "rtLastAccumulateMs",
-                    "previewFrame", "rtResetPreview", "rtPreviewFrames", "rtLastPreviewMs"]
+                    "previewFrame", "rtResetPreview", "rtPreviewFrames", "rtLastPreviewMs",
+                    "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
 HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtSceneRandomSpheres", "rtStaircaseCamera",
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
-                "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse"]
+                "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
+                "rtDisplayFrameHost"]
 
 _renderer = None
 _host = None
@@ -188,6 +190,9 @@ def load_host():
         h.rtLoadReference.restype = C.c_int
         h.rtRmse.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         h.rtRmse.restype = C.c_double
+        h.rtDisplayFrameHost.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_uint32)]
+        h.rtDisplayFrameHost.restype = C.c_int
         _host = h
     return _host
 
@@ -283,6 +288,16 @@ def load_renderer():
         r.rtPreviewFrames.restype = C.c_int
         r.rtLastPreviewMs.argtypes = []
         r.rtLastPreviewMs.restype = C.c_double
+        r.displayFrame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
+        r.displayFrame.restype = None
+        r.rtLastExposure.argtypes = []
+        r.rtLastExposure.restype = C.c_float
+        r.rtDisplayHistogram.argtypes = [C.POINTER(C.c_uint32), C.c_int]
+        r.rtDisplayHistogram.restype = C.c_int
+        r.rtResetDisplay.argtypes = []
+        r.rtResetDisplay.restype = None
+        r.rtLastDisplayMs.argtypes = []
+        r.rtLastDisplayMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -635,6 +650,75 @@ def preview_frames():
 def last_preview_ms():
     """HIP-event time of the kernels of the last previewFrame (temporal, variance, iterations), in milliseconds; 0 before the first call."""
     return load_renderer().rtLastPreviewMs()
+
+
+# displayFrame (include/rt_api.h): the flags, the tone maps, the histogram's size, the key the median luminance is exposed to, the dither matrix
+RT_DISPLAY_TOP_DOWN, RT_DISPLAY_DITHER, RT_DISPLAY_AUTO_EXPOSURE, RT_DISPLAY_FROM_PREVIEW = 1, 2, 4, 8
+RT_TONEMAP_NONE, RT_TONEMAP_REINHARD, RT_TONEMAP_ACES = 0, 1, 2
+RT_DISPLAY_BINS, RT_DISPLAY_KEY = 256, 0.18
+RT_DISPLAY_BAYER8 = ((0, 32, 8, 40, 2, 34, 10, 42), (48, 16, 56, 24, 50, 18, 58, 26), (12, 44, 4, 36, 14, 46, 6, 38), (60, 28, 52, 20, 62, 30, 54, 22),
+                     (3, 35, 11, 43, 1, 33, 9, 41), (51, 19, 59, 27, 49, 17, 57, 25), (15, 47, 7, 39, 13, 45, 5, 37), (63, 31, 55, 23, 61, 29, 53, 21))
+
+
+def _display_in_out(who, src, out, shape):
+    """The arrays of a display call, checked: (address of the (ny, nx, 3) float32 input or None, the (ny, nx, 4) uint8 output: `out` or a new one)."""
+    if src is not None and not (isinstance(src, np.ndarray) and src.dtype == np.float32 and src.flags["C_CONTIGUOUS"] and src.shape == shape + (3,)):
+        raise ValueError(f"{who}: src must be a C-contiguous float32 array of shape {shape + (3,)}")
+    if out is None:
+        out = np.empty(shape + (4,), np.uint8)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.shape == shape + (4,)):
+        raise ValueError(f"{who}: out must be a writable C-contiguous uint8 array of shape {shape + (4,)}")
+    return None if src is None else src.ctypes.data, out
+
+
+def display_frame(src=None, out=None, flags=0, tonemap=0, exposure=1.0, adapt=1.0):
+    """Exposure, tone map, sRGB and optional ordered dither on the device (include/rt_api.h): returns the (ny, nx, 4) uint8 picture R, G, B, 255 - a new array, or
+    `out`.  src: a (ny, nx, 3) float32 array, row 0 = bottom; None = the framebuffer the renderer currently delivers into, or with RT_DISPLAY_FROM_PREVIEW the
+    output of the last previewFrame where it lies on the device.  RT_DISPLAY_TOP_DOWN flips the rows; RT_DISPLAY_AUTO_EXPOSURE exposes the median luminance to
+    RT_DISPLAY_KEY, adapting by `adapt` per call.  Blocking; always the whole image on the first device."""
+    src, out = _display_in_out("display_frame", src, out, (_state["ny"], _state["nx"]))
+    load_renderer().displayFrame(src, out.ctypes.data, flags, tonemap, exposure, adapt)
+    return out
+
+
+def last_exposure():
+    """E_used of the last display_frame; 1 before the first."""
+    return load_renderer().rtLastExposure()
+
+
+def display_histogram():
+    """The RT_DISPLAY_BINS luminance bins of the last RT_DISPLAY_AUTO_EXPOSURE call (8 per octave over 2^-16 .. 2^16) as a uint32 array; zero after a reset."""
+    out = np.zeros(RT_DISPLAY_BINS, np.uint32)
+    n = load_renderer().rtDisplayHistogram(out.ctypes.data_as(C.POINTER(C.c_uint32)), RT_DISPLAY_BINS)
+    assert n == RT_DISPLAY_BINS
+    return out
+
+
+def reset_display():
+    """The next RT_DISPLAY_AUTO_EXPOSURE call adapts from nothing."""
+    load_renderer().rtResetDisplay()
+
+
+def last_display_ms():
+    """HIP-event time of the kernels of the last display_frame, in milliseconds; 0 before the first call."""
+    return load_renderer().rtLastDisplayMs()
+
+
+def display_frame_host(src, out=None, flags=0, tonemap=0, exposure=1.0, adapt=1.0, state=None, histogram=False):
+    """display_frame's definition on the CPU (librt_host.so, rtDisplayFrameHost; no GPU, no renderer state): the same bytes.  src: any (ny, nx, 3) float32
+    array.  state: None, or a one-element float32 array holding E' (NaN = adapt from nothing) that receives E.  histogram=True: returns (out, bins)."""
+    if not (isinstance(src, np.ndarray) and src.ndim == 3):
+        raise ValueError("display_frame_host: src must be a (ny, nx, 3) float32 array")
+    addr, out = _display_in_out("display_frame_host", src, out, src.shape[:2])
+    if state is not None and not (isinstance(state, np.ndarray) and state.dtype == np.float32 and state.size == 1 and state.flags["WRITEABLE"]):
+        raise ValueError("display_frame_host: state must be None or a writable float32 array of one element")
+    hist = np.zeros(RT_DISPLAY_BINS, np.uint32) if histogram else None
+    rc = load_host().rtDisplayFrameHost(addr, out.ctypes.data, src.shape[1], src.shape[0], flags, tonemap, exposure, adapt,
+                                        None if state is None else state.ctypes.data_as(C.POINTER(C.c_float)),
+                                        None if hist is None else hist.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != 0:
+        raise ValueError("display_frame_host: arguments displayFrame would refuse (flags, tonemap, exposure or adapt)")
+    return (out, hist) if histogram else out
 
 
 def cleanupRenderer():

@@ -29,6 +29,7 @@
 #include "rt_denoise.h"
 #include "rt_accumulate.h"
 #include "rt_preview.h"
+#include "rt_display.h"
 
 namespace {
 
@@ -163,6 +164,7 @@ struct RenderContext {
     double denoise_ms = 0.0;            // rtLastDenoiseMs
     double accumulate_ms = 0.0;         // rtLastAccumulateMs
     double preview_ms = 0.0;            // rtLastPreviewMs
+    double display_ms = 0.0;            // rtLastDisplayMs
 };
 
 // What the whole-image preview passes (denoiseFrame, accumulateFrame, previewFrame) each hold on the device: buffers for the whole image on ONE device, the first in-process
@@ -205,9 +207,26 @@ struct PreviewState : PassState {
     rt_camera prev_cam;                 // the camera of the last call
 };
 
+// displayFrame: no guide planes and no rt_vec3 output (begin_pass is told so): the RGBA words and the histogram with the two exposure words behind it are its own.
+// E' of the auto exposure stays on the device (d_words); `adapted` says whether it holds one.  The host keeps what the helpers report.
+struct DisplayState : PassState {
+    uint32_t* d_rgba = nullptr;         // RtDisplayParams::out, one word per pixel
+    uint32_t* d_words = nullptr;        // RtDisplayParams::hist (RT_DISPLAY_BINS words), then RtDisplayParams::state (E, E_used)
+    uint32_t h_words[RT_DISPLAY_BINS + 2] = {};     // d_words after the last RT_DISPLAY_AUTO_EXPOSURE call (rtDisplayHistogram)
+    bool adapted = false;               // d_words holds the E of a previous call: the next one blends
+    float last_exposure = 1.0f;         // rtLastExposure
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
+DisplayState g_display;
+
+// The state of displayFrame's auto exposure back to "adapt from nothing" (rtResetDisplay, setRenderOptions); the buffers stay.
+void reset_display() {
+    g_display.adapted = false;
+    memset(g_display.h_words, 0, RT_DISPLAY_BINS * sizeof(uint32_t));
+}
 
 // rtLastLaunches: the records of the last runRenderer (RT_LAUNCH_WORDS each) and the device / fp mode of the launcher being called
 std::vector<int32_t> g_launches;
@@ -273,6 +292,7 @@ void setup_devices() {
     free_pass(g_denoise);                                   // (its buffers live on the first device of the list being replaced)
     free_pass(g_accumulate);                                // (so do the history's)
     free_pass(g_preview);
+    free_pass(g_display);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -643,6 +663,7 @@ void cleanup_impl() {
     free_pass(g_denoise);
     free_pass(g_accumulate);
     free_pass(g_preview);
+    free_pass(g_display);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -744,6 +765,7 @@ void setRenderOptions(const rt_render_options* opt) {
     c.prog_samples = 0;                                     // (any call: the options of the accumulated samples may differ)
     g_accumulate.frames = 0;                                // (likewise the history of accumulateFrame)
     g_preview.frames = 0;                                   // (and previewFrame's)
+    reset_display();                                        // (and displayFrame's adapted exposure)
 }
 
 }  // extern "C"
@@ -845,9 +867,11 @@ void check_pass_args(const char* fn, int which, const rt_vec3* out, int flags, f
 // Up to a pass's own kernels, on the first in-process device (every device holds the whole scene, setup_devices): in NULL = the framebuffer being delivered
 // into; the buffers every pass has, `alloc_own()` for the pass's own and the events, when the device or the image size is not the state's; the upload of `in`
 // before anything is written (out may be in); the guide planes of the camera and options in force.  Returns the device to restore (end_pass).  The pass
-// records n.ev_start in front of its kernels.
+// records n.ev_start in front of its kernels.  `without` names what a pass does not take (displayFrame): kPassNoGuides - no guide planes, no guide launch;
+// kPassOwnOutput - no rt_vec3 output buffer, the pass delivers buffers of its own type (end_pass); kPassNoUpload - this call's input is on the device already.
+enum { kPassNoGuides = 1, kPassOwnOutput = 2, kPassNoUpload = 4 };
 template <typename State, typename AllocOwn>
-int begin_pass(State& n, const rt_vec3* in, AllocOwn alloc_own) {
+int begin_pass(State& n, const rt_vec3* in, AllocOwn alloc_own, int without = 0) {
     const RenderContext& c = g_ctx;
     if (!in) in = c.h_ext ? c.h_ext : c.h_fb;
     int current = 0;
@@ -859,15 +883,17 @@ int begin_pass(State& n, const rt_vec3* in, AllocOwn alloc_own) {
         free_pass(n);
         HIP_CHECK(hipSetDevice(d.device));
         n.device = d.device; n.npix = npix;
-        for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
+        if (!(without & kPassNoGuides))
+            for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
         n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
-        n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
+        if (!(without & kPassOwnOutput)) n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
         alloc_own();
         HIP_CHECK(hipEventCreate(&n.ev_start));
         HIP_CHECK(hipEventCreate(&n.ev_stop));
     }
-    HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));
-    launch_guides(d, whole_image_partition(), { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr });
+    if (!(without & kPassNoUpload)) HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));
+    if (!(without & kPassNoGuides))
+        launch_guides(d, whole_image_partition(), { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr });
     return current;
 }
 
@@ -883,12 +909,19 @@ Params pass_params(const PassState& n) {
 }
 
 // After a pass's kernels: the stop event, out (and the optional per-pixel planes of accumulateFrame and previewFrame, `d_history` -> `history` and
-// `d_variance` -> `variance`) to the caller, complete on return: blocking.  Returns the HIP-event time of the kernels in milliseconds.
+// `d_variance` -> `variance`) to the caller, complete on return: blocking.  A pass whose output is not an rt_vec3 frame (displayFrame) passes out = NULL and the
+// `n_own` device-to-host copies `own` it delivers instead.  Returns the HIP-event time of the kernels in milliseconds.
+struct PassCopy {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
 double end_pass(const PassState& n, int current, rt_vec3* out, float* history = nullptr, const float* d_history = nullptr, float* variance = nullptr,
-                const float* d_variance = nullptr) {
+                const float* d_variance = nullptr, const PassCopy* own = nullptr, int n_own = 0) {
     const DeviceState& d = g_ctx.devs[0];
     HIP_CHECK(hipEventRecord(n.ev_stop, d.stream));
-    HIP_CHECK(hipMemcpyAsync(out, n.d_out, n.npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
+    if (out) HIP_CHECK(hipMemcpyAsync(out, n.d_out, n.npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
+    for (int k = 0; k < n_own; k++) HIP_CHECK(hipMemcpyAsync(own[k].host, own[k].dev, own[k].bytes, hipMemcpyDeviceToHost, d.stream));
     if (history) HIP_CHECK(hipMemcpyAsync(history, d_history, n.npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
     if (variance) HIP_CHECK(hipMemcpyAsync(variance, d_variance, n.npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
     HIP_CHECK(hipStreamSynchronize(d.stream));
@@ -1355,6 +1388,72 @@ int rtPreviewFrames(void) {
 }
 
 double rtLastPreviewMs(void) { return g_ctx.preview_ms; }
+
+// The display transform (rt_api.h).  Through the passes' shared path, without guide planes: the whole image on the first in-process device, the
+// RGBA words and the histogram its own buffers.  With RT_DISPLAY_FROM_PREVIEW the input is previewFrame's output buffer where that call left it.
+void displayFrame(const rt_vec3* in, uint8_t* out_rgba, int flags, int tonemap, float exposure, float adapt) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("displayFrame before init");
+    if (!out_rgba) rt_fail("displayFrame: out_rgba is null");
+    constexpr int kAll = RT_DISPLAY_TOP_DOWN | RT_DISPLAY_DITHER | RT_DISPLAY_AUTO_EXPOSURE | RT_DISPLAY_FROM_PREVIEW;
+    if ((flags & ~kAll) != 0) rt_fail("displayFrame: unknown flag bits");
+    if (tonemap != RT_TONEMAP_NONE && tonemap != RT_TONEMAP_REINHARD && tonemap != RT_TONEMAP_ACES) rt_fail("displayFrame: unknown tonemap");
+    if (!std::isfinite(exposure) || !(exposure > 0.0f)) rt_fail("displayFrame: exposure must be finite and positive");
+    if (!std::isfinite(adapt) || !(adapt > 0.0f) || adapt > 1.0f) rt_fail("displayFrame: adapt must be finite and in (0, 1]");
+    const bool from_preview = (flags & RT_DISPLAY_FROM_PREVIEW) != 0, auto_exposure = (flags & RT_DISPLAY_AUTO_EXPOSURE) != 0;
+    if (from_preview && in) rt_fail("displayFrame: RT_DISPLAY_FROM_PREVIEW takes in = NULL");
+    if (from_preview && g_preview.frames == 0) rt_fail("displayFrame: RT_DISPLAY_FROM_PREVIEW without a previewFrame since init or the last reset of its history");
+    DisplayState& n = g_display;
+    const int current = begin_pass(n, in, [&n] {
+        n.d_rgba = dev_alloc<uint32_t>(n.owned, n.npix);
+        n.d_words = dev_alloc<uint32_t>(n.owned, RT_DISPLAY_BINS + 2);
+    }, kPassNoGuides | kPassOwnOutput | (from_preview ? kPassNoUpload : 0));
+    RtDisplayParams q;
+    memset(&q, 0, sizeof q);
+    q.in = from_preview ? g_preview.d_out : n.d_in;
+    q.out = n.d_rgba; q.hist = n.d_words;
+    q.state = auto_exposure ? reinterpret_cast<float*>(n.d_words + RT_DISPLAY_BINS) : nullptr;
+    q.nx = c.nx; q.ny = c.ny; q.flags = flags; q.tonemap = tonemap; q.adapted = n.adapted ? 1 : 0;
+    q.exposure = exposure; q.adapt = adapt;
+    const hipStream_t stream = c.devs[0].stream;
+    HIP_CHECK(hipEventRecord(n.ev_start, stream));
+    if (auto_exposure) {
+        HIP_CHECK(hipMemsetAsync(n.d_words, 0, RT_DISPLAY_BINS * sizeof(uint32_t), stream));
+        HIP_CHECK(rt_launch_display_histogram(q, stream));
+        HIP_CHECK(rt_launch_display_resolve(q, stream));
+    }
+    HIP_CHECK(rt_launch_display_transform(q, stream));
+    const PassCopy own[2] = { { out_rgba, n.d_rgba, n.npix * sizeof(uint32_t) }, { n.h_words, n.d_words, sizeof n.h_words } };
+    c.display_ms = end_pass(n, current, nullptr, nullptr, nullptr, nullptr, nullptr, own, auto_exposure ? 2 : 1);
+    if (auto_exposure) {
+        n.adapted = true;
+        memcpy(&n.last_exposure, &n.h_words[RT_DISPLAY_BINS + 1], sizeof(float));
+    } else {
+        n.last_exposure = exposure;
+    }
+}
+
+float rtLastExposure(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastExposure before init");
+    return g_display.last_exposure;
+}
+
+int rtDisplayHistogram(uint32_t* out, int cap) {
+    if (!g_ctx.initialised) rt_fail("rtDisplayHistogram before init");
+    const int n = std::min(std::max(cap, 0), RT_DISPLAY_BINS);
+    if (out && n > 0) memcpy(out, g_display.h_words, (size_t)n * sizeof(uint32_t));
+    return RT_DISPLAY_BINS;
+}
+
+void rtResetDisplay(void) {
+    if (!g_ctx.initialised) rt_fail("rtResetDisplay before init");
+    reset_display();
+}
+
+double rtLastDisplayMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastDisplayMs before init");
+    return g_ctx.display_ms;
+}
 
 void setExternalFramebuffer(rt_vec3* fb) {
     RenderContext& c = g_ctx;

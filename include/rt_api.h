@@ -307,6 +307,57 @@ void   rtResetPreview(void);      /* the next previewFrame has no history */
 int    rtPreviewFrames(void);     /* calls since the last reset */
 double rtLastPreviewMs(void);     /* HIP-event time of its kernels (not the guide kernel, not the copies); 0 before the first call */
 
+/* --- display transform: exposure, tone map, sRGB bytes ------------------------------------------------------------------------
+ * displayFrame turns a linear fp32 frame into the 8-bit sRGB picture a viewer, a video encoder or rtWritePPM (rt_host.h) wants, on the device: 4 bytes per pixel
+ * come back instead of 12, and the one powf per channel runs there.  The loop of a camera move becomes setCamera, runRenderer(1), previewFrame, displayFrame
+ * with RT_DISPLAY_FROM_PREVIEW.  All arithmetic is fp32, every operation rounded on its own (no FMA), operands in the order written, a
+ * comparison with a NaN false, max(a, b) = a > b ? a : b; lum is previewFrame's; powf is glibc's (csrc/rt_glibc_powf_pos.h restates it for the device).  So the
+ * bytes are defined bit for bit, and rtDisplayFrameHost (rt_host.h) computes the same ones without a GPU.
+ * Exposure:  without RT_DISPLAY_AUTO_EXPOSURE E_used = exposure; with it E_used = E * exposure, E from the next stage.
+ * Auto exposure, over the INPUT frame.  For every pixel p:
+ *     l = lum(in(p));  b = (int)(bits(l) >> 20) - ((127 - 16) << 3)                  (8 bins per octave over 2^-16 .. 2^16)
+ *     p is counted in bin min(b, RT_DISPLAY_BINS - 1) iff l is finite, l > 0 and b >= 0
+ *     T = the sum of the bins.  T == 0: target = 1.  Else m = the smallest bin with 2 * cum(m) >= T (integers; cum(m) = bins 0 .. m),
+ *         Lmed = the float with bits ((m + ((127 - 16) << 3)) << 20) | (1 << 19) (the middle of bin m),  target = RT_DISPLAY_KEY / Lmed
+ *     the first RT_DISPLAY_AUTO_EXPOSURE call after a reset: E = target;  otherwise, E' being the E of the previous such call: E = E' + adapt * (target - E')
+ * The counts are integers: the result does not depend on the order in which pixels are counted.
+ * Per pixel p = (i, j) and channel k:
+ *     x[k] = in(p)[k] * E_used
+ *     RT_TONEMAP_NONE:      y[k] = x[k]
+ *     RT_TONEMAP_REINHARD:  y[k] = x[k] / (1 + max(lum(x), 0))
+ *     RT_TONEMAP_ACES:      a = max(x[k], 0);  y[k] = (a * (2.51f*a + 0.03f)) / (a * (2.43f*a + 0.59f) + 0.14f)            (Narkowicz's fit)
+ *     s = max(y[k], 0)  (a NaN gives 0);  s = max(1.055f * powf(s, 0.416666667f) - 0.055f, 0);  t = s * 255.9f              (rtLinearToSRGB's lines)
+ *     with RT_DISPLAY_DITHER instead  t = s * 255.0f + ((float)B[j & 7][i & 7] + 0.5f) / 64.0f,  B = RT_DISPLAY_BAYER8, (i, j) the INPUT coordinates
+ *     u[k] = t >= 255.0f ? 255 : (uint32)t
+ * The bytes of a pixel are u[0], u[1], u[2], 255.  Row 0 is the bottom row, as in the framebuffer; RT_DISPLAY_TOP_DOWN writes input row j to output row
+ * ny - 1 - j (the order of a PPM or a video frame).  The clamp before the conversion is part of the definition: rtLinearToSRGB converts first, and C leaves
+ * (uint32_t) of a float from 2^32 up undefined - x86-64 returns garbage there, and 0 for +inf, where this call returns 255.  The two agree on every finite
+ * input below 2^40 (tests/test_display_api.py).  -inf and NaN encode to 0.
+ *
+ * displayFrame: `in` = nx*ny rt_vec3, row 0 = bottom, any host memory; NULL = the framebuffer the renderer currently delivers into.  With
+ * RT_DISPLAY_FROM_PREVIEW `in` must be NULL and the source is the output of the last previewFrame, still on the device: nothing is uploaded.  `out_rgba` =
+ * nx*ny*4 bytes of caller-owned host memory, never NULL.  Blocking.  Like the preview passes it works on the WHOLE image on the first in-process device,
+ * whatever the partition is.  It changes nothing an existing call observes: the framebuffer, getRenderStats, rtLastLaunches, the progressive frame, the
+ * histories of accumulateFrame and previewFrame and every other rtLast*Ms stay as they were.  Its state is E' and the last histogram: reset - the next
+ * RT_DISPLAY_AUTO_EXPOSURE call adapts from nothing, the histogram is zero - by every init*, cleanupRenderer, every setRenderOptions and rtResetDisplay; a call
+ * without RT_DISPLAY_AUTO_EXPOSURE neither reads nor changes it.  E' lives on the device.  The device buffers (16 bytes per pixel and RT_DISPLAY_BINS + 2 words)
+ * are allocated by the first call and freed where the other passes' are.  Defaults: flags 0, RT_TONEMAP_NONE, exposure 1, adapt 1.
+ * Misuse (rt error, exit 99): before init (the four helpers below as well), out_rgba NULL, unknown flag bits, an unknown tonemap, exposure not finite or <= 0,
+ * adapt not finite or outside (0, 1], RT_DISPLAY_FROM_PREVIEW with `in` non-NULL or without a previewFrame since init / the last reset of its history. */
+enum { RT_DISPLAY_TOP_DOWN = 1, RT_DISPLAY_DITHER = 2, RT_DISPLAY_AUTO_EXPOSURE = 4, RT_DISPLAY_FROM_PREVIEW = 8 };
+enum { RT_TONEMAP_NONE = 0, RT_TONEMAP_REINHARD = 1, RT_TONEMAP_ACES = 2 };
+#define RT_DISPLAY_BINS 256
+#define RT_DISPLAY_KEY  0.18f
+/* the 8 x 8 ordered-dither (Bayer) matrix, 0 .. 63, rows B[0] .. B[7]: the initialiser of an array [8][8] */
+#define RT_DISPLAY_BAYER8 { {  0, 32,  8, 40,  2, 34, 10, 42 }, { 48, 16, 56, 24, 50, 18, 58, 26 }, { 12, 44,  4, 36, 14, 46,  6, 38 }, \
+                            { 60, 28, 52, 20, 62, 30, 54, 22 }, {  3, 35, 11, 43,  1, 33,  9, 41 }, { 51, 19, 59, 27, 49, 17, 57, 25 }, \
+                            { 15, 47,  7, 39, 13, 45,  5, 37 }, { 63, 31, 55, 23, 61, 29, 53, 21 } }
+void   displayFrame(const rt_vec3* in, uint8_t* out_rgba, int flags, int tonemap, float exposure, float adapt);
+float  rtLastExposure(void);                       /* E_used of the last displayFrame; 1 before the first */
+int    rtDisplayHistogram(uint32_t* out, int cap); /* the bins of the last RT_DISPLAY_AUTO_EXPOSURE call (zero after a reset): min(cap, RT_DISPLAY_BINS) words; returns RT_DISPLAY_BINS */
+void   rtResetDisplay(void);                       /* the next RT_DISPLAY_AUTO_EXPOSURE call adapts from nothing */
+double rtLastDisplayMs(void);                      /* HIP-event time of its kernels (not the copies); 0 before the first call */
+
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };

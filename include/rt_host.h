@@ -77,6 +77,14 @@ int rtLoadReference(const char* path, rt_vec3* reference, int nx, int ny);
 /* sqrt( sum_i sum_c (f-g)^2 / 3 / (nx*ny) ), accumulated in double. */
 double rtRmse(const rt_vec3* f, const rt_vec3* g, int nx, int ny);
 
+/* displayFrame's definition (rt_api.h: exposure, tone map, sRGB, dither, RGBA bytes; the RT_DISPLAY_* flags without RT_DISPLAY_FROM_PREVIEW, RT_TONEMAP_*) on
+ * the CPU with libm's powf: the same bytes as the device call, for a host without a GPU.  in: nx*ny vec3, row 0 = bottom; out_rgba: nx*ny*4 bytes.  With
+ * RT_DISPLAY_AUTO_EXPOSURE the state is the caller's: *E_state is E' on entry, a NaN meaning "adapt from nothing", and E on return (E_state NULL: adapt from
+ * nothing, nothing kept); hist, unless NULL, receives the RT_DISPLAY_BINS bins.  Without the flag neither is touched.  Returns 0, or -1 for arguments
+ * displayFrame would refuse (nothing is written then). */
+int rtDisplayFrameHost(const rt_vec3* in, uint8_t* out_rgba, int nx, int ny, int flags, int tonemap, float exposure, float adapt, float* E_state,
+                       uint32_t* hist);
+
 #ifdef __cplusplus
 }
 #endif
