@@ -1174,7 +1174,7 @@ hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, const RtSwitches& 
     // RT_MESH_TWO=0: the single scattered dispatch (A/B); RT_MESH_SPLIT=<n>: samples of the first dispatch.
     const int split = sw.mesh_split;
     // (a continuation pass of a progressive frame, p.acc_first > 0, takes the single dispatch: PHASE 0 resumes every pixel from p.acc_state)
-    if (sw.mesh_two && !classic && !p.dbg && !p.counters && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.px_state && p.px_rays && p.order && p.ord_state && p.ord_rays &&
+    if (sw.mesh_two && !classic && !p.dbg && !p.counters && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.px_state && p.px_rays && (p.ord_rec || (p.order && p.ord_state && p.ord_rays)) &&
         p.acc_first == 0 && p.ns >= 4 * split && p.nx <= 65535 && p.part.local_rows <= 65535) {
         RtMeshParams q = p;
         q.s_split = split;

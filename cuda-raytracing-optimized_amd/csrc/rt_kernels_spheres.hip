@@ -1289,12 +1289,15 @@ constexpr int kCostClasses = 18;
 constexpr int kChainClasses = 4;      // lists 0..3: >= 12 rays per sample, the chains -> chain waves (see k_render_spheres_queue); list 0 (>= P.chain_top_thr / 16
                                       // rays per sample: ~100 of the 960 k pixels of the benchmark frame, among them the 45 that need > 3000 rays) has waves
                                       // that hold ONE pixel (kernel parameter `caps`) and trace it in the single-ray form (scan_single)
+constexpr int kExactCostSamples = 8;  // a cost map of at least this many samples per pixel (what a frame needs to take the two dispatches at all) rates a pixel by its own total
 constexpr int kHeavyClasses = 3;      // lists 4..6: 6..12 rays per sample -> spread over the first fill of the normal waves
 
 // A progressive pass orders its pixels by the rays of ALL their samples so far (s_split = samples accumulated): at most 255 rays per sample (max_depth),
 // so the window sum x 16 below stays within 32 bits up to the largest total runRendererProgressive accepts.
 static_assert(9ull * 16ull * 255ull * RT_PROGRESSIVE_MAX_SAMPLES <= 0xFFFFFFFFull, "cost_class: window sum of a progressive total overflows 32 bits");
-__device__ __forceinline__ int cost_class(const RtSphereParams& P, int i, int lr) {
+// `rays` over `samples` samples each: the first dispatch's px_rays over s_split, or - a frame ordered by the last frame's cost map - cost_rays over cost_samples
+// (a map is recorded for at most RT_PROGRESSIVE_MAX_SAMPLES samples per pixel: the same bound).
+__device__ __forceinline__ int cost_class(const RtSphereParams& P, const uint32_t* __restrict__ rays, uint32_t samples, bool exact, int i, int lr) {
     uint32_t sum = 0, cnt = 0;
     for (int dy = -1; dy <= 1; dy++) {
         const int y = lr + dy;
@@ -1302,14 +1305,17 @@ __device__ __forceinline__ int cost_class(const RtSphereParams& P, int i, int lr
         for (int dx = -1; dx <= 1; dx++) {
             const int x = i + dx;
             if (x < 0 || x >= P.nx) continue;
-            sum += P.px_rays[(size_t)y * P.nx + x];
+            sum += rays[(size_t)y * P.nx + x];
             cnt++;
         }
     }
     // e = 16 x (rays per sample); >= 16 always (every sample starts with one ray)
     // the window mean under-rates an isolated long pixel (its neighbours miss the glass): never below 3/4 of the pixel's own rate
-    const uint32_t own = (P.px_rays[(size_t)lr * P.nx + i] * 12u) / (uint32_t)P.s_split;
-    const uint32_t e = max((sum * 16u) / (cnt * (uint32_t)P.s_split), own);
+    // (3/4 of a rate measured on a few samples; a whole frame's total - `exact`, from kExactCostSamples samples - is little noise and counts in full: at 3/4 a
+    // pixel of 24..32 rays per sample misses chain list 0 and shares its wave.  With the 3/4 C2 gained 1.4 % and C3 lost 1.9 %, in full +6.4 % / +2.9 %; the
+    // window stays: the own rate alone gave +5.0 % / +0.6 %.  DESIGN.md 3.15)
+    const uint32_t own = (rays[(size_t)lr * P.nx + i] * (exact ? 16u : 12u)) / samples;
+    const uint32_t e = max((sum * 16u) / (cnt * samples), own);
     const uint32_t lim[kCostClasses - 1] = { (uint32_t)P.chain_top_thr, 320u, 240u, 192u, 160u, 128u, 96u, 72u, 56u, 44u, 36u, 30u, 26u, 22u, 19u, 18u, 17u };
     int cls = kCostClasses - 1;
 #pragma unroll
@@ -1346,6 +1352,11 @@ __global__ void __launch_bounds__(kThreads) k_order_by_cost(const RtSphereParams
     const uint32_t total = (uint32_t)tiles_x * (uint32_t)tiles_y * 64u;
     const uint32_t per = ((total + gridDim.x - 1u) / gridDim.x + (uint32_t)kThreads - 1u) / (uint32_t)kThreads * (uint32_t)kThreads;
     const uint32_t first = blockIdx.x * per, last = min(first + per, total);
+    // P.s_split == 0: no first dispatch has run - the cost is the last frame's map, and the records written below are fresh pixels (PHASE 2 starts them at sample 0)
+    const bool fresh = P.s_split == 0;
+    const bool exact = fresh && P.cost_samples >= kExactCostSamples;
+    const uint32_t* const rays = fresh ? P.cost_rays : P.px_rays;
+    const uint32_t samples = (uint32_t)(fresh ? P.cost_samples : P.s_split);
     uint32_t packed = 0;                                             // (local row << 16) | column of the pixel class_of() looked at
     auto class_of = [&](uint32_t p) {                                // list index x * kCostClasses + class, or -1
         const uint32_t tile = p >> 6, within = p & 63u;
@@ -1355,7 +1366,7 @@ __global__ void __launch_bounds__(kThreads) k_order_by_cost(const RtSphereParams
         packed = ((uint32_t)lr << 16) | (uint32_t)i;
         if (!(p < last && i < P.nx && lr < P.part.local_rows)) return -1;
         const int x = xq > 1 ? (int)rt_xcd_of_pixel((uint32_t)lr, (uint32_t)P.nx, (uint32_t)i) : 0;
-        return x * kCostClasses + cost_class(P, i, lr);
+        return x * kCostClasses + cost_class(P, rays, samples, exact, i, lr);
     };
     if (threadIdx.x < kLists) s_cnt[threadIdx.x] = 0u;
     __syncthreads();
@@ -1394,13 +1405,17 @@ __global__ void __launch_bounds__(kThreads) k_order_by_cost(const RtSphereParams
             const uint32_t rank = s_base[cls] + atomicAdd(&s_cnt[cls], 1u);
             const uint32_t at = s_start[cls] + (uint32_t)(((unsigned long long)rank * s_stride[cls]) % s_n[cls]);
             const size_t px = (size_t)(packed >> 16) * P.nx + (packed & 0xFFFFu);
+            // the pixel as the first dispatch parked it, or as init_pixel starts it: no colour, the seed of its global id, no rays
+            const float4 state = fresh ? make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(pixel_seed((uint32_t)(global_row(P.part, (int)(packed >> 16)) * P.nx + (int)(packed & 0xFFFFu)))))
+                                       : P.px_state[px];
+            const uint32_t parked_rays = fresh ? 0u : P.px_rays[px];
             if (P.ord_rec) {                                         // one 32-byte record per queue position (RtSphereParams::ord_rec)
-                P.ord_rec[2 * (size_t)at] = P.px_state[px];
-                P.ord_rec[2 * (size_t)at + 1] = make_float4(__uint_as_float(packed), __uint_as_float(P.px_rays[px]), 0.0f, 0.0f);
+                P.ord_rec[2 * (size_t)at] = state;
+                P.ord_rec[2 * (size_t)at + 1] = make_float4(__uint_as_float(packed), __uint_as_float(parked_rays), 0.0f, 0.0f);
             } else {
                 P.order[at] = packed;
-                P.ord_state[at] = P.px_state[px];                    // the parked state travels with the list entry (see RtSphereParams::ord_state)
-                P.ord_rays[at] = P.px_rays[px];
+                P.ord_state[at] = state;                             // the parked state travels with the list entry (see RtSphereParams::ord_state)
+                P.ord_rays[at] = parked_rays;
             }
         }
     }
@@ -1602,11 +1617,15 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                     // one 12-byte store (global_store_dwordx3): a lane finishes its pixel on its own, so three dword
                     // stores would be three partial-sector writes
                     *reinterpret_cast<float3*>(fbf + ((size_t)(P.fb_global_rows ? L.j : lr) * P.nx + L.i) * 3) = make_float3(out.x, out.y, out.z);
-                    float4* const acc = rt_cold_arg<float4*>(offsetof(RtSphereParams, acc_state));
-                    if (acc) {                                       // a progressive pass: the stream position and running sum for the next pass
+                    // the pixel's rays go to acc_rays: the cost map the next frame is ordered by (runRenderer), or a progressive pass's accumulated rays - and
+                    // with them the stream position and running sum for the next pass.  (One cold pointer and one branch on a frame that does neither,
+                    // as before the map: a second pointer of its own cost the lean kinds 3-4 VGPRs and the measured frame 0.4-1 %.)
+                    uint32_t* const rays_out = rt_cold_arg<uint32_t*>(offsetof(RtSphereParams, acc_rays));
+                    if (rays_out) {
                         const size_t px = (size_t)lr * P.nx + L.i;
-                        acc[px] = make_float4(L.col.x, L.col.y, L.col.z, __uint_as_float(L.rng));
-                        rt_cold_arg<uint32_t*>(offsetof(RtSphereParams, acc_rays))[px] = pix_rays;
+                        rays_out[px] = pix_rays;
+                        float4* const acc = rt_cold_arg<float4*>(offsetof(RtSphereParams, acc_state));
+                        if (acc) acc[px] = make_float4(L.col.x, L.col.y, L.col.z, __uint_as_float(L.rng));
                     }
                 } else {                                             // partial sum of this chunk; k_sum_chunks adds them in order
                     float* dst = reinterpret_cast<float*>(P.partial) + (((size_t)lr * P.nx + L.i) * (uint32_t)P.chunks + (uint32_t)chunk) * 3;
@@ -1951,6 +1970,7 @@ enum class SphereFrame {
     GlobalSingle,       // the scene in global memory: one scattered dispatch
     TwoDispatch,        // first samples of every pixel, k_order_by_cost, then the rest longest first
     TwoDispatchResume,  // a continuation pass of a progressive frame: the ordering pass and the second dispatch alone
+    OrderedSingle,      // a frame ordered by the last frame's cost map: the ordering pass and ONE dispatch of whole pixels, longest first - no measuring dispatch
     ClassifiedSingle,   // k_classify_spheres, then one dispatch in its order
     PlainSingle,        // one dispatch, scattered or tile-major
 };
@@ -2078,8 +2098,13 @@ static SpherePlan plan_spheres(const RtSphereParams& p, int variant, const RtSwi
     // order_mode 0 (default), reference stream, enough samples: two phases - measure the cost of every pixel on its first
     // samples, then resume all pixels longest-first (see k_order_by_cost).  Otherwise: one launch, optionally ordered
     // by the centre-ray pre-pass (k_classify_spheres: order_mode 3) or plainly scattered (2) / tile-major (1).
+    // A frame that would measure (TwoDispatch) and is handed a valid cost map (p.cost_samples > 0: the renderer's word) is ordered by the map instead: what the first
+    // dispatch learns from two samples of every pixel, the last frame's ray totals say better, and the longest pixels start at t = 0 (OrderedSingle).  Not
+    // with the time stamps on: the time-line tools keep seeing the two dispatches.
+    // Nor by a map of fewer samples than the first dispatch would measure: a 1200x800x100 frame ordered by a 1-spp frame's map took 14.5 ms against 11.0 measured.
+    const bool reuse = !resume && p.cost_rays != nullptr && p.cost_samples >= kFirstSamples && p.wave_dbg == nullptr;
     if (pl.scene == 1) pl.frame = SphereFrame::GlobalSingle;
-    else if (two_dispatch(order_mode, p.ns >= 8 || resume)) pl.frame = resume ? SphereFrame::TwoDispatchResume : SphereFrame::TwoDispatch;
+    else if (two_dispatch(order_mode, p.ns >= 8 || resume)) pl.frame = resume ? SphereFrame::TwoDispatchResume : (reuse ? SphereFrame::OrderedSingle : SphereFrame::TwoDispatch);
     else if ((order_mode == 0 || order_mode == 3) && p.order != nullptr) pl.frame = SphereFrame::ClassifiedSingle;
     else pl.frame = SphereFrame::PlainSingle;
     pl.sum_chunks = pl.chunked;
@@ -2197,11 +2222,14 @@ hipError_t RT_LAUNCH_NAME(const RtSphereParams& p, int variant, const RtSwitches
         fprintf(stderr, "rt error: RT_TUNE=%s out of range (chain_every 1..255, chain_waves 0..%d, heavy_thr 1..255, n_chain 0..15, boost 0..255, "
                         "chain_pixels 1..15, chain_pixels of list 0 / 1 / 2 1..15)\n", sw.tune->text.c_str(), kWavesPerWg);
     if (pl.error != SpherePlanError::None) return hipErrorInvalidValue;
-    if (pl.frame == SphereFrame::TwoDispatch || pl.frame == SphereFrame::TwoDispatchResume) {
+    if (pl.frame == SphereFrame::TwoDispatch || pl.frame == SphereFrame::TwoDispatchResume || pl.frame == SphereFrame::OrderedSingle) {
         RtSphereParams q = p;
         if (pl.frame == SphereFrame::TwoDispatchResume) {
             q.px_state = p.acc_state; q.px_rays = p.acc_rays; q.s_split = p.acc_first;
             e = wait_fb();
+        } else if (pl.frame == SphereFrame::OrderedSingle) {
+            q.s_split = 0;              // the ordering pass reads the cost map and writes fresh pixels; PHASE 2 runs samples [0, ns)
+            e = wait_fb();              // (no first dispatch to poison a direct host framebuffer)
         } else {
             q.phase = 1; q.s_split = kFirstSamples;
             e = launch_queue_form<1, 0, false>(pl, q, stream, pl.stride1, pl.cfg1);

@@ -121,6 +121,12 @@ struct RtSphereParams {
     float4* acc_state;
     uint32_t* acc_rays;
     int32_t acc_first;
+    // The cost map (runRenderer, reference stream in whole pixels; nullptr = none): local_rows * nx ray totals of the last frame that recorded them.  A frame
+    // records through acc_rays (with acc_state null and acc_first 0: the PHASE 0 and PHASE 2 kernels store a finished pixel's rays there, and nothing else);
+    // a frame handed a valid map - cost_samples > 0: the samples per pixel of the frame that recorded it - is ordered by cost_rays and runs as ONE
+    // cost-ordered dispatch, without the measuring first dispatch (plan_spheres: OrderedSingle).  Only a hint: the result does not depend on the work order.
+    uint32_t* cost_rays;
+    int32_t cost_samples;
 };
 constexpr int kXcdQueueWords = 64;      // words per queue block: [0] general counter [1] chain counter [2] middle-tier counter [3] first position of this XCD's lists in
                                         // `order` [4 .. 4 + 18) list lengths [22 .. 22 + 18) fill cursors
@@ -202,7 +208,8 @@ __device__ __forceinline__ T rt_cold_arg(size_t offset) {
 size_t rt_sphere_kernel_lds_bytes(int n_padded, int n);
 // The ordering pass of the two-dispatch frames (rt_kernels_spheres.hip, k_order_by_cost; also used by the mesh launcher): reads px_rays / px_state / s_split /
 // chain_top_thr / nx / part.local_rows of `q`, writes order / ord_state / ord_rays (all valid pixels, descending cost class, scattered inside a class) and the
-// list lengths into q.queue[4..]; q.queue must have been zeroed on `stream` before.
+// list lengths into q.queue[4..]; q.queue must have been zeroed on `stream` before.  q.s_split == 0: the cost is the last frame's map (q.cost_rays over
+// q.cost_samples samples) and every record written is a fresh pixel - no colour, the pixel's seed, no rays - for a PHASE 2 that starts at sample 0.
 hipError_t rt_order_pixels_by_cost(const RtSphereParams& q, hipStream_t stream);
 
 // RT_TUNE as given: its text (for the error message) and its first n comma-separated fields; the sphere launcher puts them over its defaults and validates.
@@ -229,6 +236,8 @@ struct RtSwitches {
     bool compact_leaves = true;         // RT_COMPACT_LEAVES=0: the mesh leaf tests read the caller's triangles
     bool ext_fb_no_register = false;    // RT_EXT_FB_NO_REGISTER=1: setExternalFramebuffer takes its cannot-page-lock fallback
     bool cleanup_device_reset = false;  // RT_CLEANUP_DEVICE_RESET=1: cleanupRenderer ends with hipDeviceReset
+    int cost_reuse = 1;                 // RT_COST_REUSE: sphere frames 0 = neither record nor reuse the per-pixel cost map (every frame measures), 1 = reuse it until
+                                        // setCamera changes the camera, 2 = across setCamera too (A/B: tools/bench_orbit.py)
     // the sphere launcher
     int top_thr = 384;                  // RT_TOP_THR: 16 x rays per sample from which a pixel goes to chain list 0 (24; below 320: the default)
     bool basic = true;                  // RT_BASIC=0 / RT_ONEPASS=0: keep the general shading code / pass loop where the lean kinds would do

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -114,11 +115,18 @@ struct DeviceState {
     uint32_t* d_order = nullptr;
     rt_vec3* d_partial = nullptr;
     size_t partial_bytes = 0;
+    // The parked state of the two-dispatch frames: allocated by the first frame that can take them, in the form its switches select (parked_buffers)
     float4* d_px_state = nullptr;       // two-phase rendering: per-pixel (col, rng) and rays after the first samples
     uint32_t* d_px_rays = nullptr;
     float4* d_ord_state = nullptr;      // ... and their copies in queue order (RtSphereParams::ord_state / ord_rays)
     uint32_t* d_ord_rays = nullptr;
     float4* d_ord_rec = nullptr;        // ... or as one 32-byte record per queue position (RtSphereParams::ord_rec)
+    // The cost map of sphere frames (RtSphereParams::cost_rays): the rays of every local pixel in the last runRenderer frame that recorded them, allocated
+    // by the first such frame.  cost_samples: that frame's samples per pixel, 0 = nothing recorded yet; cost_key: what the map depends on beside the
+    // device state itself (a new init or another partition builds new device states) - see cost_key_of.
+    uint32_t* d_cost_rays = nullptr;
+    int cost_samples = 0;
+    std::array<int, 10> cost_key = {};
     float4* d_acc_state = nullptr;      // progressive frame (runRendererProgressive): per local pixel (col, rng) after the samples so far, and (sphere scenes)
     uint32_t* d_acc_rays = nullptr;     // the rays they took; allocated by the first pass on this device
     void* d_guide[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };     // first-hit guide planes (renderGuides), plane k = bit k of the mask: allocated by the
@@ -160,6 +168,7 @@ struct RenderContext {
     std::vector<DeviceState> devs;
     rt_render_stats stats;
     int prog_samples = 0;               // samples per pixel of the progressive frame so far (rtProgressiveSamples)
+    int camera_moves = 0;               // setCamera calls that changed the camera: part of a cost map's key (cost_key_of)
     double guides_ms = 0.0;             // rtLastGuidesMs
     double denoise_ms = 0.0;            // rtLastDenoiseMs
     double accumulate_ms = 0.0;         // rtLastAccumulateMs
@@ -341,11 +350,6 @@ void setup_devices() {
             const size_t padded = (size_t)((c.nx + 7) / 8) * ((d.fb_rows + 7) / 8) * 64;
             d.d_fb = dev_alloc<rt_vec3>(d.owned, pixels);
             d.d_order = dev_alloc<uint32_t>(d.owned, 3 * padded);       // work-order lists of the persistent kernels: 3 x (pixels padded to 8x8 tiles)
-            d.d_px_state = dev_alloc<float4>(d.owned, pixels);          // the two-dispatch frames of both kernels: parked state + its copy in queue order
-            d.d_px_rays = dev_alloc<uint32_t>(d.owned, pixels);
-            d.d_ord_state = dev_alloc<float4>(d.owned, padded);
-            d.d_ord_rays = dev_alloc<uint32_t>(d.owned, padded);
-            d.d_ord_rec = dev_alloc<float4>(d.owned, padded * 2);
         }
         d.d_counters = dev_alloc<RtCounters>(d.owned, 1);
         HIP_CHECK(hipMemset(d.d_counters, 0, sizeof(RtCounters)));
@@ -931,6 +935,37 @@ double end_pass(const PassState& n, int current, rt_vec3* out, float* history = 
     return (double)ms;
 }
 
+// The parked state of a two-dispatch frame (both kernels), on the first frame that can take the two dispatches and in the one form that frame's switches
+// select: 32-byte records (RT_ORD_PACKED, the default) or the three arrays.  A frame under the other form frees what it does not read: a 3840x2160 frame
+// holds 20 + 32 bytes per pixel here instead of 20 + 20 + 32 from init on, and a device that never takes the two dispatches (counter stream, few samples,
+// a scene in global memory) none of them.
+void parked_buffers(DeviceState& d, bool packed) {
+    const size_t nx = (size_t)g_ctx.nx;
+    const size_t pixels = d.fb_rows * nx;
+    const size_t padded = ((nx + 7) / 8) * ((d.fb_rows + 7) / 8) * 64;
+    if (!d.d_px_state) d.d_px_state = dev_alloc<float4>(d.owned, pixels);
+    if (!d.d_px_rays) d.d_px_rays = dev_alloc<uint32_t>(d.owned, pixels);
+    if (packed) {
+        dev_release(d.owned, d.d_ord_state);
+        dev_release(d.owned, d.d_ord_rays);
+        if (!d.d_ord_rec) d.d_ord_rec = dev_alloc<float4>(d.owned, padded * 2);
+    } else {
+        dev_release(d.owned, d.d_ord_rec);
+        if (!d.d_ord_state) d.d_ord_state = dev_alloc<float4>(d.owned, padded);
+        if (!d.d_ord_rays) d.d_ord_rays = dev_alloc<uint32_t>(d.owned, padded);
+    }
+}
+
+// What a cost map depends on beside its device state: the image, the partition, what decides how many rays a pixel takes, and the camera.  Compared by
+// value (setRenderOptions with equal fields, setCamera with the same camera change nothing); counters, variant, fp and the traffic switches are not in
+// it: the ordering pass runs every frame under that frame's switches.  The camera is, because a moved camera's frame is slower ordered by the old map
+// than measured - a 2-degree step of an orbit moves the long pixels by tens of pixels: 1200x800x16 spp 3.06 ms against 2.68 (DESIGN.md 3.15,
+// tools/bench_orbit.py); RT_COST_REUSE=2 keeps the map across setCamera (that measurement, and the tests of a map that is wrong).
+std::array<int, 10> cost_key_of(const RtPartition& part, bool with_camera) {
+    const RenderContext& c = g_ctx;
+    return { c.nx, c.ny, part.stripe_rows, part.rank, part.world, part.local_rows, c.max_depth, (int)c.opt.rr, (int)c.opt.rng, with_camera ? c.camera_moves : 0 };
+}
+
 // One frame of ns samples per pixel (runRenderer), or one pass of a progressive frame (progressive): samples [first, ns) of every pixel, continued from
 // and parked into the device's accumulation buffers, the framebuffer = sum / ns.
 void render_frame(int ns, int first, bool progressive) {
@@ -992,8 +1027,25 @@ void render_frame(int ns, int first, bool progressive) {
             // work items: one per pixel in the reference-stream mode (a pixel's samples are one sequential RNG stream);
             // with the per-sample counter stream the samples are independent and a pixel is split into chunks
             p.spw = spw; p.chunks = chunks; p.partial = nullptr;
+            // the two cost-ordered dispatches need the reference stream in whole pixels, the scene in the LDS and 8 samples (plan_spheres): their buffers from then on
+            const bool whole_pixels = c.opt.rng == RT_RNG_REFERENCE_STREAM && chunks == 1 && vk == 0 && (vcb == 0 || vcb == 255) && !p.global_scene;
+            if (whole_pixels && (ns >= 8 || progressive)) parked_buffers(d, sw.ord_packed);
             p.phase = 0; p.s_split = 0; p.px_state = d.d_px_state; p.px_rays = d.d_px_rays; p.ord_state = d.d_ord_state; p.ord_rays = d.d_ord_rays;
             if (progressive) { p.acc_state = d.d_acc_state; p.acc_rays = d.d_acc_rays; p.acc_first = first; }
+            // The cost map: every such runRenderer frame records the rays of its pixels, and the next one is ordered by them if nothing the map depends on has
+            // changed (RtSphereParams::cost_rays).  A progressive pass has its own accumulated rays: it neither reads nor writes the map.  RT_COST_REUSE=0: no map.
+            if (whole_pixels && !progressive && sw.cost_reuse != 0 && ns <= RT_PROGRESSIVE_MAX_SAMPLES) {
+                if (!d.d_cost_rays) {
+                    d.d_cost_rays = dev_alloc<uint32_t>(d.owned, d.fb_rows * c.nx);
+                    d.cost_samples = 0;
+                }
+                const std::array<int, 10> key = cost_key_of(part, sw.cost_reuse != 2);
+                p.cost_rays = d.d_cost_rays;
+                p.acc_rays = d.d_cost_rays;                         // (this frame's rays: the same buffer, written behind the ordering pass that reads it)
+                p.cost_samples = key == d.cost_key ? d.cost_samples : 0;
+                d.cost_key = key;
+                d.cost_samples = ns;
+            }
             p.chain_top_thr = sw.top_thr;
             // traffic forms of the two-dispatch frame (RtSphereParams::ord_rec / xcd_queues / p1_tile_major)
             p.ord_rec = sw.ord_packed ? d.d_ord_rec : nullptr;
@@ -1037,6 +1089,7 @@ void render_frame(int ns, int first, bool progressive) {
             if (c.opt.floor && (c.opt.variant & 0xFF) == 1) rt_fail("runRenderer: the floor plane is not built into the tile-per-wave A/B kernel (variant 1)");
             p.counters = c.opt.counters ? d.d_counters : nullptr;
             p.queue = d.d_queue;
+            if (c.opt.rng == RT_RNG_REFERENCE_STREAM && sw.mesh_two && !c.opt.counters && first == 0) parked_buffers(d, sw.ord_packed);      // (rt_launch_mesh_*: its two dispatches)
             p.s_split = 0; p.px_state = d.d_px_state; p.px_rays = d.d_px_rays; p.order = d.d_order; p.ord_state = d.d_ord_state; p.ord_rays = d.d_ord_rays;
             if (progressive) { p.acc_state = d.d_acc_state; p.acc_first = first; }
             // the traffic forms of the two-dispatch frame, as for sphere scenes (the same switches; the mesh frame always renders into the device framebuffer)
@@ -1135,6 +1188,8 @@ RtSwitches rt_read_switches() {
     s.compact_leaves = env_flag("RT_COMPACT_LEAVES", s.compact_leaves);
     s.ext_fb_no_register = env_one("RT_EXT_FB_NO_REGISTER");
     s.cleanup_device_reset = env_one("RT_CLEANUP_DEVICE_RESET");
+    const int cost_reuse = env_int("RT_COST_REUSE", s.cost_reuse);
+    s.cost_reuse = (cost_reuse >= 0 && cost_reuse <= 2) ? cost_reuse : 1;
 
     const int top_thr = env_int("RT_TOP_THR", s.top_thr);
     if (top_thr >= 320) s.top_thr = top_thr;
@@ -1209,6 +1264,7 @@ void setCamera(const rt_camera* cam) {
     RenderContext& c = g_ctx;
     if (!c.initialised) rt_fail("setCamera before init");
     if (!cam) rt_fail("setCamera: null");
+    if (memcmp(&c.cam, cam, sizeof(rt_camera)) != 0) c.camera_moves++;      // (the cost maps of sphere frames: cost_key_of)
     c.cam = *cam;                                           // read by every frame's parameter block; nothing of the scene depends on it
     c.prog_samples = 0;
 }

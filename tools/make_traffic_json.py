@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """tools/make_traffic_json.py <tag> — condenses gpurun_out/prof_<tag>_{C2,C4}/ (tools/measure_traffic.sh) into
 gpurun_out/<tag>_{C2,C4}_summary.txt and gpurun_out/traffic.json; copy both to profiles/ to have them judged.
-Per-frame figures = the dispatches of the LAST full frame of each pass (the render kernel runs twice per frame: the
-first samples, then the cost-ordered rest)."""
+Per-frame figures = the dispatches of the LAST full frame of each pass (the mesh render kernel runs twice per frame: the
+first samples, then the cost-ordered rest; a sphere frame behind another is one dispatch, ordered by the last frame's cost map)."""
 import csv, glob, json, os, sys
 from collections import defaultdict
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +13,10 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
 out = {"kernel_source_hash": bench.kernel_source_hash(), "tag": tag}
 
 
+def ends_sphere_frame(kernel_name):
+    return "k_render_spheres_queue<0," in kernel_name or "k_render_spheres_queue<2," in kernel_name
+
+
 def rows(d, pattern):
     for f in glob.glob(os.path.join(d, "**", pattern), recursive=True):
         with open(f, newline="") as fh:
@@ -20,7 +24,7 @@ def rows(d, pattern):
                 yield r
 
 
-for W, per_frame in (("C2", 2), ("C4", 2), ("C3", 2), ("C5", 2)):      # (C4: two dispatches per frame since round 4)
+for W, per_frame in (("C2", 1), ("C4", 2), ("C3", 1), ("C5", 1)):      # (C4: two dispatches per frame since round 4; the sphere frames behind the first: one, ordered by the cost map)
     d = os.path.join(ROOT, "gpurun_out", f"prof_{tag}_{W}")
     if not os.path.isdir(d):
         continue
@@ -31,17 +35,32 @@ for W, per_frame in (("C2", 2), ("C4", 2), ("C3", 2), ("C5", 2)):      # (C4: tw
         lines.append(str({k: r[k] for k in r if k in ("Name", "Calls", "TotalDurationNs", "AverageNs", "Percentage", "MinNs", "MaxNs")}))
     tr = sorted((r for r in rows(d, "*kernel_trace.csv") if "k_render" in r.get("Kernel_Name", "")), key=lambda r: int(r["Start_Timestamp"]))
     dur = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in tr]
-    frames = [sum(dur[i:i + per_frame]) for i in range(per_frame, len(dur) - per_frame + 1, per_frame)]     # skip the warm-up frame
+    if W == "C4":
+        frames = [sum(dur[i:i + per_frame]) for i in range(per_frame, len(dur) - per_frame + 1, per_frame)]     # skip the warm-up frame
+    else:       # a sphere frame ends with its PHASE 0 or PHASE 2 dispatch; a measured one (the first behind the 1-spp warm-up) has a PHASE 1 dispatch in front
+        frames, cur = [], 0.0
+        for r, t in zip(tr, dur):
+            cur += t
+            if ends_sphere_frame(r["Kernel_Name"]):
+                frames.append(cur)
+                cur = 0.0
+        frames = frames[1:]
     if frames:
-        lines.append("render-kernel time per full frame (ms, %d dispatch(es) per frame): %s  avg %.3f" % (per_frame, [round(x, 3) for x in frames], sum(frames) / len(frames)))
+        lines.append("render-kernel time per full frame (ms): %s  avg %.3f" % ([round(x, 3) for x in frames], sum(frames) / len(frames)))
         lines.append("code object: %s" % {k: tr[-1].get(k) for k in ("VGPR_Count", "Accum_VGPR_Count", "SGPR_Count", "LDS_Block_Size", "Scratch_Size")} +
                      "  (rocprofv3's view; tools/kernel_resources.sh prints the code object's own metadata)")
     acc = defaultdict(list)
+    names = {}
+    last_n = per_frame                  # render dispatches of the last frame: a sphere frame behind the warm-up alone (C3 / C5 passes) is a measured one, PHASE 1 + PHASE 2
     for r in sorted(rows(d, "*counter_collection.csv"), key=lambda r: int(r.get("Dispatch_Id", 0))):
         if "k_render" in r.get("Kernel_Name", ""):
             acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
-    vals = {k: sum(v[-per_frame:]) for k, v in acc.items()}                      # the last full frame
-    lines.append("== PMC counters of the LAST full frame (its %d dispatch(es) added) ==" % per_frame)
+            names.setdefault(r["Counter_Name"], []).append(r["Kernel_Name"])
+    if W != "C4" and names:
+        seq = max(names.values(), key=len)
+        last_n = 2 if len(seq) >= 2 and "k_render_spheres_queue<1," in seq[-2] else 1
+    vals = {k: sum(v[-last_n:]) for k, v in acc.items()}                         # the last full frame
+    lines.append("== PMC counters of the LAST full frame (its %d dispatch(es) added) ==" % last_n)
     for k in sorted(vals):
         lines.append("%-28s %.6g" % (k, vals[k]))
     g = vals.get
