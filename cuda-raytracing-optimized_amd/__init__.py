@@ -135,14 +135,15 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "rtDefaultDenoiseFlags", "denoiseFrame", "rtLastDenoiseMs",
                     "accumulateFrame", "rtResetHistory", "rtHistoryFrames", "rtLastAccumulateMs",
                     "previewFrame", "rtResetPreview", "rtPreviewFrames", "rtLastPreviewMs",
-                    "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs"]
+                    "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs",
+                    "traceRays", "occludedRays", "rtLastRaysMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
 HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtSceneRandomSpheres", "rtStaircaseCamera",
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
-                "rtDisplayFrameHost"]
+                "rtDisplayFrameHost", "rtCentreRays"]
 
 _renderer = None
 _host = None
@@ -193,6 +194,8 @@ def load_host():
         h.rtDisplayFrameHost.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32)]
         h.rtDisplayFrameHost.restype = C.c_int
+        h.rtCentreRays.argtypes = [C.POINTER(camera), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, fp, fp]
+        h.rtCentreRays.restype = None
         _host = h
     return _host
 
@@ -298,6 +301,13 @@ def load_renderer():
         r.rtResetDisplay.restype = None
         r.rtLastDisplayMs.argtypes = []
         r.rtLastDisplayMs.restype = C.c_double
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        r.traceRays.argtypes = [C.c_int, fp, fp, fp, fp, C.c_int, fp, ip, fp, fp, ip]
+        r.traceRays.restype = None
+        r.occludedRays.argtypes = [C.c_int, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
+        r.occludedRays.restype = None
+        r.rtLastRaysMs.argtypes = []
+        r.rtLastRaysMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -430,7 +440,7 @@ def make_kernel_scene(host_mesh, materials, textures=(), floor=None):
 # renderer API (same names as the C symbols)
 # ---------------------------------------------------------------------------------------------
 
-_state = {"fb": None, "nx": 0, "ny": 0, "keep": None}
+_state = {"fb": None, "nx": 0, "ny": 0, "keep": None, "spheres": False}
 
 
 def _fb_view(fbp, nx, ny):
@@ -443,7 +453,7 @@ def initRenderer(ksc, cam, nx, ny, maxDepth, keepalive=None):
     r = load_renderer()
     fbp = C.POINTER(vec3)()
     r.initRenderer(ksc, cam, C.byref(fbp), nx, ny, maxDepth)
-    _state.update(fb=_fb_view(fbp, nx, ny), nx=nx, ny=ny, keep=keepalive)
+    _state.update(fb=_fb_view(fbp, nx, ny), nx=nx, ny=ny, keep=keepalive, spheres=False)
     return _state["fb"]
 
 
@@ -456,7 +466,7 @@ def initRendererSpheres(spheres, materials, cam, nx, ny, maxDepth):
         raise ValueError("one material per sphere")
     fbp = C.POINTER(vec3)()
     r.initRendererSpheres(spheres.ctypes.data, materials.ctypes.data, len(spheres), cam, C.byref(fbp), nx, ny, maxDepth)
-    _state.update(fb=_fb_view(fbp, nx, ny), nx=nx, ny=ny, keep=None)
+    _state.update(fb=_fb_view(fbp, nx, ny), nx=nx, ny=ny, keep=None, spheres=True)
     return _state["fb"]
 
 
@@ -518,6 +528,90 @@ def renderGuides(mask=RT_GUIDE_ALBEDO | RT_GUIDE_NORMAL | RT_GUIDE_DEPTH | RT_GU
 def last_guides_ms():
     """HIP-event time of the guide kernel(s) of the last renderGuides (the largest over the in-process devices), in milliseconds."""
     return load_renderer().rtLastGuidesMs()
+
+
+# traceRays / occludedRays (include/rt_api.h): batched queries with the caller's own rays
+RT_RAY_T, RT_RAY_PRIM, RT_RAY_NORMAL, RT_RAY_UV, RT_RAY_NODES = 1, 2, 4, 8, 16
+RT_RAY_CHUNK = 1 << 22
+RAY_PLANES = (("t", RT_RAY_T, np.float32, 1), ("prim", RT_RAY_PRIM, np.int32, 1), ("normal", RT_RAY_NORMAL, np.float32, 3), ("uv", RT_RAY_UV, np.float32, 2),
+              ("nodes", RT_RAY_NODES, np.int32, 1))
+
+
+def _ray_inputs(fn, org, dir, t_min, t_max):
+    """Contiguous float32 copies (or the arrays themselves) of the rays and their ctypes pointers; a wrong shape is a ValueError."""
+    org = np.ascontiguousarray(org, dtype=np.float32)
+    dir = np.ascontiguousarray(dir, dtype=np.float32)
+    if org.ndim != 2 or org.shape[1] != 3 or dir.shape != org.shape:
+        raise ValueError(f"{fn}: org and dir must both have shape (n, 3), got {org.shape} and {dir.shape}")
+    n = org.shape[0]
+    keep, ptrs = [org, dir], []
+    for name, a in (("t_min", t_min), ("t_max", t_max)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (n,):
+                raise ValueError(f"{fn}: {name} must have shape ({n},), got {a.shape}")
+        keep.append(a)
+    fp = C.POINTER(C.c_float)
+    ptrs = [None if a is None else a.ctypes.data_as(fp) for a in keep]
+    return n, keep, ptrs
+
+
+def _ray_out(fn, out, name, shape, dtype):
+    if out is not None and not isinstance(out, dict):
+        out = {name: out}
+    if out is not None and name in out:
+        a = out[name]
+        if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"] and a.shape == shape):
+            raise ValueError(f"{fn}: out[{name!r}] must be a writable C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        return a
+    return np.zeros(shape, dtype)
+
+
+def trace_rays(org, dir, t_min=None, t_max=None, mask=None, out=None):
+    """First hits of the caller's rays (traceRays, include/rt_api.h).  org, dir: (n, 3), converted to contiguous float32; t_min, t_max: (n,) or None (the
+    options' t_min, FLT_MAX).  Returns a dict with the planes of `mask` (default: every plane the scene kind has): t (n,) float32, prim (n,) int32,
+    normal (n, 3), uv (n, 2) float32, nodes (n,) int32 (mesh scenes).  `out`: a dict of caller-owned C-contiguous arrays of those shapes and types to fill
+    instead of new ones; arrays of planes that are not in the mask are left alone.  Blocking."""
+    n, keep, ptrs = _ray_inputs("trace_rays", org, dir, t_min, t_max)
+    if mask is None:
+        mask = RT_RAY_T | RT_RAY_PRIM | RT_RAY_NORMAL | RT_RAY_UV | (0 if _state.get("spheres") else RT_RAY_NODES)
+    res, outs = {}, []
+    for name, bit, dtype, comps in RAY_PLANES:
+        if not (mask & bit):
+            outs.append(None)
+            continue
+        a = _ray_out("trace_rays", out, name, (n,) if comps == 1 else (n, comps), dtype)
+        res[name] = a
+        outs.append(a.ctypes.data_as(C.POINTER(C.c_float if dtype == np.float32 else C.c_int32)))
+    load_renderer().traceRays(n, *ptrs, mask, *outs)
+    return res
+
+
+def occluded_rays(org, dir, t_min=None, t_max=None, out=None):
+    """Any-hit query of the caller's rays (occludedRays, include/rt_api.h): (n,) uint8, 1 = something lies between the ray's bounds.  `out`: a caller-owned
+    C-contiguous uint8 array of shape (n,) to fill instead of a new one.  Blocking."""
+    n, keep, ptrs = _ray_inputs("occluded_rays", org, dir, t_min, t_max)
+    a = _ray_out("occluded_rays", out, "occluded", (n,), np.uint8)
+    load_renderer().occludedRays(n, *ptrs, a.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return a
+
+
+def last_rays_ms():
+    """HIP-event time of the ray kernels of the last trace_rays / occluded_rays (not the copies), summed over its chunks, in milliseconds."""
+    return load_renderer().rtLastRaysMs()
+
+
+def centre_rays(cam, nx, ny, ij):
+    """The centre rays of pixels ij = (n, 2) int (column i, row j; row 0 = bottom) of an nx x ny image as renderGuides defines them (rtCentreRays,
+    librt_host.so; no GPU): (org, dir), both (n, 3) float32, dir of unit length."""
+    ij = np.ascontiguousarray(ij, dtype=np.int32)
+    if ij.ndim != 2 or ij.shape[1] != 2:
+        raise ValueError(f"centre_rays: ij must have shape (n, 2), got {ij.shape}")
+    n = ij.shape[0]
+    org, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    fp = C.POINTER(C.c_float)
+    load_host().rtCentreRays(C.byref(cam), nx, ny, ij.ctypes.data_as(C.POINTER(C.c_int32)), n, org.ctypes.data_as(fp), d.ctypes.data_as(fp))
+    return org, d
 
 
 # denoiseFrame (include/rt_api.h): the flags, the limits and the defaults

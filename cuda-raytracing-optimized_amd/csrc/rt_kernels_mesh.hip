@@ -274,6 +274,41 @@ __global__ void __launch_bounds__(kThreads) k_render_mesh(const RtMeshParams P) 
 // normal, texture coordinates and texture lookup as bounce 0 above does them.  No atomics, no queue: a lane writes the planes of its own pixel.
 // PARITY objects only: one arithmetic for both fp modes.
 #if defined(RT_MODE_PARITY)
+// The per-ray part, shared with the ray kernel below (traceRays, rt_api.h): hitMesh over (t_min, t_max) - a hit iff the result is below t_max -, then the
+// floor (rt_render_options.floor) against the same t_max, the geometric normal and its orientation.  A miss has t = FLT_MAX and prim = RT_GUIDE_PRIM_NONE;
+// hu, hv stay 0 unless a triangle is hit; st.nodes is the closest-hit query's count either way (0 for a ray that misses the scene bounds).
+struct FirstHitMesh {
+    float t;
+    int prim;
+    f3 normal;
+    float hu, hv;
+    Tri tri;                    // the triangle hit (prim >= 0 only)
+    TravStats st;
+};
+__device__ __forceinline__ FirstHitMesh first_hit_mesh(const RtMeshParams& P, const Ray& r, float t_min, float t_max) {
+    FirstHitMesh h;
+    h.st = { 0, 0 };
+    h.hu = 0.0f; h.hv = 0.0f;
+    h.normal = F3(0, 0, 0);
+    h.prim = RT_GUIDE_PRIM_NONE;
+    uint32_t triId = 0;
+    h.t = hit_mesh(P, r, t_min, t_max, false, triId, h.hu, h.hv, h.st);
+    if (h.t < t_max) {
+        h.tri = load_tri(P.tris, triId);                             // kernels.cu:334
+        h.normal = unit(cross(h.tri.v1 - h.tri.v0, h.tri.v2 - h.tri.v0));
+        h.prim = (int)triId;
+    } else {
+        h.t = FLT_MAX;
+        if (P.floor_on) h.t = plane_hit(ld3(P.floor.norm), ld3(P.floor.point), r, t_min, t_max);       // kernels.cu:341-345
+        if (h.t < FLT_MAX) {
+            h.normal = ld3(P.floor.norm);
+            h.prim = RT_GUIDE_PRIM_FLOOR;
+        }
+    }
+    if (h.prim != RT_GUIDE_PRIM_NONE && dot(r.d, h.normal) > 0.0f) h.normal = -h.normal;     // kernels.cu:354-355
+    return h;
+}
+
 __global__ void __launch_bounds__(kThreads) k_guides_mesh(const RtMeshParams P, const RtGuidePlanes G) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -285,15 +320,11 @@ __global__ void __launch_bounds__(kThreads) k_guides_mesh(const RtMeshParams P, 
     const f3 org = ld3(P.cam.origin);
     const f3 dir = unit(ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - org);   // camera.h:8-12, no lens offset
     const Ray r = make_ray(org, dir);                                // hit(), kernels.cu:325-360: the ray normalises the direction once more
-    uint32_t triId = 0;
-    float hu = 0.0f, hv = 0.0f;
-    TravStats st = { 0, 0 };
-    float t = hit_mesh(P, r, P.t_min, FLT_MAX, false, triId, hu, hv, st);
-    f3 albedo, normal = F3(0, 0, 0);
-    int prim = RT_GUIDE_PRIM_NONE;
-    if (t < FLT_MAX) {
-        const Tri tri = load_tri(P.tris, triId);                     // kernels.cu:334
-        normal = unit(cross(tri.v1 - tri.v0, tri.v2 - tri.v0));
+    const FirstHitMesh h = first_hit_mesh(P, r, P.t_min, FLT_MAX);
+    f3 albedo;
+    if (h.prim >= 0) {
+        const Tri& tri = h.tri;
+        const float hu = h.hu, hv = h.hv;
         const rt_material mat = P.materials[tri.meshID];             // kernels.cu:452-480
         const bool basic = mat.type == RT_DIFFUSE || mat.type == RT_METAL || mat.type == RT_GLASS;
         f3 color = ld3(mat.color);
@@ -311,25 +342,48 @@ __global__ void __launch_bounds__(kThreads) k_guides_mesh(const RtMeshParams P, 
             const float* d = P.tex_data[mat.texId];
             color = F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
         }
-        albedo = guide_albedo(mat.type, color, r.o + t * r.d);
-        prim = (int)triId;
+        albedo = guide_albedo(mat.type, color, r.o + h.t * r.d);
+    } else if (h.prim == RT_GUIDE_PRIM_FLOOR) {
+        albedo = guide_albedo(RT_FLOOR_DIFFUSE, F3(0, 0, 0), F3(0, 0, 0));          // kernels.cu:481-482
     } else {
-        if (P.floor_on) t = plane_hit(ld3(P.floor.norm), ld3(P.floor.point), r, P.t_min, FLT_MAX);     // kernels.cu:341-345
-        if (t < FLT_MAX) {
-            normal = ld3(P.floor.norm);
-            albedo = guide_albedo(RT_FLOOR_DIFFUSE, F3(0, 0, 0), F3(0, 0, 0));      // kernels.cu:481-482
-            prim = RT_GUIDE_PRIM_FLOOR;
-        } else {
-            albedo = sky_color(P.sky, dir);                          // kernels.cu:419-425: the path's direction, normalised once
-        }
+        albedo = sky_color(P.sky, dir);                              // kernels.cu:419-425: the path's direction, normalised once
     }
-    if (prim != RT_GUIDE_PRIM_NONE && dot(r.d, normal) > 0.0f) normal = -normal;     // kernels.cu:354-355
     const size_t px = (size_t)lr * P.nx + i;
     if (G.albedo) { float* o = G.albedo + px * 3; o[0] = albedo.x; o[1] = albedo.y; o[2] = albedo.z; }
-    if (G.normal) { float* o = G.normal + px * 3; o[0] = normal.x; o[1] = normal.y; o[2] = normal.z; }
-    if (G.depth) G.depth[px] = t;
-    if (G.prim) G.prim[px] = prim;
-    if (G.nodes) G.nodes[px] = (int32_t)st.nodes;
+    if (G.normal) { float* o = G.normal + px * 3; o[0] = h.normal.x; o[1] = h.normal.y; o[2] = h.normal.z; }
+    if (G.depth) G.depth[px] = h.t;
+    if (G.prim) G.prim[px] = h.prim;
+    if (G.nodes) G.nodes[px] = (int32_t)h.st.nodes;
+}
+
+// ---- batched ray queries (traceRays / occludedRays, rt_api.h) -------------------------------------------------------------
+// One lane per caller's ray in kThreads-thread workgroups, no LDS.  The direction is the caller's raw one: make_ray normalises it once (ray.h:9).  Closest
+// hit: first_hit_mesh, the guide kernel's.  ANY (occludedRays): hitMesh with is_shadow = 1, occluded iff its result is below t_max; the floor is never
+// tested, as the reference's shadow rays never test it.  Incoherent lanes diverge and a wave lasts as long as its longest ray.
+// Consecutive lanes read consecutive 12-byte triples of org / dir and consecutive floats of t_min / t_max, and store the same way; nothing is written
+// through a null pointer.
+template <bool ANY>
+__global__ void __launch_bounds__(kThreads) k_rays_mesh(const RtMeshParams P, const RtRayBatch B) {
+    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
+    if (k >= (uint32_t)B.n) return;
+    const float* o = B.org + (size_t)k * 3;
+    const float* d = B.dir + (size_t)k * 3;
+    const Ray r = make_ray(F3(o[0], o[1], o[2]), F3(d[0], d[1], d[2]));
+    const float t_min = B.t_min ? B.t_min[k] : B.t_min_default;
+    const float t_max = B.t_max ? B.t_max[k] : FLT_MAX;
+    if (ANY) {
+        uint32_t triId = 0;
+        float hu = 0.0f, hv = 0.0f;
+        TravStats st = { 0, 0 };
+        B.occluded[k] = hit_mesh(P, r, t_min, t_max, ANY, triId, hu, hv, st) < t_max ? 1 : 0;
+        return;
+    }
+    const FirstHitMesh h = first_hit_mesh(P, r, t_min, t_max);
+    if (B.t) B.t[k] = h.t;
+    if (B.prim) B.prim[k] = h.prim;
+    if (B.normal) { float* q = B.normal + (size_t)k * 3; q[0] = h.normal.x; q[1] = h.normal.y; q[2] = h.normal.z; }
+    if (B.uv) { float* q = B.uv + (size_t)k * 2; q[0] = h.hu; q[1] = h.hv; }
+    if (B.nodes) B.nodes[k] = (int32_t)h.st.nodes;
 }
 #endif
 
@@ -1127,6 +1181,13 @@ static void launch_mesh_queue(dim3 grid, dim3 block, size_t lds, hipStream_t str
 hipError_t rt_launch_guides_mesh(const RtMeshParams& p, const RtGuidePlanes& g, hipStream_t stream) {
     const dim3 grid((p.nx + 8 * kWavesPerWg - 1) / (8 * kWavesPerWg), (p.part.local_rows + 7) / 8);
     hipLaunchKernelGGL(k_guides_mesh, grid, dim3(kThreads), 0, stream, p, g);
+    return hipGetLastError();
+}
+hipError_t rt_launch_rays_mesh(const RtMeshParams& p, const RtRayBatch& b, bool any, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    const dim3 grid(((unsigned)b.n + kThreads - 1) / kThreads);
+    if (any) hipLaunchKernelGGL(k_rays_mesh<true>, grid, dim3(kThreads), 0, stream, p, b);
+    else hipLaunchKernelGGL(k_rays_mesh<false>, grid, dim3(kThreads), 0, stream, p, b);
     return hipGetLastError();
 }
 #endif

@@ -1225,6 +1225,30 @@ __global__ void __launch_bounds__(kThreads) k_classify_spheres(const RtSpherePar
 // by the ray).  Every lane scans all slots in slot order; the addresses are wave-uniform (LDS broadcasts, or scalar loads from global memory: SCENE 1).
 // No atomics, no queue: a lane writes the planes of its own pixel.  PARITY objects only: one arithmetic for both fp modes.
 #if defined(RT_MODE_PARITY)
+// The per-ray part, shared with the ray kernels below (traceRays, rt_api.h): the scan of all slots in slot order for the ray (org, dn) - dn the ray's unit
+// direction (ray.h:9) - over (t_min, t_max), the hit point, the normal and its orientation.  t_max is the reference's strict bound (a hit at t_max itself is
+// none); below it the running closest is inclusive and accept() settles equal t by the caller's index.  A miss returns closest = FLT_MAX, sid = -1.
+__device__ __forceinline__ Hit first_hit_spheres(const RtSphereParams& P, const SceneLds& S, f3 org, f3 dn, float t_min, float t_max, f3& normal) {
+    const float a = dot(dn, dn);
+    Hit h = { t_max, -1, 0x7fffffff };
+    for (int k = 0; k < P.n_padded; k++) {
+        const int orig = S.orig[k];
+        if (orig == 0x7fffffff) continue;                            // pad slot
+        const float t = sphere_hit_exact(S.sph[sidx(k)], org, dn, a, t_min, h.closest);
+        if (t < t_max) accept(h, t, k, orig);
+    }
+    normal = F3(0, 0, 0);
+    if (h.sid >= 0) {
+        const float4 sc4 = S.sph[sidx(h.sid)];
+        const f3 hp = org + h.closest * dn;                          // ray.h:12
+        normal = (hp - F3(sc4.x, sc4.y, sc4.z)) / S.rad[h.sid];      // intersections.h:95
+        if (dot(dn, normal) > 0.0f) normal = -normal;                // kernels.cu:354-355
+    } else {
+        h.closest = FLT_MAX;
+    }
+    return h;
+}
+
 template <int SCENE>
 __global__ void __launch_bounds__(kThreads) k_guides_spheres(const RtSphereParams P, const RtGuidePlanes G) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1244,21 +1268,11 @@ __global__ void __launch_bounds__(kThreads) k_guides_spheres(const RtSphereParam
     const f3 org = ld3(P.cam.origin);
     const f3 dir = unit(ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - org);   // camera.h:8-12, no lens offset
     const f3 dn = unit(dir);                                         // ray.h:9, as hit() rebuilds the ray
-    const float a = dot(dn, dn);
-    Hit h = { FLT_MAX, -1, 0x7fffffff };
-    for (int k = 0; k < P.n_padded; k++) {
-        const int orig = S.orig[k];
-        if (orig == 0x7fffffff) continue;                            // pad slot
-        const float t = sphere_hit_exact(S.sph[sidx(k)], org, dn, a, P.t_min, h.closest);
-        if (t < FLT_MAX) accept(h, t, k, orig);
-    }
+    f3 normal;
+    const Hit h = first_hit_spheres(P, S, org, dn, P.t_min, FLT_MAX, normal);
     const size_t px = (size_t)lr * P.nx + i;
-    f3 albedo, normal = F3(0, 0, 0);
+    f3 albedo;
     if (h.sid >= 0) {
-        const float4 sc4 = S.sph[sidx(h.sid)];
-        const f3 hp = org + h.closest * dn;                          // ray.h:12
-        normal = (hp - F3(sc4.x, sc4.y, sc4.z)) / S.rad[h.sid];      // intersections.h:95
-        if (dot(dn, normal) > 0.0f) normal = -normal;                // kernels.cu:354-355
         const float4 m = S.mat[h.sid];
         albedo = F3(m.x, m.y, m.z);
     } else {
@@ -1268,6 +1282,58 @@ __global__ void __launch_bounds__(kThreads) k_guides_spheres(const RtSphereParam
     if (G.normal) { float* o = G.normal + px * 3; o[0] = normal.x; o[1] = normal.y; o[2] = normal.z; }
     if (G.depth) G.depth[px] = h.closest;
     if (G.prim) G.prim[px] = h.sid >= 0 ? h.orig : RT_GUIDE_PRIM_NONE;
+}
+
+// ---- batched ray queries (traceRays / occludedRays, rt_api.h) -------------------------------------------------------------
+// One lane per caller's ray.  Staging the scene costs a workgroup tens of KB of LDS traffic, so the launcher starts no more workgroups than stay resident and
+// each loops over tiles of kThreads rays, grid-stride: the scene is staged once per resident workgroup, not once per tile.  Consecutive lanes read
+// consecutive 12-byte triples of org / dir and consecutive floats of t_min / t_max, and store the same way; nothing is written through a null pointer.  The
+// direction is the caller's raw one, normalised once (ray.h:9).  Closest hit: first_hit_spheres, the guide kernel's scan.  ANY (occludedRays): a lane stops
+// testing at its first sphere with sphereHit(s, ray, t_min, t_max) < FLT_MAX - the strict upper bound again - and the wave leaves the slot loop once a
+// ballot, taken after every group of kSphereGroup slots, shows no live lane unoccluded.  No __syncthreads after the staging: lanes past the end of the batch just idle.
+template <int SCENE, bool ANY>
+__global__ void __launch_bounds__(kThreads) k_rays_spheres(const RtSphereParams P, const RtRayBatch B) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* unused;
+    const SceneLds S = stage_scene<false, SCENE>(P, smem, &unused);
+    const uint32_t n = (uint32_t)B.n;
+    const uint32_t tiles = (n + kThreads - 1) / kThreads;
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint32_t r = tile * kThreads + threadIdx.x;
+        const bool live = r < n;
+        f3 org = F3(0, 0, 0), dn = F3(0, 0, 1);
+        float t_min = B.t_min_default, t_max = FLT_MAX;
+        if (live) {
+            const float* o = B.org + (size_t)r * 3;
+            const float* d = B.dir + (size_t)r * 3;
+            org = F3(o[0], o[1], o[2]);
+            dn = unit(F3(d[0], d[1], d[2]));                         // ray.h:9
+            if (B.t_min) t_min = B.t_min[r];
+            if (B.t_max) t_max = B.t_max[r];
+        }
+        if (ANY) {
+            const float a = dot(dn, dn);
+            bool occ = false;
+            for (int base = 0; base < P.n_padded; base += kSphereGroup) {      // (the ballot once per group of slots: the loads of a group stay in flight together)
+#pragma unroll
+                for (int kk = 0; kk < kSphereGroup; kk++) {
+                    const int k = base + kk;
+                    const int orig = S.orig[k];
+                    if (live && !occ && orig != 0x7fffffff)
+                        occ = sphere_hit_exact(S.sph[sidx(k)], org, dn, a, t_min, t_max) < t_max;
+                }
+                if (__ballot(live && !occ) == 0ull) break;
+            }
+            if (live) B.occluded[r] = occ ? 1 : 0;
+        } else if (live) {
+            f3 normal;
+            const Hit h = first_hit_spheres(P, S, org, dn, t_min, t_max, normal);
+            if (B.t) B.t[r] = h.closest;
+            if (B.prim) B.prim[r] = h.sid >= 0 ? h.orig : RT_GUIDE_PRIM_NONE;
+            if (B.normal) { float* o = B.normal + (size_t)r * 3; o[0] = normal.x; o[1] = normal.y; o[2] = normal.z; }
+            if (B.uv) { float* o = B.uv + (size_t)r * 2; o[0] = 0.0f; o[1] = 0.0f; }
+        }
+    }
 }
 #endif
 
@@ -1942,6 +2008,22 @@ hipError_t rt_launch_guides_spheres(const RtSphereParams& p, const RtGuidePlanes
     const unsigned long long total = (unsigned long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64ull;
     const dim3 grid((unsigned)((total + kThreads - 1) / kThreads));
     return launch_with_lds(kern, grid, dim3(kThreads), lds_bytes(p.n_padded, p.n, false, scene, 0), stream, p, g);
+}
+// The ray kernels take the guide kernel's scene form.  Workgroups: as many as stay resident - per CU what the LDS copy allows, at most two of 16 waves - and
+// never more than there are tiles of kThreads rays.
+hipError_t rt_launch_rays_spheres(const RtSphereParams& p, const RtRayBatch& b, bool any, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    const int scene = scene_form(p, false);
+    using Kern = void (*)(const RtSphereParams, const RtRayBatch);
+    const Kern kerns[2][3] = { { k_rays_spheres<0, false>, k_rays_spheres<1, false>, k_rays_spheres<2, false> },
+                               { k_rays_spheres<0, true>, k_rays_spheres<1, true>, k_rays_spheres<2, true> } };
+    const size_t lds = lds_bytes(p.n_padded, p.n, false, scene, 0);
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const unsigned per_cu = lds * 2 <= kLdsPerCu ? 2u : 1u;
+    const unsigned tiles = ((unsigned)b.n + kThreads - 1) / kThreads;
+    const dim3 grid(std::min(tiles, (unsigned)cus * per_cu));
+    return launch_with_lds(kerns[any ? 1 : 0][scene], grid, dim3(kThreads), lds, stream, p, b);
 }
 #endif
 

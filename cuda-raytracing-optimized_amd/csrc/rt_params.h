@@ -301,3 +301,25 @@ struct RtGuidePlanes {
 };
 hipError_t rt_launch_guides_spheres(const RtSphereParams& p, const RtGuidePlanes& g, hipStream_t stream);
 hipError_t rt_launch_guides_mesh(const RtMeshParams& p, const RtGuidePlanes& g, hipStream_t stream);
+
+// Batched ray queries (traceRays / occludedRays, rt_api.h): one chunk of caller's rays on the device.  org / dir hold n x 3 floats, t_min / t_max n floats or
+// nullptr (= t_min_default, respectively FLT_MAX for every ray).  Output planes of n entries (normal n x 3, uv n x 2), nullptr = not stored; the closest-hit
+// kernels write t / prim / normal / uv / nodes, the any-hit kernels `occluded` alone.  The ray kernels (k_rays_spheres / k_rays_mesh) exist in the PARITY
+// objects only, like the guide kernels, and read of the scene's parameter block the scene arrays alone (mesh: bounds, floor): no camera, no image size, no
+// partition.
+struct RtRayBatch {
+    const float* org;
+    const float* dir;
+    const float* t_min;
+    const float* t_max;
+    float* t;
+    int32_t* prim;
+    float* normal;
+    float* uv;
+    int32_t* nodes;             // mesh scenes only
+    uint8_t* occluded;          // any-hit
+    int32_t n;
+    float t_min_default;        // rt_render_options.t_min
+};
+hipError_t rt_launch_rays_spheres(const RtSphereParams& p, const RtRayBatch& b, bool any, hipStream_t stream);
+hipError_t rt_launch_rays_mesh(const RtMeshParams& p, const RtRayBatch& b, bool any, hipStream_t stream);

@@ -174,6 +174,7 @@ struct RenderContext {
     double accumulate_ms = 0.0;         // rtLastAccumulateMs
     double preview_ms = 0.0;            // rtLastPreviewMs
     double display_ms = 0.0;            // rtLastDisplayMs
+    double rays_ms = 0.0;               // rtLastRaysMs
 };
 
 // What the whole-image preview passes (denoiseFrame, accumulateFrame, previewFrame) each hold on the device: buffers for the whole image on ONE device, the first in-process
@@ -226,10 +227,25 @@ struct DisplayState : PassState {
     float last_exposure = 1.0f;         // rtLastExposure
 };
 
+// traceRays / occludedRays: the device buffers of one chunk of rays - four inputs, five closest-hit planes, the any-hit bytes - on the first in-process
+// device, each grown to the largest chunk that asked for it, and an event pair of their own (created with the device list, setup_devices): the timings of a
+// frame, the guides and the passes stay what they were.  Released by free_pass where the passes' buffers are.
+enum { kRayOrg = 0, kRayDir, kRayTMin, kRayTMax, kRayT, kRayPrim, kRayNormal, kRayUv, kRayNodes, kRayOccluded, kRayBuffers };
+constexpr size_t kRayBytes[kRayBuffers] = { 12, 12, 4, 4, 4, 4, 12, 8, 4, 1 };      // bytes per ray
+constexpr int kRayChunk = RT_RAY_CHUNK;     // rays per upload - kernel - download round: 65 bytes per ray, so at most ~273 MB of device memory whatever the batch
+struct RayState {
+    int device = -1;
+    std::vector<void*> owned;           // its device allocations (dev_alloc)
+    char* d_buf[kRayBuffers] = {};
+    size_t cap[kRayBuffers] = {};       // rays d_buf[k] holds
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
 DisplayState g_display;
+RayState g_rays;
 
 // The state of displayFrame's auto exposure back to "adapt from nothing" (rtResetDisplay, setRenderOptions); the buffers stay.
 void reset_display() {
@@ -302,6 +318,7 @@ void setup_devices() {
     free_pass(g_accumulate);                                // (so do the history's)
     free_pass(g_preview);
     free_pass(g_display);
+    free_pass(g_rays);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -357,6 +374,10 @@ void setup_devices() {
         HIP_CHECK(hipMemset(d.d_queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords));
         c.devs.push_back(d);
     }
+    HIP_CHECK(hipSetDevice(c.devs[0].device));              // the ray queries' own event pair, on the device they run on
+    g_rays.device = c.devs[0].device;
+    HIP_CHECK(hipEventCreate(&g_rays.ev_start));
+    HIP_CHECK(hipEventCreate(&g_rays.ev_stop));
     HIP_CHECK(hipSetDevice(current));
 }
 
@@ -668,6 +689,7 @@ void cleanup_impl() {
     free_pass(g_accumulate);
     free_pass(g_preview);
     free_pass(g_display);
+    free_pass(g_rays);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -1318,6 +1340,96 @@ void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t*
 }
 
 double rtLastGuidesMs(void) { return g_ctx.guides_ms; }
+
+// Batched ray queries (rt_api.h).  All rays run on the first in-process device (every device holds the whole scene, setup_devices), chunk by chunk: upload,
+// kernel, download on that device's stream, with buffers and events of their own (RayState) - nothing of a frame's, the guides' or the passes' state is read
+// or written.  host[k] = the caller's array of buffer k, or NULL.
+static void run_rays(int n, const void* const host_in[4], void* const host_out[kRayBuffers], bool any) {
+    RenderContext& c = g_ctx;
+    RayState& q = g_rays;
+    const DeviceState& d = c.devs[0];
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(d.device));
+    const void* host[kRayBuffers];
+    for (int k = 0; k < kRayBuffers; k++) host[k] = k < kRayT ? host_in[k] : host_out[k];
+    double ms_sum = 0.0;
+    for (size_t first = 0; first < (size_t)n; first += kRayChunk) {
+        const size_t m = std::min((size_t)kRayChunk, (size_t)n - first);
+        for (int k = 0; k < kRayBuffers; k++) {
+            if (!host[k] || q.cap[k] >= m) continue;
+            dev_release(q.owned, q.d_buf[k]);
+            q.d_buf[k] = dev_alloc<char>(q.owned, m * kRayBytes[k]);
+            q.cap[k] = m;
+        }
+        for (int k = 0; k < kRayT; k++)
+            if (host[k])
+                HIP_CHECK(hipMemcpyAsync(q.d_buf[k], static_cast<const char*>(host[k]) + first * kRayBytes[k], m * kRayBytes[k], hipMemcpyHostToDevice, d.stream));
+        auto in = [&](int k) { return host[k] ? reinterpret_cast<const float*>(q.d_buf[k]) : nullptr; };
+        auto out = [&](int k) { return host[k] ? q.d_buf[k] : nullptr; };
+        RtRayBatch b;
+        b.org = in(kRayOrg); b.dir = in(kRayDir); b.t_min = in(kRayTMin); b.t_max = in(kRayTMax);
+        b.t = reinterpret_cast<float*>(out(kRayT)); b.prim = reinterpret_cast<int32_t*>(out(kRayPrim));
+        b.normal = reinterpret_cast<float*>(out(kRayNormal)); b.uv = reinterpret_cast<float*>(out(kRayUv));
+        b.nodes = reinterpret_cast<int32_t*>(out(kRayNodes)); b.occluded = reinterpret_cast<uint8_t*>(out(kRayOccluded));
+        b.n = (int32_t)m;
+        b.t_min_default = c.opt.t_min;
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        HIP_CHECK(c.is_spheres ? rt_launch_rays_spheres(sphere_params(d, whole_image_partition()), b, any, d.stream)
+                               : rt_launch_rays_mesh(mesh_params(d, whole_image_partition()), b, any, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        for (int k = kRayT; k < kRayBuffers; k++)
+            if (host[k])
+                HIP_CHECK(hipMemcpyAsync(static_cast<char*>(host_out[k]) + first * kRayBytes[k], q.d_buf[k], m * kRayBytes[k], hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's arrays are complete on return; the events are read per chunk
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, q.ev_start, q.ev_stop));
+        ms_sum += (double)ms;
+    }
+    HIP_CHECK(hipSetDevice(current));
+    c.rays_ms = ms_sum;
+}
+
+// The checks the two calls share; returns false for the empty batch (nothing to do, nothing written).
+static bool check_rays(const char* fn, int n, const float* org, const float* dir) {
+    const RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail(" before init", fn);
+    if (n < 0) rt_fail(": n is negative", fn);
+    if (n == 0) return false;
+    if (!org || !dir) rt_fail(": org and dir must not be null", fn);
+    if (c.is_spheres && c.opt.floor) rt_fail(": the floor plane is only defined for mesh scenes (kernel_scene.floor)", fn);
+    return true;
+}
+
+void traceRays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, int mask,
+               float* t, int32_t* prim, float* normal, float* uv, int32_t* nodes) {
+    if (!check_rays("traceRays", n, org, dir)) return;
+    constexpr int kAll = RT_RAY_T | RT_RAY_PRIM | RT_RAY_NORMAL | RT_RAY_UV | RT_RAY_NODES;
+    if (mask == 0 || (mask & ~kAll) != 0) rt_fail("traceRays: mask must name at least one RT_RAY_* plane and no unknown bit");
+    void* const planes[5] = { t, prim, normal, uv, nodes };
+    for (int k = 0; k < 5; k++)
+        if ((mask >> k & 1) && !planes[k]) rt_fail("traceRays: a requested plane has a null pointer");
+    if ((mask & RT_RAY_NODES) && g_ctx.is_spheres) rt_fail("traceRays: RT_RAY_NODES is only defined for mesh scenes");
+    const void* const in[4] = { org, dir, t_min, t_max };
+    void* out[kRayBuffers] = {};
+    for (int k = 0; k < 5; k++) out[kRayT + k] = (mask >> k & 1) ? planes[k] : nullptr;
+    run_rays(n, in, out, false);
+}
+
+void occludedRays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, uint8_t* occluded) {
+    if (!g_ctx.initialised) rt_fail("occludedRays before init");
+    if (!occluded) rt_fail("occludedRays: occluded is null");
+    if (!check_rays("occludedRays", n, org, dir)) return;
+    const void* const in[4] = { org, dir, t_min, t_max };
+    void* out[kRayBuffers] = {};
+    out[kRayOccluded] = occluded;
+    run_rays(n, in, out, true);
+}
+
+double rtLastRaysMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastRaysMs before init");
+    return g_ctx.rays_ms;
+}
 
 // Guide-driven preview denoiser (rt_api.h).  The filter needs neighbours across stripe boundaries, so it works on the whole image on the first
 // in-process device (every device holds the whole scene, setup_devices) with buffers, guide planes and events of its own: like renderGuides it reads and

@@ -120,4 +120,20 @@ void rtStaircaseCamera(int nx, int ny, rt_camera* cam) {
     rtMakeCamera(from, at, up, 42.0f, float(nx) / float(ny), 0.0f, dist_to_focus, cam);
 }
 
+
+// The centre ray of a pixel (rt_api.h, renderGuides): camera.h:8-12 with no lens offset and no jitter, the sums in get_ray's order.
+void rtCentreRays(const rt_camera* cam, int nx, int ny, const int32_t* ij, int n, float* org, float* dir) {
+    const f3 o = F(cam->origin.e), llc = F(cam->lower_left_corner.e), h = F(cam->horizontal.e), vt = F(cam->vertical.e);
+    for (int k = 0; k < n; k++) {
+        const float u = ((float)ij[2 * k] + 0.5f) / (float)nx;
+        const float v = ((float)ij[2 * k + 1] + 0.5f) / (float)ny;
+        const f3 a = scale(u, h), b = scale(v, vt);
+        const f3 s1 = { llc.x + a.x, llc.y + a.y, llc.z + a.z };
+        const f3 s2 = { s1.x + b.x, s1.y + b.y, s1.z + b.z };
+        const f3 d = unit(s2 - o);
+        org[3 * k] = o.x; org[3 * k + 1] = o.y; org[3 * k + 2] = o.z;
+        dir[3 * k] = d.x; dir[3 * k + 1] = d.y; dir[3 * k + 2] = d.z;
+    }
+}
+
 }  // extern "C"

@@ -358,6 +358,53 @@ int    rtDisplayHistogram(uint32_t* out, int cap); /* the bins of the last RT_DI
 void   rtResetDisplay(void);                       /* the next RT_DISPLAY_AUTO_EXPOSURE call adapts from nothing */
 double rtLastDisplayMs(void);                      /* HIP-event time of its kernels (not the copies); 0 before the first call */
 
+/* --- batched ray queries: the caller's own rays -----------------------------------------------------------------------------
+ * traceRays finds the first hit of n rays of the caller's, occludedRays says for each whether anything lies between its bounds: picking, autofocus (the t under
+ * the cursor is the camera's focus_dist), fitting a camera to a model, visibility and ambient-occlusion probes, light placement, collision tests.  rtCentreRays
+ * (rt_host.h) turns a pixel into the ray renderGuides sends through it.  For ray k: o = org[3k..3k+2], d = dir[3k..3k+2], tmin = t_min[k] or, with t_min NULL,
+ * rt_render_options.t_min; tmax = t_max[k] or, with t_max NULL, FLT_MAX.
+ *   Direction   the ray is the reference's ray(o, d) (ray.h:9): dn = d / sqrt(d.x*d.x + d.y*d.y + d.z*d.z), and every distance is along dn.  The caller's
+ *               direction is raw and is normalised ONCE (the guide kernels normalise the centre ray, already unit, a second time: a caller who wants their
+ *               bits passes the unit direction, as rtCentreRays returns it).
+ *   Arithmetic  fp32 under the PARITY rules, in both fp modes.  The light sphere is never hit.
+ *   Spheres     closest = tmax; for s = 0 .. n_spheres-1 in the caller's order: x = sphereHit(s, ray, tmin, closest) (intersections.h:85-104); if x < closest:
+ *               closest = x, prim = s.  So on equal t the lower caller index wins, as in renderGuides, and a hit at tmax itself is none.
+ *   Meshes      if hit_bbox(scene bounds, ray, tmax) fails the ray misses and nodes = 0.  Otherwise x = hitBvh(ray, tmin, tmax, is_shadow = 0)
+ *               (kernels.cu:154-224): a hit iff x < tmax.  On a miss with rt_render_options.floor = 1: x = planeHit(kernel_scene.floor, ray, tmin, tmax), a hit
+ *               iff x < FLT_MAX, prim = RT_GUIDE_PRIM_FLOOR.  The floor is tested against the ray's own tmax (hit() passes FLT_MAX there: the two agree
+ *               whenever tmax is FLT_MAX).
+ * Planes of n entries; prim and normal have the meaning and the encoding of RT_GUIDE_PRIM and RT_GUIDE_NORMAL:
+ *   RT_RAY_T       float      hit: the distance along dn;  miss: FLT_MAX
+ *   RT_RAY_PRIM    int32      hit: the caller's sphere index, the triangle's index in mesh.tris, RT_GUIDE_PRIM_FLOOR;  miss: RT_GUIDE_PRIM_NONE
+ *   RT_RAY_NORMAL  3 x float  hit: the shading normal of hit() - (p - center) / radius, unit(cross(v1 - v0, v2 - v0)) or floor.norm - turned against dn, with
+ *                             p = o + t * dn;  miss: (0, 0, 0)
+ *   RT_RAY_UV      2 x float  hit of a triangle: hitU, hitV of triangleHit (intersections.h:54-83);  a sphere, the floor, a miss: (0, 0)
+ *   RT_RAY_NODES   int32      mesh scenes only: internal BVH nodes visited by that query, as RT_GUIDE_NODES: 0 for a ray that misses the scene bounds, and a
+ *                             ray that misses inside the bounds still carries its count
+ * occludedRays writes one byte per ray.  Sphere scenes: 1 iff some sphere has sphereHit(s, ray, tmin, tmax) < FLT_MAX (whatever the scan order).  Mesh scenes:
+ * 1 iff the bounds test passes and hitBvh(ray, tmin, tmax, is_shadow = 1) < tmax.  The floor never occludes, exactly as the reference's shadow rays never
+ * test it.
+ * The caller owes 0 <= tmin < tmax, neither a NaN, and d finite and non-zero.  Rays are not validated one by one: a ray that breaks this gets an unspecified
+ * result, the call still returns, and every other ray's result is unaffected.
+ *
+ * Both calls are blocking and answer in the caller's ray order.  org and dir hold n x 3 floats; t_min and t_max n floats each, or NULL.  The outputs are
+ * caller-owned host arrays (pageable is fine): traceRays takes one per plane named in `mask` and NULL for the others - t, prim, nodes of n entries, normal of
+ * n x 3, uv of n x 2 floats - and nothing is written through a pointer whose plane is not named.  All rays run on the first in-process device, whatever
+ * stripe_rows, num_devices, part_rank and part_world are (every device holds the whole scene), RT_RAY_CHUNK = 1 << 22 rays at a time - upload, kernel,
+ * download -, so the device buffers (65 bytes per ray of the largest chunk seen, only for the arrays that were passed) stay below ~273 MB; they are freed
+ * where the passes' buffers are: cleanupRenderer, every init*, a setRenderOptions that changes the device layout.  The calls follow setRenderOptions (t_min
+ * as the default, floor) and do not depend on the camera, nx, ny or setCamera.  They change nothing an existing call observes: the framebuffer, getRenderStats,
+ * rtLastLaunches, the progressive frame, the histories of accumulateFrame / previewFrame / displayFrame and every other rtLast*Ms stay as they were.  n == 0
+ * returns at once: nothing is written and rtLastRaysMs stays as it was.  Misuse (rt error, exit 99): before init (rtLastRaysMs as well), n < 0, org or dir
+ * NULL with n > 0, mask 0 or with unknown bits, a requested plane whose pointer is NULL, RT_RAY_NODES on a sphere scene, occluded NULL,
+ * rt_render_options.floor = 1 on a sphere scene. */
+enum { RT_RAY_T = 1, RT_RAY_PRIM = 2, RT_RAY_NORMAL = 4, RT_RAY_UV = 8, RT_RAY_NODES = 16 };
+#define RT_RAY_CHUNK (1 << 22)
+void   traceRays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, int mask,
+                 float* t, int32_t* prim, float* normal, float* uv, int32_t* nodes);
+void   occludedRays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, uint8_t* occluded);
+double rtLastRaysMs(void);   /* HIP-event time of the ray kernels of the last traceRays / occludedRays (not the copies), summed over its chunks; 0 before the first */
+
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };

@@ -39,6 +39,12 @@ int rtSceneRandomSpheres(uint32_t seed, rt_sphere* spheres, rt_material* materia
 /* setup_camera, /root/reference/staircase_scene.h:62-73. */
 void rtStaircaseCamera(int nx, int ny, rt_camera* cam);
 
+/* The centre rays of pixels ij[2k] = i (column), ij[2k+1] = j (row, 0 = bottom) of an nx x ny image, exactly as renderGuides defines them (rt_api.h):
+ * u = ((float)i + 0.5f) / (float)nx, v = ((float)j + 0.5f) / (float)ny, org = cam.origin, dir = unit(lower_left_corner + u*horizontal + v*vertical - origin):
+ * get_ray (camera.h:8-12) without the lens offset, bit for bit.  org and dir receive n x 3 floats: a cursor position becomes a pick ray or an autofocus ray
+ * for traceRays without a GPU.  Pixels outside the image are computed like any other. */
+void rtCentreRays(const rt_camera* cam, int nx, int ny, const int32_t* ij, int n, float* org, float* dir);
+
 /* ---- mesh scenes: BVH in the layout hitBvh expects (kernels.cu:154-224) ---- */
 
 typedef struct rt_host_mesh rt_host_mesh;    /* opaque; owns tris + bvh */
