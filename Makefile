@@ -54,15 +54,20 @@ $(OBJ)/preview.o: $(CSRC)/rt_kernels_preview.hip $(CSRC)/rt_preview.h include/rt
 # depends on it.
 $(OBJ)/display.o: $(CSRC)/rt_kernels_display.hip $(CSRC)/rt_display.h $(CSRC)/rt_glibc_powf_pos.h $(CSRC)/rt_glibc_powf.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_display.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The BVH refit of updateTriangles (node boxes, child-pair records, compact leaf records): comparisons, selects and one rounded subtraction per edge component,
+# defined bit for bit as the passes above, so one object with the flags of display.o.  Its own TU and header: no other kernel object depends on it.
+$(OBJ)/update.o: $(CSRC)/rt_kernels_update.hip $(CSRC)/rt_update.h include/rt_types.h include/rt_api.h | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o
 RT_OBJS += $(OBJ)/preview.o
 DISPLAY_OBJS := $(OBJ)/display.o
+UPDATE_OBJS := $(OBJ)/update.o
 
-$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) -o $@
+$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) -o $@
 
 $(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp include/rt_host.h include/rt_types.h include/rt_api.h
 	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp -o $@

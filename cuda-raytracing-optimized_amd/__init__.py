@@ -136,14 +136,15 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "accumulateFrame", "rtResetHistory", "rtHistoryFrames", "rtLastAccumulateMs",
                     "previewFrame", "rtResetPreview", "rtPreviewFrames", "rtLastPreviewMs",
                     "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs",
-                    "traceRays", "occludedRays", "rtLastRaysMs"]
+                    "traceRays", "occludedRays", "rtLastRaysMs",
+                    "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
 HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtSceneRandomSpheres", "rtStaircaseCamera",
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
-                "rtDisplayFrameHost", "rtCentreRays"]
+                "rtDisplayFrameHost", "rtCentreRays", "rtRefitBvhArrays", "rtRefitBvh"]
 
 _renderer = None
 _host = None
@@ -196,6 +197,10 @@ def load_host():
         h.rtDisplayFrameHost.restype = C.c_int
         h.rtCentreRays.argtypes = [C.POINTER(camera), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, fp, fp]
         h.rtCentreRays.restype = None
+        h.rtRefitBvhArrays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.POINTER(bbox)]
+        h.rtRefitBvhArrays.restype = C.c_int
+        h.rtRefitBvh.argtypes = [C.c_void_p]
+        h.rtRefitBvh.restype = C.c_int
         _host = h
     return _host
 
@@ -308,6 +313,16 @@ def load_renderer():
         r.occludedRays.restype = None
         r.rtLastRaysMs.argtypes = []
         r.rtLastRaysMs.restype = C.c_double
+        r.updateTriangles.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        r.updateTriangles.restype = None
+        r.updateMaterials.argtypes = [C.c_void_p, C.c_int]
+        r.updateMaterials.restype = None
+        r.updateSpheres.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        r.updateSpheres.restype = None
+        r.getMeshBvh.argtypes = [C.c_void_p, C.c_int, C.POINTER(bbox)]
+        r.getMeshBvh.restype = C.c_int
+        r.rtLastUpdateMs.argtypes = []
+        r.rtLastUpdateMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -386,6 +401,13 @@ class HostMesh:
     @property
     def bvh(self):
         return np.ctypeslib.as_array(C.cast(self.view.bvh, C.POINTER(C.c_ubyte)), (self.view.numBvhNodes * 24,)).view(bvh_node_dtype)
+
+    def refit(self):
+        """rtRefitBvh: every node and the bounds from `.tris` as they are now (a writable view: edit it in place, then refit), in the order include/rt_api.h
+        defines - what updateTriangles computes on the device, and the scene the CPU oracle renders.  `.bvh` and `.view` follow."""
+        if load_host().rtRefitBvh(self._h) != 0:
+            raise ValueError("rtRefitBvh refused the mesh")
+        self.nppl = load_host().rtMeshView(self._h, C.byref(self.view))
 
     def close(self):
         if self._h:
@@ -599,6 +621,66 @@ def occluded_rays(org, dir, t_min=None, t_max=None, out=None):
 def last_rays_ms():
     """HIP-event time of the ray kernels of the last trace_rays / occluded_rays (not the copies), summed over its chunks, in milliseconds."""
     return load_renderer().rtLastRaysMs()
+
+
+# updateTriangles / updateMaterials / updateSpheres (include/rt_api.h): edit the scene in place.  The wrappers take arrays of the exact record type and
+# convert nothing: a wrong dtype or shape is a ValueError before the library is called.
+def _records(fn, name, a, dtype):
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.ndim == 1):
+        raise ValueError(f"{fn}: {name} must be a one-dimensional numpy array of {name}_dtype records")
+    return np.ascontiguousarray(a)
+
+
+def update_triangles(first, tris):
+    """Replaces slots [first, first + len(tris)) of the leaf-ordered triangle array given to initRenderer (HostMesh.tris) and refits the BVH on every device
+    (updateTriangles).  tris: a 1-D array of triangle_dtype.  Blocking; an empty array changes nothing."""
+    tris = _records("update_triangles", "triangle", tris, triangle_dtype)
+    if isinstance(first, bool) or not isinstance(first, (int, np.integer)):
+        raise ValueError("update_triangles: first must be an integer")
+    load_renderer().updateTriangles(int(first), len(tris), tris.ctypes.data if len(tris) else None)
+
+
+def update_materials(mats):
+    """Replaces the material array of a mesh scene (updateMaterials): a 1-D array of material_dtype, as many as at init."""
+    mats = _records("update_materials", "material", mats, material_dtype)
+    load_renderer().updateMaterials(mats.ctypes.data, len(mats))
+
+
+def update_spheres(spheres, mats):
+    """Replaces spheres and materials of a sphere scene (updateSpheres): 1-D arrays of sphere_dtype and material_dtype, as many as at init."""
+    spheres = _records("update_spheres", "sphere", spheres, sphere_dtype)
+    mats = _records("update_spheres", "material", mats, material_dtype)
+    if len(spheres) != len(mats):
+        raise ValueError("update_spheres: one material per sphere")
+    load_renderer().updateSpheres(spheres.ctypes.data, mats.ctypes.data, len(spheres))
+
+
+def mesh_bvh():
+    """The first device's current BVH of a mesh scene (getMeshBvh): (nodes, bounds) - numBvhNodes records of bvh_node_dtype, node 0 unused, and the scene
+    bounds as a (2, 3) float32 array (min, max)."""
+    r = load_renderer()
+    n = r.getMeshBvh(None, 0, None)
+    nodes = np.zeros(n, bvh_node_dtype)
+    b = bbox()
+    r.getMeshBvh(nodes.ctypes.data, n, C.byref(b))
+    return nodes, np.array([list(b.min.e), list(b.max.e)], np.float32)
+
+
+def last_update_ms():
+    """HIP-event time of the refit kernels of the last update_triangles (the largest over the in-process devices), in milliseconds; 0 before the first."""
+    return load_renderer().rtLastUpdateMs()
+
+
+def refit_bvh_arrays(tris, bvh, nppl):
+    """rtRefitBvhArrays on caller-owned arrays: refits `bvh` (1-D bvh_node_dtype, writable) in place from `tris` (1-D triangle_dtype).  Returns the bounds as a
+    (2, 3) float32 array, or None where the library refuses the arrays (-1)."""
+    tris = _records("refit_bvh_arrays", "triangle", tris, triangle_dtype)
+    if not (isinstance(bvh, np.ndarray) and bvh.dtype == bvh_node_dtype and bvh.ndim == 1 and bvh.flags["C_CONTIGUOUS"] and bvh.flags["WRITEABLE"]):
+        raise ValueError("refit_bvh_arrays: bvh must be a writable C-contiguous one-dimensional array of bvh_node_dtype records")
+    b = bbox()
+    if load_host().rtRefitBvhArrays(tris.ctypes.data, len(tris), bvh.ctypes.data, len(bvh), int(nppl), C.byref(b)) != 0:
+        return None
+    return np.array([list(b.min.e), list(b.max.e)], np.float32)
 
 
 def centre_rays(cam, nx, ny, ij):

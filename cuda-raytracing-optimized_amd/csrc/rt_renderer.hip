@@ -31,6 +31,7 @@
 #include "rt_accumulate.h"
 #include "rt_preview.h"
 #include "rt_display.h"
+#include "rt_update.h"
 
 namespace {
 
@@ -86,6 +87,7 @@ struct DeviceState {
     std::vector<void*> owned;           // every device allocation of this state (dev_alloc)
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    hipEvent_t ev_upd_start = nullptr, ev_upd_stop = nullptr;   // around the refit kernels of updateTriangles (rtLastUpdateMs): a frame's and the guides' timings stay theirs
     RtSphereParams* d_params = nullptr; // device copy of the sphere kernel's parameter block (RtSphereParams::self), one per DeviceState
     RtSphereParams* h_params = nullptr; // its pinned staging copy (the source of the asynchronous upload must outlive the call)
     // sphere scene
@@ -126,7 +128,7 @@ struct DeviceState {
     // device state itself (a new init or another partition builds new device states) - see cost_key_of.
     uint32_t* d_cost_rays = nullptr;
     int cost_samples = 0;
-    std::array<int, 10> cost_key = {};
+    std::array<int, 11> cost_key = {};
     float4* d_acc_state = nullptr;      // progressive frame (runRendererProgressive): per local pixel (col, rng) after the samples so far, and (sphere scenes)
     uint32_t* d_acc_rays = nullptr;     // the rays they took; allocated by the first pass on this device
     void* d_guide[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };     // first-hit guide planes (renderGuides), plane k = bit k of the mask: allocated by the
@@ -169,6 +171,9 @@ struct RenderContext {
     rt_render_stats stats;
     int prog_samples = 0;               // samples per pixel of the progressive frame so far (rtProgressiveSamples)
     int camera_moves = 0;               // setCamera calls that changed the camera: part of a cost map's key (cost_key_of)
+    int scene_edits = 0;                // updateTriangles / updateMaterials / updateSpheres calls that changed the scene: likewise
+    bool refit_stale = false;           // the devices' nodes, child-pair records and leaf records are newer than h_bvh / h_bvh_axis / h_leaf_tri (fetch_refit)
+    double update_ms = 0.0;             // rtLastUpdateMs
     double guides_ms = 0.0;             // rtLastGuidesMs
     double denoise_ms = 0.0;            // rtLastDenoiseMs
     double accumulate_ms = 0.0;         // rtLastAccumulateMs
@@ -283,6 +288,8 @@ void free_device(DeviceState& d) {
     if (d.h_params) HIP_CHECK(hipHostFree(d.h_params));
     if (d.ev_start) HIP_CHECK(hipEventDestroy(d.ev_start));
     if (d.ev_stop) HIP_CHECK(hipEventDestroy(d.ev_stop));
+    if (d.ev_upd_start) HIP_CHECK(hipEventDestroy(d.ev_upd_start));
+    if (d.ev_upd_stop) HIP_CHECK(hipEventDestroy(d.ev_upd_stop));
     if (d.stream) HIP_CHECK(hipStreamDestroy(d.stream));
     d = DeviceState();
 }
@@ -311,9 +318,41 @@ int local_rows_of(int ny, int sr, int rank, int world) {
     return rows;
 }
 
+// The host mirrors of what the refit kernels write.  updateTriangles keeps h_tris and the scene bounds current itself; the nodes, the child-pair records and
+// the leaf records - tens of MB for a large mesh, against the few microseconds of the refit - are fetched from the first device when the host next reads
+// them: by setup_devices, which uploads the scene from the mirrors.  Every device holds the same refitted arrays and the update calls are blocking.
+void fetch_refit() {
+    RenderContext& c = g_ctx;
+    if (!c.refit_stale) return;
+    const DeviceState& d = c.devs[0];
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(d.device));
+    HIP_CHECK(hipMemcpy(c.h_bvh.data(), d.d_bvh, c.h_bvh.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(c.h_bvh_axis.data(), d.d_bvh_axis, c.h_bvh_axis.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (!c.h_leaf_tri.empty()) HIP_CHECK(hipMemcpy(c.h_leaf_tri.data(), d.d_leaf_tri, c.h_leaf_tri.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipSetDevice(current));
+    c.refit_stale = false;
+}
+
+// The sphere scene's arrays on device state `d` from the host copies (setup_devices, updateSpheres: the grouping may have changed their sizes).
+void upload_sphere_arrays(DeviceState& d) {
+    const RenderContext& c = g_ctx;
+    dev_release(d.owned, d.d_spheres); dev_release(d.owned, d.d_rad); dev_release(d.owned, d.d_mat_color); dev_release(d.owned, d.d_mat_type);
+    dev_release(d.owned, d.d_groups); dev_release(d.owned, d.d_orig); dev_release(d.owned, d.d_slot_of);
+    d.d_spheres = upload(d.owned, c.h_spheres);
+    d.d_rad = upload(d.owned, c.h_rad);
+    d.d_mat_color = upload(d.owned, c.h_mat_color);
+    d.d_mat_type = upload(d.owned, c.h_mat_type);
+    d.d_groups = upload(d.owned, c.h_groups);
+    d.d_orig = upload(d.owned, c.h_orig);
+    d.d_slot_of = upload(d.owned, c.h_slot_of);
+}
+
 // (Re)creates the per-device state for the device list in g_ctx.opt.
 void setup_devices() {
     RenderContext& c = g_ctx;
+    fetch_refit();                                          // (the scene is uploaded from the host mirrors below)
     free_pass(g_denoise);                                   // (its buffers live on the first device of the list being replaced)
     free_pass(g_accumulate);                                // (so do the history's)
     free_pass(g_preview);
@@ -335,16 +374,12 @@ void setup_devices() {
         HIP_CHECK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
         HIP_CHECK(hipEventCreate(&d.ev_start));
         HIP_CHECK(hipEventCreate(&d.ev_stop));
+        HIP_CHECK(hipEventCreate(&d.ev_upd_start));
+        HIP_CHECK(hipEventCreate(&d.ev_upd_stop));
         if (c.is_spheres) {
             d.d_params = dev_alloc<RtSphereParams>(d.owned, 1);
             HIP_CHECK(hipHostMalloc((void**)&d.h_params, sizeof(RtSphereParams), hipHostMallocDefault));
-            d.d_spheres = upload(d.owned, c.h_spheres);
-            d.d_rad = upload(d.owned, c.h_rad);
-            d.d_mat_color = upload(d.owned, c.h_mat_color);
-            d.d_mat_type = upload(d.owned, c.h_mat_type);
-            d.d_groups = upload(d.owned, c.h_groups);
-            d.d_orig = upload(d.owned, c.h_orig);
-            d.d_slot_of = upload(d.owned, c.h_slot_of);
+            upload_sphere_arrays(d);
         } else {
             d.d_tris = upload(d.owned, c.h_tris);
             d.d_bvh = upload(d.owned, c.h_bvh);
@@ -603,6 +638,25 @@ void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials,
     sp.pair_k0 = (float)(2.0 * 3.814697265625e-6 * r_max_small * r_max_small * 1.0001);     // 2 x kPairSlack (2^-18) x r_max^2, rounded up
 }
 
+// RtMeshParams::lean_ok of the materials in h_materials (build_mesh_scene, updateMaterials): every one RT_DIFFUSE / RT_METAL / RT_GLASS and untextured.
+int mesh_lean_ok() {
+    for (const rt_material& m : g_ctx.h_materials)
+        if ((m.type != RT_DIFFUSE && m.type != RT_METAL && m.type != RT_GLASS) || m.texId != -1) return 0;
+    return 1;
+}
+
+// What initRendererSpheres and updateSpheres do with the caller's arrays: the checks, the slot layout and the decision where the kernels read the scene from.
+void build_sphere_scene(const char* fn, const rt_sphere* spheres, const rt_material* materials, int n) {
+    RenderContext& c = g_ctx;
+    for (int k = 0; k < n; k++)
+        if (materials[k].type < RT_DIFFUSE || materials[k].type >= RT_MATERIAL_TYPE_COUNT) rt_fail(": bad material type", fn);
+    build_sphere_groups(spheres, materials, n);
+    // Scenes up to ~2100 spheres live in the LDS of every workgroup; larger ones are read from global memory (they stay in L2) by the
+    // same kernel (no cost-ordered second phase, no sparse form beyond 4096 groups: slower per ray, same image).
+    c.sphere_scene.global_scene = rt_sphere_kernel_lds_bytes(c.sphere_scene.n_padded, n) > 160 * 1024 ? 1 : 0;
+    if (c.sphere_scene.n_padded > (1 << 24)) rt_fail(": more than 16 M sphere slots", fn);
+}
+
 // Device layout of a mesh scene (initRenderer has validated `sc`): the caller's triangles and BVH, the axis-grouped node records, the compact leaf records,
 // materials and textures as host arrays, the scene's constants in the parameter-block template.
 void build_mesh_scene(const rt_kernel_scene& sc) {
@@ -671,9 +725,7 @@ void build_mesh_scene(const rt_kernel_scene& sc) {
         }
     }
     c.h_materials.assign(sc.materials, sc.materials + sc.numMaterials);                        // kernels.cu:617-618
-    mp.lean_ok = 1;                                         // every material is RT_DIFFUSE / RT_METAL / RT_GLASS and untextured
-    for (const rt_material& m : c.h_materials)
-        if ((m.type != RT_DIFFUSE && m.type != RT_METAL && m.type != RT_GLASS) || m.texId != -1) mp.lean_ok = 0;
+    mp.lean_ok = mesh_lean_ok();
     c.h_tex.clear(); c.h_tex_w.clear(); c.h_tex_h.clear();
     for (int t = 0; t < sc.numTextures; t++) {                                                 // kernels.cu:620-645
         const rt_stexture& tx = sc.textures[t];
@@ -767,13 +819,7 @@ void initRendererSpheres(const rt_sphere* spheres, const rt_material* materials,
     if (!spheres || !materials || n <= 0) rt_fail("initRendererSpheres: empty scene");
     c.is_spheres = true;
     default_options(&c.opt, 1);
-    for (int k = 0; k < n; k++)
-        if (materials[k].type < RT_DIFFUSE || materials[k].type >= RT_MATERIAL_TYPE_COUNT) rt_fail("initRendererSpheres: bad material type");
-    build_sphere_groups(spheres, materials, n);
-    // Scenes up to ~2100 spheres live in the LDS of every workgroup; larger ones are read from global memory (they stay in L2) by the
-    // same kernel (no cost-ordered second phase, no sparse form beyond 4096 groups: slower per ray, same image).
-    c.sphere_scene.global_scene = rt_sphere_kernel_lds_bytes(c.sphere_scene.n_padded, n) > 160 * 1024 ? 1 : 0;
-    if (c.sphere_scene.n_padded > (1 << 24)) rt_fail("initRendererSpheres: more than 16 M sphere slots");
+    build_sphere_scene("initRendererSpheres", spheres, materials, n);
     common_init(cam, fb, nx, ny, maxDepth);
 }
 
@@ -981,11 +1027,12 @@ void parked_buffers(DeviceState& d, bool packed) {
 // What a cost map depends on beside its device state: the image, the partition, what decides how many rays a pixel takes, and the camera.  Compared by
 // value (setRenderOptions with equal fields, setCamera with the same camera change nothing); counters, variant, fp and the traffic switches are not in
 // it: the ordering pass runs every frame under that frame's switches.  The camera is, because a moved camera's frame is slower ordered by the old map
-// than measured - a 2-degree step of an orbit moves the long pixels by tens of pixels: 1200x800x16 spp 3.06 ms against 2.68 (DESIGN.md 3.15,
+// than measured; an edited scene (updateSpheres) likewise, whatever RT_COST_REUSE says - a 2-degree step of an orbit moves the long pixels by tens of pixels: 1200x800x16 spp 3.06 ms against 2.68 (DESIGN.md 3.15,
 // tools/bench_orbit.py); RT_COST_REUSE=2 keeps the map across setCamera (that measurement, and the tests of a map that is wrong).
-std::array<int, 10> cost_key_of(const RtPartition& part, bool with_camera) {
+std::array<int, 11> cost_key_of(const RtPartition& part, bool with_camera) {
     const RenderContext& c = g_ctx;
-    return { c.nx, c.ny, part.stripe_rows, part.rank, part.world, part.local_rows, c.max_depth, (int)c.opt.rr, (int)c.opt.rng, with_camera ? c.camera_moves : 0 };
+    return { c.nx, c.ny, part.stripe_rows, part.rank, part.world, part.local_rows, c.max_depth, (int)c.opt.rr, (int)c.opt.rng, with_camera ? c.camera_moves : 0,
+             c.scene_edits };
 }
 
 // One frame of ns samples per pixel (runRenderer), or one pass of a progressive frame (progressive): samples [first, ns) of every pixel, continued from
@@ -1061,7 +1108,7 @@ void render_frame(int ns, int first, bool progressive) {
                     d.d_cost_rays = dev_alloc<uint32_t>(d.owned, d.fb_rows * c.nx);
                     d.cost_samples = 0;
                 }
-                const std::array<int, 10> key = cost_key_of(part, sw.cost_reuse != 2);
+                const std::array<int, 11> key = cost_key_of(part, sw.cost_reuse != 2);
                 p.cost_rays = d.d_cost_rays;
                 p.acc_rays = d.d_cost_rays;                         // (this frame's rays: the same buffer, written behind the ordering pass that reads it)
                 p.cost_samples = key == d.cost_key ? d.cost_samples : 0;
@@ -1289,6 +1336,121 @@ void setCamera(const rt_camera* cam) {
     if (memcmp(&c.cam, cam, sizeof(rt_camera)) != 0) c.camera_moves++;      // (the cost maps of sphere frames: cost_key_of)
     c.cam = *cam;                                           // read by every frame's parameter block; nothing of the scene depends on it
     c.prog_samples = 0;
+}
+
+// Scene edits (rt_api.h, "editing the scene").  Each call leaves every in-process device and the host mirrors with what a fresh init* of the
+// edited scene would have built, resets the progressive frame and retires the sphere cost maps; nothing else a frame or a pass left behind is touched.
+static void check_update(const char* fn, bool spheres) {
+    const RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail(" before init", fn);
+    if (c.is_spheres != spheres) rt_fail(spheres ? " needs a sphere scene (initRendererSpheres)" : " needs a mesh scene (initRenderer)", fn);
+}
+
+static void scene_edited() {
+    g_ctx.prog_samples = 0;                                 // as setCamera
+    g_ctx.scene_edits++;                                    // (the cost maps of sphere frames: cost_key_of)
+}
+
+void updateTriangles(int first, int count, const rt_triangle* tris) {
+    RenderContext& c = g_ctx;
+    check_update("updateTriangles", false);
+    if (first < 0 || count < 0 || (size_t)first + (size_t)count > c.h_tris.size()) rt_fail("updateTriangles: [first, first + count) must lie inside the numTris of init");
+    if (count == 0) return;
+    if (!tris) rt_fail("updateTriangles: tris is null");
+    const uint32_t first_leaf = c.mesh_scene.first_leaf;
+    if ((first_leaf & (first_leaf - 1)) != 0) rt_fail("updateTriangles: the refit needs a tree whose number of leaves is a power of two");
+    for (int k = 0; k < count; k++) {
+        const bool sentinel = std::isinf(tris[k].v[0].e[0]);
+        if (sentinel != std::isinf(c.h_tris[(size_t)first + k].v[0].e[0])) rt_fail("updateTriangles: a slot's sentinel state (isinf(v[0].x)) must not change");
+        if (!sentinel && tris[k].meshID >= c.h_materials.size()) rt_fail("updateTriangles: triangle meshID out of range");
+    }
+    std::copy(tris, tris + count, c.h_tris.begin() + first);
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    for (DeviceState& d : c.devs) {                         // every device holds the whole scene: count * 64 bytes over the bus and one refit each
+        HIP_CHECK(hipSetDevice(d.device));
+        HIP_CHECK(hipMemcpyAsync(d.d_tris + first, c.h_tris.data() + first, (size_t)count * sizeof(rt_triangle), hipMemcpyHostToDevice, d.stream));
+        RtRefitParams q;
+        q.slots = d.d_tris; q.nodes = reinterpret_cast<float*>(d.d_bvh); q.axis = d.d_bvh_axis; q.leaf_rec = d.d_leaf_tri;
+        q.first_leaf = first_leaf; q.nppl = c.mesh_scene.nppl;
+        HIP_CHECK(hipEventRecord(d.ev_upd_start, d.stream));
+        HIP_CHECK(rt_launch_refit(q, d.stream));
+        HIP_CHECK(hipEventRecord(d.ev_upd_stop, d.stream));
+    }
+    rt_bvh_node root;                                       // the scene bounds become node 1's box
+    HIP_CHECK(hipSetDevice(c.devs[0].device));
+    HIP_CHECK(hipMemcpyAsync(&root, reinterpret_cast<const char*>(c.devs[0].d_bvh) + sizeof(rt_bvh_node), sizeof root, hipMemcpyDeviceToHost, c.devs[0].stream));
+    double ms_max = 0.0;
+    for (DeviceState& d : c.devs) {
+        HIP_CHECK(hipSetDevice(d.device));
+        HIP_CHECK(hipStreamSynchronize(d.stream));          // blocking
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, d.ev_upd_start, d.ev_upd_stop));
+        ms_max = std::max(ms_max, (double)ms);
+    }
+    HIP_CHECK(hipSetDevice(current));
+    c.mesh_scene.bounds.min = root.a;
+    c.mesh_scene.bounds.max = root.b;
+    c.refit_stale = true;
+    c.update_ms = ms_max;
+    scene_edited();
+}
+
+void updateMaterials(const rt_material* materials, int n) {
+    RenderContext& c = g_ctx;
+    check_update("updateMaterials", false);
+    if (!materials) rt_fail("updateMaterials: materials is null");
+    if (n != (int)c.h_materials.size()) rt_fail("updateMaterials: n must be the numMaterials of init");
+    for (int k = 0; k < n; k++)
+        if (materials[k].texId != -1 && (materials[k].texId < 0 || materials[k].texId >= (int)c.h_tex.size())) rt_fail("updateMaterials: material texId out of range");
+    c.h_materials.assign(materials, materials + n);
+    c.mesh_scene.lean_ok = mesh_lean_ok();
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    for (DeviceState& d : c.devs) {
+        HIP_CHECK(hipSetDevice(d.device));
+        if (n > 0) HIP_CHECK(hipMemcpy(d.d_materials, c.h_materials.data(), (size_t)n * sizeof(rt_material), hipMemcpyHostToDevice));
+    }
+    HIP_CHECK(hipSetDevice(current));
+    scene_edited();
+}
+
+void updateSpheres(const rt_sphere* spheres, const rt_material* materials, int n) {
+    RenderContext& c = g_ctx;
+    check_update("updateSpheres", true);
+    if (!spheres || !materials) rt_fail("updateSpheres: spheres and materials must not be null");
+    if (n != c.sphere_scene.n) rt_fail("updateSpheres: n must be the n of init");
+    build_sphere_scene("updateSpheres", spheres, materials, n);
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    for (DeviceState& d : c.devs) {
+        HIP_CHECK(hipSetDevice(d.device));
+        upload_sphere_arrays(d);
+    }
+    HIP_CHECK(hipSetDevice(current));
+    scene_edited();
+}
+
+int getMeshBvh(rt_bvh_node* nodes, int cap, rt_bbox* bounds) {
+    const RenderContext& c = g_ctx;
+    check_update("getMeshBvh", false);
+    const int count = (int)(2 * c.mesh_scene.first_leaf);
+    const int n = std::min(count, std::max(cap, 0));
+    if (n > 0 && !nodes) rt_fail("getMeshBvh: nodes is null");
+    if (n > 0) {
+        int current = 0;
+        HIP_CHECK(hipGetDevice(&current));
+        HIP_CHECK(hipSetDevice(c.devs[0].device));
+        HIP_CHECK(hipMemcpy(nodes, c.devs[0].d_bvh, (size_t)n * sizeof(rt_bvh_node), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipSetDevice(current));
+    }
+    if (bounds) *bounds = c.mesh_scene.bounds;
+    return count;
+}
+
+double rtLastUpdateMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastUpdateMs before init");
+    return g_ctx.update_ms;
 }
 
 // First-hit guide planes (rt_api.h).  Its own kernels, device planes and timing: nothing of a frame's state (framebuffer, stats, launch report, progressive

@@ -208,6 +208,45 @@ int rtMeshView(const rt_host_mesh* m, rt_mesh* out) {
     return m->nppl;
 }
 
+// The refit as rt_api.h defines it, in that order: min' / max' are the two ternaries below (a NaN never wins, the first of two zeros stays).
+int rtRefitBvhArrays(const rt_triangle* tris, uint32_t numTris, rt_bvh_node* bvh, int numBvhNodes, int nppl, rt_bbox* bounds) {
+    if (!tris || !bvh || numBvhNodes < 4 || (numBvhNodes & 1) || nppl <= 0) return -1;
+    const uint32_t first_leaf = (uint32_t)numBvhNodes / 2;
+    if ((unsigned long long)first_leaf * (unsigned)nppl > numTris || first_leaf > (1u << 30)) return -1;
+    for (uint32_t leaf = 0; leaf < first_leaf; leaf++) {
+        rt_bvh_node n;
+        for (int a = 0; a < 3; a++) { n.a.e[a] = INFINITY; n.b.e[a] = -INFINITY; }
+        for (int k = 0; k < nppl; k++) {
+            const rt_triangle& t = tris[(size_t)leaf * nppl + k];
+            if (std::isinf(t.v[0].e[0])) break;                     // the traversal's leaf loop stops there too (kernels.cu:202)
+            for (int v = 0; v < 3; v++)
+                for (int a = 0; a < 3; a++) {
+                    const float p = t.v[v].e[a];
+                    n.a.e[a] = p < n.a.e[a] ? p : n.a.e[a];
+                    n.b.e[a] = p > n.b.e[a] ? p : n.b.e[a];
+                }
+        }
+        bvh[first_leaf + leaf] = n;
+    }
+    for (uint32_t i = first_leaf - 1; i >= 1; i--) {
+        const rt_bvh_node& L = bvh[2 * i];
+        const rt_bvh_node& R = bvh[2 * i + 1];
+        rt_bvh_node n;
+        for (int a = 0; a < 3; a++) {
+            n.a.e[a] = R.a.e[a] < L.a.e[a] ? R.a.e[a] : L.a.e[a];
+            n.b.e[a] = R.b.e[a] > L.b.e[a] ? R.b.e[a] : L.b.e[a];
+        }
+        bvh[i] = n;
+    }
+    if (bounds) { bounds->min = bvh[1].a; bounds->max = bvh[1].b; }
+    return 0;
+}
+
+int rtRefitBvh(rt_host_mesh* m) {
+    if (!m) return -1;
+    return rtRefitBvhArrays(m->tris.data(), (uint32_t)m->tris.size(), m->bvh.data(), (int)m->bvh.size(), m->nppl, &m->bounds);
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------

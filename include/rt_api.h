@@ -231,7 +231,9 @@ double rtLastDenoiseMs(void);
  *
  * A still camera gains nothing: the seed of a pixel's sample stream depends on the pixel alone, so a camera that does not move renders the same noise in every
  * frame and the blend returns it.  Accumulation pays off when the image moves by about a pixel or more per frame; a still camera is what
- * runRendererProgressive is for.  Geometry that moves between calls is not followed (the scene is fixed after init).
+ * runRendererProgressive is for.  A scene edit (updateTriangles, updateMaterials, updateSpheres below) keeps this history and previewFrame's: what moved
+ * is rejected pixel by pixel by the plane-distance, normal and (with SAME_PRIM) primitive tests above, what stayed keeps its history; rtResetHistory /
+ * rtResetPreview are there for a caller who wants a clean start after an edit.
  *
  * accumulateFrame: `in`, `out` as denoiseFrame's - `in` NULL = the framebuffer the renderer currently delivers into, `out` caller-owned and never NULL, `out`
  * may be `in`; blocking.  `history` = NULL, or nx*ny floats that receive N(p).  flags = the denoiser's bits with the same meaning, default
@@ -404,6 +406,44 @@ void   traceRays(int n, const float* org, const float* dir, const float* t_min, 
                  float* t, int32_t* prim, float* normal, float* uv, int32_t* nodes);
 void   occludedRays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, uint8_t* occluded);
 double rtLastRaysMs(void);   /* HIP-event time of the ray kernels of the last traceRays / occludedRays (not the copies), summed over its chunks; 0 before the first */
+
+/* --- editing the scene: move, recolour, animate without a new init ---------------------------------------------------------------
+ * The calls below change the scene the renderer holds, in place, on every in-process device: a picked object (traceRays) is moved or recoloured, an
+ * animation is played, without cleanupRenderer + init*.  The contract they share: after ANY sequence of them everything the library computes - runRenderer
+ * in both fp modes, runRendererProgressive, renderGuides, traceRays / occludedRays, the preview passes, the counters = 1 statistics, node visits included -
+ * is bit-identical to cleanupRenderer + init* with the edited scene followed by the same setRenderOptions and setCamera.  For a mesh the edited scene is the
+ * edited triangles with the REFITTED tree: the tree's shape and the triangles' slots stay, every box is recomputed.  The refit, stated once:
+ *   first_leaf = numBvhNodes / 2;  lo = min'(lo, p) means p < lo ? p : lo;  hi = max'(hi, p) means p > hi ? p : hi  (a NaN never wins; of two zeros of
+ *   different sign the one met first stays, which the order below decides)
+ *   Leaf L in [first_leaf, 2 * first_leaf):  lo = (+inf, +inf, +inf), hi = (-inf, -inf, -inf); for the slots k = 0 .. nppl-1 of tris[(L - first_leaf) * nppl + k]
+ *     in order, stopping at the first sentinel (v[0].x is +-inf, as the traversal's leaf loop stops): for the vertices 0, 1, 2 and within a vertex the axes
+ *     x, y, z:  lo[axis] = min'(lo[axis], p),  hi[axis] = max'(hi[axis], p).  An empty leaf keeps (+inf, -inf).
+ *   Internal node i in [1, first_leaf), children L = 2i and R = 2i + 1, per axis:  lo = lo_R < lo_L ? lo_R : lo_L;  hi = hi_R > hi_L ? hi_R : hi_L.
+ *   Node 0 is never read or written.  The scene bounds become node 1's box.
+ * Only comparisons: the refitted tree is defined bit for bit.  rtRefitBvh / rtRefitBvhArrays (rt_host.h) compute it on the CPU, so "edit the triangles of a
+ * host mesh, refit it" is the scene the CPU oracle renders, and in PARITY mode the device's frame equals the oracle's.  The device computes it in two to four
+ * kernel launches whatever the size of the edit; the tree is always refitted as a whole.
+ *
+ * updateTriangles  mesh scenes.  Replaces slots [first, first + count) of the leaf-ordered triangle array passed to initRenderer (count * 64 bytes cross the
+ *                  bus) and refits on every in-process device.  Blocking.  count == 0 returns at once and changes nothing.  The caller owes finite vertices:
+ *                  a NaN coordinate is ignored by the boxes and only that triangle's hits are unspecified.
+ * updateMaterials  mesh scenes.  Replaces the material array (n = the numMaterials of init); the textures stay.
+ * updateSpheres    sphere scenes.  Replaces spheres and materials (n = the n of init); the renderer's grouping of the spheres is rebuilt on the host.
+ * getMeshBvh       mesh scenes.  The first device's current nodes: writes min(cap, numBvhNodes) nodes (nodes may be NULL when cap <= 0) and, unless bounds is NULL,
+ *                  the scene bounds; returns numBvhNodes.
+ * An edit resets the progressive frame, as setCamera does, and retires the cost maps of sphere frames.  It does NOT touch the framebuffer, getRenderStats,
+ * rtLastLaunches, the histories of accumulateFrame / previewFrame (see there), displayFrame's adapted exposure and the other rtLast*Ms values.  A later
+ * setRenderOptions that changes the device layout re-uploads the EDITED scene.
+ * Misuse (rt error, exit 99): any of the five before init; updateTriangles / updateMaterials / getMeshBvh on a sphere scene, updateSpheres on a mesh scene;
+ * first < 0, count < 0, first + count > numTris, a NULL pointer with count > 0 (updateMaterials, updateSpheres: any NULL pointer); a slot whose sentinel state
+ * would change - isinf(v[0].x) must be the same before and after; a real triangle's meshID >= numMaterials; n different from init's; a material texId
+ * (updateMaterials) or type (updateSpheres) that init* would refuse; updateTriangles on a tree whose number of leaves is not a power of two (every tree of
+ * rtBuildBvh* is one). */
+void   updateTriangles(int first, int count, const rt_triangle* tris);
+void   updateMaterials(const rt_material* materials, int n);
+void   updateSpheres(const rt_sphere* spheres, const rt_material* materials, int n);
+int    getMeshBvh(rt_bvh_node* nodes, int cap, rt_bbox* bounds);
+double rtLastUpdateMs(void);   /* HIP-event time of the refit kernels of the last updateTriangles (not the copies), the largest over the in-process devices; 0 before the first */
 
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,

@@ -65,6 +65,14 @@ void rtFreeMesh(rt_host_mesh* m);
 /* Fills an rt_mesh view (pointers stay owned by m) and returns nppl. */
 int  rtMeshView(const rt_host_mesh* m, rt_mesh* out);
 
+/* The refit of rt_api.h ("editing the scene": the definition is stated there, once) on the CPU, in plain C++: every node 1 .. numBvhNodes-1 from the
+ * triangles as they are now, bottom up, and *bounds (unless NULL) = node 1's box.  Node 0 is neither read nor written.  It is what updateTriangles computes
+ * on the device, bit for bit: "edit the triangles in place, then refit" yields the scene the CPU oracle renders.  Returns 0, or -1 for arrays initRenderer
+ * would refuse (a NULL pointer, numBvhNodes odd or below 4, nppl <= 0, (numBvhNodes / 2) * nppl > numTris, more than 2^30 leaves); nothing is written then. */
+int rtRefitBvhArrays(const rt_triangle* tris, uint32_t numTris, rt_bvh_node* bvh, int numBvhNodes, int nppl, rt_bbox* bounds);
+/* The same on an owned mesh: its nodes and bounds in place (views taken with rtMeshView before keep their pointers; take the bounds again). */
+int rtRefitBvh(rt_host_mesh* m);
+
 /* Procedural stand-in for the staircase asset (absent from the reference snapshot, SURVEY.md
  * §7.4 H6): a room with a flight of steps, a glass ball, a metal ball and boxes, sized to the
  * staircase camera and light of staircase_scene.h:62-73 / kernels.cu:93.  Writes up to cap
