@@ -137,14 +137,15 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "previewFrame", "rtResetPreview", "rtPreviewFrames", "rtLastPreviewMs",
                     "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs",
                     "traceRays", "occludedRays", "rtLastRaysMs",
-                    "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs"]
+                    "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
+                    "rebuildBvh", "rtLastRebuildMs"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
 HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtSceneRandomSpheres", "rtStaircaseCamera",
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
-                "rtDisplayFrameHost", "rtCentreRays", "rtRefitBvhArrays", "rtRefitBvh"]
+                "rtDisplayFrameHost", "rtCentreRays", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh"]
 
 _renderer = None
 _host = None
@@ -201,6 +202,10 @@ def load_host():
         h.rtRefitBvhArrays.restype = C.c_int
         h.rtRefitBvh.argtypes = [C.c_void_p]
         h.rtRefitBvh.restype = C.c_int
+        h.rtRebuildBvhArrays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.POINTER(bbox), C.c_void_p]
+        h.rtRebuildBvhArrays.restype = C.c_int
+        h.rtRebuildBvh.argtypes = [C.c_void_p, C.c_void_p]
+        h.rtRebuildBvh.restype = C.c_int
         _host = h
     return _host
 
@@ -323,6 +328,10 @@ def load_renderer():
         r.getMeshBvh.restype = C.c_int
         r.rtLastUpdateMs.argtypes = []
         r.rtLastUpdateMs.restype = C.c_double
+        r.rebuildBvh.argtypes = [C.c_void_p]
+        r.rebuildBvh.restype = None
+        r.rtLastRebuildMs.argtypes = []
+        r.rtLastRebuildMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -409,6 +418,16 @@ class HostMesh:
             raise ValueError("rtRefitBvh refused the mesh")
         self.nppl = load_host().rtMeshView(self._h, C.byref(self.view))
 
+    def rebuild(self):
+        """rtRebuildBvh: the visible triangles assigned to the leaf slots anew by the builder, the tree's shape kept, then the refit - the rebuild include/rt_api.h
+        defines and rebuildBvh computes on the device.  Returns old_slot (int32, one entry per slot: the slot its triangle came from, -1 for a sentinel).
+        `.tris`, `.bvh` and `.view` follow."""
+        old_slot = np.zeros(self.view.numTris, np.int32)
+        if load_host().rtRebuildBvh(self._h, old_slot.ctypes.data) != 0:
+            raise ValueError("rtRebuildBvh refused the mesh")
+        self.nppl = load_host().rtMeshView(self._h, C.byref(self.view))
+        return old_slot
+
     def close(self):
         if self._h:
             load_host().rtFreeMesh(self._h)
@@ -475,7 +494,7 @@ def initRenderer(ksc, cam, nx, ny, maxDepth, keepalive=None):
     r = load_renderer()
     fbp = C.POINTER(vec3)()
     r.initRenderer(ksc, cam, C.byref(fbp), nx, ny, maxDepth)
-    _state.update(fb=_fb_view(fbp, nx, ny), nx=nx, ny=ny, keep=keepalive, spheres=False)
+    _state.update(fb=_fb_view(fbp, nx, ny), nx=nx, ny=ny, keep=keepalive, spheres=False, num_tris=int(ksc.m.contents.numTris))
     return _state["fb"]
 
 
@@ -669,6 +688,49 @@ def mesh_bvh():
 def last_update_ms():
     """HIP-event time of the refit kernels of the last update_triangles (the largest over the in-process devices), in milliseconds; 0 before the first."""
     return load_renderer().rtLastUpdateMs()
+
+
+def _header_constant(name):
+    """An integer #define of include/rt_api.h (a literal or 1 << k): constants the header exports are read from it, not written down twice."""
+    import re
+    text = open(os.path.join(os.path.dirname(_HERE), "include", "rt_api.h")).read()
+    m = re.search(r"^#define\s+%s\s+\(?\s*(\d+)\s*(?:<<\s*(\d+))?\s*\)?\s*$" % name, text, re.M)
+    if not m:
+        raise ImportError(f"include/rt_api.h does not define {name}")
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+RT_REBUILD_TILE = _header_constant("RT_REBUILD_TILE")            # elements one workgroup of the rebuild's scan kernels covers
+RT_REBUILD_MAX_TRIS = _header_constant("RT_REBUILD_MAX_TRIS")
+
+
+def rebuild_bvh():
+    """Re-splits the BVH of a mesh scene on every device (rebuildBvh): the tree's shape stays, the triangles are assigned to leaf slots anew, the boxes are
+    refitted.  Blocking.  Returns old_slot: int32, one entry per slot of the triangle array - the slot its triangle came from, -1 for a sentinel."""
+    r = load_renderer()
+    old_slot = np.zeros(int(_state.get("num_tris") or 0) if not _state.get("spheres") else 0, np.int32)
+    r.rebuildBvh(old_slot.ctypes.data if len(old_slot) else None)
+    return old_slot
+
+
+def last_rebuild_ms():
+    """HIP-event time of the build and refit kernels of the last rebuild_bvh (the largest over the in-process devices), in milliseconds; 0 before the first."""
+    return load_renderer().rtLastRebuildMs()
+
+
+def rebuild_bvh_arrays(tris, bvh, nppl):
+    """rtRebuildBvhArrays on caller-owned arrays: rebuilds in place `tris` (1-D triangle_dtype, writable) and `bvh` (1-D bvh_node_dtype, writable).  Returns
+    (bounds, old_slot) - the bounds as a (2, 3) float32 array, old_slot as int32 per slot - or None where the library refuses the arrays (-1)."""
+    for name, a, dt in (("tris", tris, triangle_dtype), ("bvh", bvh, bvh_node_dtype)):
+        if not (isinstance(a, np.ndarray) and a.dtype == dt and a.ndim == 1 and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"]):
+            raise ValueError(f"rebuild_bvh_arrays: {name} must be a writable C-contiguous one-dimensional array of its record dtype")
+    if isinstance(nppl, bool) or not isinstance(nppl, (int, np.integer)):
+        raise ValueError("rebuild_bvh_arrays: nppl must be an integer")
+    b = bbox()
+    old_slot = np.zeros(len(tris), np.int32)
+    if load_host().rtRebuildBvhArrays(tris.ctypes.data, len(tris), bvh.ctypes.data, len(bvh), int(nppl), C.byref(b), old_slot.ctypes.data) != 0:
+        return None
+    return np.array([list(b.min.e), list(b.max.e)], np.float32), old_slot
 
 
 def refit_bvh_arrays(tris, bvh, nppl):

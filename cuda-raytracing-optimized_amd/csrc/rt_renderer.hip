@@ -32,6 +32,7 @@
 #include "rt_preview.h"
 #include "rt_display.h"
 #include "rt_update.h"
+#include "rt_build.h"
 
 namespace {
 
@@ -88,6 +89,7 @@ struct DeviceState {
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     hipEvent_t ev_upd_start = nullptr, ev_upd_stop = nullptr;   // around the refit kernels of updateTriangles (rtLastUpdateMs): a frame's and the guides' timings stay theirs
+    hipEvent_t ev_reb_start = nullptr, ev_reb_stop = nullptr;   // around the build + refit kernels of rebuildBvh (rtLastRebuildMs)
     RtSphereParams* d_params = nullptr; // device copy of the sphere kernel's parameter block (RtSphereParams::self), one per DeviceState
     RtSphereParams* h_params = nullptr; // its pinned staging copy (the source of the asynchronous upload must outlive the call)
     // sphere scene
@@ -105,6 +107,10 @@ struct DeviceState {
     float4* d_leaf_tri = nullptr;
     uint32_t* d_leaf_ofs = nullptr;
     rt_material* d_materials = nullptr;
+    rt_triangle* d_tris_alt = nullptr;  // rebuildBvh: the second slot buffer (the rebuilt order is written there, then the two are swapped),
+    int32_t* d_old_slot = nullptr;      // the permutation of the last rebuild and
+    uint32_t* d_build_work = nullptr;   // the build's workspace of build_words words; allocated by the first rebuild on this device
+    size_t build_words = 0;
     float** d_tex_data = nullptr;
     int32_t* d_tex_width = nullptr;
     int32_t* d_tex_height = nullptr;
@@ -174,6 +180,7 @@ struct RenderContext {
     int scene_edits = 0;                // updateTriangles / updateMaterials / updateSpheres calls that changed the scene: likewise
     bool refit_stale = false;           // the devices' nodes, child-pair records and leaf records are newer than h_bvh / h_bvh_axis / h_leaf_tri (fetch_refit)
     double update_ms = 0.0;             // rtLastUpdateMs
+    double rebuild_ms = 0.0;            // rtLastRebuildMs
     double guides_ms = 0.0;             // rtLastGuidesMs
     double denoise_ms = 0.0;            // rtLastDenoiseMs
     double accumulate_ms = 0.0;         // rtLastAccumulateMs
@@ -290,6 +297,8 @@ void free_device(DeviceState& d) {
     if (d.ev_stop) HIP_CHECK(hipEventDestroy(d.ev_stop));
     if (d.ev_upd_start) HIP_CHECK(hipEventDestroy(d.ev_upd_start));
     if (d.ev_upd_stop) HIP_CHECK(hipEventDestroy(d.ev_upd_stop));
+    if (d.ev_reb_start) HIP_CHECK(hipEventDestroy(d.ev_reb_start));
+    if (d.ev_reb_stop) HIP_CHECK(hipEventDestroy(d.ev_reb_stop));
     if (d.stream) HIP_CHECK(hipStreamDestroy(d.stream));
     d = DeviceState();
 }
@@ -376,6 +385,8 @@ void setup_devices() {
         HIP_CHECK(hipEventCreate(&d.ev_stop));
         HIP_CHECK(hipEventCreate(&d.ev_upd_start));
         HIP_CHECK(hipEventCreate(&d.ev_upd_stop));
+        HIP_CHECK(hipEventCreate(&d.ev_reb_start));
+        HIP_CHECK(hipEventCreate(&d.ev_reb_stop));
         if (c.is_spheres) {
             d.d_params = dev_alloc<RtSphereParams>(d.owned, 1);
             HIP_CHECK(hipHostMalloc((void**)&d.h_params, sizeof(RtSphereParams), hipHostMallocDefault));
@@ -1451,6 +1462,88 @@ int getMeshBvh(rt_bvh_node* nodes, int cap, rt_bbox* bounds) {
 double rtLastUpdateMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastUpdateMs before init");
     return g_ctx.update_ms;
+}
+
+// rebuildBvh (rt_api.h, "editing the scene"): the level-synchronous build of rt_kernels_build.hip into the second slot buffer, the swap, the
+// refit of the new slots.  The host counts the visible triangles in its mirror (the build's n), applies the permutation to the mirror and takes the leaf
+// count bytes back; the nodes, the child-pair records and the leaf records stay on the devices until a relayout asks for them (fetch_refit).
+void rebuildBvh(int32_t* old_slot) {
+    RenderContext& c = g_ctx;
+    check_update("rebuildBvh", false);
+    RtMeshParams& mp = c.mesh_scene;
+    const uint32_t first_leaf = mp.first_leaf, per_leaf = mp.nppl;
+    if ((first_leaf & (first_leaf - 1)) != 0) rt_fail("rebuildBvh: the rebuild needs a tree whose number of leaves is a power of two");
+    const size_t slots = (size_t)first_leaf * per_leaf, num_tris = c.h_tris.size();
+    size_t n = 0;
+    for (uint32_t leaf = 0; leaf < first_leaf; leaf++)
+        for (uint32_t k = 0; k < per_leaf && !std::isinf(c.h_tris[(size_t)leaf * per_leaf + k].v[0].e[0]); k++) n++;
+    if (n > (size_t)RT_REBUILD_MAX_TRIS) rt_fail("rebuildBvh: more than RT_REBUILD_MAX_TRIS visible triangles");
+    const bool records = per_leaf <= 255;                   // as build_mesh_scene: after a rebuild the sentinels trail in every leaf
+    const size_t words = rt_build_workspace_words((uint32_t)n, first_leaf);
+    std::vector<int32_t> from(num_tris);
+    if (records) c.h_leaf_ofs.assign(((size_t)first_leaf + 3) / 4, 0u);
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    for (DeviceState& d : c.devs) {
+        HIP_CHECK(hipSetDevice(d.device));
+        if (!d.d_tris_alt) d.d_tris_alt = dev_alloc<rt_triangle>(d.owned, num_tris);
+        if (!d.d_old_slot) d.d_old_slot = dev_alloc<int32_t>(d.owned, num_tris);
+        if (d.build_words != words) {
+            dev_release(d.owned, d.d_build_work);
+            d.d_build_work = dev_alloc<uint32_t>(d.owned, words);
+            d.build_words = words;
+        }
+        if (records && !d.d_leaf_tri) d.d_leaf_tri = dev_alloc<float4>(d.owned, slots * 3);
+        if (records && !d.d_leaf_ofs) d.d_leaf_ofs = dev_alloc<uint32_t>(d.owned, ((size_t)first_leaf + 3) / 4);
+        RtBuildParams b;
+        b.slots_in = d.d_tris; b.slots_out = d.d_tris_alt; b.old_slot = d.d_old_slot; b.leaf_ofs = records ? d.d_leaf_ofs : nullptr; b.work = d.d_build_work;
+        b.num_tris = (uint32_t)num_tris; b.first_leaf = first_leaf; b.nppl = per_leaf; b.n = (uint32_t)n;
+        HIP_CHECK(hipEventRecord(d.ev_reb_start, d.stream));
+        HIP_CHECK(rt_launch_rebuild(b, d.stream));
+        std::swap(d.d_tris, d.d_tris_alt);
+        if (d.d_leaf_tri) HIP_CHECK(hipMemsetAsync(d.d_leaf_tri, 0, slots * 3 * sizeof(float4), d.stream));   // (the refit writes the real slots only)
+        RtRefitParams q;
+        q.slots = d.d_tris; q.nodes = reinterpret_cast<float*>(d.d_bvh); q.axis = d.d_bvh_axis; q.leaf_rec = d.d_leaf_tri;
+        q.first_leaf = first_leaf; q.nppl = per_leaf;
+        HIP_CHECK(rt_launch_refit(q, d.stream));
+        HIP_CHECK(hipEventRecord(d.ev_reb_stop, d.stream));
+    }
+    const DeviceState& d0 = c.devs[0];
+    rt_bvh_node root;
+    HIP_CHECK(hipSetDevice(d0.device));
+    HIP_CHECK(hipMemcpyAsync(&root, reinterpret_cast<const char*>(d0.d_bvh) + sizeof(rt_bvh_node), sizeof root, hipMemcpyDeviceToHost, d0.stream));
+    HIP_CHECK(hipMemcpyAsync(from.data(), d0.d_old_slot, num_tris * sizeof(int32_t), hipMemcpyDeviceToHost, d0.stream));
+    if (records) HIP_CHECK(hipMemcpyAsync(c.h_leaf_ofs.data(), d0.d_leaf_ofs, c.h_leaf_ofs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, d0.stream));
+    double ms_max = 0.0;
+    for (DeviceState& d : c.devs) {
+        HIP_CHECK(hipSetDevice(d.device));
+        HIP_CHECK(hipStreamSynchronize(d.stream));          // blocking
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, d.ev_reb_start, d.ev_reb_stop));
+        ms_max = std::max(ms_max, (double)ms);
+    }
+    HIP_CHECK(hipSetDevice(current));
+    {   // the host mirror of the triangles follows the permutation
+        rt_triangle sentinel;
+        memset(&sentinel, 0, sizeof sentinel);
+        for (int v = 0; v < 3; v++) for (int a = 0; a < 3; a++) sentinel.v[v].e[a] = INFINITY;
+        std::vector<rt_triangle> moved(num_tris);
+        for (size_t s = 0; s < num_tris; s++) moved[s] = from[s] < 0 ? sentinel : c.h_tris[(size_t)from[s]];
+        c.h_tris.swap(moved);
+    }
+    if (records) c.h_leaf_tri.resize(slots * 3);            // (fetch_refit fills it)
+    mp.leaf_sentinels_trailing = 1;
+    mp.bounds.min = root.a;
+    mp.bounds.max = root.b;
+    c.refit_stale = true;
+    c.rebuild_ms = ms_max;
+    if (old_slot) std::copy(from.begin(), from.end(), old_slot);
+    scene_edited();
+}
+
+double rtLastRebuildMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastRebuildMs before init");
+    return g_ctx.rebuild_ms;
 }
 
 // First-hit guide planes (rt_api.h).  Its own kernels, device planes and timing: nothing of a frame's state (framebuffer, stats, launch report, progressive

@@ -55,6 +55,7 @@ struct Builder {
     rt_host_mesh* out;
     int numLeaves;
     int nppl;
+    std::vector<int32_t>* slot_src = nullptr;   // unless null: per output slot, the index into `in` of the triangle written there (rtRebuildBvhArrays)
 
     explicit Builder(const std::vector<rt_triangle>& t) : in(t) {}
 
@@ -70,7 +71,10 @@ struct Builder {
         set_node(idx, nb);
         if (leaves == 1) {
             const int leaf = idx - numLeaves;
-            for (int i = begin; i < end; i++) out->tris[(size_t)leaf * nppl + (i - begin)] = in[order[i]];
+            for (int i = begin; i < end; i++) {
+                out->tris[(size_t)leaf * nppl + (i - begin)] = in[order[i]];
+                if (slot_src) (*slot_src)[(size_t)leaf * nppl + (i - begin)] = order[i];
+            }
             return nb;
         }
         const int n = end - begin;
@@ -116,6 +120,32 @@ rt_triangle sentinel_triangle() {
     return t;
 }
 
+// The builder over a tree of `leaves` leaf slots (a power of two, leaves * nppl >= in.size()): rtBuildBvhLevels chooses the leaf count from the triangle count,
+// rtRebuildBvhArrays keeps the tree's.  slot_src, unless null, receives per slot the index into `in` of its triangle, -1 for a sentinel.
+rt_host_mesh* build_tree(const std::vector<rt_triangle>& in, int nppl, int leaves, std::vector<int32_t>* slot_src) {
+    const int num_tris = (int)in.size();
+    rt_host_mesh* m = new rt_host_mesh();
+    m->nppl = nppl;
+    m->tris.assign((size_t)leaves * nppl, sentinel_triangle());
+    m->bvh.resize((size_t)2 * leaves);
+    memset(m->bvh.data(), 0, sizeof(rt_bvh_node));
+    if (slot_src) slot_src->assign((size_t)leaves * nppl, -1);
+
+    Builder b(in);
+    b.out = m; b.numLeaves = leaves; b.nppl = nppl; b.slot_src = slot_src;
+    b.boxes.resize(num_tris);
+    for (int a = 0; a < 3; a++) b.cent[a].resize(num_tris);
+    b.order.resize(num_tris);
+    for (int i = 0; i < num_tris; i++) {
+        b.boxes[i] = tri_box(in[i]);
+        for (int a = 0; a < 3; a++) b.cent[a][i] = 0.5f * (b.boxes[i].lo[a] + b.boxes[i].hi[a]);
+        b.order[i] = i;
+    }
+    const Box root = b.build(1, 0, num_tris, leaves);
+    for (int a = 0; a < 3; a++) { m->bounds.min.e[a] = root.lo[a]; m->bounds.max.e[a] = root.hi[a]; }
+    return m;
+}
+
 }  // namespace
 
 extern "C" {
@@ -136,25 +166,7 @@ rt_host_mesh* rtBuildBvhLevels(const rt_triangle* tris, int num_tris, int nppl, 
     for (int k = 0; k < extra_levels && leaves < (1 << 30); k++) leaves *= 2;
     if (leaves > (1 << 30)) return nullptr;           // bit-stack depth limit of the traversal (32 bits)
 
-    rt_host_mesh* m = new rt_host_mesh();
-    m->nppl = nppl;
-    m->tris.assign((size_t)leaves * nppl, sentinel_triangle());
-    m->bvh.resize((size_t)2 * leaves);
-    memset(m->bvh.data(), 0, sizeof(rt_bvh_node));
-
-    Builder b(in);
-    b.out = m; b.numLeaves = leaves; b.nppl = nppl;
-    b.boxes.resize(num_tris);
-    for (int a = 0; a < 3; a++) b.cent[a].resize(num_tris);
-    b.order.resize(num_tris);
-    for (int i = 0; i < num_tris; i++) {
-        b.boxes[i] = tri_box(in[i]);
-        for (int a = 0; a < 3; a++) b.cent[a][i] = 0.5f * (b.boxes[i].lo[a] + b.boxes[i].hi[a]);
-        b.order[i] = i;
-    }
-    const Box root = b.build(1, 0, num_tris, leaves);
-    for (int a = 0; a < 3; a++) { m->bounds.min.e[a] = root.lo[a]; m->bounds.max.e[a] = root.hi[a]; }
-    return m;
+    return build_tree(in, nppl, leaves, nullptr);
 }
 
 static const char kBvhHeader[] = "BVH_00.04";        // staircase_scene.h:78, written with its NUL
@@ -245,6 +257,41 @@ int rtRefitBvhArrays(const rt_triangle* tris, uint32_t numTris, rt_bvh_node* bvh
 int rtRefitBvh(rt_host_mesh* m) {
     if (!m) return -1;
     return rtRefitBvhArrays(m->tris.data(), (uint32_t)m->tris.size(), m->bvh.data(), (int)m->bvh.size(), m->nppl, &m->bounds);
+}
+
+
+// The rebuild as rt_api.h defines it ("editing the scene"): the visible triangles in slot order through the builder above with the tree's own leaf count, then
+// the refit.  Nothing is written before every refusal has been ruled out.
+int rtRebuildBvhArrays(rt_triangle* tris, uint32_t numTris, rt_bvh_node* bvh, int numBvhNodes, int nppl, rt_bbox* bounds, int32_t* old_slot) {
+    if (!tris || !bvh || numBvhNodes < 4 || (numBvhNodes & 1) || nppl <= 0) return -1;
+    const uint32_t first_leaf = (uint32_t)numBvhNodes / 2;
+    if ((unsigned long long)first_leaf * (unsigned)nppl > numTris || first_leaf > (1u << 30)) return -1;
+    if ((first_leaf & (first_leaf - 1)) != 0) return -1;
+    const size_t slots = (size_t)first_leaf * nppl;
+    if (slots > (size_t)INT32_MAX) return -1;
+    std::vector<rt_triangle> in;
+    std::vector<int32_t> src;
+    for (uint32_t leaf = 0; leaf < first_leaf; leaf++)
+        for (int k = 0; k < nppl; k++) {
+            const size_t s = (size_t)leaf * nppl + k;
+            if (std::isinf(tris[s].v[0].e[0])) break;
+            in.push_back(tris[s]);
+            src.push_back((int32_t)s);
+        }
+    std::vector<int32_t> slot_src;
+    rt_host_mesh* built = build_tree(in, nppl, (int)first_leaf, &slot_src);
+    std::copy(built->tris.begin(), built->tris.end(), tris);
+    delete built;
+    if (old_slot) {
+        for (size_t s = 0; s < slots; s++) old_slot[s] = slot_src[s] < 0 ? -1 : src[slot_src[s]];
+        for (size_t s = slots; s < numTris; s++) old_slot[s] = (int32_t)s;
+    }
+    return rtRefitBvhArrays(tris, numTris, bvh, numBvhNodes, nppl, bounds);
+}
+
+int rtRebuildBvh(rt_host_mesh* m, int32_t* old_slot) {
+    if (!m) return -1;
+    return rtRebuildBvhArrays(m->tris.data(), (uint32_t)m->tris.size(), m->bvh.data(), (int)m->bvh.size(), m->nppl, &m->bounds, old_slot);
 }
 
 }  // extern "C"

@@ -422,7 +422,8 @@ double rtLastRaysMs(void);   /* HIP-event time of the ray kernels of the last tr
  *   Node 0 is never read or written.  The scene bounds become node 1's box.
  * Only comparisons: the refitted tree is defined bit for bit.  rtRefitBvh / rtRefitBvhArrays (rt_host.h) compute it on the CPU, so "edit the triangles of a
  * host mesh, refit it" is the scene the CPU oracle renders, and in PARITY mode the device's frame equals the oracle's.  The device computes it in two to four
- * kernel launches whatever the size of the edit; the tree is always refitted as a whole.
+ * kernel launches whatever the size of the edit; the tree is always refitted as a whole.  A refit keeps every triangle in its slot: after
+ * large moves the boxes overlap and rays visit more nodes - rebuildBvh (below) assigns the triangles to the leaves anew.
  *
  * updateTriangles  mesh scenes.  Replaces slots [first, first + count) of the leaf-ordered triangle array passed to initRenderer (count * 64 bytes cross the
  *                  bus) and refits on every in-process device.  Blocking.  count == 0 returns at once and changes nothing.  The caller owes finite vertices:
@@ -444,6 +445,35 @@ void   updateMaterials(const rt_material* materials, int n);
 void   updateSpheres(const rt_sphere* spheres, const rt_material* materials, int n);
 int    getMeshBvh(rt_bvh_node* nodes, int cap, rt_bbox* bounds);
 double rtLastUpdateMs(void);   /* HIP-event time of the refit kernels of the last updateTriangles (not the copies), the largest over the in-process devices; 0 before the first */
+
+/* rebuildBvh       mesh scenes.  Re-splits the tree on every in-process device: the shape stays (numBvhNodes, first_leaf = numBvhNodes / 2, nppl, numTris),
+ *                  the triangles are assigned to leaf slots anew, then the tree is refitted.  Blocking.  It is an edit: the contract above holds for any
+ *                  sequence of edits and rebuilds - the rebuilt scene is the one rtRebuildBvh / rtRebuildBvhArrays (rt_host.h) compute on the CPU, bit for
+ *                  bit, getMeshBvh and rtLastLaunches included - and what an edit resets or leaves alone is reset or left alone.  The rebuild, stated once:
+ *   Input: the triangles the traversal can see - leaves 0 .. first_leaf-1 in order, within a leaf the slots k = 0 .. nppl-1 up to the first sentinel
+ *     (isinf(v[0].x)) - are triangles i = 0 .. n-1 in that order.  A real triangle behind a sentinel is invisible to every ray; it is dropped (its slot
+ *     becomes a sentinel).  Slots at or beyond first_leaf * nppl are not touched.
+ *   Per triangle: box = min / max over the three vertices; cent[a] = 0.5f * (lo[a] + hi[a]) (one rounded add, one rounded multiply);
+ *     area(box) = hi[0] < lo[0] ? 0 : 2.0f * (dx*dy + dy*dz + dz*dx) with d = hi - lo, every operation rounded on its own, operands in that order, no FMA.
+ *     Boxes enter only through area and cent; an area does not depend on the sign of a zero and centroids are compared as numbers (-0 == +0), so the order
+ *     in which a box is accumulated is free.
+ *   Node idx with `leaves` leaf slots below it and the triangle set S, m = |S| (the root: all n, leaves = first_leaf):  capHalf = (leaves / 2) * nppl;
+ *     lo = max(m - capHalf, m > 1 ? 1 : 0);  hi = min(capHalf, m > 1 ? m - 1 : m).  For axis 0, 1, 2 order S by (cent[axis], i);
+ *     cost(axis, cut) = area(first cut) * (float)cut + area(the rest) * (float)(m - cut), the area of an empty rest being 0.0f.  The winner is the first
+ *     (axis, cut), axis-major with cut ascending over [max(lo, 1), hi], whose cost is strictly below every earlier one and below +inf; a NaN cost never
+ *     wins; without a winner axis 0 and cut (m + 1) / 2.  nl = min(max(cut, lo), hi); with m == 0, nl = 0.  The left child gets the first nl triangles
+ *     of the winning axis's order, the right child the rest.
+ *   Leaf L holds its triangles in the order of its parent's winning axis in slots 0 .., sentinels (all nine coordinates +inf, everything else zero) follow.
+ *   Nodes 1 .. and the scene bounds: the refit (above) of the new slots.
+ *                  old_slot, unless NULL, receives numTris entries: the slot the triangle now in slot s came from, -1 for a sentinel, s itself at or
+ *                  beyond first_leaf * nppl.  The caller owes finite vertices, as for updateTriangles.  Adding or removing triangles stays a new init.
+ *                  The device builds level by level; RT_REBUILD_TILE is the number of elements one workgroup of its scans covers.
+ * Misuse (rt error, exit 99): either call before init; rebuildBvh on a sphere scene, on a tree whose number of leaves is not a power of two, or with more
+ * than RT_REBUILD_MAX_TRIS visible triangles. */
+#define RT_REBUILD_MAX_TRIS (1 << 24)
+#define RT_REBUILD_TILE 256
+void   rebuildBvh(int32_t* old_slot);
+double rtLastRebuildMs(void);  /* HIP-event time of the build + refit kernels of the last rebuildBvh, the largest over the in-process devices; 0 before the first */
 
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,

@@ -73,6 +73,15 @@ int rtRefitBvhArrays(const rt_triangle* tris, uint32_t numTris, rt_bvh_node* bvh
 /* The same on an owned mesh: its nodes and bounds in place (views taken with rtMeshView before keep their pointers; take the bounds again). */
 int rtRefitBvh(rt_host_mesh* m);
 
+/* The rebuild of rt_api.h ("editing the scene": the definition is stated there, once) on the CPU, in place: the triangles the traversal can see, in slot order,
+ * go through the builder of rtBuildBvhLevels with the tree's own leaf count (numBvhNodes / 2) and into the leaf slots it assigns; sentinels fill the rest of
+ * slots 0 .. (numBvhNodes / 2) * nppl - 1, later slots are not touched; then the refit above.  It is what rebuildBvh computes on the device, bit for bit.
+ * old_slot, unless NULL, receives numTris entries: the slot the triangle now in slot s came from, -1 for a sentinel, s itself at or beyond
+ * (numBvhNodes / 2) * nppl.  Returns 0, or -1 for what rtRefitBvhArrays refuses or a leaf count that is not a power of two; nothing is written then. */
+int rtRebuildBvhArrays(rt_triangle* tris, uint32_t numTris, rt_bvh_node* bvh, int numBvhNodes, int nppl, rt_bbox* bounds, int32_t* old_slot);
+/* The same on an owned mesh (views taken with rtMeshView before keep their pointers; take the bounds again). */
+int rtRebuildBvh(rt_host_mesh* m, int32_t* old_slot);
+
 /* Procedural stand-in for the staircase asset (absent from the reference snapshot, SURVEY.md
  * §7.4 H6): a room with a flight of steps, a glass ball, a metal ball and boxes, sized to the
  * staircase camera and light of staircase_scene.h:62-73 / kernels.cu:93.  Writes up to cap
