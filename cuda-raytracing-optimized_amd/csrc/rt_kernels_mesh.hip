@@ -19,6 +19,7 @@
 //   * a lean instantiation (template LEAN) for untextured scenes of the three basic materials: fewer registers, no (u, v) through the traversal.
 #include "rt_device.h"
 #include "rt_params.h"
+#include "rt_mesh_plan.h"
 
 #include <float.h>
 #include <cstdlib>
@@ -37,12 +38,6 @@ using namespace rtd;
 #endif
 
 namespace {
-
-#ifndef RT_MESH_WG_WAVES
-#define RT_MESH_WG_WAVES 4          // waves per workgroup (experiment: 16 = one workgroup per CU, one LDS copy of the tables)
-#endif
-constexpr int kWavesPerWg = RT_MESH_WG_WAVES;
-constexpr int kThreads = 64 * kWavesPerWg;
 
 __device__ __forceinline__ int global_row(const RtPartition& pt, int lr) {
     const int stripe = lr / pt.stripe_rows;
@@ -399,8 +394,7 @@ __global__ void __launch_bounds__(kThreads) k_rays_mesh(const RtMeshParams P, co
 //             exactly in the reference's order, kernels.cu:415-527) and set up their next job: the shadow ray, the next
 //             bounce, the next sample, or the next pixel from the global queue (ballot + mbcnt allocation).
 // Lanes that are still traversing simply keep their state across a PROCESS phase.
-constexpr int kMinTraversing = 40;
-constexpr uint32_t kLeafCntLds = 32768;     // leaves whose triangle counts the default kernel keeps in the LDS (one byte each, beside its 5 KB of pair-round scratch)
+// (kMinTraversing, kLeafCntLds, the workgroup's shape and the bit fields of the arguments leaf_thr and min_traversing: rt_mesh_plan.h, shared with the launcher's plan)
 
 struct Job {
     f3 d, inv;              // unit direction and its reciprocal (ray.h:9, intersections.h:28); the ORIGIN is the path's `org`: every job of a path starts there,
@@ -449,9 +443,6 @@ __device__ __forceinline__ void job_start(const RtMeshParams& P, Job& J, f3 org,
 #if RT_MESH_TAIL_DIAG
 __device__ uint32_t* g_diag_items;      // per pixel: (start, end) of its second-dispatch item, microseconds
 #endif
-#ifndef RT_MESH_LEAN_WAVES
-#define RT_MESH_LEAN_WAVES 4
-#endif
 // PHASE (the cost-ordered frame, rt_params.h): 0 = whole pixels in one dispatch (scattered order); 1 = samples [0, s_split) of every pixel, then park the pixel;
 // 2 = resume the parked pixels in the order of P.order (longest first; since round 4 from one set of lists and counters per XCD, with 32-byte records - the sphere
 // kernel's traffic forms, DESIGN.md 3.8: here they halve the reads of the parked state, the writes still leave the L2 as partial lines).  A frame ends one pixel-time after its queue runs empty, and a pixel of C4 is 1/8 of a
@@ -496,7 +487,7 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
     // pixel advances one node step per step of its wave, whose time grows with the lanes that are traversing (the loads, not their latency, bound a step): a wave
     // full of long traversals makes each of them ~1.5x longer, and the frame ends with them.  So the expensive lists (the first `heavy_cls` classes: nH pixels)
     // are SPREAD evenly over the first S queue positions, S = spread_rounds x (lanes in flight): position p takes an expensive pixel iff floor((p + 1) nH / S) >
-    // floor(p nH / S), else the next of the rest (also by descending cost).  (leaf_thr >> 8: heavy_cls | spread_rounds << 4, from the launcher.)
+    // floor(p nH / S), else the next of the rest (also by descending cost).  (kLeafHeavyClasses and kLeafSpreadRounds of leaf_thr, from the launcher's plan.)
     // One set of lists and counters for the machine, or (P.xcd_queues, as in the sphere kernel: rt_params.h) one per XCD: a wave serves the queue of the XCD it runs
     // on - the numbers below are then those of that XCD's lists and of an eighth of the grid - and when that is empty takes what the others have left (s_mx, `stolen`).
     __shared__ uint32_t s_m[4];         // [0] nH  [1] S  [2] E  [3] chain lanes (PHASE 2; of this wave's own queue)
@@ -508,18 +499,18 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
         const uint32_t grid_x = xq > 1u ? max(gridDim.x / xq, 1u) : gridDim.x;      // workgroups that serve this queue first
         uint32_t pixels = 0;
         for (int c = 0; c < 18; c++) pixels += Q[4 + c];
-        const int heavy_cls = (leaf_thr >> 8) & 0xF, rounds = (leaf_thr >> 12) & 0xF;
+        const int heavy_cls = kLeafHeavyClasses.get(leaf_thr), rounds = kLeafSpreadRounds.get(leaf_thr);
         uint32_t nH = 0;
         for (int c = 0; c < heavy_cls; c++) nH += Q[4 + c];
         // the chains: list 0 (the launcher's threshold: pixels several times the mean) goes, `chain_lanes` pixels per wave, to the first waves that ask, and those
         // waves take nothing else while these run (below); at most one wave in eight
-        uint32_t chain_lanes = (uint32_t)(leaf_thr >> 16) & 0xFFu;
+        uint32_t chain_lanes = (uint32_t)kLeafChainLanes.get(leaf_thr);
         uint32_t E = chain_lanes ? Q[4] : 0u;
         if (E > nH) E = nH;
-        if (E > (pixels >> ((leaf_thr >> 24) & 0xF))) E = 0u;
+        if (E > (pixels >> kLeafChainFrac.get(leaf_thr))) E = 0u;
         // The chains end the frame only when a pixel of 10-20 x the mean (at about half the time per node visit of a cheap one) outlasts the whole queue, i.e. when
         // the frame is less than ~16 fills of the machine (C4: 7.9; 3840x2160: 31.6 - chain waves measured -3 % there, +12 % on C4; profiles/r04_mesh_chain_scenes.txt)
-        if (((leaf_thr >> 24) & 0xF) != 0 && (uint32_t)P.part.local_rows * (uint32_t)P.nx > 16u * gridDim.x * blockDim.x) E = 0u;      // list 0 is not "a few pixels" in this scene (its threshold is absolute): no chain waves
+        if (kLeafChainFrac.get(leaf_thr) != 0 &&(uint32_t)P.part.local_rows * (uint32_t)P.nx > 16u * gridDim.x * blockDim.x) E = 0u;      // list 0 is not "a few pixels" in this scene (its threshold is absolute): no chain waves
         const uint32_t max_waves = grid_x * (blockDim.x >> 6) >> 3;
         if (max_waves == 0u) E = 0u;          // fewer than 8 waves serve this queue (a frame of < 16 workgroups): no chain waves, as the cap below gave before
         if (E > max_waves * chain_lanes) chain_lanes = min(64u, (E + max_waves - 1u) / max_waves);      // (a long list: more of its pixels per wave, not fewer of them in chain waves)
@@ -535,7 +526,7 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
     }
     if (PHASE == 2) __syncthreads();
     const int chain_lanes = PHASE == 2 ? (int)s_m[3] : 0;
-    leaf_thr &= 0xFF;
+    leaf_thr = kLeafThr.get(leaf_thr);
 
     // path state (path, helper_structs.h:48-71)
     uint32_t rng = 1;
@@ -559,8 +550,8 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
     uint32_t* const Qown = P.queue + (size_t)myx * kXcdQueueWords;
     uint32_t stolen = 0;                // (a queue per XCD) stages beyond this wave's own general queue known to be empty: stage 2k + 1 = what is left of the chain
                                         // pixels of queue (myx + k) mod 8, stage 2k + 2 = the general part of queue (myx + k + 1) mod 8
-    const bool p1seg = PHASE == 1 && (min_traversing & 256) != 0;      // first dispatch: the permutation moves row segments of 8 pixels (a line of px_state per 8 lanes)
-    min_traversing &= 255;
+    const bool p1seg = PHASE == 1 && kMinTravSegments.get(min_traversing) != 0;     // first dispatch: the permutation moves row segments of 8 pixels (a line of px_state per 8 lanes)
+    min_traversing = kMinTravLanes.get(min_traversing);
     // diagnostics (P.dbg): cycles and active lanes per phase, per wave; summed over the waves at the end
     unsigned long long g_cyc[4] = { 0, 0, 0, 0 };   // process, refill, node loop, leaf
     unsigned long long g_act[4] = { 0, 0, 0, 0 }, g_it[4] = { 0, 0, 0, 0 };   // active lanes summed over steps; steps
@@ -1170,11 +1161,34 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
 
 }  // namespace
 
-// Every launch of the persistent kernel: launch and note its template arguments for the launch report (rtLastLaunches)
-template <int TRAV, bool DBG, bool STATS, bool LEAN = false, int PHASE = 0>
-static void launch_mesh_queue(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const RtMeshParams& p, uint32_t stride, int min_traversing, int leaf_thr) {
-    hipLaunchKernelGGL((k_render_mesh_queue<TRAV, DBG, STATS, LEAN, PHASE>), grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-    rt_note_launch(RT_KERNEL_MESH_QUEUE, PHASE, TRAV, 0, (DBG ? 1 : 0) | (STATS ? 2 : 0), 0, LEAN ? 1 : 0, (int)block.x, grid.x);
+// One instantiation of k_render_mesh_queue, named by its template arguments: launch_mesh_queue launches it with the plan's grid and LDS and notes those
+// arguments for the launch report (rtLastLaunches).  Every launch of the persistent kernel goes through it.
+template <int TRAV, bool DBG, bool STATS, bool LEAN, int PHASE> struct MeshQueueForm {};
+
+template <int TRAV, bool DBG, bool STATS, bool LEAN, int PHASE>
+static hipError_t launch_mesh_queue(MeshQueueForm<TRAV, DBG, STATS, LEAN, PHASE>, const MeshPlan& pl, const RtMeshParams& q, hipStream_t stream,
+                                    uint32_t stride, int min_traversing, int leaf_thr) {
+    hipLaunchKernelGGL((k_render_mesh_queue<TRAV, DBG, STATS, LEAN, PHASE>), dim3(pl.grid_x), dim3(pl.threads), pl.lds, stream, q, stride, min_traversing, leaf_thr);
+    rt_note_launch(RT_KERNEL_MESH_QUEUE, PHASE, TRAV, 0, (DBG ? 1 : 0) | (STATS ? 2 : 0), 0, LEAN ? 1 : 0, pl.threads, pl.grid_x);
+    return hipGetLastError();
+}
+
+// The planned instantiation (TRAV, DBG, STATS, LEAN) of one dispatch (PHASE).  The classic traversal and the diagnostic and counting instantiations exist as
+// single dispatches only; the lean kernel is never one of them (plan_mesh).
+template <int PHASE>
+static hipError_t launch_mesh_form(const MeshPlan& pl, const RtMeshParams& q, hipStream_t stream, uint32_t stride, int min_traversing, int leaf_thr) {
+    auto go = [&](auto form) -> hipError_t { return launch_mesh_queue(form, pl, q, stream, stride, min_traversing, leaf_thr); };
+    if constexpr (PHASE == 0) {
+        if (pl.trav == 1 && pl.dbg) return go(MeshQueueForm<1, true, false, false, 0>{});
+        if (pl.trav == 1 && pl.stats) return go(MeshQueueForm<1, false, true, false, 0>{});
+        if (pl.trav == 1) return go(MeshQueueForm<1, false, false, false, 0>{});
+    }
+    if (pl.lean) return go(MeshQueueForm<0, false, false, true, PHASE>{});      // (named here, between the two: the kernels lie in the code object in the order they are named)
+    if constexpr (PHASE == 0) {
+        if (pl.dbg) return go(MeshQueueForm<0, true, false, false, 0>{});
+        if (pl.stats) return go(MeshQueueForm<0, false, true, false, 0>{});
+    }
+    return go(MeshQueueForm<0, false, false, false, PHASE>{});
 }
 
 #if defined(RT_MODE_PARITY)
@@ -1192,101 +1206,89 @@ hipError_t rt_launch_rays_mesh(const RtMeshParams& p, const RtRayBatch& b, bool 
 }
 #endif
 
-// variant: bits 0..7  0 = persistent state-machine kernel (default), 1 = first kernel (one tile per wave);
-//          bits 8..15 workgroups per CU of the persistent kernel (0 = default 4);
-//          bits 16..23 keep traversing while at least this many lanes have nodes left (0 = default: 24, classic 40);
-//          bits 24..25 traversal of the persistent kernel: 0 = thresholded while-while (default), 1 = classic while-while;
-//          bits 26..31 leaf threshold of the former (0 = default 16).
-hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
-    if ((variant & 0xFF) == 1) {
-        const dim3 grid((p.nx + 8 * kWavesPerWg - 1) / (8 * kWavesPerWg), (p.part.local_rows + 7) / 8);
-        hipLaunchKernelGGL(k_render_mesh<0>, grid, dim3(kThreads), 0, stream, p);
-        rt_note_launch(RT_KERNEL_MESH_TILES, 0, 0, 0, 0, 0, 0, kThreads, grid.x * grid.y);
-        return hipGetLastError();
+#if RT_MESH_TAIL_DIAG
+// The diagnostic build (tools/build_variant.sh taildiag -DRT_MESH_TAIL_DIAG=1; tools/mesh_tail_diag.py): when did the second dispatch's queue run empty, when
+// did its last wave end, and the per-pixel items.  Before the second dispatch: the items' buffer (once) and the time marks in p.queue[48..56).
+static uint32_t* s_diag_items = nullptr;
+static void tail_diag_begin(const RtMeshParams& p, hipStream_t stream) {
+    if (!s_diag_items) {
+        (void)hipMalloc(&s_diag_items, (size_t)p.part.local_rows * p.nx * 8);
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_diag_items), &s_diag_items, sizeof s_diag_items);
     }
-    if (!p.queue) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(p.queue, 0, 64, stream);
-    if (e != hipSuccess) return e;
+    const unsigned long long init[4] = { ~0ull, ~0ull, 0ull, 0ull };
+    (void)hipMemcpyAsync(p.queue + 48, init, sizeof init, hipMemcpyHostToDevice, stream);
+    (void)hipStreamSynchronize(stream);
+}
+// After it: the report on stderr, and the items with the first dispatch's ray counts into RT_MESH_DIAG_FILE.
+static void tail_diag_end(const RtMeshParams& p, const MeshPlan& pl, const RtSwitches& sw, hipStream_t stream) {
+    const size_t n_px = (size_t)p.part.local_rows * p.nx;
+    const unsigned waves = pl.grid_x * (pl.threads / 64);
+    unsigned long long r[4];
+    unsigned list0 = 0;
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(r, p.queue + 48, sizeof r, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&list0, p.queue + 4, 4, hipMemcpyDeviceToHost);
+    fprintf(stderr, "list 0: %u pixels; ", list0);
+    fprintf(stderr, "mesh tail diag: queue empty at %.1f ms, last wave ends at %.1f ms, mean wave life %.1f ms (%u waves)\n", (double)(r[0] - r[1]) * 1e-5,
+            (double)(r[2] - r[1]) * 1e-5, (double)r[3] * 1e-5 / (double)waves, waves);
+    if (!sw.mesh_diag_file) return;
+    std::vector<uint32_t> h(n_px * 3);
+    (void)hipMemcpy(h.data(), s_diag_items, n_px * 8, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(h.data() + n_px * 2, p.px_rays, n_px * 4, hipMemcpyDeviceToHost);
+    FILE* f = fopen(sw.mesh_diag_file->c_str(), "wb");
+    if (!f) return;
+    fwrite(h.data(), 4, h.size(), f);
+    fclose(f);
+}
+#else
+static void tail_diag_begin(const RtMeshParams&, hipStream_t) {}
+static void tail_diag_end(const RtMeshParams&, const MeshPlan&, const RtSwitches&, hipStream_t) {}
+#endif
+
+// What the ordering pass between the two dispatches reads (rt_params.h: rt_order_pixels_by_cost).
+static RtSphereParams mesh_order_params(const RtMeshParams& p, const MeshPlan& pl) {
+    RtSphereParams o;
+    memset(&o, 0, sizeof o);
+    o.nx = p.nx;
+    o.ny = p.ny;
+    o.part = p.part;
+    o.s_split = pl.split;
+    o.chain_top_thr = pl.chain_top_thr;
+    o.px_rays = p.px_rays;
+    o.px_state = p.px_state;
+    o.order = p.order;
+    o.ord_state = p.ord_state;
+    o.ord_rays = p.ord_rays;
+    o.queue = p.queue;
+    o.ord_rec = p.ord_rec;
+    o.xcd_queues = pl.xcd_queues;
+    return o;
+}
+
+// Plans the frame (plan_mesh, rt_mesh_plan.h: `variant`, the switches, every size and scheduling constant), then issues what the plan says.
+hipError_t RT_LAUNCH_NAME(const RtMeshParams& p, int variant, const RtSwitches& sw, hipStream_t stream) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int wg_per_cu = (variant >> 8) & 0xFF;
-    const bool classic0 = ((variant >> 24) & 3) == 1;
-    const bool lean = sw.mesh_lean && !classic0 && !p.dbg && !p.counters && p.lean_ok && !p.floor_on && p.leaf_sentinels_trailing && p.leaf_ofs && p.leaf_tri &&
-                      p.nppl >= 1u && p.nppl <= 16u && p.first_leaf <= kLeafCntLds;
-    if (wg_per_cu == 0) wg_per_cu = lean ? RT_MESH_LEAN_WAVES : (classic0 ? 5 : 4);   // = the launch bounds (96 / 128 VGPRs); the pair rounds spill at 96      // launch bound: 5 waves per SIMD (96 VGPRs); 6 gave the same rate, 8 spills
-    const long long total_px = (long long)((p.nx + 7) / 8) * ((p.part.local_rows + 7) / 8) * 64;
-    long long blocks = (long long)cus * wg_per_cu * 4 / kWavesPerWg;
-    const long long useful = (total_px + kThreads - 1) / kThreads;
-    if (blocks > useful) blocks = useful;
-    if (blocks < 1) blocks = 1;
-    uint32_t stride = 1;
-    if (total_px > 64 && !sw.mesh_tile_order) stride = rt_coprime_stride((unsigned long long)total_px);
-    const bool classic = ((variant >> 24) & 3) == 1;
-    int min_traversing = (variant >> 16) & 0xFF;
-    if (min_traversing == 0) min_traversing = classic ? kMinTraversing : 24;    // measured: 16 -> 409, 20 -> 435, 24 -> 446, 32 -> 429 Msamples/s
-    int leaf_thr = (variant >> 26) & 0x3F;
-    // default leaf threshold = one full pair round: 64 / nppl waiting rays (12 at 5 triangles per leaf).  Measured on C4 with full rounds
-    // only: 8 -> 607, 12 -> 648, 16 -> 616, 24 -> 541 Msamples/s (round 1, with partial rounds: 16 -> 610).
-    if (leaf_thr == 0) leaf_thr = (p.nppl >= 1u && p.nppl <= 16u) ? (int)(64u / p.nppl) : 16;
-    const dim3 grid((unsigned)blocks), block(kThreads);
-    const size_t lds = (!classic && p.leaf_ofs && p.first_leaf <= kLeafCntLds) ? (size_t)((p.first_leaf + 15u) & ~15u) : 0;      // the leaf-count table
-    // the counting instantiation (STATS: the reference's ray statistics as device atomics) runs only when counters are asked for
-    // The cost-ordered frame in two dispatches (template parameter PHASE): reference RNG stream, no diagnostics, enough samples for the first few to be a small part.
-    // RT_MESH_TWO=0: the single scattered dispatch (A/B); RT_MESH_SPLIT=<n>: samples of the first dispatch.
-    const int split = sw.mesh_split;
-    // (a continuation pass of a progressive frame, p.acc_first > 0, takes the single dispatch: PHASE 0 resumes every pixel from p.acc_state)
-    if (sw.mesh_two && !classic && !p.dbg && !p.counters && p.rng_mode == RT_RNG_REFERENCE_STREAM && p.px_state && p.px_rays && (p.ord_rec || (p.order && p.ord_state && p.ord_rays)) &&
-        p.acc_first == 0 && p.ns >= 4 * split && p.nx <= 65535 && p.part.local_rows <= 65535) {
-        RtMeshParams q = p;
-        q.s_split = split;
-        // (p.p1_segments: the first dispatch scatters row segments of 8 pixels - `stride` coprime with total / 8, flag in bit 8 of min_traversing)
-        uint32_t stride1 = stride;
-        int mt1 = min_traversing;
-        if (p.p1_segments && total_px > 512 && !sw.mesh_tile_order) {
-            stride1 = rt_coprime_stride((unsigned long long)total_px >> 3);
-            mt1 |= 256;
-        }
-        if (lean) launch_mesh_queue<0, false, false, true, 1>(grid, block, lds, stream, q, stride1, mt1, leaf_thr);
-        else launch_mesh_queue<0, false, false, false, 1>(grid, block, lds, stream, q, stride1, mt1, leaf_thr);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords, stream);
-        if (e != hipSuccess) return e;
-        RtSphereParams o;                                            // what the ordering pass reads (rt_params.h: rt_order_pixels_by_cost)
-        memset(&o, 0, sizeof o);
-        o.nx = p.nx; o.ny = p.ny; o.part = p.part; o.s_split = split; o.chain_top_thr = sw.mesh_chain_thr;
-        o.px_rays = p.px_rays; o.px_state = p.px_state; o.order = p.order; o.ord_state = p.ord_state; o.ord_rays = p.ord_rays; o.queue = p.queue;
-        o.ord_rec = p.ord_rec; o.xcd_queues = p.xcd_queues;
-        e = rt_order_pixels_by_cost(o, stream);
-        if (e != hipSuccess) return e;
-        const uint32_t stride2 = sw.mesh_rev ? 0xFFFFFFFFu : stride;
-        const int lt2 = leaf_thr | ((sw.mesh_heavy & 0xF) << 8) | ((sw.mesh_rounds & 0xF) << 12) | (sw.mesh_chain_lanes << 16) | (sw.mesh_chain_frac << 24);
-#if RT_MESH_TAIL_DIAG
-        static uint32_t* d_items = nullptr; const size_t n_px = (size_t)p.part.local_rows * p.nx;
-        if (!d_items) { (void)hipMalloc(&d_items, n_px * 8); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_diag_items), &d_items, sizeof d_items); }
-        { const unsigned long long init[4] = { ~0ull, ~0ull, 0ull, 0ull }; (void)hipMemcpyAsync(p.queue + 48, init, sizeof init, hipMemcpyHostToDevice, stream); (void)hipStreamSynchronize(stream); }
-#endif
-        if (lean) launch_mesh_queue<0, false, false, true, 2>(grid, block, lds, stream, q, stride2, min_traversing, lt2);
-        else launch_mesh_queue<0, false, false, false, 2>(grid, block, lds, stream, q, stride2, min_traversing, lt2);
-#if RT_MESH_TAIL_DIAG
-        { unsigned long long r[4]; (void)hipStreamSynchronize(stream); (void)hipMemcpy(r, p.queue + 48, sizeof r, hipMemcpyDeviceToHost);
-          unsigned q4[2]; (void)hipMemcpy(q4, p.queue + 4, 4, hipMemcpyDeviceToHost); fprintf(stderr, "list 0: %u pixels; ", q4[0]);
-          fprintf(stderr, "mesh tail diag: queue empty at %.1f ms, last wave ends at %.1f ms, mean wave life %.1f ms (%u waves)\n", (double)(r[0] - r[1]) * 1e-5, (double)(r[2] - r[1]) * 1e-5,
-                  (double)r[3] * 1e-5 / ((double)grid.x * (block.x / 64)), grid.x * (block.x / 64));
-          if (sw.mesh_diag_file) { std::vector<uint32_t> h(n_px * 3); (void)hipMemcpy(h.data(), d_items, n_px * 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(h.data() + n_px * 2, p.px_rays, n_px * 4, hipMemcpyDeviceToHost); if (FILE* o = fopen(sw.mesh_diag_file->c_str(), "wb")) { fwrite(h.data(), 4, h.size(), o); fclose(o); } } }
-#endif
+    const MeshPlan pl = plan_mesh(p, variant, sw, cus);
+    if (pl.error != MeshPlanError::None) return hipErrorInvalidValue;
+    if (pl.frame == MeshFrame::Tiles) {
+        hipLaunchKernelGGL(k_render_mesh<0>, dim3(pl.grid_x, pl.grid_y), dim3(pl.threads), 0, stream, p);
+        rt_note_launch(RT_KERNEL_MESH_TILES, 0, 0, 0, 0, 0, 0, pl.threads, pl.grid_x * pl.grid_y);
         return hipGetLastError();
     }
-    if (classic) {
-        if (p.dbg) launch_mesh_queue<1, true, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else if (p.counters) launch_mesh_queue<1, false, true>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else launch_mesh_queue<1, false, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-    } else {
-        if (lean) launch_mesh_queue<0, false, false, true>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else if (p.dbg) launch_mesh_queue<0, true, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else if (p.counters) launch_mesh_queue<0, false, true>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
-        else launch_mesh_queue<0, false, false>(grid, block, lds, stream, p, stride, min_traversing, leaf_thr);
+    hipError_t e = hipMemsetAsync(p.queue, 0, 64, stream);
+    if (e != hipSuccess) return e;
+    if (pl.frame == MeshFrame::TwoDispatch) {
+        RtMeshParams q = p;
+        q.s_split = pl.split;
+        q.xcd_queues = pl.xcd_queues;
+        if ((e = launch_mesh_form<1>(pl, q, stream, pl.stride1, pl.min_traversing1, pl.leaf_thr1)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(p.queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords, stream)) != hipSuccess) return e;
+        if ((e = rt_order_pixels_by_cost(mesh_order_params(p, pl), stream)) != hipSuccess) return e;
+        tail_diag_begin(p, stream);
+        e = launch_mesh_form<2>(pl, q, stream, pl.stride, pl.min_traversing, pl.leaf_thr);
+        tail_diag_end(p, pl, sw, stream);
+        return e;
     }
-    return hipGetLastError();
+    return launch_mesh_form<0>(pl, p, stream, pl.stride, pl.min_traversing, pl.leaf_thr);
 }

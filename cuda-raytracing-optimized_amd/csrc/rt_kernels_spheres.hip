@@ -1495,11 +1495,7 @@ __global__ void __launch_bounds__(kThreads) k_order_by_cost(const RtSphereParams
 // therefore traces a ray in (almost) every iteration until the queue is empty; which lane renders which pixel is
 // irrelevant to the result because the seed is a function of the global pixel id only.
 
-// The bit-fields of the kernel parameters cfg, chain_cfg and caps: the launcher (plan_spheres) packs them, the kernel reads them, both by these names.
-struct BitField {
-    int shift, mask;
-    constexpr int put(int value) const { return value << shift; }            // (the launcher has checked the range)
-};
+// The bit-fields (BitField, rt_params.h) of the kernel parameters cfg, chain_cfg and caps: the launcher (plan_spheres) packs them, the kernel reads them, both by these names.
 constexpr int kCfgCull = 1 << 0;               // sphere-group culling
 constexpr int kCfgChainSingle = 1 << 1;        // chain waves take ONE pixel per grab
 constexpr int kCfgSingleRay = 1 << 2;          // scan_single for waves with one live ray

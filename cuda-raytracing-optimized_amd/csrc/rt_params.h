@@ -194,6 +194,14 @@ struct RtMeshParams {
     int32_t acc_first;
 };
 
+// A bit-field of a packed kernel argument (the sphere kernel's cfg / chain_cfg / caps, the mesh kernel's leaf_thr / min_traversing: rt_mesh_plan.h): the
+// launcher packs it with put, the kernel reads it with get, both by the field's name.
+struct BitField {
+    int shift, mask;
+    constexpr int put(int value) const { return value << shift; }            // (the launcher has checked the range)
+    constexpr int get(int word) const { return (word >> shift) & mask; }
+};
+
 // A field of a render kernel's parameter block (its first argument: offset 0 of the kernarg segment), loaded where it is used.  The base is opaque to the
 // optimiser, so it cannot hoist the load to the kernel's head and hold the value in SGPRs for the life of the wave: the progressive-pass fields are read
 // once per pixel, and held they cost the persistent kernels SGPR and VGPR spills (the six-wave kernel 6 -> 17 spilled VGPRs).

@@ -1,7 +1,8 @@
 """CPU tripwire: the table of production forms (tests/kernel_forms.py, rendered by test_gpu_kernel_forms.py) against the launch sites in the kernel
 sources.  Every instantiation a launcher can launch without diagnostics must have a row, and every row must name an instantiation that is still
 launched: a new kind in the lists of rt_kernels_spheres.hip (KindsFull, KindsChunked, KindsHybrid) without a test, or a deleted one with a stale row,
-fails here without a GPU.  The sphere launcher's shape is held too: a plan without HIP calls, one place that sets the LDS attribute, one statement of the kinds."""
+fails here without a GPU.  The sphere launcher's shape is held too: a plan without HIP calls, one place that sets the LDS attribute, one statement of the kinds;
+and the mesh launcher's: a plan without HIP calls in a header of its own, one function that names the kernel, the packed arguments read by their fields' names."""
 import os
 import re
 
@@ -67,16 +68,25 @@ def sphere_source_forms():
 
 
 def mesh_source_forms():
-    """(phase, trav, lean) of every non-diagnostic k_render_mesh_queue launch and the tile kernel's variants."""
+    """(phase, trav, lean) of every non-diagnostic k_render_mesh_queue instantiation and the tile kernel's variants.  The instantiations are the MeshQueueForm<...>
+    that launch_mesh_form names: one whose last argument is PHASE exists for every phase the launcher calls launch_mesh_form<phase> with, one inside an
+    `if constexpr (PHASE == 0)` block for phase 0 alone (it must say 0)."""
     src = _code("rt_kernels_mesh.hip")
+    form_fn = _function(src, "static hipError_t launch_mesh_form(")
+    phases = {int(p) for p in re.findall(r"launch_mesh_form<(\d+)>\(", src)}
+    assert phases == {0, 1, 2}, phases
+    only0 = "".join(re.findall(r"if constexpr \(PHASE == 0\) \{(.*?)\n    \}", form_fn, re.S))
     forms = set()
-    for args in re.findall(r"launch_mesh_queue<([^>]*)>\(grid", src):
+    for args in re.findall(r"MeshQueueForm<([^>]*)>\{\}", form_fn):
         a = [x.strip() for x in args.split(",")]
-        trav, dbg, stats = int(a[0]), _bool(a[1]), _bool(a[2])
-        lean = _bool(a[3]) if len(a) > 3 else 0
-        phase = int(a[4]) if len(a) > 4 else 0
-        if not dbg and not stats:
-            forms.add((phase, trav, lean))
+        assert len(a) == 5, args
+        trav, dbg, stats, lean = int(a[0]), _bool(a[1]), _bool(a[2]), _bool(a[3])
+        assert (a[4] == "0") == (("MeshQueueForm<%s>{}" % args) in only0), args
+        for phase in (phases if a[4] == "PHASE" else {int(a[4])}):
+            if not dbg and not stats:
+                forms.add((phase, trav, lean))
+    # every instantiation is named in launch_mesh_form (through MeshQueueForm) and launched by launch_mesh_queue alone
+    assert set(re.findall(r"MeshQueueForm<([^>]*)>", src.replace(form_fn, ""))) == {"TRAV, DBG, STATS, LEAN, PHASE"}
     tiles = {int(v) for v in re.findall(r"hipLaunchKernelGGL\(k_render_mesh<(\d+)>", src)}
     assert forms and tiles
     return forms, tiles
@@ -156,3 +166,37 @@ def test_lean_literals_of_the_built_kinds_occur_only_in_the_kind_lists():
     found += [(m.group(0), int(m.group(1), 0)) for m in re.finditer(r"\blean\w*\s*(?:==|!=|\|=|&=|=|&|\|)\s*(\d+|0x[0-9a-fA-F]+)\b", host)]
     found += [(m.group(0), int(m.group(1), 0)) for m in re.finditer(r"(?:SphereQueueForm|k_render_spheres_queue)<(?:[^<>,]*,){5}\s*(\d+)\s*>", host)]
     assert [f for f in found if f[1] in built] == [], found
+
+
+# ---- the mesh launcher: a pure plan in its own header, one function that names the kernel, the packed arguments by name ----------------------------------
+
+def test_plan_mesh_makes_no_hip_call():
+    hdr = _code("rt_mesh_plan.h")
+    body = _function(hdr, "inline MeshPlan plan_mesh(")
+    assert len(body) > 2000 and "return pl;" in body
+    assert re.findall(r"hip[A-Z]\w*\(", hdr) == []
+    assert re.findall(r"#include\s*[<\"]([^>\"]*)[>\"]", hdr) == ["rt_params.h"]           # the parameter blocks, nothing of the kernels
+    launcher = _function(_code("rt_kernels_mesh.hip"), "hipError_t RT_LAUNCH_NAME(const RtMeshParams& p")
+    assert len(re.findall(r"\bplan_mesh\(", launcher)) == 1 and len(re.findall(r"\bvariant\b", launcher)) == 2          # (the parameter, and the plan's argument)
+
+
+def test_mesh_queue_kernel_is_named_in_one_function():
+    src = _code("rt_kernels_mesh.hip")
+    assert len(re.findall(r"k_render_mesh_queue<", src)) == 1
+    assert "k_render_mesh_queue<TRAV, DBG, STATS, LEAN, PHASE>" in _function(src, "static hipError_t launch_mesh_queue(")
+
+
+def test_mesh_packed_arguments_are_read_by_field_name():
+    """Outside rt_mesh_plan.h neither the kernel nor the launcher applies a literal shift or mask to leaf_thr or min_traversing (or to a copy named after them)."""
+    src = _code("rt_kernels_mesh.hip")
+    words = r"\b(?:leaf_thr|min_traversing|lt|mt)\w*"
+    lit = r"(?:0[xX][0-9a-fA-F]+|\d+)[uU]?\b"
+    found = re.findall(r"%s\s*(?:>>|<<|&|\||\^|>>=|<<=|&=|\|=)\s*%s" % (words, lit), src)
+    found += re.findall(r"%s\s*(?:>>|<<|&|\||\^)\s*%s" % (lit, words), src)
+    found += re.findall(r"\(\s*%s\s*\)\s*(?:>>|<<|&|\|)" % words, src)
+    assert found == [], found
+    for field in ("kLeafThr", "kLeafHeavyClasses", "kLeafSpreadRounds", "kLeafChainLanes", "kLeafChainFrac"):
+        assert re.search(r"%s\.get\(leaf_thr\)" % field, src), field
+    for field in ("kMinTravLanes", "kMinTravSegments"):
+        assert re.search(r"%s\.get\(min_traversing\)" % field, src), field
+    assert len(re.findall(r"\bstruct BitField\b", _code("rt_params.h") + _code("rt_kernels_spheres.hip") + _code("rt_mesh_plan.h") + src)) == 1
