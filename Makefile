@@ -62,7 +62,7 @@ $(OBJ)/update.o: $(CSRC)/rt_kernels_update.hip $(CSRC)/rt_update.h include/rt_ty
 # operation by operation as the host builder's, so one object with the flags of display.o.  Its own TU and header: no other kernel object depends on it.
 $(OBJ)/build.o: $(CSRC)/rt_kernels_build.hip $(CSRC)/rt_build.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h include/rt_api.h include/rt_types.h | $(OBJ)
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o

@@ -54,7 +54,7 @@ struct RtSphereParams {
     int32_t n_big_groups;       // groups [0, n_big_groups) hold the big spheres: always scanned
     int32_t n_big;              // real big spheres: slots [0, n_big)
     const float4* spheres;      // the kernel's sphere image: slot k at index k + k/16 (one pad entry per group of 16: LDS banks), (cx, cy, cz, radius*radius);
-                                // n_padded + n_groups entries, spatially sorted (see rt_renderer.hip build_sphere_groups)
+                                // n_padded + n_groups entries, spatially sorted (see rt_scene_layout.h layout_spheres)
     const float*  rad;          // n_padded: radius of slot k (the hit normal divides by it, intersections.h:95)
     int32_t fb_global_rows;     // 1 = `fb` is the WHOLE image (the pinned host framebuffer, written over the bus as pixels finish): rows are global, not local
     const struct RtSphereParams* self;   // a device copy of this struct (launcher): the kernel re-reads what it needs once per sample / pixel from it

@@ -27,6 +27,7 @@
 
 #include "../../include/rt_api.h"
 #include "rt_params.h"
+#include "rt_scene_layout.h"
 #include "rt_denoise.h"
 #include "rt_accumulate.h"
 #include "rt_preview.h"
@@ -152,33 +153,16 @@ struct RenderContext {
     rt_vec3* h_fb = nullptr;            // pinned, nx*ny, handed to the caller
     rt_vec3* h_ext = nullptr;           // caller-owned framebuffer (setExternalFramebuffer), or null
     bool ext_registered = false;        // h_ext is page-locked and device-mapped (hipHostRegister succeeded): the kernels may store into it directly
-    // The scene's constants in parameter-block form, every pointer null: written once at init (build_sphere_groups / build_mesh_scene), the start of every
-    // parameter block (sphere_params / mesh_params).  Sphere scenes: the slot and group counts, global_scene, basic_materials, the culling constants and the
-    // cell tables' geometry; mesh scenes: first_leaf, nppl, leaf_sentinels_trailing, lean_ok, bounds and floor (kernel_scene.floor, helper_structs.h:219).
-    RtSphereParams sphere_scene = {};
-    RtMeshParams mesh_scene = {};
-    // host copies of the scene's arrays (so devices can be (re)configured by setRenderOptions)
-    std::vector<float4> h_spheres;      // the kernel's sphere image (rt_params.h): (n_padded + n_groups) x (cx, cy, cz, r*r)
-    std::vector<float> h_rad;           // n_padded radii
-    std::vector<float4> h_mat_color;
-    std::vector<int32_t> h_mat_type;
-    std::vector<float4> h_groups;       // three float4 per group of kSphereGroup slots: per axis (lo, hi, lo, -) of the tight AABB; then the cell tables
-    std::vector<int32_t> h_orig;        // slot -> caller's sphere index (INT_MAX = pad)
-    std::vector<int32_t> h_slot_of;     // caller's sphere index -> slot
-    std::vector<rt_triangle> h_tris;
-    std::vector<float4> h_bvh;          // numBvhNodes * 24 B viewed as float4 (padded)
-    std::vector<float> h_bvh_axis;      // RtMeshParams::bvh_axis
-    std::vector<float4> h_leaf_tri;     // RtMeshParams::leaf_tri (empty = not built: sentinels inside leaves, or more than 16 M triangles)
-    std::vector<uint32_t> h_leaf_ofs;   // RtMeshParams::leaf_ofs
-    std::vector<rt_material> h_materials;
-    std::vector<std::vector<float>> h_tex;
-    std::vector<int32_t> h_tex_w, h_tex_h;
+    // The scene as the kernels read it (rt_scene_layout.h): the host copies of its arrays (so devices can be (re)configured by setRenderOptions) and its
+    // constants in parameter-block form, the start of every parameter block (sphere_params / mesh_params).  One of the two is in use (is_spheres).
+    SphereLayout sphere;
+    MeshLayout mesh;
     std::vector<DeviceState> devs;
     rt_render_stats stats;
     int prog_samples = 0;               // samples per pixel of the progressive frame so far (rtProgressiveSamples)
     int camera_moves = 0;               // setCamera calls that changed the camera: part of a cost map's key (cost_key_of)
     int scene_edits = 0;                // updateTriangles / updateMaterials / updateSpheres calls that changed the scene: likewise
-    bool refit_stale = false;           // the devices' nodes, child-pair records and leaf records are newer than h_bvh / h_bvh_axis / h_leaf_tri (fetch_refit)
+    bool refit_stale = false;           // the devices' nodes, child-pair records and leaf records are newer than mesh.bvh / bvh_axis / leaf_tri (fetch_refit)
     double update_ms = 0.0;             // rtLastUpdateMs
     double rebuild_ms = 0.0;            // rtLastRebuildMs
     double guides_ms = 0.0;             // rtLastGuidesMs
@@ -327,7 +311,7 @@ int local_rows_of(int ny, int sr, int rank, int world) {
     return rows;
 }
 
-// The host mirrors of what the refit kernels write.  updateTriangles keeps h_tris and the scene bounds current itself; the nodes, the child-pair records and
+// The host mirrors of what the refit kernels write.  updateTriangles keeps mesh.tris and the scene bounds current itself; the nodes, the child-pair records and
 // the leaf records - tens of MB for a large mesh, against the few microseconds of the refit - are fetched from the first device when the host next reads
 // them: by setup_devices, which uploads the scene from the mirrors.  Every device holds the same refitted arrays and the update calls are blocking.
 void fetch_refit() {
@@ -337,9 +321,9 @@ void fetch_refit() {
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
     HIP_CHECK(hipSetDevice(d.device));
-    HIP_CHECK(hipMemcpy(c.h_bvh.data(), d.d_bvh, c.h_bvh.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(c.h_bvh_axis.data(), d.d_bvh_axis, c.h_bvh_axis.size() * sizeof(float), hipMemcpyDeviceToHost));
-    if (!c.h_leaf_tri.empty()) HIP_CHECK(hipMemcpy(c.h_leaf_tri.data(), d.d_leaf_tri, c.h_leaf_tri.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(c.mesh.bvh.data(), d.d_bvh, c.mesh.bvh.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(c.mesh.bvh_axis.data(), d.d_bvh_axis, c.mesh.bvh_axis.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (!c.mesh.leaf_tri.empty()) HIP_CHECK(hipMemcpy(c.mesh.leaf_tri.data(), d.d_leaf_tri, c.mesh.leaf_tri.size() * sizeof(float4), hipMemcpyDeviceToHost));
     HIP_CHECK(hipSetDevice(current));
     c.refit_stale = false;
 }
@@ -349,13 +333,13 @@ void upload_sphere_arrays(DeviceState& d) {
     const RenderContext& c = g_ctx;
     dev_release(d.owned, d.d_spheres); dev_release(d.owned, d.d_rad); dev_release(d.owned, d.d_mat_color); dev_release(d.owned, d.d_mat_type);
     dev_release(d.owned, d.d_groups); dev_release(d.owned, d.d_orig); dev_release(d.owned, d.d_slot_of);
-    d.d_spheres = upload(d.owned, c.h_spheres);
-    d.d_rad = upload(d.owned, c.h_rad);
-    d.d_mat_color = upload(d.owned, c.h_mat_color);
-    d.d_mat_type = upload(d.owned, c.h_mat_type);
-    d.d_groups = upload(d.owned, c.h_groups);
-    d.d_orig = upload(d.owned, c.h_orig);
-    d.d_slot_of = upload(d.owned, c.h_slot_of);
+    d.d_spheres = upload(d.owned, c.sphere.spheres);
+    d.d_rad = upload(d.owned, c.sphere.rad);
+    d.d_mat_color = upload(d.owned, c.sphere.mat_color);
+    d.d_mat_type = upload(d.owned, c.sphere.mat_type);
+    d.d_groups = upload(d.owned, c.sphere.groups);
+    d.d_orig = upload(d.owned, c.sphere.orig);
+    d.d_slot_of = upload(d.owned, c.sphere.slot_of);
 }
 
 // (Re)creates the per-device state for the device list in g_ctx.opt.
@@ -392,18 +376,18 @@ void setup_devices() {
             HIP_CHECK(hipHostMalloc((void**)&d.h_params, sizeof(RtSphereParams), hipHostMallocDefault));
             upload_sphere_arrays(d);
         } else {
-            d.d_tris = upload(d.owned, c.h_tris);
-            d.d_bvh = upload(d.owned, c.h_bvh);
-            d.d_bvh_axis = upload(d.owned, c.h_bvh_axis);
-            d.d_leaf_tri = upload(d.owned, c.h_leaf_tri);
-            d.d_leaf_ofs = upload(d.owned, c.h_leaf_ofs);
-            d.d_materials = upload(d.owned, c.h_materials);
-            if (!c.h_tex.empty()) {
+            d.d_tris = upload(d.owned, c.mesh.tris);
+            d.d_bvh = upload(d.owned, c.mesh.bvh);
+            d.d_bvh_axis = upload(d.owned, c.mesh.bvh_axis);
+            d.d_leaf_tri = upload(d.owned, c.mesh.leaf_tri);
+            d.d_leaf_ofs = upload(d.owned, c.mesh.leaf_ofs);
+            d.d_materials = upload(d.owned, c.mesh.materials);
+            if (!c.mesh.tex.empty()) {
                 std::vector<float*> ptrs;
-                for (const std::vector<float>& t : c.h_tex) ptrs.push_back(upload(d.owned, t));
+                for (const std::vector<float>& t : c.mesh.tex) ptrs.push_back(upload(d.owned, t));
                 d.d_tex_data = upload(d.owned, ptrs);
-                d.d_tex_width = upload(d.owned, c.h_tex_w);
-                d.d_tex_height = upload(d.owned, c.h_tex_h);
+                d.d_tex_width = upload(d.owned, c.mesh.tex_w);
+                d.d_tex_height = upload(d.owned, c.mesh.tex_h);
             }
         }
         const int world = c.opt.part_world * nd, rank = c.opt.part_rank * nd + k;
@@ -453,297 +437,16 @@ void common_init(const rt_camera& cam, rt_vec3** fb, int nx, int ny, int maxDept
     c.initialised = true;
 }
 
-
-// Device layout of a sphere scene.  The spheres are re-ordered into SLOTS, kSphereGroup (G) slots per group:
-//   * "big" spheres (radius > 4 x the median radius: the ground and the three unit spheres of the benchmark scene)
-//     come first; their groups are always scanned, by every lane, and give each ray a first `closest`;
-//   * "small" spheres are split recursively at medians so that the G slots of a group are neighbours in space; each
-//     group of G gets its tight axis-aligned bounding box, three entries (lo, hi, lo, -), one per axis, with the cell
-//     tables behind them; the kernel uses it to skip the group for rays that cannot reach it before their current hit,
-//     and the culling is exact through the margin every ray adds for itself (make_box_ray), not through an inflation;
-//   * pad slots fill the last group of each class and the tail up to a multiple of 64 slots; they carry
-//     orig = INT_MAX and are never accepted.
-// Scanning in slot order instead of the caller's order cannot change the result: the kernel resolves equal-t ties
-// by the caller's index (h_orig), which is exactly the reference's first-index-wins rule.
-void build_sphere_groups(const rt_sphere* spheres, const rt_material* materials, int n) {
-    RenderContext& c = g_ctx;
-    std::vector<float> radii(n);
-    for (int k = 0; k < n; k++) radii[k] = fabsf(spheres[k].radius);
-    std::vector<float> sorted = radii;
-    std::nth_element(sorted.begin(), sorted.begin() + n / 2, sorted.end());
-    const float big_above = 4.0f * sorted[n / 2];
-    std::vector<int> small, big;
-    double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
-    for (int k = 0; k < n; k++) {
-        if (radii[k] > big_above || !std::isfinite(radii[k])) { big.push_back(k); continue; }
-        small.push_back(k);
-        for (int a = 0; a < 3; a++) {
-            lo[a] = std::min(lo[a], (double)spheres[k].center.e[a]);
-            hi[a] = std::max(hi[a], (double)spheres[k].center.e[a]);
-        }
-    }
-    // Groups of G = kSphereGroup: recursive median split of the small spheres along the axis of largest centre extent, the left part
-    // rounded to a multiple of G, until a part fits one group.  Compact parts = small boxes = few (ray, group) pairs; a
-    // 3D Morton sort (the first version) makes strips and L-shapes when the spheres lie on a plane.  ceil(n / G) groups.
-    constexpr size_t G = (size_t)kSphereGroup;
-    std::vector<int> ordered;
-    std::function<void(std::vector<int>&, size_t, size_t)> split = [&](std::vector<int>& v, size_t b0, size_t e0) {
-        const size_t cnt = e0 - b0;
-        if (cnt <= (size_t)G) {
-            for (size_t q = b0; q < e0; q++) ordered.push_back(v[q]);
-            while (ordered.size() % G) ordered.push_back(-1);      // pad this group
-            return;
-        }
-        double l3[3] = { 1e300, 1e300, 1e300 }, h3[3] = { -1e300, -1e300, -1e300 };
-        for (size_t q = b0; q < e0; q++)
-            for (int a = 0; a < 3; a++) {
-                l3[a] = std::min(l3[a], (double)spheres[v[q]].center.e[a]);
-                h3[a] = std::max(h3[a], (double)spheres[v[q]].center.e[a]);
-            }
-        int axis = 0;
-        for (int a = 1; a < 3; a++) if (h3[a] - l3[a] > h3[axis] - l3[axis]) axis = a;
-        std::stable_sort(v.begin() + b0, v.begin() + e0, [&](int x, int y) { return spheres[x].center.e[axis] < spheres[y].center.e[axis]; });
-        const size_t groups = (cnt + G - 1) / G;
-        const size_t left = std::min(cnt - 1, (groups / 2) * G);     // a multiple of G: only the last group of the scene is padded
-        split(v, b0, b0 + left);
-        split(v, b0 + left, e0);
-    };
-    std::vector<int> slots;                                     // slot -> caller index, -1 = pad
-    for (int k : big) slots.push_back(k);                       // big spheres first: groups [0, n_big_groups)
-    while (slots.size() % G) slots.push_back(-1);
-    const int n_big_groups = (int)slots.size() / G;
-    if (!small.empty()) split(small, 0, small.size());
-    for (int k : ordered) slots.push_back(k);
-    while (slots.size() % 64) slots.push_back(-1);
-
-    RtSphereParams& sp = c.sphere_scene;                         // the scene's constants go straight into the parameter-block template
-    sp.n = n;
-    sp.n_padded = (int)slots.size();
-    sp.n_groups = sp.n_padded / G;
-    sp.n_big_groups = n_big_groups;
-    sp.n_big = (int)big.size();
-    const auto sidx = [](int slot) { return slot + slot / kSphereGroup; };
-    c.h_spheres.assign(sp.n_padded + sp.n_groups, make_float4(0.0f, 3.0e18f, 0.0f, 0.0f));      // pad: radius 0, far away
-    c.h_rad.assign(sp.n_padded, 0.0f);
-    c.h_mat_color.assign(sp.n_padded, make_float4(0, 0, 0, 0));
-    c.h_mat_type.assign(sp.n_padded, RT_DIFFUSE);
-    c.h_orig.assign(sp.n_padded, INT_MAX);
-    c.h_slot_of.assign(n, 0);
-    // bounds: 3 float4 per group, one per AXIS: (lo, hi, lo, -) - a ray reads two consecutive floats, at 0 or at 1 by the sign of its direction,
-    // and has (near plane, far plane).  Empty group: lo > hi on every axis (never reachable).
-    c.h_groups.assign((size_t)sp.n_groups * 3, make_float4(3.0e38f, -3.0e38f, 3.0e38f, 0.0f));
-    sp.basic_materials = 1;
-    for (int k = 0; k < n; k++) if (materials[k].type != RT_DIFFUSE && materials[k].type != RT_METAL && materials[k].type != RT_GLASS) sp.basic_materials = 0;
-    for (int s = 0; s < sp.n_padded; s++) {
-        const int k = slots[s];
-        if (k < 0) continue;
-        const float r = spheres[k].radius;
-        const float r2 = r * r;                                    // intersections.h:89 radius*radius: one IEEE multiply, the same bits as on the device
-        c.h_spheres[sidx(s)] = make_float4(spheres[k].center.e[0], spheres[k].center.e[1], spheres[k].center.e[2], r2);
-        c.h_rad[s] = r;
-        c.h_mat_color[s] = make_float4(materials[k].color.e[0], materials[k].color.e[1], materials[k].color.e[2], materials[k].param);
-        c.h_mat_type[s] = materials[k].type;
-        c.h_orig[s] = k;
-        c.h_slot_of[k] = s;
-    }
-    // Group boxes: the tight AABB of the group's spheres, pushed out by one float on conversion.  What makes the culling EXACT is
-    // not a static inflation but the per-ray margin the kernel adds (make_box_ray): it covers (a) the rounding of the
-    // reference's own fp32 discriminant b*b - a*c, whose error grows like |org - centre|^2 - for a far camera the reference
-    // accepts "hits" of rays that geometrically miss a sphere by more than any fixed inflation - and (b) the rounding of the slab test.
-    float coord_max = 0.0f;
-    double r_min = 1e300;
-    float shared_lo[3] = { 0, 0, 0 }, shared_hi[3] = { 0, 0, 0 };
-    bool shared_ok[3] = { true, true, true };
-    int n_boxes = 0;
-    for (int g = n_big_groups; g < sp.n_groups; g++) {
-        double blo[3] = { 1e300, 1e300, 1e300 }, bhi[3] = { -1e300, -1e300, -1e300 };
-        int cnt = 0;
-        for (int s = g * G; s < g * G + G; s++) {
-            if (slots[s] < 0) continue;
-            cnt++;
-            r_min = std::min(r_min, (double)radii[slots[s]]);
-            for (int a = 0; a < 3; a++) {
-                blo[a] = std::min(blo[a], (double)spheres[slots[s]].center.e[a] - radii[slots[s]]);
-                bhi[a] = std::max(bhi[a], (double)spheres[slots[s]].center.e[a] + radii[slots[s]]);
-            }
-        }
-        if (cnt == 0) continue;
-        float flo[3], fhi[3];
-        for (int a = 0; a < 3; a++) {
-            flo[a] = std::nextafter((float)blo[a], -INFINITY);
-            fhi[a] = std::nextafter((float)bhi[a], INFINITY);
-            coord_max = std::max(coord_max, std::max(fabsf(flo[a]), fabsf(fhi[a])));
-        }
-        for (int a = 0; a < 3; a++) c.h_groups[3 * g + a] = make_float4(flo[a], fhi[a], flo[a], 0.0f);
-        for (int a = 0; a < 3; a++) {                                // an axis on which every group box has the same extent?
-            if (n_boxes == 0) { shared_lo[a] = flo[a]; shared_hi[a] = fhi[a]; }
-            else if (shared_lo[a] != flo[a] || shared_hi[a] != fhi[a]) shared_ok[a] = false;
-        }
-        n_boxes++;
-    }
-    sp.box_shared_axis = 0;
-    for (int a = 2; a >= 0; a--) if (n_boxes > 0 && shared_ok[a]) { sp.box_shared_axis = a + 1; sp.box_shared_lo = shared_lo[a]; sp.box_shared_hi = shared_hi[a]; }
-    // Cell tables (rt_params.h, group_needs_cells): for scenes of up to 32 x kCellWordsMax groups, on all three axes.  Bit g of a word = small group g.
-    // begins[c] = boxes with lo <= upper edge of cell c, ends[c] = boxes with hi >= lower edge of cell c, both with a slack of kCellSlack cells for
-    // the rounding of the device's cell index (x * scale + off in fp32 with |index| <= kCellCount: off by < 2e-5 cells); the last begins-word and the
-    // first ends-word hold every box, so that a coordinate beyond the tables' extent - clamped to the first / last cell on the device - rejects
-    // nothing it should not.  An axis on which every box has the same extent (spheres resting on a plane: the vertical one) gets no bit in cell_axes:
-    // its table could not reject anything.  ubox = the union of the boxes, to which the kernel clips the ray before it looks anything up.
-    constexpr double kCellSlack = 1.0e-3;
-    sp.cell_on = 0;
-    sp.cell_axes = 0;
-    const int cell_words = rt_cell_words(sp.n_groups);
-    c.h_groups.resize((size_t)sp.n_groups * 3 + (size_t)rt_cell_f4(sp.n_groups), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (int a = 0; a < 3; a++) { sp.ubox[a] = 0.0f; sp.ubox[3 + a] = 0.0f; sp.cell_scale[a] = 0.0f; sp.cell_off[a] = 0.0f; }
-    if (n_boxes > 0 && cell_words > 0) {
-        const int W = cell_words;
-        uint32_t* tab = reinterpret_cast<uint32_t*>(c.h_groups.data() + (size_t)sp.n_groups * 3);
-        std::vector<char> real(sp.n_groups, 0);
-        for (int g = n_big_groups; g < sp.n_groups; g++) real[g] = c.h_groups[3 * g].x <= c.h_groups[3 * g].y;
-        bool ok = true;
-        for (int a = 0; a < 3 && ok; a++) {
-            double amin = 1e300, amax = -1e300;
-            for (int g = n_big_groups; g < sp.n_groups; g++) {
-                if (!real[g]) continue;
-                amin = std::min(amin, (double)c.h_groups[3 * g + a].x);
-                amax = std::max(amax, (double)c.h_groups[3 * g + a].y);
-            }
-            sp.ubox[a] = (float)amin; sp.ubox[3 + a] = (float)amax;      // (box coordinates are floats: exact)
-            const double w = (amax - amin) / kCellCount;
-            if (!(w > 1e-30) || !std::isfinite(w) || !std::isfinite(1.0 / w) || !std::isfinite(amin / w)) { ok = false; break; }
-            sp.cell_scale[a] = (float)(1.0 / w);
-            sp.cell_off[a] = (float)(-amin / w);
-            if (!shared_ok[a]) sp.cell_axes |= 1 << a;
-            for (int cell = 0; cell < kCellCount; cell++) {
-                uint32_t* begins = tab + ((size_t)(2 * a) * kCellCount + cell) * W;
-                uint32_t* ends = tab + ((size_t)(2 * a + 1) * kCellCount + cell) * W;
-                for (int g = n_big_groups; g < sp.n_groups; g++) {
-                    if (!real[g]) continue;
-                    const int k = g - n_big_groups;
-                    if (cell == kCellCount - 1 || (double)c.h_groups[3 * g + a].x <= amin + (cell + 1 + kCellSlack) * w) begins[k >> 5] |= 1u << (k & 31);
-                    if (cell == 0 || (double)c.h_groups[3 * g + a].y >= amin + (cell - kCellSlack) * w) ends[k >> 5] |= 1u << (k & 31);
-                }
-            }
-        }
-        sp.cell_on = (ok && rt_read_switches().box_cells) ? 1 : 0;
-    }
-    // per-ray margin constants
-    double cc[3] = { 0, 0, 0 }, rad = 0.0;
-    if (!small.empty()) {
-        for (int a = 0; a < 3; a++) cc[a] = 0.5 * (lo[a] + hi[a]);
-        for (int k : small) {
-            double d2 = 0.0;
-            for (int a = 0; a < 3; a++) d2 += (spheres[k].center.e[a] - cc[a]) * (spheres[k].center.e[a] - cc[a]);
-            rad = std::max(rad, std::sqrt(d2) + radii[k]);
-        }
-    } else r_min = 1.0;
-    const double K_eps = 96.0 * 5.9604645e-8;            // K x 2^-24, see make_box_ray
-    sp.cull_cx = (float)cc[0]; sp.cull_cy = (float)cc[1]; sp.cull_cz = (float)cc[2];
-    sp.cull_radius = (float)(rad * 1.000001 + 1e-30);
-    sp.cull_k1 = (float)(K_eps / (2.0 * std::max(r_min, 1e-30)));
-    sp.cull_k2 = (float)std::sqrt(K_eps);
-    sp.cull_k3 = 16.0f * 5.9604645e-8f;
-    sp.cull_coord_max = coord_max;
-    double r_max_small = 0.0;
-    for (int k : small) r_max_small = std::max(r_max_small, (double)radii[k]);
-    sp.pair_k0 = (float)(2.0 * 3.814697265625e-6 * r_max_small * r_max_small * 1.0001);     // 2 x kPairSlack (2^-18) x r_max^2, rounded up
-}
-
-// RtMeshParams::lean_ok of the materials in h_materials (build_mesh_scene, updateMaterials): every one RT_DIFFUSE / RT_METAL / RT_GLASS and untextured.
-int mesh_lean_ok() {
-    for (const rt_material& m : g_ctx.h_materials)
-        if ((m.type != RT_DIFFUSE && m.type != RT_METAL && m.type != RT_GLASS) || m.texId != -1) return 0;
-    return 1;
-}
-
 // What initRendererSpheres and updateSpheres do with the caller's arrays: the checks, the slot layout and the decision where the kernels read the scene from.
 void build_sphere_scene(const char* fn, const rt_sphere* spheres, const rt_material* materials, int n) {
     RenderContext& c = g_ctx;
     for (int k = 0; k < n; k++)
         if (materials[k].type < RT_DIFFUSE || materials[k].type >= RT_MATERIAL_TYPE_COUNT) rt_fail(": bad material type", fn);
-    build_sphere_groups(spheres, materials, n);
+    c.sphere = layout_spheres(spheres, materials, n, rt_read_switches().box_cells);
     // Scenes up to ~2100 spheres live in the LDS of every workgroup; larger ones are read from global memory (they stay in L2) by the
     // same kernel (no cost-ordered second phase, no sparse form beyond 4096 groups: slower per ray, same image).
-    c.sphere_scene.global_scene = rt_sphere_kernel_lds_bytes(c.sphere_scene.n_padded, n) > 160 * 1024 ? 1 : 0;
-    if (c.sphere_scene.n_padded > (1 << 24)) rt_fail(": more than 16 M sphere slots", fn);
-}
-
-// Device layout of a mesh scene (initRenderer has validated `sc`): the caller's triangles and BVH, the axis-grouped node records, the compact leaf records,
-// materials and textures as host arrays, the scene's constants in the parameter-block template.
-void build_mesh_scene(const rt_kernel_scene& sc) {
-    RenderContext& c = g_ctx;
-    RtMeshParams& mp = c.mesh_scene;
-    const int nppl = sc.numPrimitivesPerLeaf;
-    const uint32_t first_leaf = (uint32_t)sc.m->numBvhNodes / 2;                               // kernels.cu:614
-    mp.first_leaf = first_leaf;
-    mp.nppl = (uint32_t)nppl;                                                                  // kernels.cu:648
-    mp.bounds = sc.m->bounds;
-    mp.floor = sc.floor;
-    c.h_tris.assign(sc.m->tris, sc.m->tris + sc.m->numTris);                                  // kernels.cu:582-583
-    const size_t nfloats = (size_t)sc.m->numBvhNodes * 6;                                      // kernels.cu:587-605
-    c.h_bvh.assign((nfloats + 3) / 4 + 1, make_float4(0, 0, 0, 0));
-    memcpy(c.h_bvh.data(), sc.m->bvh, nfloats * sizeof(float));
-    {   // axis-grouped child-pair records (rt_params.h, bvh_axis): 24 floats per internal node
-        const size_t nrec = (size_t)sc.m->numBvhNodes / 2;
-        c.h_bvh_axis.assign(nrec * 24, 0.0f);
-        const float* nodes = reinterpret_cast<const float*>(sc.m->bvh);
-        for (size_t i = 0; i < nrec; i++) {
-            const float* L = nodes + (2 * i) * 6;
-            const float* R = nodes + (2 * i + 1) * 6;
-            for (int a = 0; a < 3; a++) {
-                float* o = c.h_bvh_axis.data() + i * 24 + a * 8;
-                o[0] = L[a]; o[1] = R[a]; o[2] = L[3 + a]; o[3] = R[3 + a];
-                o[4] = L[3 + a]; o[5] = R[3 + a]; o[6] = L[a]; o[7] = R[a];
-            }
-        }
-    }
-    // The leaf loop of kernels.cu:196-214 stops at the first sentinel (inf) triangle of a leaf.  The pair rounds of the mesh
-    // kernel test a leaf's triangles in parallel and rely on sentinels being TRAILING (true for every builder that pads
-    // leaves at the end); a leaf with a real triangle behind a sentinel sends the kernel to its sequential leaf loop.
-    mp.leaf_sentinels_trailing = 1;
-    for (uint32_t leaf = 0; leaf < first_leaf && mp.leaf_sentinels_trailing; leaf++) {
-        bool seen = false;
-        for (int k = 0; k < nppl; k++) {
-            const bool sent = std::isinf(c.h_tris[(size_t)leaf * nppl + k].v[0].e[0]);
-            if (seen && !sent) mp.leaf_sentinels_trailing = 0;
-            seen = seen || sent;
-        }
-    }
-    // Compact leaf records for the pair rounds (rt_params.h, leaf_tri / leaf_ofs): what triangleHit reads of a triangle and nothing else - v0 and the
-    // two edges, e1 = v1 - v0 and e2 = v2 - v0 computed here with the same single fp32 subtraction per component as intersections.h:56-57 (same bits) -
-    // for the REAL triangles only.  The caller's 64-byte array stays the ABI of this boundary (helper_structs.h:81-96) and is what a closest hit re-reads.
-    c.h_leaf_tri.clear(); c.h_leaf_ofs.clear();
-    if (mp.leaf_sentinels_trailing && nppl <= 255) {
-        c.h_leaf_tri.assign((size_t)first_leaf * nppl * 3, make_float4(0, 0, 0, 0));
-        c.h_leaf_ofs.assign(((size_t)first_leaf + 3) / 4, 0u);
-        for (uint32_t leaf = 0; leaf < first_leaf; leaf++) {
-            uint32_t cnt = 0;
-            for (int k = 0; k < nppl; k++) {
-                const rt_triangle& t = c.h_tris[(size_t)leaf * nppl + k];
-                if (std::isinf(t.v[0].e[0])) break;
-                volatile float e1[3], e2[3];                         // (volatile: one rounded fp32 subtraction each, never a contracted or widened form)
-                for (int a = 0; a < 3; a++) { e1[a] = t.v[1].e[a] - t.v[0].e[a]; e2[a] = t.v[2].e[a] - t.v[0].e[a]; }
-                float4* rec = c.h_leaf_tri.data() + ((size_t)leaf * nppl + k) * 3;
-                rec[0] = make_float4(t.v[0].e[0], t.v[0].e[1], t.v[0].e[2], e1[0]);
-                rec[1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-                uint32_t mesh_bits = (uint32_t)t.meshID;
-                float mesh_f;
-                memcpy(&mesh_f, &mesh_bits, 4);
-                rec[2] = make_float4(e2[2], mesh_f, 0.0f, 0.0f);       // (.y: meshID as an integer bit pattern - a closest hit reads its record again for the normal and the material)
-                cnt++;
-            }
-            c.h_leaf_ofs[leaf >> 2] |= cnt << (8 * (leaf & 3));
-        }
-    }
-    c.h_materials.assign(sc.materials, sc.materials + sc.numMaterials);                        // kernels.cu:617-618
-    mp.lean_ok = mesh_lean_ok();
-    c.h_tex.clear(); c.h_tex_w.clear(); c.h_tex_h.clear();
-    for (int t = 0; t < sc.numTextures; t++) {                                                 // kernels.cu:620-645
-        const rt_stexture& tx = sc.textures[t];
-        c.h_tex.emplace_back(tx.data, tx.data + (size_t)tx.width * tx.height * 3);
-        c.h_tex_w.push_back(tx.width);
-        c.h_tex_h.push_back(tx.height);
-    }
+    c.sphere.scene.global_scene = rt_sphere_kernel_lds_bytes(c.sphere.scene.n_padded, n) > 160 * 1024 ? 1 : 0;
+    if (c.sphere.scene.n_padded > (1 << 24)) rt_fail(": more than 16 M sphere slots", fn);
 }
 
 void cleanup_impl() {
@@ -819,7 +522,7 @@ void initRenderer(const rt_kernel_scene sc, const rt_camera cam, rt_vec3** fb, i
         if (!sc.textures[t].data || sc.textures[t].width <= 0 || sc.textures[t].height <= 0) rt_fail("initRenderer: bad texture");
     for (int k = 0; k < sc.numMaterials; k++)
         if (sc.materials[k].texId != -1 && (sc.materials[k].texId < 0 || sc.materials[k].texId >= sc.numTextures)) rt_fail("initRenderer: material texId out of range");
-    build_mesh_scene(sc);
+    c.mesh = layout_mesh(sc);
     common_init(cam, fb, nx, ny, maxDepth);
 }
 
@@ -882,7 +585,7 @@ RtPartition whole_image_partition() {
 // a frame (render_frame) adds what belongs to a frame, the guide kernels (launch_guides) take it as it is.
 RtSphereParams sphere_params(const DeviceState& d, const RtPartition& part) {
     const RenderContext& c = g_ctx;
-    RtSphereParams p = c.sphere_scene;
+    RtSphereParams p = c.sphere.scene;
     p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
     p.spheres = d.d_spheres; p.rad = d.d_rad; p.mat_color = d.d_mat_color; p.mat_type = d.d_mat_type;
     p.groups = d.d_groups; p.orig = d.d_orig; p.slot_of = d.d_slot_of;
@@ -892,7 +595,7 @@ RtSphereParams sphere_params(const DeviceState& d, const RtPartition& part) {
 
 RtMeshParams mesh_params(const DeviceState& d, const RtPartition& part) {
     const RenderContext& c = g_ctx;
-    RtMeshParams p = c.mesh_scene;
+    RtMeshParams p = c.mesh.scene;
     p.cam = c.cam; p.nx = c.nx; p.ny = c.ny;
     p.tris = d.d_tris; p.bvh4 = d.d_bvh; p.bvh_axis = d.d_bvh_axis;
     p.materials = d.d_materials;
@@ -1046,6 +749,21 @@ std::array<int, 11> cost_key_of(const RtPartition& part, bool with_camera) {
              c.scene_edits };
 }
 
+// Blocks until every device's stream has drained (kernels.cu:660-661: the calls are blocking) and returns the longest time between the two events each device
+// recorded on it, in ms.  with_rows: only the devices that render rows of the image (the others recorded nothing).
+double finish_devices(hipEvent_t DeviceState::*start, hipEvent_t DeviceState::*stop, bool with_rows) {
+    double ms_max = 0.0;
+    for (DeviceState& d : g_ctx.devs) {
+        if (with_rows && d.fb_rows == 0) continue;
+        HIP_CHECK(hipSetDevice(d.device));
+        HIP_CHECK(hipStreamSynchronize(d.stream));
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, d.*start, d.*stop));
+        ms_max = std::max(ms_max, (double)ms);
+    }
+    return ms_max;
+}
+
 // One frame of ns samples per pixel (runRenderer), or one pass of a progressive frame (progressive): samples [first, ns) of every pixel, continued from
 // and parked into the device's accumulation buffers, the framebuffer = sum / ns.
 void render_frame(int ns, int first, bool progressive) {
@@ -1187,17 +905,13 @@ void render_frame(int ns, int first, bool progressive) {
         samples += (int64_t)d.fb_rows * c.nx * (ns - first);
     }
 
-    double kernel_ms = 0.0;
+    const double kernel_ms = finish_devices(&DeviceState::ev_start, &DeviceState::ev_stop, true);
     rt_render_stats st;
     memset(&st, 0, sizeof st);
     for (int k = 0; k < nd; k++) {
         DeviceState& d = c.devs[k];
         if (d.fb_rows == 0) continue;
         HIP_CHECK(hipSetDevice(d.device));
-        HIP_CHECK(hipStreamSynchronize(d.stream));                      // kernels.cu:660-661: blocking
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, d.ev_start, d.ev_stop));
-        kernel_ms = std::max(kernel_ms, (double)ms);
         if (d.d_wave_dbg && sw.wave_debug) {
             std::vector<unsigned long long> h(kWaveDbgWords);
             HIP_CHECK(hipMemcpy(h.data(), d.d_wave_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1357,6 +1071,14 @@ static void check_update(const char* fn, bool spheres) {
     if (c.is_spheres != spheres) rt_fail(spheres ? " needs a sphere scene (initRendererSpheres)" : " needs a mesh scene (initRenderer)", fn);
 }
 
+// The refit of the mesh tree over the slots device `d` holds, on its stream (updateTriangles, rebuildBvh).
+static void launch_refit(const DeviceState& d) {
+    RtRefitParams q;
+    q.slots = d.d_tris; q.nodes = reinterpret_cast<float*>(d.d_bvh); q.axis = d.d_bvh_axis; q.leaf_rec = d.d_leaf_tri;
+    q.first_leaf = g_ctx.mesh.scene.first_leaf; q.nppl = g_ctx.mesh.scene.nppl;
+    HIP_CHECK(rt_launch_refit(q, d.stream));
+}
+
 static void scene_edited() {
     g_ctx.prog_samples = 0;                                 // as setCamera
     g_ctx.scene_edits++;                                    // (the cost maps of sphere frames: cost_key_of)
@@ -1365,43 +1087,33 @@ static void scene_edited() {
 void updateTriangles(int first, int count, const rt_triangle* tris) {
     RenderContext& c = g_ctx;
     check_update("updateTriangles", false);
-    if (first < 0 || count < 0 || (size_t)first + (size_t)count > c.h_tris.size()) rt_fail("updateTriangles: [first, first + count) must lie inside the numTris of init");
+    if (first < 0 || count < 0 || (size_t)first + (size_t)count > c.mesh.tris.size()) rt_fail("updateTriangles: [first, first + count) must lie inside the numTris of init");
     if (count == 0) return;
     if (!tris) rt_fail("updateTriangles: tris is null");
-    const uint32_t first_leaf = c.mesh_scene.first_leaf;
+    const uint32_t first_leaf = c.mesh.scene.first_leaf;
     if ((first_leaf & (first_leaf - 1)) != 0) rt_fail("updateTriangles: the refit needs a tree whose number of leaves is a power of two");
     for (int k = 0; k < count; k++) {
         const bool sentinel = std::isinf(tris[k].v[0].e[0]);
-        if (sentinel != std::isinf(c.h_tris[(size_t)first + k].v[0].e[0])) rt_fail("updateTriangles: a slot's sentinel state (isinf(v[0].x)) must not change");
-        if (!sentinel && tris[k].meshID >= c.h_materials.size()) rt_fail("updateTriangles: triangle meshID out of range");
+        if (sentinel != std::isinf(c.mesh.tris[(size_t)first + k].v[0].e[0])) rt_fail("updateTriangles: a slot's sentinel state (isinf(v[0].x)) must not change");
+        if (!sentinel && tris[k].meshID >= c.mesh.materials.size()) rt_fail("updateTriangles: triangle meshID out of range");
     }
-    std::copy(tris, tris + count, c.h_tris.begin() + first);
+    std::copy(tris, tris + count, c.mesh.tris.begin() + first);
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
     for (DeviceState& d : c.devs) {                         // every device holds the whole scene: count * 64 bytes over the bus and one refit each
         HIP_CHECK(hipSetDevice(d.device));
-        HIP_CHECK(hipMemcpyAsync(d.d_tris + first, c.h_tris.data() + first, (size_t)count * sizeof(rt_triangle), hipMemcpyHostToDevice, d.stream));
-        RtRefitParams q;
-        q.slots = d.d_tris; q.nodes = reinterpret_cast<float*>(d.d_bvh); q.axis = d.d_bvh_axis; q.leaf_rec = d.d_leaf_tri;
-        q.first_leaf = first_leaf; q.nppl = c.mesh_scene.nppl;
+        HIP_CHECK(hipMemcpyAsync(d.d_tris + first, c.mesh.tris.data() + first, (size_t)count * sizeof(rt_triangle), hipMemcpyHostToDevice, d.stream));
         HIP_CHECK(hipEventRecord(d.ev_upd_start, d.stream));
-        HIP_CHECK(rt_launch_refit(q, d.stream));
+        launch_refit(d);
         HIP_CHECK(hipEventRecord(d.ev_upd_stop, d.stream));
     }
     rt_bvh_node root;                                       // the scene bounds become node 1's box
     HIP_CHECK(hipSetDevice(c.devs[0].device));
     HIP_CHECK(hipMemcpyAsync(&root, reinterpret_cast<const char*>(c.devs[0].d_bvh) + sizeof(rt_bvh_node), sizeof root, hipMemcpyDeviceToHost, c.devs[0].stream));
-    double ms_max = 0.0;
-    for (DeviceState& d : c.devs) {
-        HIP_CHECK(hipSetDevice(d.device));
-        HIP_CHECK(hipStreamSynchronize(d.stream));          // blocking
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, d.ev_upd_start, d.ev_upd_stop));
-        ms_max = std::max(ms_max, (double)ms);
-    }
+    const double ms_max = finish_devices(&DeviceState::ev_upd_start, &DeviceState::ev_upd_stop, false);
     HIP_CHECK(hipSetDevice(current));
-    c.mesh_scene.bounds.min = root.a;
-    c.mesh_scene.bounds.max = root.b;
+    c.mesh.scene.bounds.min = root.a;
+    c.mesh.scene.bounds.max = root.b;
     c.refit_stale = true;
     c.update_ms = ms_max;
     scene_edited();
@@ -1411,16 +1123,16 @@ void updateMaterials(const rt_material* materials, int n) {
     RenderContext& c = g_ctx;
     check_update("updateMaterials", false);
     if (!materials) rt_fail("updateMaterials: materials is null");
-    if (n != (int)c.h_materials.size()) rt_fail("updateMaterials: n must be the numMaterials of init");
+    if (n != (int)c.mesh.materials.size()) rt_fail("updateMaterials: n must be the numMaterials of init");
     for (int k = 0; k < n; k++)
-        if (materials[k].texId != -1 && (materials[k].texId < 0 || materials[k].texId >= (int)c.h_tex.size())) rt_fail("updateMaterials: material texId out of range");
-    c.h_materials.assign(materials, materials + n);
-    c.mesh_scene.lean_ok = mesh_lean_ok();
+        if (materials[k].texId != -1 && (materials[k].texId < 0 || materials[k].texId >= (int)c.mesh.tex.size())) rt_fail("updateMaterials: material texId out of range");
+    c.mesh.materials.assign(materials, materials + n);
+    c.mesh.scene.lean_ok = mesh_lean_ok(c.mesh.materials);
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
     for (DeviceState& d : c.devs) {
         HIP_CHECK(hipSetDevice(d.device));
-        if (n > 0) HIP_CHECK(hipMemcpy(d.d_materials, c.h_materials.data(), (size_t)n * sizeof(rt_material), hipMemcpyHostToDevice));
+        if (n > 0) HIP_CHECK(hipMemcpy(d.d_materials, c.mesh.materials.data(), (size_t)n * sizeof(rt_material), hipMemcpyHostToDevice));
     }
     HIP_CHECK(hipSetDevice(current));
     scene_edited();
@@ -1430,7 +1142,7 @@ void updateSpheres(const rt_sphere* spheres, const rt_material* materials, int n
     RenderContext& c = g_ctx;
     check_update("updateSpheres", true);
     if (!spheres || !materials) rt_fail("updateSpheres: spheres and materials must not be null");
-    if (n != c.sphere_scene.n) rt_fail("updateSpheres: n must be the n of init");
+    if (n != c.sphere.scene.n) rt_fail("updateSpheres: n must be the n of init");
     build_sphere_scene("updateSpheres", spheres, materials, n);
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
@@ -1445,7 +1157,7 @@ void updateSpheres(const rt_sphere* spheres, const rt_material* materials, int n
 int getMeshBvh(rt_bvh_node* nodes, int cap, rt_bbox* bounds) {
     const RenderContext& c = g_ctx;
     check_update("getMeshBvh", false);
-    const int count = (int)(2 * c.mesh_scene.first_leaf);
+    const int count = (int)(2 * c.mesh.scene.first_leaf);
     const int n = std::min(count, std::max(cap, 0));
     if (n > 0 && !nodes) rt_fail("getMeshBvh: nodes is null");
     if (n > 0) {
@@ -1455,7 +1167,7 @@ int getMeshBvh(rt_bvh_node* nodes, int cap, rt_bbox* bounds) {
         HIP_CHECK(hipMemcpy(nodes, c.devs[0].d_bvh, (size_t)n * sizeof(rt_bvh_node), hipMemcpyDeviceToHost));
         HIP_CHECK(hipSetDevice(current));
     }
-    if (bounds) *bounds = c.mesh_scene.bounds;
+    if (bounds) *bounds = c.mesh.scene.bounds;
     return count;
 }
 
@@ -1470,18 +1182,18 @@ double rtLastUpdateMs(void) {
 void rebuildBvh(int32_t* old_slot) {
     RenderContext& c = g_ctx;
     check_update("rebuildBvh", false);
-    RtMeshParams& mp = c.mesh_scene;
+    RtMeshParams& mp = c.mesh.scene;
     const uint32_t first_leaf = mp.first_leaf, per_leaf = mp.nppl;
     if ((first_leaf & (first_leaf - 1)) != 0) rt_fail("rebuildBvh: the rebuild needs a tree whose number of leaves is a power of two");
-    const size_t slots = (size_t)first_leaf * per_leaf, num_tris = c.h_tris.size();
+    const size_t slots = (size_t)first_leaf * per_leaf, num_tris = c.mesh.tris.size();
     size_t n = 0;
     for (uint32_t leaf = 0; leaf < first_leaf; leaf++)
-        for (uint32_t k = 0; k < per_leaf && !std::isinf(c.h_tris[(size_t)leaf * per_leaf + k].v[0].e[0]); k++) n++;
+        for (uint32_t k = 0; k < per_leaf && !std::isinf(c.mesh.tris[(size_t)leaf * per_leaf + k].v[0].e[0]); k++) n++;
     if (n > (size_t)RT_REBUILD_MAX_TRIS) rt_fail("rebuildBvh: more than RT_REBUILD_MAX_TRIS visible triangles");
-    const bool records = per_leaf <= 255;                   // as build_mesh_scene: after a rebuild the sentinels trail in every leaf
+    const bool records = per_leaf <= 255;                   // as layout_mesh: after a rebuild the sentinels trail in every leaf
     const size_t words = rt_build_workspace_words((uint32_t)n, first_leaf);
     std::vector<int32_t> from(num_tris);
-    if (records) c.h_leaf_ofs.assign(((size_t)first_leaf + 3) / 4, 0u);
+    if (records) c.mesh.leaf_ofs.assign(((size_t)first_leaf + 3) / 4, 0u);
     int current = 0;
     HIP_CHECK(hipGetDevice(&current));
     for (DeviceState& d : c.devs) {
@@ -1502,10 +1214,7 @@ void rebuildBvh(int32_t* old_slot) {
         HIP_CHECK(rt_launch_rebuild(b, d.stream));
         std::swap(d.d_tris, d.d_tris_alt);
         if (d.d_leaf_tri) HIP_CHECK(hipMemsetAsync(d.d_leaf_tri, 0, slots * 3 * sizeof(float4), d.stream));   // (the refit writes the real slots only)
-        RtRefitParams q;
-        q.slots = d.d_tris; q.nodes = reinterpret_cast<float*>(d.d_bvh); q.axis = d.d_bvh_axis; q.leaf_rec = d.d_leaf_tri;
-        q.first_leaf = first_leaf; q.nppl = per_leaf;
-        HIP_CHECK(rt_launch_refit(q, d.stream));
+        launch_refit(d);
         HIP_CHECK(hipEventRecord(d.ev_reb_stop, d.stream));
     }
     const DeviceState& d0 = c.devs[0];
@@ -1513,25 +1222,11 @@ void rebuildBvh(int32_t* old_slot) {
     HIP_CHECK(hipSetDevice(d0.device));
     HIP_CHECK(hipMemcpyAsync(&root, reinterpret_cast<const char*>(d0.d_bvh) + sizeof(rt_bvh_node), sizeof root, hipMemcpyDeviceToHost, d0.stream));
     HIP_CHECK(hipMemcpyAsync(from.data(), d0.d_old_slot, num_tris * sizeof(int32_t), hipMemcpyDeviceToHost, d0.stream));
-    if (records) HIP_CHECK(hipMemcpyAsync(c.h_leaf_ofs.data(), d0.d_leaf_ofs, c.h_leaf_ofs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, d0.stream));
-    double ms_max = 0.0;
-    for (DeviceState& d : c.devs) {
-        HIP_CHECK(hipSetDevice(d.device));
-        HIP_CHECK(hipStreamSynchronize(d.stream));          // blocking
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, d.ev_reb_start, d.ev_reb_stop));
-        ms_max = std::max(ms_max, (double)ms);
-    }
+    if (records) HIP_CHECK(hipMemcpyAsync(c.mesh.leaf_ofs.data(), d0.d_leaf_ofs, c.mesh.leaf_ofs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, d0.stream));
+    const double ms_max = finish_devices(&DeviceState::ev_reb_start, &DeviceState::ev_reb_stop, false);
     HIP_CHECK(hipSetDevice(current));
-    {   // the host mirror of the triangles follows the permutation
-        rt_triangle sentinel;
-        memset(&sentinel, 0, sizeof sentinel);
-        for (int v = 0; v < 3; v++) for (int a = 0; a < 3; a++) sentinel.v[v].e[a] = INFINITY;
-        std::vector<rt_triangle> moved(num_tris);
-        for (size_t s = 0; s < num_tris; s++) moved[s] = from[s] < 0 ? sentinel : c.h_tris[(size_t)from[s]];
-        c.h_tris.swap(moved);
-    }
-    if (records) c.h_leaf_tri.resize(slots * 3);            // (fetch_refit fills it)
+    permute_triangles(c.mesh, from);                        // the host mirror of the triangles follows the permutation
+    if (records) c.mesh.leaf_tri.resize(slots * 3);         // (fetch_refit fills it)
     mp.leaf_sentinels_trailing = 1;
     mp.bounds.min = root.a;
     mp.bounds.max = root.b;
@@ -1580,18 +1275,8 @@ void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t*
         for (int q = 0; q < 5; q++)
             if (plane[q]) deliver_stripes(d, part, static_cast<char*>(host[q]), static_cast<const char*>(plane[q]), kGuideBytes[q]);
     }
-    double ms_max = 0.0;
-    for (int k = 0; k < nd; k++) {
-        DeviceState& d = c.devs[k];
-        if (d.fb_rows == 0) continue;
-        HIP_CHECK(hipSetDevice(d.device));
-        HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's arrays are complete on return
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, d.ev_start, d.ev_stop));
-        ms_max = std::max(ms_max, (double)ms);
-    }
+    c.guides_ms = finish_devices(&DeviceState::ev_start, &DeviceState::ev_stop, true);      // blocking: the caller's arrays are complete on return
     HIP_CHECK(hipSetDevice(current));
-    c.guides_ms = ms_max;
 }
 
 double rtLastGuidesMs(void) { return g_ctx.guides_ms; }

@@ -1,14 +1,16 @@
 """CPU tripwire: the host runtime (rt_renderer.hip) says each thing once.  Device memory is allocated by one function that records the pointer with its
 owner and freed only by the functions that walk that record, so a new buffer cannot be forgotten in a hand-kept list of frees; every scene pointer of a
 kernel parameter block is assigned in exactly one place (sphere_params / mesh_params), so a frame, the guide planes and the denoiser cannot disagree about
-the scene; RenderContext holds the scene's constants in parameter-block form (sphere_scene / mesh_scene), not as a second set of members that is
-copied across field by field; and the whole-image preview passes (denoiseFrame, accumulateFrame) share one state struct (PassState), one release (free_pass)
-and one path around their kernels (begin_pass / end_pass), so a third pass is not a third copy of them."""
+the scene; RenderContext holds the scene as the two layout structs of rt_scene_layout.h, which keep the scene's constants in parameter-block form (their
+`scene` templates), not as a second set of members that is copied across field by field; and the whole-image preview passes (denoiseFrame,
+accumulateFrame) share one state struct (PassState), one release (free_pass) and one path around their kernels (begin_pass / end_pass), so a third pass
+is not a third copy of them."""
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RENDERER = os.path.join(ROOT, "cuda-raytracing-optimized_amd", "csrc", "rt_renderer.hip")
+LAYOUT = os.path.join(ROOT, "cuda-raytracing-optimized_amd", "csrc", "rt_scene_layout.h")
 # a function definition at column 0: return type, name, parameters, the opening brace
 FUNC = re.compile(r"^[A-Za-z_][\w:<>,*& ]*?\b(\w+)\s*\([^;{}]*\)\s*(?:const\s*)?\{", re.M)
 
@@ -24,8 +26,8 @@ PASS_MEMBERS = ["device", "npix", "owned", "d_guide", "d_in", "d_out"]
 PASSES = {"denoiseFrame", "accumulateFrame"}
 
 
-def _source():
-    return re.sub(r"//[^\n]*", "", open(RENDERER).read())
+def _source(path=RENDERER):
+    return re.sub(r"//[^\n]*", "", open(path).read())
 
 
 def _functions(src):
@@ -66,9 +68,18 @@ def test_render_context_does_not_mirror_the_parameter_blocks():
     m = re.search(r"^struct RenderContext \{(.*?)^\};", _source(), re.M | re.S)
     assert m, "struct RenderContext not found"
     body = m.group(1)
-    assert re.search(r"\bRtSphereParams\s+\w+", body) and re.search(r"\bRtMeshParams\s+\w+", body), "no scene template in RenderContext"
+    assert re.search(r"\bSphereLayout\s+\w+", body) and re.search(r"\bMeshLayout\s+\w+", body), "no scene layout in RenderContext"
     mirrored = [name for name in MIRRORED if re.search(r"\b%s\b" % name, body)]
     assert mirrored == [], f"RenderContext mirrors parameter-block fields: {mirrored}"
+    # the layout structs it holds: one template each, and no field of it a second time beside the template
+    for struct, template in (("SphereLayout", "RtSphereParams"), ("MeshLayout", "RtMeshParams")):
+        m = re.search(r"^struct %s \{(.*?)^\};" % struct, _source(LAYOUT), re.M | re.S)
+        assert m, f"struct {struct} not found"
+        members = re.findall(r"\b%s\s+\w+[^;]*;" % template, m.group(1))
+        assert len(members) == 1, f"{struct} holds {len(members)} {template} templates"
+        rest = m.group(1).replace(members[0], "")
+        mirrored = [name for name in MIRRORED if re.search(r"\b%s\b" % name, rest)]
+        assert mirrored == [], f"{struct} mirrors parameter-block fields: {mirrored}"
 
 
 def test_one_function_builds_the_whole_image_partition():
