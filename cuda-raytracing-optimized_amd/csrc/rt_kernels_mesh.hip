@@ -365,7 +365,7 @@ __global__ void __launch_bounds__(kThreads) k_rays_mesh(const RtMeshParams P, co
     const float* d = B.dir + (size_t)k * 3;
     const Ray r = make_ray(F3(o[0], o[1], o[2]), F3(d[0], d[1], d[2]));
     const float t_min = B.t_min ? B.t_min[k] : B.t_min_default;
-    const float t_max = B.t_max ? B.t_max[k] : FLT_MAX;
+    const float t_max = B.t_max ? fminf(B.t_max[k], FLT_MAX) : FLT_MAX;       // a t_max above FLT_MAX (+inf) is taken as FLT_MAX (rt_api.h)
     if (ANY) {
         uint32_t triId = 0;
         float hu = 0.0f, hv = 0.0f;

@@ -1309,7 +1309,7 @@ __global__ void __launch_bounds__(kThreads) k_rays_spheres(const RtSphereParams 
             org = F3(o[0], o[1], o[2]);
             dn = unit(F3(d[0], d[1], d[2]));                         // ray.h:9
             if (B.t_min) t_min = B.t_min[r];
-            if (B.t_max) t_max = B.t_max[r];
+            if (B.t_max) t_max = fminf(B.t_max[r], FLT_MAX);         // a t_max above FLT_MAX (+inf) is taken as FLT_MAX (rt_api.h)
         }
         if (ANY) {
             const float a = dot(dn, dn);

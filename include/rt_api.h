@@ -386,8 +386,9 @@ double rtLastDisplayMs(void);                      /* HIP-event time of its kern
  * occludedRays writes one byte per ray.  Sphere scenes: 1 iff some sphere has sphereHit(s, ray, tmin, tmax) < FLT_MAX (whatever the scan order).  Mesh scenes:
  * 1 iff the bounds test passes and hitBvh(ray, tmin, tmax, is_shadow = 1) < tmax.  The floor never occludes, exactly as the reference's shadow rays never
  * test it.
- * The caller owes 0 <= tmin < tmax, neither a NaN, and d finite and non-zero.  Rays are not validated one by one: a ray that breaks this gets an unspecified
- * result, the call still returns, and every other ray's result is unaffected.
+ * The caller owes 0 <= tmin < tmax, neither a NaN, and d finite and non-zero.  A tmax above FLT_MAX (+inf, a caller's "no bound") is taken as FLT_MAX:
+ * everything above is stated with min(tmax, FLT_MAX) (taken literally, tmax = +inf would accept the FLT_MAX a miss returns as a hit).  Rays are not
+ * validated one by one: a ray that breaks this gets an unspecified result, the call still returns, and every other ray's result is unaffected.
  *
  * Both calls are blocking and answer in the caller's ray order.  org and dir hold n x 3 floats; t_min and t_max n floats each, or NULL.  The outputs are
  * caller-owned host arrays (pageable is fine): traceRays takes one per plane named in `mask` and NULL for the others - t, prim, nodes of n entries, normal of

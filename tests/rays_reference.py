@@ -4,7 +4,8 @@ conditions every set is there to meet, the reference against the guide reference
 The reference is built from the CPU oracle's own functions through ctypes, the way tests/guides_reference.py is, and from nothing of the code under test:
 orc_sphere_hit in the caller's order against the running closest t (which starts at the ray's t_max), orc_hit_bbox + orc_hit_bvh with is_shadow 0 and 1 and
 orc_counters.node_visits, orc_plane_hit against the ray's own t_max.  The oracle's functions normalise the direction they are given once (ray.h:9), as
-traceRays does.  Hit point and normal are restated in numpy float32, operation by operation (guides_reference's _unit / _dot / _cross).
+traceRays does.  A t_max above FLT_MAX is taken as FLT_MAX before any of them is called, as the contract says (clamp_t_max; tests/test_rays_api.py records
+what the unclamped calls answer).  Hit point and normal are restated in numpy float32, operation by operation (guides_reference's _unit / _dot / _cross).
 
 The scenes are frames of guides_reference (the ray calls do not depend on the camera or the image size; the frame only names the scene to initialise).
 Every set is seeded."""
@@ -19,7 +20,10 @@ from guides_reference import F, FLT_MAX, PRIM_FLOOR, PRIM_NONE, _cross, _dot, _f
 PLANES = ("t", "prim", "normal", "uv", "nodes")
 CENTRE_FRAMES = ("random_50x37", "tie_mirror", "cloud_hybrid", "cloud_global", "staircase_a", "tris300_floor")
 SETS = tuple("centre:" + f for f in CENTRE_FRAMES) + ("sph_random:three_spheres", "sph_random:random_50x37", "sph_axis:tie_mirror",
-                                                      "mesh_random:tris300", "mesh_random:tris300_floor", "mesh_random:staircase_a")
+                                                      "mesh_random:tris300", "mesh_random:tris300_floor", "mesh_random:staircase_a",
+                                                      "mesh_axis:tris300", "mesh_axis:staircase_a", "mesh_surface:staircase_a", "mesh_surface:tris300",
+                                                      "sph_surface:random_50x37", "sph_axis:cloud_hybrid", "sph_axis:cloud_global",
+                                                      "mesh_inf:tris300", "sph_inf:three_spheres")
 RANDOM_SETS = tuple(s for s in SETS if "_random:" in s)
 OWN_BOUNDS_SHARE = 0.3                                          # of the rays of a random set draw their own t_min / t_max
 
@@ -44,6 +48,11 @@ def _c3(v):
     return (C.c_float * 3)(float(v[0]), float(v[1]), float(v[2]))
 
 
+def clamp_t_max(t_max):
+    """The contract's reading of the upper bounds: a t_max above FLT_MAX (+inf) is taken as FLT_MAX."""
+    return np.minimum(np.asarray(t_max, np.float32), np.float32(FLT_MAX))
+
+
 def _empty(n, mesh):
     out = {"t": np.full(n, FLT_MAX, np.float32), "prim": np.full(n, PRIM_NONE, np.int32), "normal": np.zeros((n, 3), np.float32),
            "uv": np.zeros((n, 2), np.float32), "occluded": np.zeros(n, np.uint8)}
@@ -52,14 +61,16 @@ def _empty(n, mesh):
     return out
 
 
-def sphere_rays(rt, O, spheres, org, dir, t_min, t_max):
-    """t, prim, normal, uv and occluded of rays against a sphere scene; t_min, t_max: one float32 per ray."""
+def sphere_rays(rt, O, spheres, org, dir, t_min, t_max, clamp=True):
+    """t, prim, normal, uv and occluded of rays against a sphere scene; t_min, t_max: one float32 per ray.  clamp = False: the oracle's calls on the raw
+    t_max, which is not the contract (only the test that records why the clamp exists asks for it)."""
     lib = O.load_oracle()
     spheres = np.ascontiguousarray(spheres, dtype=rt.sphere_dtype)
     sp_ptr = [C.cast(spheres.ctypes.data + 16 * k, C.POINTER(rt.sphere)) for k in range(len(spheres))]
     hit = lib.orc_sphere_hit
     n = len(org)
     out = _empty(n, False)
+    t_max = clamp_t_max(t_max) if clamp else np.asarray(t_max, np.float32)
     for r in range(n):
         o, d = _c3(org[r]), _c3(dir[r])
         tmin, tmax = C.c_float(t_min[r]), float(np.float32(t_max[r]))
@@ -98,8 +109,9 @@ def sphere_occluded_by_definition(rt, O, spheres, org, dir, t_min, t_max):
     return out
 
 
-def mesh_rays(rt, O, hm, materials, textures, floor, org, dir, t_min, t_max):
-    """The five planes and occluded of rays against a mesh scene; floor = (norm xyz, point xyz) with rt_render_options.floor = 1, None without."""
+def mesh_rays(rt, O, hm, materials, textures, floor, org, dir, t_min, t_max, clamp=True):
+    """The five planes and occluded of rays against a mesh scene; floor = (norm xyz, point xyz) with rt_render_options.floor = 1, None without.
+    clamp = False: as in sphere_rays."""
     lib = O.load_oracle()
     scene = O.mesh_scene(hm, materials, textures, floor)
     tris = hm.tris
@@ -111,6 +123,7 @@ def mesh_rays(rt, O, hm, materials, textures, floor, org, dir, t_min, t_max):
             plane.norm.e[a] = float(floor[a]); plane.point.e[a] = float(floor[3 + a])
     n = len(org)
     out = _empty(n, True)
+    t_max = clamp_t_max(t_max) if clamp else np.asarray(t_max, np.float32)
     for r in range(n):
         o, d = _c3(org[r]), _c3(dir[r])
         tmin, tmax = C.c_float(t_min[r]), C.c_float(t_max[r])
@@ -213,9 +226,10 @@ def _sph_random_set(rt, O, frame):
 
 
 def _sph_axis_set(rt, O, frame):
-    """48 rays against tie_mirror with one or two direction components exactly 0: 16 in the plane x = 0 aimed into the lens the overlapping pair (indices 1, 2 at
+    """48 rays with one or two direction components exactly 0.  The clouds: _sph_axis_cloud_set.  tie_mirror: 16 in the plane x = 0 aimed into the lens the overlapping pair (indices 1, 2 at
     x = +-0.2) shares - both spheres at the same t bit for bit -, 16 along an axis through a sphere's centre, 16 with one zero component elsewhere."""
-    assert frame == "tie_mirror"
+    if frame != "tie_mirror":
+        return _sph_axis_cloud_set(rt, O, frame)
     sp = np.ascontiguousarray(G.sphere_frame(rt, frame)[0], dtype=rt.sphere_dtype)
     rng = np.random.default_rng(103)
     org, d = np.zeros((48, 3), np.float32), np.zeros((48, 3), np.float32)
@@ -242,7 +256,8 @@ def _sph_axis_set(rt, O, frame):
 def _mesh_random_set(rt, O, frame):
     """tris300 and tris300_floor share their rays (the floor is an option, not geometry).  Origins: half inside the bounds; a quarter outside aimed
     at a triangle; a quarter outside pointing away from the centre (these miss the bounds).  Every component of every unit direction is at least 1e-3 in magnitude:
-    a ray lying in a slab plane puts 0 * inf into the box test, whose device form belongs to the render path (csrc/rt_device.h)."""
+    a ray lying in a slab plane puts 0 * inf into the box test, whose device form belongs to the render path (csrc/rt_device.h).  Those rays are the mesh_axis
+    sets' (mesh_axis_build)."""
     n = 600 if frame == "staircase_a" else 1000
     f = G.mesh_frame(rt, O, "tris300" if frame.startswith("tris300") else frame)
     b = f["hm"].view.bounds
@@ -274,11 +289,179 @@ def _mesh_random_set(rt, O, frame):
     return org.astype(np.float32), d.astype(np.float32), t_min, t_max
 
 
+def _zero(kind):
+    """The zero of a ray kind: +0.0 for the even kinds, -0.0 for the odd ones (1 / -0 = -inf takes the swap branch of the slab test)."""
+    return np.float32(-0.0) if kind % 2 else np.float32(0.0)
+
+
+def _in_plane_direction(rng, axis, zero):
+    """A direction with `zero` on `axis` and the other two components at least 2e-3 of its length in magnitude, scaled by 10**U(-2, 2)."""
+    while True:
+        v = rng.normal(size=2)
+        v /= np.sqrt((v * v).sum())
+        if np.abs(v).min() >= 2e-3:
+            break
+    d = np.zeros(3, np.float32)
+    d[[a for a in range(3) if a != axis]] = (v * 10.0 ** rng.uniform(-2, 2)).astype(np.float32)
+    d[axis] = zero
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def mesh_axis_build(rt, O, frame):
+    """(org, dir, t_min, t_max, info) of mesh_axis:<frame>: 600 rays, six kinds of 100, every ray with at least one direction component exactly zero (+0.0 in
+    the even kinds, -0.0 in the odd ones) and own bounds drawn by _own_bounds.
+    0, 1: two zero components - along one axis from 1.0 outside the scene bounds, the other two origin coordinates inside them.
+    2, 3: one zero component, the origin anywhere in the bounds widened by half their extent.
+    4:    one zero component on axis a and org[a] exactly on a plane of a node box: on staircase_a a box that is flat on a (lo[a] == hi[a]), the origin displaced
+          inside that plane and the ray aimed at a point of the flat box - both slab products of that axis are 0 * inf = NaN -; on tris300, which has no flat
+          box, either plane of one of the nodes 1 to 64, the ray aimed at a point of that box.
+    5:    as 4 with a plane of the scene bounds (node 1): the root test itself meets the NaN.  The ray is aimed at a point of the bounds.
+    info: kind, axis (the zero axis of kinds 2 to 5, the ray's axis of kinds 0 and 1), node and side (0: lo, 1: hi) of kinds 4 and 5, one entry per ray."""
+    n, per = 600, 100
+    hm = G.mesh_frame(rt, O, frame)["hm"]
+    nodes = hm.bvh
+    first_leaf = hm.view.numBvhNodes // 2
+    lo, hi = nodes["a"][1].astype(np.float64), nodes["b"][1].astype(np.float64)
+    assert np.array_equal(nodes["a"][1], [hm.view.bounds.min.e[a] for a in range(3)]) and np.array_equal(nodes["b"][1], [hm.view.bounds.max.e[a] for a in range(3)])
+    ext = hi - lo
+    rng = np.random.default_rng(106 if frame == "staircase_a" else 107)
+    real = np.isfinite(nodes["a"]).all(axis=1) & np.isfinite(nodes["b"]).all(axis=1)
+    real[0] = False
+    flat = [np.flatnonzero(real & (nodes["a"][:, a] == nodes["b"][:, a])) for a in range(3)]
+    org, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    info = {k: np.full(n, -1, np.int32) for k in ("kind", "axis", "node", "side")}
+    for k in range(n):
+        kind = k // per
+        zero = _zero(kind)
+        a = int(rng.integers(0, 3))
+        others = [b for b in range(3) if b != a]
+        node = side = -1
+        if kind < 2:
+            sign = float(rng.choice([-1.0, 1.0]))
+            o = rng.uniform(lo, hi)
+            o[a] = lo[a] - 1.0 if sign > 0 else hi[a] + 1.0
+            v = np.full(3, zero, np.float32)
+            v[a] = np.float32(sign * 10.0 ** rng.uniform(-2, 2))
+        elif kind < 4:
+            o = rng.uniform(lo - ext / 2, hi + ext / 2)
+            v = _in_plane_direction(rng, a, zero)
+        else:
+            if kind == 5:
+                node = 1
+            elif frame == "staircase_a":
+                assert all(len(f) >= 100 for f in flat), [len(f) for f in flat]
+                node = int(rng.choice(flat[a]))
+            else:
+                assert not any(len(f) for f in flat) and first_leaf > 64
+                node = int(rng.integers(1, 65))
+            side = int(rng.integers(0, 2))
+            blo, bhi = nodes["a"][node].astype(np.float64), nodes["b"][node].astype(np.float64)
+            target = rng.uniform(blo, bhi)
+            o = target + rng.normal(size=3) * np.maximum(bhi - blo, 0.05 * ext)        # displaced inside the plane: axis a is overwritten below
+            v = ((target - o) * 10.0 ** rng.uniform(-2, 2)).astype(np.float32)
+            assert np.all(v[others] != 0)
+            v[a] = zero
+            o = o.astype(np.float32)
+            o[a] = (nodes["a"] if side == 0 else nodes["b"])[node][a]                   # the plane's own float32
+        org[k], d[k] = o, v
+        info["kind"][k], info["axis"][k], info["node"][k], info["side"][k] = kind, a, node, side
+    t_min, t_max, _ = _own_bounds(rng, n, frame)
+    for arr in info.values():
+        arr.setflags(write=False)
+    return org, d, t_min, t_max, info
+
+
+def _mesh_axis_set(rt, O, frame):
+    return mesh_axis_build(rt, O, frame)[:4]
+
+
+SURFACE_T_MIN = {"mesh": (0.0, 1e-42, 1e-6, 0.01), "sph": (0.0, 1e-42, 1e-6, 0.001)}      # cycled over the rays; 1e-42 is a denormal
+
+
+@functools.lru_cache(maxsize=None)
+def surface_build(rt, O, name):
+    """(org, dir, t_min, t_max, prim) of mesh_surface:<frame> / sph_surface:<frame>: the origins are the float32 hit points org + t * unit(dir) of the
+    NULL-bounds reference of the frame's random set (triangles and spheres only, not the floor; the first 600 of them), prim the primitive each origin lies on; new directions from
+    _directions(rng, m, 2e-3); t_min cycles through SURFACE_T_MIN, t_max is FLT_MAX."""
+    kind, frame = name.split(":")
+    src = ("mesh_random:" if kind == "mesh_surface" else "sph_random:") + frame
+    o, dd, _, _ = ray_set(rt, O, src)
+    ref = reference(rt, O, src, own=False)
+    hit = np.flatnonzero(ref["prim"] >= 0)[:600]                    # (a set holds at most 600 rays)
+    org = np.zeros((len(hit), 3), np.float32)
+    for k, r in enumerate(hit):
+        of, dn, t = _f3(o[r]), _unit(_f3(dd[r])), F(ref["t"][r])
+        org[k] = [of[a] + t * dn[a] for a in range(3)]
+    rng = np.random.default_rng({"mesh_surface:staircase_a": 108, "mesh_surface:tris300": 109, "sph_surface:random_50x37": 110}[name])
+    d = _directions(rng, len(hit), 2e-3)
+    cycle = np.array(SURFACE_T_MIN["mesh" if kind == "mesh_surface" else "sph"], np.float32)
+    t_min = cycle[np.arange(len(hit)) % 4]
+    t_max = np.full(len(hit), FLT_MAX, np.float32)
+    prim = ref["prim"][hit].copy()
+    prim.setflags(write=False)
+    return org, d, t_min, t_max, prim
+
+
+def _surface_set(name):
+    return lambda rt, O, frame: surface_build(rt, O, name)[:4]
+
+
+def _sph_axis_cloud_set(rt, O, frame):
+    """48 rays against a cloud (the hybrid and the global scene copy, whose culling must keep a node on the NaN of an axis-parallel ray): 16 along an axis
+    through a sphere's centre, 16 with two zero components through random points of the scene's extent, 16 with one zero component; every other zero is -0.0."""
+    sp = np.ascontiguousarray(G.sphere_frame(rt, frame)[0], dtype=rt.sphere_dtype)
+    rng = np.random.default_rng(116 if frame == "cloud_hybrid" else 112)
+    c = sp["center"].astype(np.float64)
+    small = sp["radius"] < 10.0                                    # (not a ground sphere, should the scene have one)
+    lo, hi = c[small].min(axis=0), c[small].max(axis=0)
+    org, d = np.zeros((48, 3), np.float32), np.zeros((48, 3), np.float32)
+    zeros = 0
+
+    def zero():
+        nonlocal zeros
+        zeros += 1
+        return np.float32(-0.0) if zeros % 2 else np.float32(0.0)
+
+    for k in range(32):
+        axis, sign = int(rng.integers(0, 3)), float(rng.choice([-1.0, 1.0]))
+        v = np.array([zero() if a != axis else 0.0 for a in range(3)], np.float32)
+        v[axis] = sign * rng.uniform(0.05, 20.0)
+        if k < 16:                                                  # through a centre, from outside the sphere
+            pick = int(rng.choice(np.flatnonzero(small)))
+            o = sp["center"][pick].copy()
+            o[axis] -= np.float32(sign * (sp["radius"][pick] + rng.uniform(0.5, 4.0)))
+        else:                                                       # through a random point of the extent
+            o = rng.uniform(lo, hi).astype(np.float32)
+        org[k], d[k] = o, v
+    for k in range(32, 48):                                         # one zero component
+        v = (rng.normal(size=3) * 10.0 ** rng.uniform(-1, 1)).astype(np.float32)
+        v[int(rng.integers(0, 3))] = zero()
+        org[k] = rng.uniform(lo, hi)
+        d[k] = v
+    return org, d, None, None
+
+
+def _inf_set(src):
+    """The rays of `src` with the t_max of every ray k % 3 == 0 replaced by +inf and of every ray k % 3 == 1 by FLT_MAX."""
+    def build(rt, O, frame):
+        org, d, t_min, t_max = ray_set(rt, O, src)
+        t_max = t_max.copy()
+        k = np.arange(len(t_max))
+        t_max[k % 3 == 0] = np.inf
+        t_max[k % 3 == 1] = FLT_MAX
+        return org, d, t_min, t_max
+    return build
+
+
 @functools.lru_cache(maxsize=None)
 def ray_set(rt, O, name):
     """(org (n, 3), dir (n, 3), t_min (n,) or None, t_max (n,) or None) of a named set; None: the set has no bounds of its own."""
     kind, frame = name.split(":")
-    org, d, t_min, t_max = {"centre": _centre_set, "sph_random": _sph_random_set, "sph_axis": _sph_axis_set, "mesh_random": _mesh_random_set}[kind](rt, O, frame)
+    builders = {"centre": _centre_set, "sph_random": _sph_random_set, "mesh_random": _mesh_random_set, "mesh_axis": _mesh_axis_set,
+                "sph_axis": _sph_axis_set, "mesh_surface": _surface_set(name), "sph_surface": _surface_set(name),
+                "mesh_inf": _inf_set("mesh_random:" + frame), "sph_inf": _inf_set("sph_random:" + frame)}
+    org, d, t_min, t_max = builders[kind](rt, O, frame)
     for a in (org, d, t_min, t_max):
         if a is not None:
             a.setflags(write=False)

@@ -30,16 +30,28 @@ def _area(lo, hi):
     return np.where(hi[:, 0] < lo[:, 0], F(0.0), a).astype(F)
 
 
-def numpy_rebuild(rt, tris, num_nodes, nppl):
-    """(new tris, old_slot, nodes, bounds) of the rebuild of the leaf-ordered `tris` in a tree of num_nodes nodes."""
+COUNTS = ("winner", "no_winner", "mixed_nodes", "inf_costs", "nan_costs", "nonzero_costs", "inf_centroids", "denormal_centroids_pos", "denormal_centroids_neg")
+
+
+def numpy_rebuild(rt, tris, num_nodes, nppl, counts=None):
+    """(new tris, old_slot, nodes, bounds) of the rebuild of the leaf-ordered `tris` in a tree of num_nodes nodes.  counts: a dict that receives, for this
+    rebuild, the nodes with m > 1 that have a winner and those that have none, the nodes that hold finite and +inf costs together, the +inf, NaN and non-zero
+    costs seen, the infinite centroid coordinates and the denormal ones of either sign (COUNTS)."""
     first_leaf = num_nodes // 2
     slots = first_leaf * nppl
     src = visible_slots(tris, first_leaf, nppl)
     n = len(src)
     v = tris["v"][src].astype(F)
     lo, hi = v.min(axis=1), v.max(axis=1)
-    cent = (F(0.5) * (lo + hi)).astype(F)
+    with np.errstate(over="ignore"):
+        cent = (F(0.5) * (lo + hi)).astype(F)
     ids = np.arange(n)
+    if counts is not None:
+        counts.update(dict.fromkeys(COUNTS, 0))
+        tiny = np.finfo(F).tiny
+        counts["inf_centroids"] = int(np.isinf(cent).sum())
+        counts["denormal_centroids_pos"] = int(((cent > 0) & (cent < tiny)).sum())
+        counts["denormal_centroids_neg"] = int(((cent < 0) & (cent > -tiny)).sum())
     order = [np.lexsort((ids, cent[:, a])) for a in range(3)]          # by (cent[axis], i): -0.0 == 0.0 in the comparison
     beg, end = {1: 0}, {1: n}
     waxis = {}
@@ -65,6 +77,13 @@ def numpy_rebuild(rt, tris, num_nodes, nppl):
                         right = np.append(right, F(0.0))
                         costs.append((left[cuts - 1] * cuts.astype(F) + right[cuts] * (m - cuts).astype(F)).astype(F))
                     flat = np.concatenate(costs)
+                    if counts is not None and m > 1:
+                        finite = flat < F(np.inf)
+                        counts["winner" if finite.any() else "no_winner"] += 1
+                        counts["mixed_nodes"] += int(finite.any() and bool(np.isposinf(flat).any()))
+                        counts["inf_costs"] += int(np.isposinf(flat).sum())
+                        counts["nan_costs"] += int(np.isnan(flat).sum())
+                        counts["nonzero_costs"] += int((flat != 0).sum())
                     flat = np.where(flat < F(np.inf), flat, F(np.inf))          # a NaN never wins
                     cut = (m + 1) // 2
                     if len(flat) and flat.min() < F(np.inf):
@@ -106,6 +125,36 @@ def quantised_tris(rt, n, seed=17):
     tris["meshID"] = rng.integers(0, 4, n)
     assert (v.view(np.uint32) == 0x80000000).any() and (v.view(np.uint32) == 0).any()
     return tris
+
+
+def scaled_blob(rt, n, scale, every=None, seed=5):
+    """S.blob_tris(rt, n, seed) with the vertices scaled in float64 and then rounded to float32; every = k: only each k-th triangle is scaled.  Scales near the
+    ends of the float32 range: areas and costs that overflow to +inf, costs that underflow to 0, denormal coordinates and centroids."""
+    tris = S.blob_tris(rt, n, seed)
+    v = tris["v"].astype(np.float64)
+    sel = slice(None) if every is None else slice(0, None, every)
+    v[sel] *= scale
+    tris["v"] = v.astype(F)
+    assert np.isfinite(tris["v"]).all()
+    return tris
+
+
+# case -> (scale, every, flat).  What each is there for is asserted from numpy_rebuild's counts by tests/test_rebuild_api.py::test_twin_against_numpy (_claims).
+# A single triangle scaled by 1e25 already has an infinite area, so a node that holds one has no finite cost at all: finite and +inf costs in one node need
+# 1e18, where one scaled triangle's box is finite and two of them overflow.  At 1e37 every centroid is still finite (|lo + hi| < 2.4e38): 2e37 has infinite
+# ones.  A NaN cost needs 0 * inf: boxes of zero width (every x equal) and infinite height.
+EXTREMES = {"scale 3e18": (3e18, None, False), "scale 1e25": (1e25, None, False), "scale 1e37": (1e37, None, False), "scale 2e37": (2e37, None, False),
+            "scale 1e25, every 7th": (1e25, 7, False), "scale 1e18, every 7th": (1e18, 7, False), "scale 1e-25": (1e-25, None, False),
+            "scale 1e-38": (1e-38, None, False), "scale 1e-44": (1e-44, None, False), "flat in x, scale 2e37": (2e37, None, True)}
+
+
+def extreme_mesh(rt, case):
+    """The mesh of a case of EXTREMES: 200 scaled triangles (flat: every x coordinate 1.0), 3 slots per leaf, scrambled."""
+    scale, every, flat = EXTREMES[case]
+    tris = scaled_blob(rt, 200, scale, every)
+    if flat:
+        tris["v"][:, :, 0] = 1.0
+    return scrambled(rt.HostMesh.build(tris, 3))
 
 
 def scrambled(hm, seed=71):

@@ -32,6 +32,21 @@ def jitter(tris, seed, amount=3.0):
     return out
 
 
+def extremes(tris, seed=61):
+    """A copy of `tris` in which 60 real triangles, chosen by seed, sit at the edges of what updateTriangles takes: twenty with one coordinate a NaN (the boxes
+    ignore it; a NaN is no infinity, so no slot's sentinel state changes), twenty scaled by 1e37 (finite, near FLT_MAX) and twenty by 1e-44 (denormals of a few
+    units in the last place, zeros among them).  Returns (copy, the three index arrays)."""
+    rng = np.random.default_rng(seed)
+    out = tris.copy()
+    pick = rng.permutation(np.flatnonzero(is_real(tris)))[:60]
+    nan, big, small = pick[:20], pick[20:40], pick[40:]
+    out["v"].reshape(len(out), 9)[nan, rng.integers(0, 9, 20)] = np.nan
+    out["v"][big] = (out["v"][big].astype(np.float64) * 1e37).astype(np.float32)
+    out["v"][small] = (out["v"][small].astype(np.float64) * 1e-44).astype(np.float32)
+    assert np.array_equal(is_real(out), is_real(tris)) and np.isfinite(out["v"][big]).all() and int(np.isnan(out["v"]).sum()) == 20
+    return out, (nan, big, small)
+
+
 def blob_tris(rt, n, seed, mats=4):
     """n small seeded triangles scattered in a cube of side 20."""
     rng = np.random.default_rng(seed)

@@ -5,6 +5,7 @@ partitions, the three sphere scene copies, no side effects, the empty batch, two
 import numpy as np
 import pytest
 
+import guides_reference as G
 import rays_reference as R
 from preview_support import bits as _bits, exits_99, init_frame, same, stats_tuple as _stats_tuple
 
@@ -42,8 +43,10 @@ def _check(rt, O, name, ref, own, what):
 @pytest.mark.parametrize("name", R.SETS)
 def test_sets_match_the_reference(rt, O, name):
     """centre: six guide frames - the full LDS copy (random_50x37, tie_mirror), the hybrid and the global scene copy, the staircase with its textures, the
-    loose triangles with the floor -, also against renderGuides of the same initialised frame on the GPU; sph_random, sph_axis, mesh_random: see
-    tests/test_rays_api.py for what each set holds.  Once with the set's t_min / t_max arrays, once with NULL for both."""
+    loose triangles with the floor -, also against renderGuides of the same initialised frame on the GPU; sph_random, sph_axis, mesh_random and the edge sets
+    - mesh_axis and sph_axis on the clouds (exactly-zero direction components of both signs, origins on box planes), mesh_surface and sph_surface (origins
+    on a surface, t_min = 0 and a denormal), mesh_inf and sph_inf (t_max = +inf) -: see tests/test_rays_api.py for what each set holds.  Once with the set's
+    t_min / t_max arrays, once with NULL for both."""
     frame = R.frame_of(name)
     init_frame(rt, O, frame)
     has_own = R.ray_set(rt, O, name)[2] is not None
@@ -273,11 +276,14 @@ def test_empty_batch_and_timing(rt, O):
 
 # ---- 8. isolation ------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("frame", ["random_50x37", "cloud_global"])
+@pytest.mark.parametrize("frame", ["random_50x37", "cloud_global", "tris300"])
 def test_broken_rays_do_not_disturb_the_others(rt, O, frame):
     """130 rays, ray 7 with d = (0, 0, 0) and ray 70 with a NaN origin: the call returns and the other 128 results equal the reference.  Nothing is asserted
-    about the two rays themselves.  Sphere scenes only: the LDS copy and the global one."""
-    name = "sph_random:random_50x37" if frame == "random_50x37" else "centre:cloud_global"
+    about the two rays themselves.  Sphere scenes: the LDS copy and the global one.  A mesh: tris300, a tree of 256 nodes and nothing larger - every box test
+    of a NaN ray passes, so it visits every node."""
+    name = {"random_50x37": "sph_random:random_50x37", "cloud_global": "centre:cloud_global", "tris300": "mesh_random:tris300"}[frame]
+    if frame == "tris300":
+        assert G.mesh_frame(rt, O, frame)["hm"].view.numBvhNodes == 256
     org, d, t_min, t_max = [None if a is None else np.array(a[:130]) for a in R.ray_set(rt, O, name)]
     ref = R.reference(rt, O, name)
     d[7] = 0.0

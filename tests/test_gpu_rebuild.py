@@ -148,6 +148,8 @@ def _shape_mesh(rt, O, case):
         return R.scrambled(rt.HostMesh.build(src[S.is_real(src)], 1, extra_levels=8))
     if case == "sentinel before real":
         return S.sentinel_first_mesh(rt)
+    if case in R.EXTREMES:
+        return R.extreme_mesh(rt, case)
     n = {"T - 1": T - 1, "T": T, "T + 1": T + 1, "2 T + 3": 2 * T + 3}[case]
     hm = R.scrambled(rt.HostMesh.build(S.blob_tris(rt, n, 40 + n % 7), 5))
     assert int(S.is_real(hm.tris).sum()) == n
@@ -155,13 +157,15 @@ def _shape_mesh(rt, O, case):
 
 
 SHAPES = [(2, 1), (4, 1), (4, 7), (256, 7), (512, 5), "full tree", "one triangle", "quantised", "2^17 mostly empty leaves", "sentinel before real",
-          "T - 1", "T", "T + 1", "2 T + 3"]
+          "T - 1", "T", "T + 1", "2 T + 3"] + list(R.EXTREMES)
 
 
 @pytest.mark.parametrize("case", SHAPES, ids=[str(c) for c in SHAPES])
 def test_shapes(rt, O, case):
     """getMeshBvh and old_slot against the twin, no render: the lowest trees, trees of several workgroups, every cut forced, one triangle, equal centroids and
-    costs, a mostly empty tree, hidden triangles, and triangle counts either side of one and two tiles of the scan kernels."""
+    costs, a mostly empty tree, hidden triangles, triangle counts either side of one and two tiles of the scan kernels, and the float extremes of
+    rebuild_support.EXTREMES (areas and costs that are +inf or NaN, nodes without a winner, costs of 0, infinite and denormal centroids: what each case holds is
+    asserted on the CPU by tests/test_rebuild_api.py)."""
     hm = _shape_mesh(rt, O, case)
     if isinstance(case, tuple):
         assert hm.view.numBvhNodes // 2 == case[0] and hm.nppl == case[1]

@@ -218,17 +218,20 @@ def _shape_mesh(rt, O, case):
         return S.sentinel_first_mesh(rt)
     if case == "signed zeros":
         return rt.HostMesh.build(S.zero_tris(rt), 5)
+    if case == "extremes":
+        return S.blob_mesh(rt, 128, 5)
     first_leaf, nppl = case
     return S.blob_mesh(rt, first_leaf, nppl)
 
 
-SHAPES = [(2, 1), (4, 1), (4, 7), (128, 5), (256, 1), (256, 7), (512, 5), "tris300 nppl 1, 2^17 leaves", "sentinel before real", "signed zeros"]
+SHAPES = [(2, 1), (4, 1), (4, 7), (128, 5), (256, 1), (256, 7), (512, 5), "tris300 nppl 1, 2^17 leaves", "sentinel before real", "signed zeros", "extremes"]
 
 
 @pytest.mark.parametrize("case", SHAPES, ids=[str(c) for c in SHAPES])
 def test_tree_shapes(rt, O, case):
     """getMeshBvh against the twin, no render: trees lower than one workgroup's subtree, exactly one, two, and three reduction passes (2^17 mostly empty
-    leaves); 1, 5 and 7 slots per leaf; a mesh without compact leaf records; boxes whose zeros' signs depend on the visiting order."""
+    leaves); 1, 5 and 7 slots per leaf; a mesh without compact leaf records; boxes whose zeros' signs depend on the visiting order; an edit that brings NaN
+    coordinates (ignored by the boxes), coordinates near FLT_MAX and denormal ones."""
     hm = _shape_mesh(rt, O, case)
     if isinstance(case, tuple):
         assert hm.view.numBvhNodes // 2 == case[0] and hm.nppl == case[1]
@@ -251,6 +254,13 @@ def test_tree_shapes(rt, O, case):
             new["v"][real] = -new["v"][real]
             _apply(rt, hm, 0, new)
             _nodes_match_twin(rt, hm, f"{case}: negated")
+        elif case == "extremes":                                # NaN, near-FLT_MAX and denormal coordinates (scene_update_support.extremes)
+            _apply(rt, hm, 0, S.extremes(hm.tris)[0])
+            nodes = _nodes_match_twin(rt, hm, f"{case}: edited")
+            want_nodes, want_bounds = S.numpy_refit(hm.tris, hm.bvh, hm.nppl)
+            same(hm.bvh, want_nodes, f"{case}: the twin against the numpy restatement")
+            same(S.view_bounds(hm), want_bounds, f"{case}: the twin's bounds against the numpy restatement")
+            assert not np.array_equal(bits(nodes), bits(before)) and not np.isnan(nodes["a"][1:]).any() and not np.isnan(nodes["b"][1:]).any()
         else:
             _apply(rt, hm, 0, S.jitter(hm.tris, 50))
             nodes = _nodes_match_twin(rt, hm, f"{case}: jittered")

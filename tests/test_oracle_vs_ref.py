@@ -12,6 +12,7 @@ import pytest
 
 from oracle import oracle as O
 
+FLT_MAX = float(np.finfo(np.float32).max)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vs_ref.npz")
 MINT = os.environ.get("RT_MINT_VS_REF")
 _minted = {}
@@ -89,6 +90,70 @@ def _function_cases(rt):
         pl = rt.plane(); pl.norm.e[:] = (0.0, 1.0, 0.0); pl.point.e[:] = (0.0, float(rng.uniform(-1, 1)), 0.0)
         c["plane"] = pl
         cases.append(c)
+    return cases + _edge_cases(rt, rng)
+
+
+def _edge_cases(rt, rng):
+    """480 more cases at the edges the ray queries reach (tests/rays_reference.py: mesh_axis, the _inf sets), drawn after the random ones so that those keep
+    their inputs.  Every coordinate is rounded to float32 first, so that "on the plane" survives the conversion.  Kind k % 6:
+    0: a box flat on one axis, the origin in its plane, that direction component zero (both slab products of the axis are 0 * inf);
+    1: the same flat box with the origin off the plane (the axis alone rejects the ray: -inf, -inf or +inf, +inf);
+    2: an ordinary box, the origin exactly on its lo or hi plane of an axis whose direction component is zero (one product is NaN, the other +-inf);
+    3: as 2 with two zero components and the origin on a plane of each of the two axes;
+    4: as 2 but a non-zero component on the plane's axis (t0 or t1 is exactly 0, below the test's t_min of 0.001);
+    5: an ordinary box, no zero component, the origin inside it.
+    Zeros are +0.0 in the first half of the cases and -0.0 in the second (1 / -0 = -inf takes the swap branch).  Every other case takes FLT_MAX as the box's
+    and the triangle's t_max.  Triangles: the ray lies in the triangle's plane - from a point of the plane towards another one - in the kinds 0 to 2 (the
+    determinant is 0 up to rounding: either side of the EPS test), starts on a vertex or an edge in the kinds 3 and 4, and is an ordinary hit in kind 5."""
+    f = np.float32
+    cases = []
+    n = 480
+    for k in range(n):
+        kind = k % 6
+        zero = f(0.0) if k < n // 2 else f(-0.0)
+        c = {"seed": int(rng.integers(1, 2 ** 32)) | 1}
+        lo = rng.uniform(-2, 1, 3).astype(f)
+        hi = (lo + rng.uniform(0.1, 2, 3).astype(f)).astype(f)
+        a, b = (int(x) for x in rng.permutation(3)[:2])
+        d = rng.normal(size=3).astype(f)
+        org = rng.uniform(lo, hi).astype(f)
+        if kind in (0, 1):
+            hi[a] = lo[a]
+            org = (rng.uniform(lo, hi) + rng.normal(size=3) * (0 if k % 4 < 2 else 1.5)).astype(f)       # inside the flat box's rectangle, or around it
+            org[a] = lo[a] if kind == 0 else lo[a] + f(rng.choice([-0.5, 0.5]))
+            d[a] = zero
+        elif kind in (2, 3, 4):
+            org[a] = (lo if rng.integers(0, 2) else hi)[a]
+            if kind != 4:
+                d[a] = zero
+            if kind == 3:
+                org[b] = (lo if rng.integers(0, 2) else hi)[b]
+                d[b] = zero
+        c["lo"], c["hi"], c["org"], c["d"], c["d_box"] = lo, hi, org, d, d
+        sp = rt.sphere(); sp.center.e[:] = rng.uniform(-2, 2, 3); sp.radius = rng.uniform(0.1, 2.5)
+        c["sphere"] = sp
+        tri = rt.triangle()
+        v = rng.uniform(-2, 2, (3, 3)).astype(f)
+        for q in range(3):
+            tri.v[q].e[:] = v[q]
+        inside = (v * rng.dirichlet([1, 1, 1])[:, None]).sum(axis=0)
+        if kind in (0, 1, 2):                                       # in the plane: from one affine combination of the vertices towards another
+            w = rng.normal(size=3); w += (1 - w.sum()) / 3
+            start = (v * w[:, None]).sum(axis=0)
+            c["tri_org"], c["dd"] = start.astype(f), ((inside - start) * 10.0 ** rng.uniform(-1, 1)).astype(f)
+        elif kind == 3:                                             # from a vertex
+            c["tri_org"], c["dd"] = v[k % 3].copy(), rng.normal(size=3).astype(f)
+        elif kind == 4:                                             # from a point of an edge, to the rounding of the midpoint
+            c["tri_org"], c["dd"] = ((v[0] + v[1]) * f(0.5)).astype(f), rng.normal(size=3).astype(f)
+        else:
+            c["tri_org"] = org
+            c["dd"] = (inside - org).astype(f)
+        c["tri"] = tri
+        pl = rt.plane(); pl.norm.e[:] = (0.0, 1.0, 0.0); pl.point.e[:] = (0.0, float(rng.uniform(-1, 1)), 0.0)
+        c["plane"] = pl
+        if k % 2:
+            c["box_tmax"] = c["tri_tmax"] = FLT_MAX
+        cases.append(c)
     return cases
 
 
@@ -104,10 +169,12 @@ def _functions(lib, p, cases):
         r["unit_sphere"][k], r["rng_after"][k] = o[:], s.value
         org, d, db = f3(c["org"]), f3(c["d"]), f3(c["d_box"])
         r["sphere_t"][k] = getattr(lib, p + "sphere_hit")(C.byref(c["sphere"]), org, d, 0.001, 3.0e38)
-        r["box_dist"][k] = getattr(lib, p + "hit_bbox_dist")(f3(c["lo"]), f3(c["hi"]), org, db, 10.0)
-        r["box_hit"][k] = getattr(lib, p + "hit_bbox")(f3(c["lo"]), f3(c["hi"]), org, db, 10.0)
+        box_tmax, tri_tmax = c.get("box_tmax", 10.0), c.get("tri_tmax", 3.0e38)                # (the edge cases: FLT_MAX for every other one)
+        r["box_dist"][k] = getattr(lib, p + "hit_bbox_dist")(f3(c["lo"]), f3(c["hi"]), org, db, box_tmax)
+        r["box_hit"][k] = getattr(lib, p + "hit_bbox")(f3(c["lo"]), f3(c["hi"]), org, db, box_tmax)
         u = C.c_float(); v = C.c_float()
-        r["tri_t"][k] = getattr(lib, p + "triangle_hit")(C.byref(c["tri"]), org, f3(c["dd"]), 0.01, 3.0e38, C.byref(u), C.byref(v))
+        tri_org = f3(c["tri_org"]) if "tri_org" in c else org
+        r["tri_t"][k] = getattr(lib, p + "triangle_hit")(C.byref(c["tri"]), tri_org, f3(c["dd"]), 0.01, tri_tmax, C.byref(u), C.byref(v))
         r["tri_u"][k], r["tri_v"][k] = u.value, v.value
         r["plane_t"][k] = getattr(lib, p + "plane_hit")(C.byref(c["plane"]), org, db, 0.01, 3.0e38)
     return r
@@ -123,6 +190,21 @@ def test_functions_random(rt):
     assert np.array_equal(orc["box_hit"], ref["box_hit"])
     hit = orc["tri_t"] < 1e30
     assert np.array_equal(orc["tri_u"][hit], ref["tri_u"][hit]) and np.array_equal(orc["tri_v"][hit], ref["tri_v"][hit])
+    # the edge cases are what they claim: NaN slab products that leave a hit standing, boxes rejected and accepted under FLT_MAX, in-plane rays on both
+    # sides of the determinant test
+    edge = np.arange(1500, len(cases))
+    assert len(edge) == 480
+    kind = (edge - 1500) % 6
+    with np.errstate(all="ignore"):
+        nan_slab = np.array([np.isnan(np.stack([c["lo"] - c["org"], c["hi"] - c["org"]]) * (np.float32(1) / c["d_box"])).any() for c in cases[1500:]])
+    neg_zero = np.array([(np.float32(c["d_box"]).view(np.uint32) == 0x80000000).any() for c in cases[1500:]])
+    print("edge cases: NaN slab products", int(nan_slab.sum()), "of them box hits", int(orc["box_hit"][edge][nan_slab].sum()), "-0.0 directions", int(neg_zero.sum()),
+          "box hits per kind", [int(orc["box_hit"][edge][kind == q].sum()) for q in range(6)], "triangle hits per kind", [int(hit[edge][kind == q].sum()) for q in range(6)])
+    assert np.all(nan_slab == ((kind == 0) | (kind == 2) | (kind == 3)))
+    assert orc["box_hit"][edge][nan_slab].sum() >= 40 and (orc["box_hit"][edge][nan_slab] == 0).sum() >= 30
+    assert neg_zero.sum() >= 150 and orc["box_hit"][edge][neg_zero].sum() >= 20
+    assert orc["box_hit"][edge][kind == 1].sum() == 0 and orc["box_hit"][edge][kind == 5].all()
+    assert hit[edge][kind == 5].all() and 0 < hit[edge][kind <= 2].sum() < (kind <= 2).sum()
 
 
 def test_light_sampling_expressions(rt):

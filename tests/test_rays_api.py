@@ -1,7 +1,9 @@
 """CPU checks of the batched ray queries (include/rt_api.h): traceRays / occludedRays / rtLastRaysMs and rtCentreRays are declared, exported and bound with
 their argument types, the constants agree between header and Python, the ABI version and struct sizes are the parent's, every call before init is the
 library's misuse exit, rt.centre_rays is orc_get_ray on the lens-less camera bit for bit, and the test reference (tests/rays_reference.py) shows on every
-ray set of the GPU tests what that set is there to cover - a set that exercises nothing fails here, without a GPU - and agrees with the guide reference."""
+ray set of the GPU tests what that set is there to cover - a set that exercises nothing fails here, without a GPU - and agrees with the guide reference.
+The edge sets (exactly-zero direction components, origins on box planes and on surfaces, t_max = +inf) carry conditions on their inputs, not tolerances: a
+seed that misses one is changed, never the threshold."""
 import ctypes as C
 import os
 import re
@@ -216,6 +218,178 @@ def test_mesh_sets_meet_their_conditions(rt, O, name):
         assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(R.ray_set(rt, O, name), other))
     else:
         assert floor == 0
+
+
+# ---- the edge sets: exactly-zero direction components, origins on a surface, t_max = +inf ------------------------------------------------
+
+def _zero_bits(d):
+    w = bits(d)
+    return w == 0, w == 0x80000000
+
+
+@pytest.mark.parametrize("frame", ["tris300", "staircase_a"])
+def test_mesh_axis_sets_meet_their_conditions(rt, O, frame):
+    """600 rays, six kinds of 100; every ray has a direction component whose bits are 0 or 0x80000000, at least 250 rays of each sign, kinds 0 and 1 two of
+    them; kinds 4 and 5 have org[a] bit-equal to the named plane of the named node (kind 5: node 1, the scene bounds; kind 4 on staircase_a: a box flat on a)
+    and every kind-5 ray whose other two slabs overlap visits nodes.  tris300: at least 40 hits and 150 rays that pass the bounds and hit nothing;
+    staircase_a: at least 200 hits, 50 misses and 60 hits among kind 4.
+    Figures (hits, nodes > 0 without a hit, hits among kind 4, kind-5 rays past the bounds): tris300 74, 353, 14, 86; staircase_a 338, 76, 78, 81."""
+    name = "mesh_axis:" + frame
+    lib = O.load_oracle()
+    org, d, t_min, t_max, info = R.mesh_axis_build(rt, O, frame)
+    assert all(a is b for a, b in zip(R.ray_set(rt, O, name), (org, d, t_min, t_max)))
+    assert len(org) == 600 and np.array_equal(info["kind"], np.arange(600) // 100)
+    pos, neg = _zero_bits(d)
+    assert np.all((pos | neg).any(axis=1))
+    assert pos.any(axis=1).sum() >= 250 and neg.any(axis=1).sum() >= 250
+    even = info["kind"] % 2 == 0
+    assert not neg[even].any() and not pos[~even].any()
+    zeros = (pos | neg).sum(axis=1)
+    assert np.all(zeros[info["kind"] < 2] == 2) and np.all(zeros[info["kind"] >= 2] == 1)
+    rows = np.arange(600)
+    assert np.all((pos | neg)[rows, info["axis"]] == (info["kind"] >= 2)) and np.all(d[rows, info["axis"]][info["kind"] < 2] != 0)
+    own = t_max < FLT_MAX
+    assert 0.25 <= own.mean() <= 0.35
+    hm = G.mesh_frame(rt, O, frame)["hm"]                       # (held: the node array is a view of the mesh's memory)
+    nodes = hm.bvh
+    ref = R.reference(rt, O, name)
+    past = 0
+    for r in np.flatnonzero(info["kind"] >= 4):
+        a, node, side = int(info["axis"][r]), int(info["node"][r]), int(info["side"][r])
+        plane = (nodes["a"] if side == 0 else nodes["b"])[node][a]
+        assert bits(org[r, a:a + 1])[0] == bits(np.array([plane], np.float32))[0], r
+        if info["kind"][r] == 5:
+            assert node == 1
+            lo, hi = nodes["a"][1].copy(), nodes["b"][1].copy()
+            lo[a], hi[a] = org[r, a] - np.float32(1.0), org[r, a] + np.float32(1.0)         # axis a no longer constrains: the other two slabs alone
+            if lib.orc_hit_bbox((C.c_float * 3)(*lo), (C.c_float * 3)(*hi), (C.c_float * 3)(*org[r]), (C.c_float * 3)(*d[r]), C.c_float(t_max[r])):
+                past += 1
+                assert ref["nodes"][r] > 0, r
+        elif frame == "staircase_a":
+            assert nodes["a"][node][a] == nodes["b"][node][a]
+        else:
+            assert 1 <= node <= 64
+    hit = _hit(ref)
+    inside_miss = int((~hit & (ref["nodes"] > 0)).sum())
+    kind4 = int(hit[info["kind"] == 4].sum())
+    print(name, "hits", int(hit.sum()), "nodes > 0 without a hit", inside_miss, "hits among kind 4", kind4, "kind-5 rays past the bounds", past)
+    assert past >= 50
+    if frame == "tris300":
+        assert hit.sum() >= 40 and inside_miss >= 150
+    else:
+        assert hit.sum() >= 200 and (~hit).sum() >= 50 and kind4 >= 60
+
+
+@pytest.mark.parametrize("name", ["mesh_surface:staircase_a", "mesh_surface:tris300", "sph_surface:random_50x37"])
+def test_surface_sets_start_on_a_surface(rt, O, name):
+    """The origins are the float32 hit points of the random set's NULL-bounds reference; t_min cycles through 0, 1e-42 (a denormal), 1e-6 and the scene
+    kind's default, t_max is FLT_MAX.  With t_min = 0 for every ray and with the default for every ray the reference differs in at least 4 rays, and at least 3
+    rays with t_min in {0, 1e-42} hit the primitive they start on again below the default t_min: a device that started such rays at its own epsilon would
+    differ.  Figures (rays, differ between t_min 0 and the default, re-hits below the default among t_min in {0, 1e-42}):
+    mesh_surface:staircase_a 396, 13, 5; mesh_surface:tris300 283, 141, 71; sph_surface:random_50x37 600 (the first 600 of 675 hit points), 214, 107."""
+    org, d, t_min, t_max, prim = R.surface_build(rt, O, name)
+    frame = R.frame_of(name)
+    dflt = np.float32(R.default_t_min(frame))
+    n = len(org)
+    assert n <= 600
+    if name == "mesh_surface:staircase_a":
+        assert n == 396
+    src = R.reference(rt, O, ("mesh_random:" if R.is_mesh(frame) else "sph_random:") + frame, own=False)
+    assert n == min(600, int((src["prim"] >= 0).sum())) >= 200 and np.all(prim >= 0)
+    cycle = np.array([0.0, 1e-42, 1e-6, dflt], np.float32)
+    assert 0 < cycle[1] < np.finfo(np.float32).tiny and np.array_equal(bits(t_min), bits(cycle[np.arange(n) % 4])) and np.all(t_max == np.float32(FLT_MAX))
+    d64 = d.astype(np.float64)
+    assert np.abs(d64 / np.sqrt((d64 * d64).sum(axis=1, keepdims=True))).min() >= 1e-3
+    at0, at_default = R.reference(rt, O, name, own=False, t_min=0.0), R.reference(rt, O, name, own=False)
+    differ = int(_changed(at0, at_default).sum())
+    ref = R.reference(rt, O, name)
+    early = (t_min < np.float32(1e-30)) & (ref["prim"] == prim) & (ref["t"] < dflt)
+    print(name, "rays", n, "differ between t_min 0 and the default", differ, "re-hits below the default", int(early.sum()))
+    assert differ >= 4
+    assert early.sum() >= 3
+
+
+@pytest.mark.parametrize("frame", ["cloud_hybrid", "cloud_global"])
+def test_cloud_axis_sets_meet_their_conditions(rt, O, frame):
+    """48 rays: 32 with two zero components (16 of them through a sphere's centre), 16 with one; half of the zeros are -0.0; at least 10 hits and 10 misses.
+    Figures (hits, misses): cloud_hybrid 33, 15; cloud_global 34, 14."""
+    name = "sph_axis:" + frame
+    org, d, t_min, t_max = R.ray_set(rt, O, name)
+    assert len(org) == 48 and t_min is None and t_max is None
+    pos, neg = _zero_bits(d)
+    zeros = (pos | neg).sum(axis=1)
+    assert np.all(zeros[:32] == 2) and np.all(zeros[32:] == 1)
+    assert pos.sum() == neg.sum() == 40
+    sp = G.sphere_frame(rt, frame)[0]
+    for r in range(16):
+        axis = int(np.flatnonzero(d[r])[0])
+        other = [a for a in range(3) if a != axis]
+        assert np.any(np.all(sp["center"][:, other] == org[r][other], axis=1)), r
+    hit = _hit(R.reference(rt, O, name))
+    print(name, "hits", int(hit.sum()), "misses", int((~hit).sum()))
+    assert hit.sum() >= 10 and (~hit).sum() >= 10
+
+
+@pytest.mark.parametrize("name", ["mesh_inf:tris300", "sph_inf:three_spheres"])
+def test_inf_sets_are_the_flt_max_sets(rt, O, name):
+    """Every third ray of the random set carries t_max = +inf and every third FLT_MAX; among the +inf rays at least 30 hits and 30 misses; the reference on
+    +inf equals the reference with those entries set to FLT_MAX.  Figures (+inf rays, hits, misses): mesh_inf:tris300 334, 83, 251; sph_inf:three_spheres
+    334, 223, 111."""
+    org, d, t_min, t_max = R.ray_set(rt, O, name)
+    src = R.ray_set(rt, O, name.replace("_inf:", "_random:"))
+    k = np.arange(len(org))
+    inf = k % 3 == 0
+    assert np.all(np.isposinf(t_max[inf])) and np.all(t_max[k % 3 == 1] == np.float32(FLT_MAX)) and np.array_equal(bits(t_max[k % 3 == 2]), bits(src[3][k % 3 == 2]))
+    assert org is src[0] and d is src[1] and t_min is src[2]
+    ref = R.reference(rt, O, name)
+    hit = _hit(ref)
+    print(name, "+inf rays", int(inf.sum()), "hits", int(hit[inf].sum()), "misses", int((~hit[inf]).sum()))
+    assert hit[inf].sum() >= 30 and (~hit[inf]).sum() >= 30
+    finite = np.where(inf, np.float32(FLT_MAX), t_max)
+    frame = R.frame_of(name)
+    if R.is_mesh(frame):
+        f = G.mesh_frame(rt, O, frame)
+        want = R.mesh_rays(rt, O, f["hm"], f["mats"], f["tex"], f["floor"], org, d, t_min, finite, clamp=False)
+    else:
+        want = R.sphere_rays(rt, O, G.sphere_frame(rt, frame)[0], org, d, t_min, finite, clamp=False)
+    assert sorted(want) == sorted(ref)
+    for key in ref:
+        same(ref[key], want[key], f"{name}: {key}, +inf against FLT_MAX")
+
+
+def test_why_t_max_is_clamped(rt, O):
+    """The record of why "a tmax above FLT_MAX is taken as FLT_MAX" is in the contract: the oracle's calls on the raw +inf turn a miss into a hit.  A miss
+    returns FLT_MAX, and FLT_MAX < inf accepts it: on three_spheres every +inf ray that misses everything comes back as prim 0, t = FLT_MAX, occluded 1 (the
+    first three of them are pinned below); on tris300 a box the ray missed (leftHit = FLT_MAX < closest = inf) is walked into, so +inf rays that miss inside
+    the bounds visit more nodes, and every +inf ray that passes the bounds without a hit is reported as prim >= 0 and occluded."""
+    name = "sph_inf:three_spheres"
+    org, d, t_min, t_max = R.ray_set(rt, O, name)
+    ref = R.reference(rt, O, name)
+    raw = R.sphere_rays(rt, O, G.sphere_frame(rt, "three_spheres")[0], org, d, t_min, t_max, clamp=False)
+    inf = np.isinf(t_max)
+    miss = inf & ~_hit(ref)
+    assert miss.sum() >= 30
+    assert np.all(raw["prim"][miss] == 0) and np.all(raw["t"][miss] == np.float32(FLT_MAX)) and np.all(raw["occluded"][miss] == 1)
+    assert not ref["occluded"][miss].any() and np.all(ref["t"][miss] == np.float32(FLT_MAX))
+    three = np.flatnonzero(miss)[:3]
+    print("three_spheres, the first three +inf rays that miss:", three.tolist(), "raw prim", raw["prim"][three].tolist(), "occluded", raw["occluded"][three].tolist())
+    assert three.tolist() == THREE_MISSES
+    assert not _changed({k: v[~miss] for k, v in raw.items()}, {k: v[~miss] for k, v in ref.items()}).any()      # nothing else differs
+    name = "mesh_inf:tris300"
+    f = G.mesh_frame(rt, O, "tris300")
+    org, d, t_min, t_max = R.ray_set(rt, O, name)
+    ref = R.reference(rt, O, name)
+    raw = R.mesh_rays(rt, O, f["hm"], f["mats"], f["tex"], f["floor"], org, d, t_min, t_max, clamp=False)
+    inf = np.isinf(t_max)
+    miss = inf & ~_hit(ref) & (ref["nodes"] > 0)
+    assert miss.sum() >= 30
+    assert np.all(raw["prim"][miss] >= 0) and np.all(raw["occluded"][miss] == 1)
+    more = int((raw["nodes"][miss] > ref["nodes"][miss]).sum())
+    print("tris300: +inf rays that miss inside the bounds", int(miss.sum()), "of which the raw calls visit more nodes on", more)
+    assert np.all(raw["nodes"][miss] >= ref["nodes"][miss]) and more >= 10
+
+
+THREE_MISSES = [36, 123, 162]
 
 
 # ---- the reference against itself and against the guide reference ---------------------------------------------------------------

@@ -1,7 +1,8 @@
 """CPU: the host side of rebuildBvh (include/rt_api.h "editing the scene", include/rt_host.h).  rtRebuildBvh is the builder over the tree's own leaf count
 followed by the refit: on the visible triangles of a mesh it yields the triangle bytes of rtBuildBvhLevels; an independent, level-synchronous numpy
-restatement of the definition (tests/rebuild_support.py) agrees with it on quantised meshes, tiny, full and nearly full trees, hidden triangles and a
-mostly empty tree; old_slot is a bijection that moves whole triangles; refusals write nothing; and the rebuilt tree of a scrambled staircase is visited
+restatement of the definition (tests/rebuild_support.py) agrees with it on quantised meshes, tiny, full and nearly full trees, hidden triangles, a
+mostly empty tree and meshes at the float extremes (areas and costs that overflow to +inf or are NaN, nodes without a winner, costs that underflow to 0,
+infinite and denormal centroids: each asserted from the restatement's own counts); old_slot is a bijection that moves whole triangles; refusals write nothing; and the rebuilt tree of a scrambled staircase is visited
 less.  Every comparison is np.array_equal on raw words or bytes."""
 import os
 import re
@@ -59,10 +60,32 @@ def _numpy_cases(rt, O):
     yield "sentinel before real", S.sentinel_first_mesh(rt)
     src = G.mesh_frame(rt, O, "tris300")["hm"].tris
     yield "tris300 nppl 1, 2^17 leaves", rt.HostMesh.build(src[S.is_real(src)], 1, extra_levels=8)
+    for case in R.EXTREMES:                                     # the float extremes: already scrambled
+        yield case, R.extreme_mesh(rt, case)
 
 
 CASES = ["quantised, nppl 3", "quantised, nppl 1, no spare level", "n = 1", "n = 2", "n = 3", "n = 7", "full tree", "full tree less one", "sentinel before real",
-         "tris300 nppl 1, 2^17 leaves"]
+         "tris300 nppl 1, 2^17 leaves"] + list(R.EXTREMES)
+
+
+def _claims(case, c):
+    """What numpy_rebuild's counts must show for a case of R.EXTREMES to be what it claims."""
+    nodes = c["winner"] + c["no_winner"]
+    assert nodes >= 50, c
+    if case == "scale 3e18":
+        assert c["winner"] >= 10 and c["no_winner"] >= 10 and c["inf_costs"] >= 100 and c["nan_costs"] == 0
+    if case in ("scale 1e25", "scale 1e37", "scale 2e37"):
+        assert c["winner"] == 0 and c["no_winner"] == nodes and c["nan_costs"] == 0 and c["inf_costs"] == c["nonzero_costs"] > 0
+        assert (c["inf_centroids"] > 0) == (case == "scale 2e37")
+    if case.endswith("every 7th"):
+        assert c["winner"] >= 10 and c["no_winner"] >= 10
+        assert (c["mixed_nodes"] >= 1) == case.startswith("scale 1e18")
+    if case == "flat in x, scale 2e37":
+        assert c["nan_costs"] >= 100 and c["inf_costs"] >= 100 and c["winner"] == 0
+    if case in ("scale 1e-25", "scale 1e-38", "scale 1e-44"):
+        assert c["nonzero_costs"] == 0 and c["no_winner"] == 0 and c["inf_costs"] == 0
+        small = c["denormal_centroids_pos"] >= 10 and c["denormal_centroids_neg"] >= 10
+        assert small == (case != "scale 1e-25")
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -72,12 +95,17 @@ def test_twin_against_numpy(rt, O, case):
     if case.startswith("full tree"):
         n = int(S.is_real(hm.tris).sum())
         assert first_leaf == 8 and n == (24 if case == "full tree" else 23)
-    if not case.startswith("sentinel"):
+    if not case.startswith("sentinel") and case not in R.EXTREMES:
         R.scrambled(hm, 72)
     before = hm.tris.copy()
     hidden = int(S.is_real(before).sum()) - len(R.visible_slots(before, first_leaf, nppl))
     assert (hidden >= 4) == case.startswith("sentinel")
-    want_tris, want_old, want_nodes, want_bounds = R.numpy_rebuild(rt, before, hm.view.numBvhNodes, nppl)
+    counts = {}
+    want_tris, want_old, want_nodes, want_bounds = R.numpy_rebuild(rt, before, hm.view.numBvhNodes, nppl, counts)
+    if case in R.EXTREMES:
+        print(case, counts)
+        assert sorted(counts) == sorted(R.COUNTS) and int(S.is_real(before).sum()) == 200 and np.isfinite(before["v"][S.is_real(before)]).all()
+        _claims(case, counts)
     old_slot = hm.rebuild()
     assert hm.tris.tobytes() == want_tris.tobytes(), case + ": triangles"
     assert np.array_equal(old_slot, want_old), case + ": old_slot"

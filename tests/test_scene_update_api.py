@@ -86,6 +86,29 @@ def test_numpy_refit_agrees_signed_zeros(rt):
     assert np.array_equal(nodes2["a"][1:], nodes["a"][1:]) and np.array_equal(nodes2["b"][1:], nodes["b"][1:])     # equal as numbers, not as bits
 
 
+def test_numpy_refit_agrees_extremes(rt):
+    """The (128, 5) blob with twenty triangles that carry a NaN coordinate, twenty scaled by 1e37 and twenty by 1e-44 (scene_update_support.extremes): the
+    twin and the restatement agree bit for bit, no box holds a NaN, the large triangles reach the root's box and denormal bounds appear in the leaves."""
+    hm = S.blob_mesh(rt, 128, 5)
+    before = hm.bvh.copy()
+    new, (nan, big, small) = S.extremes(hm.tris)
+    hm.tris[:] = new
+    nodes = _against_numpy(rt, hm, "extremes")
+    assert not np.isnan(nodes["a"][1:]).any() and not np.isnan(nodes["b"][1:]).any()
+    assert np.abs(nodes["a"][1]).max() > 1e37 and np.abs(nodes["b"][1]).max() > 1e37
+    first_leaf = len(nodes) // 2
+    tiny = np.finfo(np.float32).tiny
+    leaf = np.concatenate([nodes["a"][first_leaf:], nodes["b"][first_leaf:]]).reshape(-1)
+    assert ((leaf != 0) & (np.abs(leaf) < tiny)).sum() >= 10
+    # a leaf that holds a NaN triangle: its box is the box of all its other coordinates, as numbers
+    for leaf in np.unique(nan // hm.nppl):
+        t = hm.tris[leaf * hm.nppl:(leaf + 1) * hm.nppl]
+        v = t["v"][S.is_real(t)].reshape(-1, 3)
+        assert np.isnan(v).any()
+        assert np.array_equal(nodes["a"][first_leaf + leaf], np.nanmin(v, axis=0)) and np.array_equal(nodes["b"][first_leaf + leaf], np.nanmax(v, axis=0)), leaf
+    assert (_words(nodes[1:]) != _words(before[1:])).any()
+
+
 def test_refit_arrays_refuses_bad_arrays(rt):
     hm = S.blob_mesh(rt, 8, 3)
     tris, bvh = hm.tris.copy(), hm.bvh.copy()
