@@ -138,7 +138,8 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs",
                     "traceRays", "occludedRays", "rtLastRaysMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
-                    "rebuildBvh", "rtLastRebuildMs"]
+                    "rebuildBvh", "rtLastRebuildMs",
+                    "rtLastSphereForm"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
 ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle, bvh_node, mesh, kernel_scene, stexture, plane, bbox, vec3]
@@ -1019,6 +1020,17 @@ def last_launches():
     buf = (C.c_int32 * (n * len(LAUNCH_FIELDS)))()
     n = min(n, lib.rtLastLaunches(buf, n))
     return [dict(zip(LAUNCH_FIELDS, buf[k * len(LAUNCH_FIELDS):(k + 1) * len(LAUNCH_FIELDS)])) for k in range(n)]
+
+
+RT_SPHERE_FORM_NONE, RT_SPHERE_FORM_GENERAL, RT_SPHERE_FORM_DEFAULT = -1, 0, 1
+
+
+def last_sphere_form():
+    """rtLastSphereForm (include/rt_api.h): the form of the cost-ordered sphere dispatch of the last frame or pass, RT_SPHERE_FORM_NONE if it had none."""
+    lib = load_renderer()
+    lib.rtLastSphereForm.argtypes = []
+    lib.rtLastSphereForm.restype = C.c_int
+    return lib.rtLastSphereForm()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -44,6 +44,7 @@
 //     hit data in global memory (two workgroups per CU up to ~1500 spheres, LDS-resident up to ~5000); everything read from global memory beyond that.
 #include "rt_device.h"
 #include "rt_params.h"
+#include "rt_sphere_form.h"
 
 #include <float.h>
 #include <cstdio>
@@ -1528,8 +1529,24 @@ constexpr BitField kCapsMidCap = { 20, 0xFF }; // ... and the pixels such a wave
 //            behind the cell-table prefilter (scan_pairs<OP>: at most 32 groups, 64 with bit 4, 128 with bit 5); bit 3: that prefilter is the general 3-axis one (no shared
 //            vertical extent: spheres scattered in space); only with SCENE = 0 (a few kinds also with SCENE = 2) and without DBG.  Bits 0 + 1 need ~100 VGPRs instead of 128; bit 2 (with
 //            both): compiled for SIX waves per SIMD (80 VGPRs, ~20 of them spilled) and launched as two 12-wave workgroups per CU - see plan_spheres for when
-template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE = 0, int LEAN = 0>
-__global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres_queue(const RtSphereParams P, uint32_t stride, int cfg, int chain_cfg, int caps) {
+//   FORM     (rt_sphere_form.h) kSphereFormGeneral: the frame's switches - a queue per XCD or one, parked records or three arrays, the middle tier, the direct
+//            framebuffer - are run-time state; kSphereFormDefault: compiled for their default values (PHASE 2, CLS 2 only), so that the iteration every
+//            wave runs carries neither their tests nor their registers, and with the scheduling constants (cfg, chain_cfg, caps) at their defaults as
+//            immediates.  The folded form only deletes: it has no path the general one lacks.
+//            FormTag<FORM>, the kernel's last (empty) argument, lets the launcher's ONE naming of the kernel by its first six template arguments
+//            (launch_sphere_queue) take FORM from the type of the function pointer it initialises.
+template <int FORM> struct FormTag {};
+// The scheduling constants of a default frame (plan_spheres: no RT_TUNE, RT_POOL / RT_CHAIN_SINGLE / RT_SINGLE_RAY and the variant's scheduling bits at their
+// defaults; three chain waves in a 16-wave workgroup, two in a 12-wave one): the folded form is compiled with them, so the plan takes it for these words only.
+constexpr int kDefaultCfg = kCfgCull | kCfgChainSingle | kCfgSingleRay | kCfgPool.put(1) | kCfgBoost.put(1) | kCfgSparseMax.put(4);
+constexpr int default_chain_cfg(bool six_waves) { return kChainEvery.put(1) | kChainWaves.put(six_waves ? 2 : 3) | kChainPixels.put(4) | kChainHeavyThr.put(8) | kChainLists.put(4); }
+constexpr int kDefaultCaps = caps_list(0).put(1) | caps_list(1).put(4) | caps_list(2).put(4) | caps_list(3).put(4) | kCapsMidWaves.put(0) | kCapsMidCap.put(16);
+template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE = 0, int LEAN = 0, int FORM = 0>
+__global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres_queue(const RtSphereParams P, uint32_t stride, int cfg, int chain_cfg, int caps, FormTag<FORM>) {
+    static_assert(FORM == kSphereFormGeneral || (PHASE == 2 && CLS == 2 && !CHUNKED && !DBG && SCENE == 0), "the folded form is the cost-ordered dispatch of whole pixels, LDS scene, no diagnostics");
+    constexpr bool FOLDED = FORM == kSphereFormDefault;
+    constexpr bool MID = CLS == 2 && !FOLDED;          // the middle tier (role 1, ccls 6, s_q word [5]) exists
+    if (FOLDED) { cfg = kDefaultCfg; chain_cfg = default_chain_cfg((LEAN & 4) != 0); caps = kDefaultCaps; }      // immediates, not SGPRs or spilled lanes
     extern __shared__ __align__(16) unsigned char smem[];
     float* unused;
     const SceneLds S = stage_scene<false, SCENE>(P, smem, &unused);
@@ -1551,7 +1568,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
     // serves the queue of the XCD it runs on (XCC_ID) and, when that is empty, the general queues of the others in turn (`stolen`); the list tables
     // (s_cls_*) are those of the wave's own XCD - only its chain waves look at them.
     __shared__ uint32_t s_q[8 * kXcdQueues];
-    const uint32_t xq = (CLS == 2 && P.xcd_queues == kXcdQueues) ? (uint32_t)kXcdQueues : 1u;
+    const uint32_t xq = (FOLDED || (CLS == 2 && P.xcd_queues == kXcdQueues)) ? (uint32_t)kXcdQueues : 1u;
     const uint32_t myx = xq > 1u ? ((uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) & (uint32_t)(kXcdQueues - 1)) : 0u;       // XCC_ID
     if (threadIdx.x < xq) {
         const uint32_t x = threadIdx.x;
@@ -1586,7 +1603,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
         // waves but served, from their own counter (queue word [2]), by "middle" waves that hold only a few pixels - see the role comment below.  The general
         // queue is then the rest lists alone.
         sq[5] = 0u;
-        if (CLS == 2 && ((caps >> kCapsMidWaves.shift) & kCapsMidWaves.mask) != 0 && n0 > 0u) { sq[5] = 1u; sq[2] = n_rest; sq[4] = 0u; }
+        if (MID && ((caps >> kCapsMidWaves.shift) & kCapsMidWaves.mask) != 0 && n0 > 0u) { sq[5] = 1u; sq[2] = n_rest; sq[4] = 0u; }
         sq[6] = seg;
     }
     __syncthreads();
@@ -1604,7 +1621,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
     // with the rays): such pixels end in half the time for ~2.5x the cost per ray, on a few per cent of the frame's rays.
     int role = 2;
     if (CLS == 2 && s_q[8 * myx] > 0u && (int)(threadIdx.x >> 6) < ((chain_cfg >> kChainWaves.shift) & kChainWaves.mask) && (blockIdx.x % (uint32_t)(chain_cfg & kChainEvery.mask)) == 0u) role = 0;
-    else if (CLS == 2 && s_q[8 * myx + 5] != 0u && (int)(threadIdx.x >> 6) < ((chain_cfg >> kChainWaves.shift) & kChainWaves.mask) + ((caps >> kCapsMidWaves.shift) & kCapsMidWaves.mask)) role = 1;
+    else if (MID && s_q[8 * myx + 5] != 0u && (int)(threadIdx.x >> 6) < ((chain_cfg >> kChainWaves.shift) & kChainWaves.mask) + ((caps >> kCapsMidWaves.shift) & kCapsMidWaves.mask)) role = 1;
     const int mid_cap = (caps >> kCapsMidCap.shift) & kCapsMidCap.mask;
     // wave-uniform (a queue per XCD only): how far this wave has moved on from its own XCD's queue.  Even: it draws from the general queue of XCD
     // (myx + stolen / 2) mod 8; odd: that general queue is empty and the wave (role 2) takes what is LEFT ON THAT QUEUE'S CHAIN LISTS.  Chain lists are served
@@ -1678,7 +1695,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                     const f3 out = L.col / (float)P.ns;              // kernels.cu:568
                     // one 12-byte store (global_store_dwordx3): a lane finishes its pixel on its own, so three dword
                     // stores would be three partial-sector writes
-                    *reinterpret_cast<float3*>(fbf + ((size_t)(P.fb_global_rows ? L.j : lr) * P.nx + L.i) * 3) = make_float3(out.x, out.y, out.z);
+                    *reinterpret_cast<float3*>(fbf + ((size_t)((!FOLDED && P.fb_global_rows) ? L.j : lr) * P.nx + L.i) * 3) = make_float3(out.x, out.y, out.z);
                     // the pixel's rays go to acc_rays: the cost map the next frame is ordered by (runRenderer), or a progressive pass's accumulated rays - and
                     // with them the stream position and running sum for the next pass.  (One cold pointer and one branch on a frame that does neither,
                     // as before the map: a second pointer of its own cost the lean kinds 3-4 VGPRs and the measured frame 0.4-1 %.)
@@ -1718,7 +1735,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
             // live-lane cap of this wave: by its role and by the tiers of the pixels it still holds
             const unsigned long long live_m = __ballot(have_pixel);
             int cap = 64;
-            if (CLS == 2 && (role == 1 || __ballot(have_pixel && ccls == 6) != 0ull)) cap = mid_cap;        // a middle wave, or a wave that still holds a middle-tier pixel
+            if (MID && (role == 1 || __ballot(have_pixel && ccls == 6) != 0ull)) cap = mid_cap;        // a middle wave, or a wave that still holds a middle-tier pixel
             if (CLS == 2 && (role == 0 || __ballot(have_pixel && ccls < 6) != 0ull)) {
                 cap = (chain_cfg >> kChainPixels.shift) & kChainPixels.mask;
                 if (__ballot(have_pixel && ccls == 2) != 0ull) cap = min(cap, (caps >> caps_list(2).shift) & caps_list(2).mask);
@@ -1744,9 +1761,9 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                 // (PHASE 2, experiments: kCfgPool x 4 = positions a normal wave reserves at least per grab)
                 const bool leftovers = (stolen & 1u) != 0u;             // (role 2 only)
                 const uint32_t grab = leftovers ? 1u : ((CHUNKED || PHASE == 1) ? max(cnt, 128u) : ((PHASE == 2 && role == 2) ? max(cnt, (uint32_t)((cfg >> kCfgPool.shift) & kCfgPool.mask) * 4u) : cnt));
-                const uint32_t limit = (role == 0 || leftovers) ? sq[0] : (role == 1 ? sq[1] : total);
+                const uint32_t limit = (role == 0 || leftovers) ? sq[0] : ((MID && role == 1) ? sq[1] : total);
                 uint32_t b = 0;
-                if ((threadIdx.x & 63) == 0) b = atomicAdd(P.queue + (size_t)qx * kXcdQueueWords + ((role == 0 || leftovers) ? 1 : (role == 1 ? 2 : 0)), grab);
+                if ((threadIdx.x & 63) == 0) b = atomicAdd(P.queue + (size_t)qx * kXcdQueueWords + ((role == 0 || leftovers) ? 1 : ((MID && role == 1) ? 2 : 0)), grab);
                 b = __builtin_amdgcn_readfirstlane(b);
                 if (b >= limit) {
                     if (role < 2) { role = 2; continue; }            // this wave's lists are empty: a normal wave from now on
@@ -1784,8 +1801,8 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                     // else; position p is a heavy-list position iff floor((p+1) n0 / spread) > floor(p n0 / spread)
                     uint32_t q;                                      // position in the concatenation of all lists
                     if (role == 0 || (stolen & 1u) != 0u) q = pos;                           // a chain-list position
-                    else if (role == 1) q = sq[0] + pos;                                    // the heavy lists, in order (longest estimates first)
-                    else if (CLS == 2 && sq[5] != 0u) q = sq[0] + sq[1] + pos;           // middle tier on: the general queue is the rest lists
+                    else if (MID && role == 1) q = sq[0] + pos;                                    // the heavy lists, in order (longest estimates first)
+                    else if (MID && sq[5] != 0u) q = sq[0] + sq[1] + pos;           // middle tier on: the general queue is the rest lists
                     else {
                         const uint32_t nA = sq[0], n0 = sq[1], spread = sq[3];
                         const bool spread_ok = sq[4] != 0u;
@@ -1805,7 +1822,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                     if (CLS == 2) {
                         // the lists of a queue lie one behind the other in P.order: position = first position of the queue's lists + q, whichever list q falls into
                         opos = sq[6] + q;
-                        if (P.ord_rec) {                             // one 32-byte record: parked state | pixel, rays (k_order_by_cost)
+                        if (FOLDED || P.ord_rec) {                   // one 32-byte record: parked state | pixel, rays (k_order_by_cost)
                             rec0 = P.ord_rec[2 * (size_t)opos];
                             const float4 rec1 = P.ord_rec[2 * (size_t)opos + 1];
                             p = __float_as_uint(rec1.x);
@@ -1850,20 +1867,20 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                         init_pixel(P, L, i, global_row(P.part, lr), 0);
                         pix_rays = 0;
                     } else {                                         // resume: the pixel's stream continues where phase 1 left it
-                        const float4 st4 = (CLS == 2 && P.ord_rec) ? rec0 : P.ord_state[opos];
+                        const float4 st4 = (CLS == 2 && (FOLDED || P.ord_rec)) ? rec0 : P.ord_state[opos];
                         L.i = i; L.j = global_row(P.part, lr);
                         L.pixelId = (uint32_t)(L.j * P.nx + i);
                         L.rng = __float_as_uint(st4.w);
                         L.col = F3(st4.x, st4.y, st4.z);
                         L.s = P.s_split;
-                        pix_rays = (CLS == 2 && P.ord_rec) ? rec_rays : P.ord_rays[opos];
+                        pix_rays = (CLS == 2 && (FOLDED || P.ord_rec)) ? rec_rays : P.ord_rays[opos];
                         if (wdbg) { dbg_grab = (float)(__builtin_amdgcn_s_memrealtime() - dbg_t0) * 1e-5f; dbg_p1 = (float)pix_rays; }
                     }
                     need_sample = true;
                     have_pixel = true;
                     ccls = 7;
                     if (CLS == 2 && role == 0) { ccls = 0; for (int k = 1; k < kChainClasses; k++) if (pos >= s_cls_pos[k]) ccls = k; }
-                    if (CLS == 2 && role == 1) ccls = 6;
+                    if (MID && role == 1) ccls = 6;
                     if (CLS == 2 && role == 2 && (stolen & 1u) != 0u) ccls = kChainClasses - 1;        // a chain pixel nobody had taken
                 }
             }
@@ -1885,7 +1902,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
         // one ray).  Scheduling only: the lane consumes its own RNG stream in order, so results do not change.
         // (One call site for both: the scan is large and must not be inlined twice.)
         // (a wave of the middle tier is fast already: no boost steps while it holds such a pixel)
-        const int steps = (boost > 0 && __popcll(live_now) > sparse_max && !(CLS == 2 && s_q[8 * myx + 5] != 0u && __ballot(have_pixel && ccls == 6) != 0ull)) ? 1 + boost : 1;
+        const int steps = (boost > 0 && __popcll(live_now) > sparse_max && !(MID && s_q[8 * myx + 5] != 0u && __ballot(have_pixel && ccls == 6) != 0ull)) ? 1 + boost : 1;
         for (int x = 0; x < steps; x++) {
             bool sel = have_pixel;
             if (x > 0) {
@@ -2038,20 +2055,16 @@ constexpr bool built(int scene, bool chunked, int lean) {
     if (scene == 0) return chunked ? in_kinds(KindsChunked{}, lean) : in_kinds(KindsFull{}, lean);
     return scene == 2 && !chunked && in_kinds(KindsHybrid{}, lean);
 }
+// The instantiations that are also built in the folded form (FORM = kSphereFormDefault): the cost-ordered dispatch of the kinds of KindsFull.
+constexpr bool folded_built(int phase, int cls, bool chunked, bool dbg, int scene, int lean) {
+    return phase == 2 && cls == 2 && !chunked && !dbg && scene == 0 && in_kinds(KindsFull{}, lean);
+}
 // The kind a scene takes of those that are built: its own, else the lean shading alone, else the general kernel.
 constexpr int clip_lean(int scene, bool chunked, int lean) {
     return built(scene, chunked, lean) ? lean : (built(scene, chunked, lean & kLeanBasic) ? (lean & kLeanBasic) : 0);
 }
 
-enum class SphereFrame {
-    Tiles,              // the tile kernel
-    GlobalSingle,       // the scene in global memory: one scattered dispatch
-    TwoDispatch,        // first samples of every pixel, k_order_by_cost, then the rest longest first
-    TwoDispatchResume,  // a continuation pass of a progressive frame: the ordering pass and the second dispatch alone
-    OrderedSingle,      // a frame ordered by the last frame's cost map: the ordering pass and ONE dispatch of whole pixels, longest first - no measuring dispatch
-    ClassifiedSingle,   // k_classify_spheres, then one dispatch in its order
-    PlainSingle,        // one dispatch, scattered or tile-major
-};
+// (SphereFrame, the kinds of frame: rt_sphere_form.h)
 enum class SpherePlanError { None, Mid, Tune };
 constexpr int kFirstSamples = 2;    // samples of the first dispatch; measured: 1 -> 15.5 ms, 2 -> 15.0, 3 -> 15.1 (round 2); 2 -> 24.5, 4 -> 24.8, 6 -> 25.4 (round 1)
 
@@ -2066,6 +2079,7 @@ struct SpherePlan {
     bool chunked = false;
     int lean = 0;               // LEAN bits of the instantiation (0 = the general kernel)
     int lean_dbg = 0;           // the kind the scene would take without the diagnostics (time lines of the production kernel), if it is built with the stamps
+    int form = kSphereFormGeneral;      // FORM of the cost-ordered dispatch (sphere_frame_form, rt_sphere_form.h)
     int threads = kThreads;     // workgroup size (16 waves, 12 for the six-wave kinds, or 8 when only that fits)
     size_t lds = 0;
     unsigned blocks = 1, blocks_y = 1;
@@ -2214,8 +2228,11 @@ static SpherePlan plan_spheres(const RtSphereParams& p, int variant, const RtSwi
     }
     pl.chain_cfg = kChainEvery.put(t[kTuneChainEvery]) | kChainWaves.put(t[kTuneChainWaves]) | kChainPixels.put(t[kTuneChainPixels]) | kChainHeavyThr.put(t[kTuneHeavyThr]) |
                    kChainLists.put(t[kTuneChainLists]);
+    // The middle tier's lists are served by the middle waves of their own XCD alone - the leftovers rule of the kernel covers the chain lists only.  With a queue per
+    // XCD, a grid that does not put a workgroup on every XCD (96x64: six) would leave the heavy pixels of the others unrendered: such a frame runs without the tier.
+    const int mid_waves = (p.xcd_queues == kXcdQueues && pl.blocks < (unsigned)kXcdQueues) ? 0 : sw.mid_waves;
     pl.caps = caps_list(0).put(t[kTuneList0]) | caps_list(1).put(t[kTuneList1]) | caps_list(2).put(t[kTuneList2]) | caps_list(3).put(t[kTuneChainPixels]) |
-              kCapsMidWaves.put(sw.mid_waves) | kCapsMidCap.put(sw.mid_cap);
+              kCapsMidWaves.put(mid_waves) | kCapsMidCap.put(sw.mid_cap);
     // kCfgPool: a normal wave of phase 2 reserves at least 8 queue positions per grab (one atomic round trip per ~6 finished pixels instead of per ~1: +1.3 % on C2;
     // 16 and more hoard pixels at the end of the frame and lose: 8 -> 7144, 16 -> 6616, 32 -> 6019 Msamples/s, profiles/r03_sweep_pool.txt)
     // (RT_POOL, round 4, lean kernel: 4 -> 8517, 8 -> 8420, 16 -> 8110 Msamples/s, profiles/r04_sweep_tune_c2.txt)
@@ -2225,6 +2242,8 @@ static SpherePlan plan_spheres(const RtSphereParams& p, int variant, const RtSwi
     // as row segments of 8 pixels - a line of px_state per 8 lanes, the scattering kept)
     pl.stride1 = p.p1_tile_major == 1 ? 1u : pl.stride;
     pl.cfg1 = pl.cfg;
+    const bool default_constants = pl.cfg == kDefaultCfg && pl.chain_cfg == default_chain_cfg((pl.lean & kLeanSixWaves) != 0) && pl.caps == kDefaultCaps;
+    pl.form = sphere_frame_form(pl.frame, p, sw, folded_built(2, 2, pl.chunked, false, pl.scene, pl.lean), default_constants);
     if (p.p1_tile_major == 2 && total_px > 512) {
         pl.stride1 = rt_coprime_stride((unsigned long long)total_px >> 3);
         pl.cfg1 |= kCfgP1Segments;
@@ -2238,11 +2257,25 @@ template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN = 0> s
 
 // (The global scene's launch asks for 86 KB, the per-wave scratch of 16 waves, and used to leave the attribute unset, which the runtime let pass; it now sets it
 // like every other launch above 64 KB.)
+// The cost-ordered dispatch of a frame in the default form (pl.form, sphere_frame_form) is launched with FORM = kSphereFormDefault; the launch record is the
+// same (the form is reported by rtLastSphereForm).  A plan that asks for the folded form of an instantiation that has none is an error.
 template <int PHASE, int CLS, bool CHUNKED, bool DBG, int SCENE, int LEAN>
 static hipError_t launch_sphere_queue(SphereQueueForm<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>, const RtSphereParams& q, const SpherePlan& pl, hipStream_t stream,
                                       uint32_t stride, int cfg, int caps) {
-    const hipError_t e = launch_with_lds(k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, q, stride, cfg, pl.chain_cfg, caps);
+    const int form = (PHASE == 2 && CLS == 2) ? pl.form : kSphereFormGeneral;
+    auto launch_form = [&](auto tag) -> hipError_t {         // (FORM: deduced from the tag's type)
+        void (*kern)(const RtSphereParams, uint32_t, int, int, int, decltype(tag)) = k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>;
+        return launch_with_lds(kern, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, q, stride, cfg, pl.chain_cfg, caps, tag);
+    };
+    hipError_t e;
+    if constexpr (folded_built(PHASE, CLS, CHUNKED, DBG, SCENE, LEAN)) {
+        e = form == kSphereFormDefault ? launch_form(FormTag<kSphereFormDefault>{}) : launch_form(FormTag<kSphereFormGeneral>{});
+    } else {
+        if (form != kSphereFormGeneral) return hipErrorInvalidValue;
+        e = launch_form(FormTag<kSphereFormGeneral>{});
+    }
     rt_note_launch(RT_KERNEL_SPHERE_QUEUE, PHASE, CLS, CHUNKED, DBG, SCENE, LEAN, pl.threads, pl.blocks);
+    if (PHASE == 2 && CLS == 2) rt_note_sphere_form(form);
     return e;
 }
 

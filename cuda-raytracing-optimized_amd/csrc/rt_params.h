@@ -296,6 +296,8 @@ hipError_t rt_launch_mesh_fast(const RtMeshParams& p, int variant, const RtSwitc
 // The launch report (rtLastLaunches, rt_api.h): the launchers note every render-kernel launch with the template arguments of the instantiation they launched
 // (RT_KERNEL_* family and the RT_LAUNCH_* words up to RT_LAUNCH_BLOCKS); the renderer adds the device and the fp mode of the frame.  Host bookkeeping only.
 void rt_note_launch(int family, int phase, int cls, int chunked, int dbg, int scene, int lean, int threads, unsigned blocks);
+// ... and the form of the cost-ordered sphere dispatch it launched (rtLastSphereForm; rt_sphere_form.h)
+void rt_note_sphere_form(int form);
 
 // First-hit guide planes (renderGuides, rt_api.h): compact device planes of part.local_rows x nx entries, nullptr = not requested.  The guide kernels
 // (k_guides_spheres / k_guides_mesh) exist in the PARITY objects only - one arithmetic for both fp modes - and read of the parameter block what a

@@ -252,6 +252,7 @@ void reset_display() {
 // rtLastLaunches: the records of the last runRenderer (RT_LAUNCH_WORDS each) and the device / fp mode of the launcher being called
 std::vector<int32_t> g_launches;
 int g_launch_device = 0, g_launch_fp = 0;
+int g_sphere_form = RT_SPHERE_FORM_NONE;        // rtLastSphereForm
 
 void default_options(rt_render_options* o, int spheres) {
     memset(o, 0, sizeof *o);
@@ -469,6 +470,8 @@ void rt_note_launch(int family, int phase, int cls, int chunked, int dbg, int sc
     const int32_t rec[RT_LAUNCH_WORDS] = { family, phase, cls, chunked, dbg, scene, lean, threads, (int32_t)blocks, g_launch_device, g_launch_fp };
     g_launches.insert(g_launches.end(), rec, rec + RT_LAUNCH_WORDS);
 }
+// (several devices render one frame under the same switches; should their forms ever differ, the general one is what is reported)
+void rt_note_sphere_form(int form) { g_sphere_form = g_sphere_form == RT_SPHERE_FORM_NONE ? form : std::min(g_sphere_form, form); }
 
 extern "C" {
 
@@ -485,6 +488,8 @@ int rtStructSizes(int32_t* out, int n) {
     for (int k = 0; k < n && k < RT_SIZEOF_COUNT; k++) out[k] = sizes[k];
     return RT_SIZEOF_COUNT;
 }
+
+int rtLastSphereForm(void) { return g_sphere_form; }
 
 int rtLastLaunches(int32_t* out, int cap) {
     const int count = (int)(g_launches.size() / RT_LAUNCH_WORDS);
@@ -776,6 +781,7 @@ void render_frame(int ns, int first, bool progressive) {
     int64_t samples = 0;
     int launches = 0;
     g_launches.clear();
+    g_sphere_form = RT_SPHERE_FORM_NONE;
     g_launch_fp = c.opt.fp;
     const RtSwitches sw = rt_read_switches();           // the environment switches of this frame
 

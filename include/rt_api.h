@@ -480,6 +480,12 @@ enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QU
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
        RT_LAUNCH_THREADS, RT_LAUNCH_BLOCKS, RT_LAUNCH_DEVICE, RT_LAUNCH_FP, RT_LAUNCH_WORDS };
 int rtLastLaunches(int32_t* out, int cap);
+/* The form of the cost-ordered sphere dispatch (the record with PHASE 2, CLS 2) of the last runRenderer or progressive pass.  That kernel exists in two forms
+ * with the same template arguments and the same launch record: the general one, which decides the frame's switches at run time, and one compiled for the
+ * default frame (a queue per XCD, packed parked records, no middle tier, the compact device framebuffer, no diagnostics), which the launcher takes whenever
+ * the frame is that one.  Both render the same bits.  RT_SPHERE_FORM_NONE: the frame had no such dispatch.  Host-side bookkeeping only. */
+enum { RT_SPHERE_FORM_NONE = -1, RT_SPHERE_FORM_GENERAL = 0, RT_SPHERE_FORM_DEFAULT = 1 };
+int rtLastSphereForm(void);
 
 #ifdef __cplusplus
 }
