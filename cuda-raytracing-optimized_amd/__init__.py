@@ -1065,7 +1065,7 @@ def rmse(f, g):
 # ---------------------------------------------------------------------------------------------
 
 PROBE_SYMBOLS = [f"rtProbe{n}_{m}" for n in ("Rng", "DiskSphere", "GetRay", "SphereHit", "TriangleHit", "Bbox", "Scatter", "Math", "ShadowRay", "PlaneHit", "SinCos", "Schlick")
-                 for m in ("parity", "fast")]
+                 for m in ("parity", "fast")] + ["rtProbeRenorm_parity"]
 
 
 def _f32(a):
@@ -1169,6 +1169,14 @@ class Probe:
         out = np.zeros(n, np.float32); above = np.zeros(n, np.int32)
         self._fn("Schlick")(_p(c), _p(r), _p(u), C.c_int(n), _p(out), _p(above))
         return out, above
+
+    def renorm(self, v):
+        """unit_vector of directions that are unit already, as hit() renormalises the path's direction (csrc/rt_renorm.h).  The parity build only."""
+        assert self.sfx == "_parity", "the fast build keeps the plain operators: it has no rtProbeRenorm"
+        v = _f32(v).reshape(-1, 3); n = len(v)
+        out = np.zeros((n, 3), np.float32)
+        self._fn("Renorm")(_p(v), C.c_int(n), _p(out))
+        return out
 
     def math(self, a, b):
         a = _f32(a); b = _f32(b); n = len(a)

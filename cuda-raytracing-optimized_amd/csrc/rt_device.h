@@ -95,6 +95,22 @@ __device__ __forceinline__ f3 unit(f3 a) {                                      
     return a / len(a);
 #endif
 }
+// unit() of a direction that the path stored as unit(v) already - what hit() does when it rebuilds the ray (ray.h:9): the same bits by the exact correction
+// of rt_renorm.h, its argument and its host twin.  Every other direction (not unit, a component of zero) takes unit() under one branch, which a wave skips
+// when none of its lanes with a ray (`live`) needs it.  The FAST build's division is not IEEE: it keeps unit().
+#ifdef RT_MODE_PARITY
+#define RT_RENORM_FN __device__ __forceinline__
+#include "rt_renorm.h"
+__device__ __forceinline__ f3 renorm_unit(f3 a, bool live = true) {
+    RtRenorm3 r;
+    const bool exact = rt_renorm_exact(a.x, a.y, a.z, &r);
+    f3 d = F3(r.x, r.y, r.z);
+    if (live && !exact) d = unit(a);
+    return d;
+}
+#else
+__device__ __forceinline__ f3 renorm_unit(f3 a, bool = true) { return unit(a); }
+#endif
 __device__ __forceinline__ float max3(f3 a) { return fmaxf(a.x, fmaxf(a.y, a.z)); }                    // vec3.h:113
 
 // ---- rnd.h ------------------------------------------------------------------------------------
@@ -388,7 +404,7 @@ struct Ray {
 __device__ __forceinline__ Ray make_ray(f3 o, f3 dir) {     // ray.h:9 + the hoisted invD of intersections.h:28
     Ray r;
     r.o = o;
-    r.d = unit(dir);
+    r.d = renorm_unit(dir);                                 // the path's directions are unit already; a raw one (ray queries, probes) takes unit() in there
     r.inv = F3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
     return r;
 }

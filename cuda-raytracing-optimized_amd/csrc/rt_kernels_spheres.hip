@@ -1067,7 +1067,7 @@ __device__ __forceinline__ bool trace_rays(const RtSphereParams& P, const SceneL
     unsigned long long tc = tm ? __builtin_amdgcn_s_memtime() : 0ull;
     auto lap = [&](int k) { if (tm) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); tm[k] += n_ - tc; tc = n_; } };
     // ---- hit(), kernels.cu:325-360: the ray is rebuilt from the path, which renormalises the direction
-    const f3 dn = unit(L.dir);
+    const f3 dn = renorm_unit(L.dir, has_ray);                       // (L.dir is unit already: start_sample and shade store unit(v))
     const float a = dot(dn, dn);
     Hit h = { FLT_MAX, -1, 0x7fffffff };
     const unsigned long long live = __ballot(has_ray);

@@ -141,6 +141,14 @@ __global__ void k_math(const float* a, const float* b, int n, float* quot, float
     stv(unit3, k, unit(F3(a[k], b[k], a[k] - b[k])));
 }
 
+#if defined(RT_MODE_PARITY)
+__global__ void k_renorm(const float* v, int n, float* out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    stv(out, k, renorm_unit(ld(v, k)));                              // as trace_rays and make_ray call it (rt_renorm.h)
+}
+#endif
+
 __global__ void k_sincos(const float* y, int n, float* s_out, float* c_out) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -262,6 +270,14 @@ void PROBE(rtProbeMath)(const float* a_, const float* b_, int n, float* quot, fl
     hipLaunchKernelGGL(k_math, grid_for(n), dim3(256), 0, 0, a.d, b.d, n, c.d, d.d, e.d, f.d);
     sync();
 }
+
+#if defined(RT_MODE_PARITY)
+void rtProbeRenorm_parity(const float* v3, int n, float* out3) {
+    auto a = in(v3, (size_t)3 * n); auto b = outb(out3, (size_t)3 * n);
+    hipLaunchKernelGGL(k_renorm, grid_for(n), dim3(256), 0, 0, a.d, n, b.d);
+    sync();
+}
+#endif
 
 void PROBE(rtProbeSinCos)(const float* y_, int n, float* s_out, float* c_out) {
     auto y = in(y_, n);

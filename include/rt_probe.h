@@ -22,6 +22,7 @@
  *   rtProbePlaneHit     planeHit                              intersections.h:43-52
  *   rtProbeSinCos       sinf / cosf of generateShadowRay      kernels.cu:378-379 (glibc's algorithm restated: csrc/rt_glibc_sincosf.h)
  *   rtProbeSchlick      schlick (with its powf(x, 5))         material.h:9-13 (glibc's powf restated: csrc/rt_glibc_powf.h)
+ *   rtProbeRenorm       unit_vector of a unit direction       vec3.h:194-196 via ray.h:9 (csrc/rt_renorm.h; _parity only)
  */
 #ifndef RT_PROBE_H
 #define RT_PROBE_H
@@ -57,6 +58,10 @@ void rtProbeSchlick##sfx(const float* cosine, const float* ref_idx, const float*
 
 RT_PROBE_DECL(_parity)
 RT_PROBE_DECL(_fast)
+
+/* unit_vector of a direction that is unit already, as hit() renormalises the path's direction (ray.h:9): the exact bit correction of csrc/rt_renorm.h
+ * with its plain path for every other input.  The parity build only: the fast build's kernels keep the plain operators. */
+void rtProbeRenorm_parity(const float* v3, int n, float* out3);
 
 #ifdef __cplusplus
 }
