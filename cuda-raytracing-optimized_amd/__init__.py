@@ -1065,7 +1065,7 @@ def rmse(f, g):
 # ---------------------------------------------------------------------------------------------
 
 PROBE_SYMBOLS = [f"rtProbe{n}_{m}" for n in ("Rng", "DiskSphere", "GetRay", "SphereHit", "TriangleHit", "Bbox", "Scatter", "Math", "ShadowRay", "PlaneHit", "SinCos", "Schlick")
-                 for m in ("parity", "fast")] + ["rtProbeRenorm_parity"]
+                 for m in ("parity", "fast")] + ["rtProbeRenorm_parity", "rtProbeExactDiv_parity"]
 
 
 def _f32(a):
@@ -1176,6 +1176,15 @@ class Probe:
         v = _f32(v).reshape(-1, 3); n = len(v)
         out = np.zeros((n, 3), np.float32)
         self._fn("Renorm")(_p(v), C.c_int(n), _p(out))
+        return out
+
+    def exactdiv(self, xyzl):
+        """The divisions of csrc/rt_exactdiv.h beside the plain operators, per operand set (x, y, z, l): 14 floats each (include/rt_probe.h).  The parity
+        build only."""
+        assert self.sfx == "_parity", "the fast build keeps the plain operators: it has no rtProbeExactDiv"
+        v = _f32(xyzl).reshape(-1, 4); n = len(v)
+        out = np.zeros((n, 14), np.float32)
+        self._fn("ExactDiv")(_p(v), C.c_int(n), _p(out))
         return out
 
     def math(self, a, b):

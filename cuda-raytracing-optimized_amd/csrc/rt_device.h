@@ -73,6 +73,41 @@ __device__ __forceinline__ f3 operator/(f3 a, float t) {                        
     return { a.x / t, a.y / t, a.z / t };
 #endif
 }
+// The bounce's divisions by a special divisor (rt_exactdiv.h: the arguments, the guards and the host twin), used by the folded kinds of the sphere kernel's
+// cost-ordered dispatch alone (the template switch XD of trace_rays): every other kernel compiles to what it was.  Operands a form does not handle take the
+// plain operators under one branch, which a wave skips when none of its lanes needs it.  The FAST build's division is not IEEE: it keeps the operators.
+// RT_EXDIV_B=0 / RT_EXDIV_C=0 (A/B) compile one form out.
+#ifdef RT_MODE_PARITY
+#define RT_EXDIV_FN __device__ __forceinline__
+#include "rt_exactdiv.h"
+#ifndef RT_EXDIV_B
+#define RT_EXDIV_B 1        // the roots of sphere_hit_exact over a = dot(dn, dn): one fma each (div_a2)
+#endif
+#ifndef RT_EXDIV_C
+#define RT_EXDIV_C 1        // unit_shared() in material_scatter
+#endif
+constexpr bool kExdivB = RT_EXDIV_B != 0, kExdivC = RT_EXDIV_C != 0;
+#else
+constexpr bool kExdivB = false, kExdivC = false;
+#endif
+// x / a for a = dot(dn, dn) of a normalised direction (the two roots of sphereHit, intersections.h:98,100): one fma each when a is one of the seven handled
+// floats next to 1 (rt_exactdiv.h form B, with the two exceptions its caller must not observe), the division for any other a - one branch for both roots.
+// (The empty asm makes it a real branch: without it the compiler runs the divisions for every lane and selects, and the form costs more than it saves.)
+__device__ __forceinline__ void div_a2(float x0, float x1, float a, float& q0, float& q1) {
+#if defined(RT_MODE_PARITY) && RT_EXDIV_B
+    const float r = rt_exdiv_a_r(a);
+    q0 = rt_exdiv_a_quot(x0, r);
+    q1 = rt_exdiv_a_quot(x1, r);
+    if (!rt_exdiv_a_handled(a)) {
+        asm volatile("");
+        q0 = x0 / a;
+        q1 = x1 / a;
+    }
+#else
+    q0 = x0 / a;
+    q1 = x1 / a;
+#endif
+}
 __device__ __forceinline__ f3 operator-(f3 a) { return { -a.x, -a.y, -a.z }; }                         // vec3.h:23
 __device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }         // vec3.h:87
 __device__ __forceinline__ f3 cross(f3 a, f3 b) {                                                      // vec3.h:91
@@ -93,6 +128,19 @@ __device__ __forceinline__ f3 unit(f3 a) {                                      
     return rt_div3_plain(a, rt_sqrt(s));
 #else
     return a / len(a);
+#endif
+}
+// unit() of the bounce vector (material_scatter<.., XD>): the three quotients share the reciprocal of the length (rt_exactdiv.h form C)
+__device__ __forceinline__ f3 unit_shared(f3 a) {
+#if defined(RT_MODE_PARITY) && RT_EXDIV_C && !RT_DIV64
+    const float xx = a.x * a.x, yy = a.y * a.y, zz = a.z * a.z, s2 = xx + yy + zz;                     // vec3.h:35-36, the reference's roundings
+    const float l = rt_sqrt(s2);
+    const RtExdiv3 q = rt_exdiv3(a.x, a.y, a.z, l, __builtin_amdgcn_rcpf(l));
+    f3 d = F3(q.x, q.y, q.z);
+    if (!rt_exdiv_unit_window(xx, yy, zz, s2)) d = a / l;
+    return d;
+#else
+    return unit(a);
 #endif
 }
 // unit() of a direction that the path stored as unit(v) already - what hit() does when it rebuilds the ray (ray.h:9): the same bits by the exact correction
@@ -255,7 +303,8 @@ __device__ __forceinline__ bool fresnel_layer(f3 normal, bool inside, f3 wo, flo
 // BASIC (the sphere kernel's instantiation for scenes whose materials are all RT_DIFFUSE / RT_METAL / RT_GLASS - every scene of the README-era renderer): the
 // same three BSDFs without the presets' parameter tables, layers, absorption and subsurface events around them - the same operations on the same operands,
 // so the same bits (1.0f * tint is tint), in a third of the code and registers.
-template <bool BASIC = false>
+// XD: the bounce vector is normalised by unit_shared() (the sphere kernel's folded kinds)
+template <bool BASIC = false, bool XD = false>
 __device__ __forceinline__ void material_scatter(Scatter& out, float hit_t, f3 hp, f3 normal, bool inside, f3 wo,
                                                  int type, f3 color, float param, uint32_t& rng) {
     if (BASIC) {
@@ -278,7 +327,7 @@ __device__ __forceinline__ void material_scatter(Scatter& out, float hit_t, f3 h
             refracted = true;
             thr = F3(1.0f, 1.0f, 1.0f);
         }
-        out.wi = unit(v);
+        out.wi = (XD && kExdivC) ? unit_shared(v) : unit(v);
         out.throughput = thr;
         out.specular = !diffuse;
         out.refracted = refracted;
@@ -367,7 +416,7 @@ __device__ __forceinline__ void material_scatter(Scatter& out, float hit_t, f3 h
         v = refract(wo, normal, inside ? ior : (1.0f / ior));
         refracted = true;
     }
-    out.wi = normalise ? unit(v) : v;
+    out.wi = normalise ? ((XD && kExdivC) ? unit_shared(v) : unit(v)) : v;
     out.throughput = thr;
     out.specular = specular;
     out.refracted = refracted;

@@ -113,6 +113,8 @@ __global__ void __launch_bounds__(256) k_poison_fb(const RtSphereParams P) {
 // sphereHit, intersections.h:85-104, on a pre-normalised direction `dn` with a = dot(dn,dn) hoisted (same bits every
 // call) and r2 = radius*radius precomputed (same bits).  `t_max` is INCLUSIVE here: the caller applies the reference's
 // strict `t < closest` itself, extended by the first-index-wins tie rule (see accept()).
+// XD (the folded kinds of the cost-ordered dispatch): the two roots over a by rt_exactdiv.h form B
+template <bool XD = false>
 __device__ __forceinline__ float sphere_hit_exact(float4 s, f3 org, f3 dn, float a, float t_min, float t_max) {
     const f3 oc = org - F3(s.x, s.y, s.z);
     const float b = dot(oc, dn);
@@ -120,6 +122,15 @@ __device__ __forceinline__ float sphere_hit_exact(float4 s, f3 org, f3 dn, float
     const float discriminant = b * b - a * c;
     if (discriminant > 0) {
         const float sq = rt_sqrt(discriminant);
+        // (x / a: on the render path a is one of seven floats next to 1 and each quotient is one fma - rt_exactdiv.h form B.  A root that fails the range
+        // test goes nowhere, which covers the form's two exceptions: a zero fails temp > t_min for t_min >= 0, an infinity and a NaN fail temp <= t_max.)
+        if (XD && kExdivB) {
+            float t0, t1;
+            div_a2(-b - sq, -b + sq, a, t0, t1);
+            if (t0 <= t_max && t0 > t_min) return t0;
+            if (t1 <= t_max && t1 > t_min) return t1;
+            return FLT_MAX;
+        }
         float temp = (-b - sq) / a;
         if (temp <= t_max && temp > t_min) return temp;
         temp = (-b + sq) / a;
@@ -570,7 +581,7 @@ __device__ __forceinline__ int wave_inclusive_scan(int x) {
 // loop below runs exactly once with every pass-level decision known at compile time (no windows, no carry between passes, no choice of the box test).
 //   OP   words of the one-list form: 0 = the general pass loop; 1 / 2 = the scene has at most 32 / 64 small groups, which take ONE list per ray batch
 //   C3   (with OP > 0) the prefilter is the general 3-axis one (group_needs_cells) instead of the shared-vertical-axis one (group_needs_cells_shared<1>)
-template <int OP = 0, bool C3 = false>
+template <int OP = 0, bool C3 = false, bool XD = false>
 __device__ __forceinline__ Hit scan_pairs(const RtSphereParams& P, const SceneLds& S, f3 org, f3 dn, float a, bool has_ray, bool cull,
                                           uint32_t& groups_done, uint32_t& boxes_done, unsigned long long* tm = nullptr) {
     // tm (diagnostic instantiation only): cycles in [1] big spheres, [2] group boxes + pair list, [3] pair rounds, [4] candidates
@@ -593,7 +604,7 @@ __device__ __forceinline__ Hit scan_pairs(const RtSphereParams& P, const SceneLd
     auto resolve = [&](uint32_t e) {
         const int owner = (int)(e >> 24), k = (int)(e & 0xFFFFFFu);
         const float4 ro = w_ray[owner], rd = w_ray[64 + owner];
-        const float t = sphere_hit_exact(S.sph[sidx(k)], F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z), ro.w, t_min, FLT_MAX);
+        const float t = sphere_hit_exact<XD>(S.sph[sidx(k)], F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z), ro.w, t_min, FLT_MAX);
         const int o = S.orig[k];
         if (o != 0x7fffffff && t < FLT_MAX)
             atomicMin(&w_best[owner], ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)(uint32_t)o);
@@ -834,6 +845,7 @@ __device__ __forceinline__ Hit scan_pairs(const RtSphereParams& P, const SceneLd
 // boxes are tested one group per lane.  Same exact tests, same (t, original index) merge as scan_pairs.  WAVE-LEVEL.
 constexpr int kSparseRays = 4;
 
+template <bool XD = false>
 __device__ __forceinline__ void sparse_test_slot(const RtSphereParams& P, const SceneLds& S, int slot, f3 O, f3 D, float A,
                                                  unsigned long long* best) {
     const float4 sph = S.sph[sidx(slot)];
@@ -844,7 +856,7 @@ __device__ __forceinline__ void sparse_test_slot(const RtSphereParams& P, const 
     const float c = __builtin_fmaf(oc.z, oc.z, __builtin_fmaf(oc.y, oc.y, __builtin_fmaf(oc.x, oc.x, -sph.w)));
     const float v = __builtin_fmaf(A - 3.814697265625e-6f, c, -__builtin_fmaf(b, b, 7.62939453125e-6f * sph.w));
     if (v < 0.0f) {
-        const float t = sphere_hit_exact(sph, O, D, A, P.t_min, FLT_MAX);
+        const float t = sphere_hit_exact<XD>(sph, O, D, A, P.t_min, FLT_MAX);
         const int o = S.orig[slot];
         if (o != 0x7fffffff && t < FLT_MAX)
             atomicMin(best, ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)(uint32_t)o);
@@ -855,7 +867,7 @@ __device__ __forceinline__ void sparse_test_slot(const RtSphereParams& P, const 
 // (reachable (ray, group) pair, sphere of the group) - are numbered across the rays and dealt to the 64 lanes, 64 at a time;
 // a lane fetches the ray of its item from the wave's LDS ray table.  Two rays therefore cost three lane passes like one
 // ray does (16 + 16 big slots, 31 + 31 boxes, ~2 x 16 spheres), where handling the rays one after the other cost six.
-template <bool ONEPASS = false>
+template <bool ONEPASS = false, bool XD = false>
 __device__ __forceinline__ Hit scan_sparse(const RtSphereParams& P, const SceneLds& S, f3 org, f3 dn, float a, unsigned long long live,
                                            bool cull, unsigned long long* tm = nullptr) {
     // tm (diagnostic instantiation only): cycles in [10] ray table + box set-up, [11] big spheres, [12] group boxes, [13] sphere tests + read-back
@@ -890,7 +902,7 @@ __device__ __forceinline__ Hit scan_sparse(const RtSphereParams& P, const SceneL
         if (w < m * nbs) {
             const int r = w / nbs, sl = w - r * nbs;
             const float4 ro = w_ray[r], rd = w_ray[64 + r];
-            sparse_test_slot(P, S, sl, F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z), ro.w, &w_best[r]);
+            sparse_test_slot<XD>(P, S, sl, F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z), ro.w, &w_best[r]);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -935,7 +947,7 @@ __device__ __forceinline__ Hit scan_sparse(const RtSphereParams& P, const SceneL
             const unsigned pr = w_pair[w >> kSphereGroupShift];
             const int r = (int)(pr >> 12), g = (int)(pr & 0xFFFu);
             const float4 ro = w_ray[r], rd = w_ray[64 + r];
-            sparse_test_slot(P, S, (g << kSphereGroupShift) + (w & (kSphereGroup - 1)), F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z), ro.w, &w_best[r]);
+            sparse_test_slot<XD>(P, S, (g << kSphereGroupShift) + (w & (kSphereGroup - 1)), F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z), ro.w, &w_best[r]);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -962,6 +974,7 @@ __device__ __forceinline__ Hit scan_sparse(const RtSphereParams& P, const SceneL
 // independent LDS reads for the 488-sphere scene), resolves its own candidates with the literal sphereHit tail, and the per-lane (t, original
 // index) keys are merged on the scalar unit.  Same pre-test and slack as sparse_test_slot, same exact tail, same tie rule.  WAVE-LEVEL; q is
 // wave-uniform; at most 32 rounds (2048 slots).
+template <bool XD = false>
 __device__ __forceinline__ Hit scan_single(const RtSphereParams& P, const SceneLds& S, int q, f3 org, f3 dn, float a) {
     const int lane = threadIdx.x & 63;
     auto bc = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), q)); };
@@ -984,7 +997,7 @@ __device__ __forceinline__ Hit scan_single(const RtSphereParams& P, const SceneL
         const int r = __builtin_ctz(mask);
         mask &= mask - 1u;
         const int k = (r << 6) + lane;
-        const float t = sphere_hit_exact(S.sph[sidx(k)], O, D, A, P.t_min, FLT_MAX);
+        const float t = sphere_hit_exact<XD>(S.sph[sidx(k)], O, D, A, P.t_min, FLT_MAX);
         const int o = S.orig[k];
         if (o != 0x7fffffff && t < FLT_MAX) accept(h, t, k, o);
     }
@@ -1013,7 +1026,7 @@ __device__ __forceinline__ Hit scan_single(const RtSphereParams& P, const SceneL
 template <bool STATS>
 __device__ __forceinline__ void ray_stat(const RtSphereParams& P, int k) { if (STATS && P.counters) atomicAdd(&P.counters->ref_stats[k], 1ull); }
 
-template <bool STATS, bool BASIC = false>
+template <bool STATS, bool BASIC = false, bool XD = false>
 __device__ __forceinline__ bool shade(const RtSphereParams& P, const SceneLds& S, Lane& L, f3 dn, Hit h, f3& sample) {
     sample = F3(0, 0, 0);                                            // kernels.cu:397
     const bool primary = L.bounce == 0;
@@ -1035,7 +1048,7 @@ __device__ __forceinline__ bool shade(const RtSphereParams& P, const SceneLds& S
     if (dot(dn, normal) > 0.0f) normal = -normal;                    // kernels.cu:354-355
     const float4 m = S.mat[h.sid];
     Scatter sc;
-    material_scatter<BASIC>(sc, h.closest, hp, normal, L.inside, L.dir, S.typ[h.sid], F3(m.x, m.y, m.z), m.w, L.rng);
+    material_scatter<BASIC, XD>(sc, h.closest, hp, normal, L.inside, L.dir, S.typ[h.sid], F3(m.x, m.y, m.z), m.w, L.rng);
     L.org = L.org + sc.t * L.dir;                                    // kernels.cu:485-489
     L.dir = sc.wi;
     L.atten = L.atten * sc.throughput;
@@ -1060,7 +1073,7 @@ __device__ __forceinline__ bool shade(const RtSphereParams& P, const SceneLds& S
 // lanes must call it together.  With many live lanes each lane scans the sphere list for its own ray; with few
 // (the tail of a tile / of the frame, where a handful of pixels in sphere / ground wedges need thousands of rays each) the
 // whole wave works on one ray at a time, which cuts the latency of a ray ~30x and with it the critical path.
-template <bool LEGACY, bool STATS = false, bool BASIC = false, int OP = 0, bool C3 = false>
+template <bool LEGACY, bool STATS = false, bool BASIC = false, int OP = 0, bool C3 = false, bool XD = false>
 __device__ __forceinline__ bool trace_rays(const RtSphereParams& P, const SceneLds& S, Lane& L, bool has_ray, int coop_below, bool cull,
                                            uint32_t& groups_done, uint32_t& boxes_done, f3& sample, int sparse_max = kSparseRays, unsigned long long* tm = nullptr, bool single = false) {
     // tm (diagnostic instantiation only): cycles in [0] ray set-up, [1..4] scan_pairs, [5] shade, [6] sparse scan
@@ -1075,14 +1088,14 @@ __device__ __forceinline__ bool trace_rays(const RtSphereParams& P, const SceneL
     if (!LEGACY) {                                                   // default: pair-compacted scan, sparse form for the tail
         // (the sparse form lists its reachable (ray, group) pairs in the wave's pair list: rays x groups must fit it)
         if (single && __popcll(live) == 1 && P.n_padded <= 2048 && sparse_max > 0) {     // one live ray: the shortest dependency chain (scan_single)
-            const Hit hq = scan_single(P, S, (int)__builtin_ctzll(live), L.org, dn, a);
+            const Hit hq = scan_single<XD>(P, S, (int)__builtin_ctzll(live), L.org, dn, a);
             if (has_ray) h = hq;
             if (tm) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); tm[6] += n_ - tc; tc = n_; }
         } else
         // (one list of 32 groups: at most 16 rays x 32 groups = 512 entries always fit)
         if (__popcll(live) <= min(sparse_max, 16) && coop_below == -1 && (OP == 1 || (P.n_groups <= 4096 &&
-            (int)__popcll(live) * (P.n_groups - P.n_big_groups) <= ws_list_cap(OP > 0)))) { h = scan_sparse<(OP > 0)>(P, S, L.org, dn, a, live, cull, tm); if (tm) tc = __builtin_amdgcn_s_memtime(); }
-        else { h = scan_pairs<OP, C3>(P, S, L.org, dn, a, has_ray, cull, groups_done, boxes_done, tm); if (tm) tc = __builtin_amdgcn_s_memtime(); }
+            (int)__popcll(live) * (P.n_groups - P.n_big_groups) <= ws_list_cap(OP > 0)))) { h = scan_sparse<(OP > 0), XD>(P, S, L.org, dn, a, live, cull, tm); if (tm) tc = __builtin_amdgcn_s_memtime(); }
+        else { h = scan_pairs<OP, C3, XD>(P, S, L.org, dn, a, has_ray, cull, groups_done, boxes_done, tm); if (tm) tc = __builtin_amdgcn_s_memtime(); }
     } else if (__popcll(live) >= coop_below) {
         if (has_ray) h = scan_lane_parallel(P, S, L.org, dn, a, groups_done);
     } else {
@@ -1096,7 +1109,7 @@ __device__ __forceinline__ bool trace_rays(const RtSphereParams& P, const SceneL
         }
     }
     bool done = false;
-    if (has_ray) done = shade<STATS, BASIC>(P, S, L, dn, h, sample);
+    if (has_ray) done = shade<STATS, BASIC, XD>(P, S, L, dn, h, sample);
     lap(5);
     return done;
 }
@@ -1922,7 +1935,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
             if (sel) { nrays++; pix_rays++; }
             if (x > 0 || steps == 1) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
             f3 sample;
-            const bool done = trace_rays<false, DBG, (LEAN & 1) != 0, (LEAN & 2) ? ((LEAN & 32) ? 4 : ((LEAN & 16) ? 2 : 1)) : 0, (LEAN & 8) != 0>(P, S, L, sel, -1, cull, groups_done, boxes_done, sample, sparse_max, dbg_timers ? dbg_tm : nullptr, (cfg & kCfgSingleRay) != 0);
+            const bool done = trace_rays<false, DBG, (LEAN & 1) != 0, (LEAN & 2) ? ((LEAN & 32) ? 4 : ((LEAN & 16) ? 2 : 1)) : 0, (LEAN & 8) != 0, FOLDED>(P, S, L, sel, -1, cull, groups_done, boxes_done, sample, sparse_max, dbg_timers ? dbg_tm : nullptr, (cfg & kCfgSingleRay) != 0);
             if (dbg_timers) { dbg_tm[x > 0 ? 9 : 8] += 1ull; }
             finish(done && sel, steps > 1, sample);
         }

@@ -147,6 +147,25 @@ __global__ void k_renorm(const float* v, int n, float* out) {
     if (k >= n) return;
     stv(out, k, renorm_unit(ld(v, k)));                              // as trace_rays and make_ray call it (rt_renorm.h)
 }
+// rt_exactdiv.h as the kernels call it, beside the plain operators on the same operands: (x, y, z, l) in, 14 floats out
+__global__ void k_exactdiv(const float* in4, int n, float* out14) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const f3 v = F3(in4[4 * k], in4[4 * k + 1], in4[4 * k + 2]);
+    const float l = in4[4 * k + 3];
+    float* o = out14 + (size_t)14 * k;
+    const RtExdiv3 e = rt_exdiv3(v.x, v.y, v.z, l, __builtin_amdgcn_rcpf(l));   // the shared reciprocal over a divisor of any size, under the header's general guard
+    f3 q = F3(e.x, e.y, e.z);
+    const f3 qp = v / l;                                             // vec3.h:79
+    if (!rt_exdiv3_window(v.x, v.y, v.z, l)) q = qp;
+    const f3 u = unit_shared(v), up = v / len(v);                    // unit() of the bounce (material_scatter) / vec3.h:194 as written
+    o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = qp.x; o[4] = qp.y; o[5] = qp.z;
+    o[6] = u.x; o[7] = u.y; o[8] = u.z; o[9] = up.x; o[10] = up.y; o[11] = up.z;
+    float r0, r1;
+    div_a2(v.x, v.y, l, r0, r1);                                     // the two roots of sphere_hit_exact, x and y over a = l
+    o[12] = r0;
+    o[13] = r1;
+}
 #endif
 
 __global__ void k_sincos(const float* y, int n, float* s_out, float* c_out) {
@@ -275,6 +294,11 @@ void PROBE(rtProbeMath)(const float* a_, const float* b_, int n, float* quot, fl
 void rtProbeRenorm_parity(const float* v3, int n, float* out3) {
     auto a = in(v3, (size_t)3 * n); auto b = outb(out3, (size_t)3 * n);
     hipLaunchKernelGGL(k_renorm, grid_for(n), dim3(256), 0, 0, a.d, n, b.d);
+    sync();
+}
+void rtProbeExactDiv_parity(const float* in4, int n, float* out14) {
+    auto a = in(in4, (size_t)4 * n); auto b = outb(out14, (size_t)14 * n);
+    hipLaunchKernelGGL(k_exactdiv, grid_for(n), dim3(256), 0, 0, a.d, n, b.d);
     sync();
 }
 #endif

@@ -23,6 +23,7 @@
  *   rtProbeSinCos       sinf / cosf of generateShadowRay      kernels.cu:378-379 (glibc's algorithm restated: csrc/rt_glibc_sincosf.h)
  *   rtProbeSchlick      schlick (with its powf(x, 5))         material.h:9-13 (glibc's powf restated: csrc/rt_glibc_powf.h)
  *   rtProbeRenorm       unit_vector of a unit direction       vec3.h:194-196 via ray.h:9 (csrc/rt_renorm.h; _parity only)
+ *   rtProbeExactDiv     vec3 / float, unit_vector, root / a   vec3.h:79,194; intersections.h:98,100 (csrc/rt_exactdiv.h; _parity only)
  */
 #ifndef RT_PROBE_H
 #define RT_PROBE_H
@@ -62,6 +63,12 @@ RT_PROBE_DECL(_fast)
 /* unit_vector of a direction that is unit already, as hit() renormalises the path's direction (ray.h:9): the exact bit correction of csrc/rt_renorm.h
  * with its plain path for every other input.  The parity build only: the fast build's kernels keep the plain operators. */
 void rtProbeRenorm_parity(const float* v3, int n, float* out3);
+
+/* The bounce's divisions by a special divisor (csrc/rt_exactdiv.h) beside the plain operators, on the device, per operand set in4 = (x, y, z, l):
+ * out14 = (x, y, z) / l through the shared reciprocal under the header's general guard [0..2] and through vec3.h:79 as written [3..5]; unit((x, y, z)) as
+ * material_scatter normalises the bounce vector in the folded sphere kernels [6..8] and as vec3.h:194 writes it [9..11]; x / l and y / l as
+ * sphere_hit_exact divides its two roots by a = l [12..13].  The parity build only. */
+void rtProbeExactDiv_parity(const float* in4, int n, float* out14);
 
 #ifdef __cplusplus
 }
