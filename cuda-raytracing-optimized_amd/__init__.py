@@ -137,6 +137,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "previewFrame", "rtResetPreview", "rtPreviewFrames", "rtLastPreviewMs",
                     "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs",
                     "traceRays", "occludedRays", "rtLastRaysMs",
+                    "renderPixels", "rtLastPixelsMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
                     "rtLastSphereForm"]
@@ -319,6 +320,11 @@ def load_renderer():
         r.occludedRays.restype = None
         r.rtLastRaysMs.argtypes = []
         r.rtLastRaysMs.restype = C.c_double
+        up = C.POINTER(C.c_uint32)
+        r.renderPixels.argtypes = [C.c_int, ip, C.c_int, ip, ip, up, C.POINTER(vec3), up]
+        r.renderPixels.restype = None
+        r.rtLastPixelsMs.argtypes = []
+        r.rtLastPixelsMs.restype = C.c_double
         r.updateTriangles.argtypes = [C.c_int, C.c_int, C.c_void_p]
         r.updateTriangles.restype = None
         r.updateMaterials.argtypes = [C.c_void_p, C.c_int]
@@ -641,6 +647,66 @@ def occluded_rays(org, dir, t_min=None, t_max=None, out=None):
 def last_rays_ms():
     """HIP-event time of the ray kernels of the last trace_rays / occluded_rays (not the copies), summed over its chunks, in milliseconds."""
     return load_renderer().rtLastRaysMs()
+
+
+# renderPixels (include/rt_api.h): path-trace a list of pixels, resumable
+RT_PIXEL_CHUNK = 1 << 22
+RT_PROGRESSIVE_MAX_SAMPLES = 65536
+
+
+def render_pixels(ij, ns, first=None, state=None, rays=False):
+    """Path-traces the pixels ij = (n, 2) int (column i, row j; row 0 = bottom) (renderPixels, include/rt_api.h).  ns: an int - samples for every pixel - or
+    an (n,) int array; first: None (every pixel starts its stream) or an (n,) int array of the first sample of each pixel, which needs `state` = the (n, 4)
+    uint32 array an earlier call returned for the same pixels after that many samples.  Returns (out, state, rays): out (n, 3) float32 = sum / (first + ns);
+    state (n, 4) uint32 after the last sample (a new array: the caller's is not written); rays (n,) uint32 closest-hit queries of these samples, or None
+    unless rays=True.  Blocking."""
+    ij = np.ascontiguousarray(ij, dtype=np.int32)
+    if ij.ndim != 2 or ij.shape[1] != 2:
+        raise ValueError(f"render_pixels: ij must have shape (n, 2), got {ij.shape}")
+    n = ij.shape[0]
+    ip, up = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+
+    def per_pixel(name, a):
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        if a.shape != (n,):
+            raise ValueError(f"render_pixels: {name} must be an int or have shape ({n},), got {a.shape}")
+        return a
+
+    ns_all, ns_arr = 0, None
+    if isinstance(ns, (int, np.integer)) and not isinstance(ns, bool):
+        ns_all = int(ns)
+    else:
+        ns_arr = per_pixel("ns", ns)
+    first_arr = None if first is None else per_pixel("first", first)
+    if state is None:
+        if first_arr is not None:
+            raise ValueError("render_pixels: first needs the state the pixels resume from")
+        st = np.zeros((n, 4), np.uint32)
+    else:
+        st = np.array(state, dtype=np.uint32, order="C")            # (a copy: renderPixels updates the states in place)
+        if st.shape != (n, 4):
+            raise ValueError(f"render_pixels: state must have shape ({n}, 4), got {st.shape}")
+    out = np.zeros((n, 3), np.float32)
+    nrays = np.zeros(n, np.uint32) if rays else None
+    load_renderer().renderPixels(n, ij.ctypes.data_as(ip), ns_all, None if ns_arr is None else ns_arr.ctypes.data_as(ip),
+                                 None if first_arr is None else first_arr.ctypes.data_as(ip), st.ctypes.data_as(up),
+                                 out.ctypes.data_as(C.POINTER(vec3)), None if nrays is None else nrays.ctypes.data_as(up))
+    return out, st, nrays
+
+
+def render_region(x0, y0, x1, y1, ns):
+    """The pixel rectangle [x0, x1) x [y0, y1) (columns, rows from the bottom) at ns samples per pixel, path-traced by render_pixels: a (y1 - y0, x1 - x0, 3)
+    float32 array, row 0 = row y0 - in PARITY mode the bits runRenderer(ns) stores there."""
+    if not (x0 <= x1 and y0 <= y1):
+        raise ValueError("render_region: needs x0 <= x1 and y0 <= y1")
+    jj, ii = np.mgrid[y0:y1, x0:x1]
+    out, _, _ = render_pixels(np.stack([ii.ravel(), jj.ravel()], axis=1), ns)
+    return out.reshape(y1 - y0, x1 - x0, 3)
+
+
+def last_pixels_ms():
+    """HIP-event time of the pixel kernels of the last render_pixels / render_region (not the copies), summed over its chunks, in milliseconds."""
+    return load_renderer().rtLastPixelsMs()
 
 
 # updateTriangles / updateMaterials / updateSpheres (include/rt_api.h): edit the scene in place.  The wrappers take arrays of the exact record type and

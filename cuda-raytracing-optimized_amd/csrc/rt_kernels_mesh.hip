@@ -22,6 +22,7 @@
 #include "rt_mesh_plan.h"
 
 #include <float.h>
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -31,8 +32,10 @@ using namespace rtd;
 
 #if defined(RT_MODE_PARITY)
 #define RT_LAUNCH_NAME rt_launch_mesh_parity
+#define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_mesh_parity
 #elif defined(RT_MODE_FAST)
 #define RT_LAUNCH_NAME rt_launch_mesh_fast
+#define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_mesh_fast
 #else
 #error "define RT_MODE_PARITY or RT_MODE_FAST"
 #endif
@@ -262,9 +265,182 @@ __global__ void __launch_bounds__(kThreads) k_render_mesh(const RtMeshParams P) 
     }
 }
 
+// ---- a list of pixels (renderPixels, rt_api.h) -----------------------------------------------------------------------------
+// One lane = one entry of the caller's list in 256-thread workgroups of persistent waves: a lane whose pixel is finished takes the next unassigned entry -
+// per refill round a wave takes ONE atomicAdd of the number of its idle lanes on B.queue and the lanes take their positions by mbcnt (the entries' costs
+// differ by more than an order of magnitude).  One iteration of the wave-uniform loop is one iteration of the bounce loop of k_render_mesh above for every
+// lane that holds an entry - closest hit, textures, next-event estimation with its shadow traversal, Russian roulette, the light - with the floor plane of
+// rt_render_options.floor where the default kernel tests it (a ray that misses the mesh; kernels.cu:341-345).  Not the default kernel's ray-job state
+// machine: the lanes of a wave wait for its slowest traversal.  An entry that continues a stream (first > 0) loads (colour sum, xorshift word) from
+// B.state instead of the pixel's seed; a finished entry stores state / out / rays from the lane that owns it.  No spin: the loop ends when the queue is
+// empty and the wave's lanes are done.
+constexpr int kPixelThreads = 256;
+__global__ void __launch_bounds__(kPixelThreads) k_pixels_mesh(const RtMeshParams P, const RtPixelBatch B) {
+    const uint32_t n = (uint32_t)B.n;
+    const float eps = P.t_min;
+    const f3 lightC = ld3(P.light.center);
+    const float lightR = P.light.radius;
+
+    int pi = 0, pj = 0;
+    uint32_t rng = 0u;
+    f3 col = F3(0, 0, 0);
+    f3 org = F3(0, 0, 0), dir = F3(0, 0, 1), atten = F3(1, 1, 1), pcolor = F3(0, 0, 0);
+    int bounce = 0;
+    bool inside = false, specular = false;
+    int s = 0, s_end = 0;               // the lane's entry ends with sample s_end - 1
+    TravStats st = { 0, 0 };
+    uint32_t entry = 0, pix_rays = 0;
+    bool active = false;                // the lane owns an unfinished entry
+    bool exhausted = false;             // wave-uniform: the queue is empty
+
+    auto start_sample = [&]() {                                      // kernels.cu:549-555, 397-398 (the reference stream: renderPixels refuses RT_RNG_COUNTER)
+        const float u = ((float)pi + rnd(rng)) / (float)P.nx;
+        const float v = ((float)pj + rnd(rng)) / (float)P.ny;
+        f3 d;
+        get_ray(P.cam, u, v, rng, org, d);
+        dir = unit(d);
+        atten = F3(1.0f, 1.0f, 1.0f);
+        pcolor = F3(0, 0, 0);
+        bounce = 0;
+        inside = false;
+        specular = false;
+    };
+
+    while (true) {
+        const unsigned long long idle = __ballot(!active);
+        if (!exhausted && idle != 0ull) {                            // one refill round
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            uint32_t base = 0;
+            if ((threadIdx.x & 63) == 0) base = atomicAdd(B.queue, cnt);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + cnt >= n) exhausted = true;
+            const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            if (!active && k < n) {
+                entry = k;
+                pi = B.ij[2 * (size_t)k]; pj = B.ij[2 * (size_t)k + 1];
+                s = B.first ? B.first[k] : 0;
+                s_end = s + (B.ns ? B.ns[k] : B.ns_all);
+                if (s > 0) {                                         // the stream continues where an earlier call stopped
+                    const uint4 st4 = reinterpret_cast<const uint4*>(B.state)[k];
+                    col = F3(__uint_as_float(st4.x), __uint_as_float(st4.y), __uint_as_float(st4.z));
+                    rng = st4.w;
+                } else {
+                    col = F3(0, 0, 0);
+                    rng = pixel_seed((uint32_t)(pj * P.nx + pi));    // kernels.cu:541 (global id -> seed)
+                }
+                start_sample();
+                pix_rays = 0;
+                active = true;
+            }
+        }
+        if (__ballot(active) == 0ull) break;
+        if (active) {
+            bool path_done = false;
+            if (P.max_depth <= 0) {                                  // the loop of kernels.cu:402 never runs: no ray, a black sample
+                path_done = true;
+            } else {
+                // ---- hit(context, p, FLT_MAX, false, inters), kernels.cu:325-360
+                const Ray r = make_ray(org, dir);
+                uint32_t triId = 0;
+                float hu = 0.0f, hv = 0.0f;
+                pix_rays++;
+                const float t = hit_mesh(P, r, eps, FLT_MAX, false, triId, hu, hv, st);
+                int obj = 0;                                         // 0 none, 1 triangle mesh, 2 floor, 3 light
+                float t_hit = t;
+                f3 normal = F3(0, 1, 0);
+                f3 albedo = F3(0, 0, 0);
+                int mtype = RT_FLOOR_DIFFUSE;                        // floor_diffuse_scatter, scene_materials.h:30-33 (kernels.cu:481-482)
+                float mparam = 0.0f;
+                if (t < FLT_MAX) {
+                    obj = 1;
+                    const Tri tri = load_tri(P.tris, triId);         // kernels.cu:334
+                    normal = unit(cross(tri.v1 - tri.v0, tri.v2 - tri.v0));
+                    const float w0 = 1 - hu - hv;
+                    const float tcu = (hu * tri.tc[2] + hv * tri.tc[4] + w0 * tri.tc[0]);
+                    const float tcv = (hu * tri.tc[3] + hv * tri.tc[5] + w0 * tri.tc[1]);
+                    const rt_material mat = P.materials[tri.meshID]; // kernels.cu:452-480
+                    mtype = mat.type; mparam = mat.param;
+                    if (mat.texId != -1) {
+                        const int width = P.tex_width[mat.texId];
+                        const int height = P.tex_height[mat.texId];
+                        float tu = tcu; tu = tu - floorf(tu);
+                        float tv = tcv; tv = tv - floorf(tv);
+                        const int tx = (int)((float)(width - 1) * tu);
+                        const int ty = (int)((float)(height - 1) * tv);
+                        const int tIdx = ty * width + tx;
+                        const float* d = P.tex_data[mat.texId];
+                        albedo = F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
+                    } else {
+                        albedo = ld3(mat.color);
+                    }
+                } else {
+                    float tp = FLT_MAX;
+                    if (P.floor_on) tp = plane_hit(ld3(P.floor.norm), ld3(P.floor.point), r, eps, FLT_MAX);      // kernels.cu:341-345, re-enabled by rt_render_options.floor
+                    if (tp < FLT_MAX) {
+                        obj = 2; t_hit = tp; normal = ld3(P.floor.norm);
+                    } else if (specular && sphere_hit(lightC, lightR, r, eps, FLT_MAX) < FLT_MAX) {               // kernels.cu:346
+                        obj = 3;
+                    }
+                }
+                if (obj == 0) {
+                    pcolor = pcolor + atten * sky_color(P.sky, dir); // kernels.cu:419-425
+                    path_done = true;
+                } else if (obj == 3) {
+                    if (!P.nee) pcolor = pcolor + atten * ld3(P.lightColor);                                      // kernels.cu:440-446
+                    path_done = true;
+                } else {
+                    if (dot(r.d, normal) > 0.0f) normal = -normal;   // kernels.cu:354-355
+                    Scatter sc;
+                    material_scatter(sc, t_hit, r.o + t_hit * r.d, normal, inside, dir, mtype, albedo, mparam, rng);
+                    org = org + sc.t * dir;                          // kernels.cu:485-489
+                    dir = sc.wi;
+                    atten = atten * sc.throughput;
+                    specular = sc.specular;
+                    inside = sc.refracted ? !inside : inside;
+
+                    if (P.nee && !specular) {                        // generateShadowRay, kernels.cu:363-393 (rt_device.h)
+                        ShadowSample sh;
+                        if (generate_shadow_ray(lightC, lightR, ld3(P.lightColor), org, atten, normal, rng, sh)) {
+                            const Ray sr = make_ray(org, sh.dir);
+                            uint32_t tid2 = 0; float u2, v2;
+                            const float ts = hit_mesh(P, sr, eps, sh.dist, true, tid2, u2, v2, st);
+                            if (!(ts < sh.dist)) pcolor = pcolor + sh.contrib;       // kernels.cu:504-510
+                        }
+                    }
+                    if (P.rr && bounce > 3) {                        // kernels.cu:512-527
+                        const float mx = max3(atten);
+                        if (rnd(rng) > mx) {
+                            path_done = true;
+                        } else {
+                            const float kk = 1.0f / mx;
+                            atten = F3(atten.x * kk, atten.y * kk, atten.z * kk);
+                        }
+                    }
+                    bounce++;
+                    if (bounce >= P.max_depth) path_done = true;
+                }
+            }
+            if (path_done) {
+                col = col + pcolor;                                  // kernels.cu:558
+                s++;
+                if (s < s_end) {
+                    start_sample();
+                } else {
+                    if (B.state) reinterpret_cast<uint4*>(B.state)[entry] = make_uint4(__float_as_uint(col.x), __float_as_uint(col.y), __float_as_uint(col.z), rng);
+                    if (B.out) {
+                        const f3 out = col / (float)s_end;           // kernels.cu:568
+                        *reinterpret_cast<float3*>(reinterpret_cast<float*>(B.out) + (size_t)entry * 3) = make_float3(out.x, out.y, out.z);
+                    }
+                    if (B.rays) B.rays[entry] = pix_rays;
+                    active = false;
+                }
+            }
+        }
+    }
+}
 
 // ---- first-hit guide planes (renderGuides, rt_api.h) ------------------------------------------------------------------
-// One lane per pixel of an 8x8 tile per wave, the grid of the kernel above: the centre ray (no lens offset, no jitter) through hitMesh / hitBvh in the
+// One lane per pixel of an 8x8 tile per wave, the grid of k_render_mesh above: the centre ray (no lens offset, no jitter) through hitMesh / hitBvh in the
 // reference's own visiting order with its TravStats, so the node count of the closest-hit query is the oracle's; then the floor (rt_render_options.floor);
 // normal, texture coordinates and texture lookup as bounce 0 above does them.  No atomics, no queue: a lane writes the planes of its own pixel.
 // PARITY objects only: one arithmetic for both fp modes.
@@ -1205,6 +1381,21 @@ hipError_t rt_launch_rays_mesh(const RtMeshParams& p, const RtRayBatch& b, bool 
     return hipGetLastError();
 }
 #endif
+
+// renderPixels (rt_api.h): k_pixels_mesh over one chunk of the list, in this object's arithmetic.  Waves: four per SIMD of every CU - what stays resident -
+// and never more than ceil(n / 64), so a one-pixel call is one wave; max_waves > 0 caps them.
+hipError_t RT_PIXELS_LAUNCH_NAME(const RtMeshParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    if (!b.queue || !b.ij) return hipErrorInvalidValue;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    constexpr unsigned wg_waves = kPixelThreads / 64;
+    unsigned waves = std::min((unsigned)cus * 16u, ((unsigned)b.n + 63u) / 64u);
+    if (max_waves > 0) waves = std::min(waves, (unsigned)max_waves);
+    const dim3 grid((waves + wg_waves - 1) / wg_waves), block(64u * std::min(waves, wg_waves));
+    hipLaunchKernelGGL(k_pixels_mesh, grid, block, 0, stream, p, b);
+    return hipGetLastError();
+}
 
 #if RT_MESH_TAIL_DIAG
 // The diagnostic build (tools/build_variant.sh taildiag -DRT_MESH_TAIL_DIAG=1; tools/mesh_tail_diag.py): when did the second dispatch's queue run empty, when

@@ -56,8 +56,10 @@ using namespace rtd;
 
 #if defined(RT_MODE_PARITY)
 #define RT_LAUNCH_NAME rt_launch_spheres_parity
+#define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_spheres_parity
 #elif defined(RT_MODE_FAST)
 #define RT_LAUNCH_NAME rt_launch_spheres_fast
+#define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_spheres_fast
 #else
 #error "define RT_MODE_PARITY or RT_MODE_FAST"
 #endif
@@ -1173,6 +1175,78 @@ __global__ void __launch_bounds__(kThreads) k_render_spheres_tiles(const RtSpher
     }
 }
 
+// ---- a list of pixels (renderPixels, rt_api.h) -----------------------------------------------------------------------------
+// One lane = one entry of the caller's list, persistent waves: a lane whose pixel is finished takes the next unassigned entry.  The entries' costs differ by
+// more than an order of magnitude (a sky pixel: one ray per sample; a pixel inside glass: dozens), so they are handed out by a queue: per refill round a wave
+// takes ONE atomicAdd of the number of its idle lanes on B.queue and the lanes take their positions by mbcnt.  The loop is the tile kernel's wave-uniform
+// one around trace_rays - the pair-compacted scan, the sparse and the single-ray form for the few live lanes of a wave's tail, which is where a lone
+// expensive pixel lives.  An entry that continues a stream (first > 0) loads (colour sum, xorshift word) from B.state instead of the pixel's seed; a
+// finished entry stores its state / out / rays with plain vector stores from the lane that owns it.  Nothing of a frame's state is read or written, and
+// there is no spin: the loop ends when the queue is empty and the wave's lanes are done.
+template <int SCENE>
+__global__ void __launch_bounds__(kThreads) k_pixels_spheres(const RtSphereParams P, const RtPixelBatch B) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* unused;
+    const SceneLds S = stage_scene<false, SCENE>(P, smem, &unused);
+    const uint32_t n = (uint32_t)B.n;
+
+    Lane L;
+    L.rng = 0u; L.col = F3(0, 0, 0);
+    L.org = F3(0, 0, 0); L.dir = F3(0, 0, 1); L.atten = F3(1, 1, 1);
+    L.bounce = 0; L.inside = false; L.s = 0; L.i = 0; L.j = 0; L.pixelId = 0u;
+    uint32_t entry = 0, pix_rays = 0, groups_done = 0, boxes_done = 0;
+    int s_end = 0;                      // the lane's entry ends with sample s_end - 1
+    bool active = false;                // the lane owns an unfinished entry
+    bool exhausted = false;             // wave-uniform: the queue is empty
+    while (true) {
+        const unsigned long long idle = __ballot(!active);
+        if (!exhausted && idle != 0ull) {                            // one refill round
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            uint32_t base = 0;
+            if ((threadIdx.x & 63) == 0) base = atomicAdd(B.queue, cnt);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + cnt >= n) exhausted = true;
+            const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            if (!active && k < n) {
+                entry = k;
+                const int first = B.first ? B.first[k] : 0;
+                s_end = first + (B.ns ? B.ns[k] : B.ns_all);
+                init_pixel(P, L, B.ij[2 * (size_t)k], B.ij[2 * (size_t)k + 1], first);
+                if (first > 0) {                                     // the stream continues where an earlier call stopped
+                    const uint4 st = reinterpret_cast<const uint4*>(B.state)[k];
+                    L.col = F3(__uint_as_float(st.x), __uint_as_float(st.y), __uint_as_float(st.z));
+                    L.rng = st.w;
+                }
+                start_sample(P, L);
+                pix_rays = 0;
+                active = true;
+            }
+        }
+        if (__ballot(active) == 0ull) break;
+        f3 sample = F3(0, 0, 0);
+        bool done = true;                                            // (max_depth <= 0: the loop of kernels.cu:402 never runs - no ray, a black sample)
+        if (P.max_depth > 0) {
+            if (active) pix_rays++;
+            done = trace_rays<false>(P, S, L, active, -1, true, groups_done, boxes_done, sample, kSparseRays, nullptr, true);
+        }
+        if (active && done) {
+            L.col = L.col + sample;                                  // kernels.cu:558
+            L.s++;
+            if (L.s < s_end) {
+                start_sample(P, L);
+            } else {
+                if (B.state) reinterpret_cast<uint4*>(B.state)[entry] = make_uint4(__float_as_uint(L.col.x), __float_as_uint(L.col.y), __float_as_uint(L.col.z), L.rng);
+                if (B.out) {
+                    const f3 out = L.col / (float)s_end;             // kernels.cu:568
+                    *reinterpret_cast<float3*>(reinterpret_cast<float*>(B.out) + (size_t)entry * 3) = make_float3(out.x, out.y, out.z);
+                }
+                if (B.rays) B.rays[entry] = pix_rays;
+                active = false;
+            }
+        }
+    }
+}
+
 // ---- work-order pre-pass ------------------------------------------------------------------------------------------
 // The persistent kernel ends with a tail in which every lane finishes the pixel it happens to hold.  That tail is short
 // when the LAST pixels handed out are cheap and alike.  A pixel whose centre ray (no lens offset, no jitter) misses every
@@ -2052,6 +2126,24 @@ hipError_t rt_launch_rays_spheres(const RtSphereParams& p, const RtRayBatch& b, 
     return launch_with_lds(kerns[any ? 1 : 0][scene], grid, dim3(kThreads), lds, stream, p, b);
 }
 #endif
+
+// renderPixels (rt_api.h): k_pixels_spheres over one chunk of the list, in this object's arithmetic.  The scene form is the guide kernel's choice with the
+// render kernels' per-wave scratch (the hybrid copy in 8-wave workgroups where 16 do not fit, as the frame's plan does).  Waves: as many as stay resident
+// - one workgroup per CU, the launch bound's 4 waves per SIMD - and never more than ceil(n / 64), so a one-pixel call is one wave; max_waves > 0 caps them.
+hipError_t RT_PIXELS_LAUNCH_NAME(const RtSphereParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    if (!b.queue || !b.ij) return hipErrorInvalidValue;
+    const int scene = scene_form(p, false);
+    const unsigned wg_waves = (scene == 2 && lds_bytes(p.n_padded, p.n, false, 2, kWavesPerWg) > kLdsPerCu) ? 8u : (unsigned)kWavesPerWg;
+    const size_t lds = lds_bytes(p.n_padded, p.n, false, scene, (int)wg_waves);
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    unsigned waves = std::min((unsigned)cus * wg_waves, ((unsigned)b.n + 63u) / 64u);
+    if (max_waves > 0) waves = std::min(waves, (unsigned)max_waves);
+    const dim3 grid((waves + wg_waves - 1) / wg_waves), block(64u * std::min(waves, wg_waves));
+    const auto kern = scene == 0 ? k_pixels_spheres<0> : (scene == 1 ? k_pixels_spheres<1> : k_pixels_spheres<2>);
+    return launch_with_lds(kern, grid, block, lds, stream, p, b);
+}
 
 // The LEAN kinds of k_render_spheres_queue that are built beside the general kernel (LEAN 0), by scene form and chunking: the one statement of them.  The
 // launch expands these lists into the instantiations (launch_kind_of), the plan clips a scene's kind to them (clip_lean).

@@ -246,6 +246,7 @@ struct RtSwitches {
     bool cleanup_device_reset = false;  // RT_CLEANUP_DEVICE_RESET=1: cleanupRenderer ends with hipDeviceReset
     int cost_reuse = 1;                 // RT_COST_REUSE: sphere frames 0 = neither record nor reuse the per-pixel cost map (every frame measures), 1 = reuse it until
                                         // setCamera changes the camera, 2 = across setCamera too (A/B: tools/bench_orbit.py)
+    int pixels_waves = 0;               // RT_PIXELS_WAVES=<w>: renderPixels launches at most w waves (0 = no cap; tests: the refill path with a few hundred pixels)
     // the sphere launcher
     int top_thr = 384;                  // RT_TOP_THR: 16 x rays per sample from which a pixel goes to chain list 0 (24; below 320: the default)
     bool basic = true;                  // RT_BASIC=0 / RT_ONEPASS=0: keep the general shading code / pass loop where the lean kinds would do
@@ -333,3 +334,25 @@ struct RtRayBatch {
 };
 hipError_t rt_launch_rays_spheres(const RtSphereParams& p, const RtRayBatch& b, bool any, hipStream_t stream);
 hipError_t rt_launch_rays_mesh(const RtMeshParams& p, const RtRayBatch& b, bool any, hipStream_t stream);
+
+// A list of pixels (renderPixels, rt_api.h): one chunk of the caller's list on the device.  ij holds n x 2 words (column, row from the bottom); ns / first n
+// words each or nullptr (= ns_all, respectively 0 for every entry); state n x 4 words - (colour sum bits, xorshift word), read by an entry whose first
+// sample is not 0, written by every entry - or nullptr; out n x 3 floats = sum / (first + count) or nullptr; rays n words or nullptr.  queue: one zeroed
+// word, the next unassigned entry.  The pixel kernels (k_pixels_spheres / k_pixels_mesh) exist in both fp objects - they are the frame's arithmetic - and
+// read of the scene's parameter block the scene, the camera, the image size, max_depth and the options of a frame (sky, t_min, rr; mesh: nee, light, floor);
+// nothing of its partition, framebuffer, queue, parked or progressive state.  max_waves: RT_PIXELS_WAVES, 0 = as many as stay resident.
+struct RtPixelBatch {
+    const int32_t* ij;
+    const int32_t* ns;
+    const int32_t* first;
+    uint32_t* state;
+    rt_vec3* out;
+    uint32_t* rays;
+    uint32_t* queue;
+    int32_t n;
+    int32_t ns_all;
+};
+hipError_t rt_launch_pixels_spheres_parity(const RtSphereParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream);
+hipError_t rt_launch_pixels_spheres_fast(const RtSphereParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream);
+hipError_t rt_launch_pixels_mesh_parity(const RtMeshParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream);
+hipError_t rt_launch_pixels_mesh_fast(const RtMeshParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream);

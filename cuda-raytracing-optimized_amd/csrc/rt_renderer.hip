@@ -171,6 +171,7 @@ struct RenderContext {
     double preview_ms = 0.0;            // rtLastPreviewMs
     double display_ms = 0.0;            // rtLastDisplayMs
     double rays_ms = 0.0;               // rtLastRaysMs
+    double pixels_ms = 0.0;             // rtLastPixelsMs
 };
 
 // What the whole-image preview passes (denoiseFrame, accumulateFrame, previewFrame) each hold on the device: buffers for the whole image on ONE device, the first in-process
@@ -237,11 +238,27 @@ struct RayState {
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
 
+// renderPixels: the device buffers of one chunk of the list - three inputs, the stream states (read and written), two outputs - and the queue word, on the
+// first in-process device, each grown to the largest chunk that asked for it, with an event pair of their own beside the ray queries' (setup_devices).
+// Released by free_pass where the ray buffers are.
+enum { kPixIj = 0, kPixNs, kPixFirst, kPixState, kPixOut, kPixRays, kPixBuffers };
+constexpr size_t kPixBytes[kPixBuffers] = { 8, 4, 4, 16, 12, 4 };      // bytes per pixel: 48 in all
+constexpr int kPixelChunk = RT_PIXEL_CHUNK; // pixels per upload - kernel - download round
+struct PixelState {
+    int device = -1;
+    std::vector<void*> owned;           // its device allocations (dev_alloc)
+    char* d_buf[kPixBuffers] = {};
+    size_t cap[kPixBuffers] = {};       // pixels d_buf[k] holds
+    uint32_t* d_queue = nullptr;        // RtPixelBatch::queue
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
 DisplayState g_display;
 RayState g_rays;
+PixelState g_pixels;
 
 // The state of displayFrame's auto exposure back to "adapt from nothing" (rtResetDisplay, setRenderOptions); the buffers stay.
 void reset_display() {
@@ -352,6 +369,7 @@ void setup_devices() {
     free_pass(g_preview);
     free_pass(g_display);
     free_pass(g_rays);
+    free_pass(g_pixels);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -409,6 +427,9 @@ void setup_devices() {
     g_rays.device = c.devs[0].device;
     HIP_CHECK(hipEventCreate(&g_rays.ev_start));
     HIP_CHECK(hipEventCreate(&g_rays.ev_stop));
+    g_pixels.device = c.devs[0].device;                     // ... and renderPixels'
+    HIP_CHECK(hipEventCreate(&g_pixels.ev_start));
+    HIP_CHECK(hipEventCreate(&g_pixels.ev_stop));
     HIP_CHECK(hipSetDevice(current));
 }
 
@@ -457,6 +478,7 @@ void cleanup_impl() {
     free_pass(g_preview);
     free_pass(g_display);
     free_pass(g_rays);
+    free_pass(g_pixels);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -990,6 +1012,7 @@ RtSwitches rt_read_switches() {
     s.cleanup_device_reset = env_one("RT_CLEANUP_DEVICE_RESET");
     const int cost_reuse = env_int("RT_COST_REUSE", s.cost_reuse);
     s.cost_reuse = (cost_reuse >= 0 && cost_reuse <= 2) ? cost_reuse : 1;
+    s.pixels_waves = std::max(0, env_int("RT_PIXELS_WAVES", s.pixels_waves));
 
     const int top_thr = env_int("RT_TOP_THR", s.top_thr);
     if (top_thr >= 320) s.top_thr = top_thr;
@@ -1375,6 +1398,94 @@ void occludedRays(int n, const float* org, const float* dir, const float* t_min,
 double rtLastRaysMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastRaysMs before init");
     return g_ctx.rays_ms;
+}
+
+// A list of pixels (rt_api.h).  Like the ray queries: all entries run on the first in-process device, chunk by chunk - the queue word zeroed,
+// upload, kernel, download on that device's stream - with buffers and events of their own (PixelState); the parameter block is a frame's without
+// anything a frame parks, records or reports, over the whole image as one member's rows.  host[k] = the caller's array of buffer k, or NULL.
+static void run_pixels(int n, int ns_all, void* const host[kPixBuffers]) {
+    RenderContext& c = g_ctx;
+    PixelState& q = g_pixels;
+    const DeviceState& d = c.devs[0];
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(d.device));
+    if (!q.d_queue) q.d_queue = dev_alloc<uint32_t>(q.owned, 1);
+    const int max_waves = rt_read_switches().pixels_waves;
+    double ms_sum = 0.0;
+    for (size_t first = 0; first < (size_t)n; first += kPixelChunk) {
+        const size_t m = std::min((size_t)kPixelChunk, (size_t)n - first);
+        for (int k = 0; k < kPixBuffers; k++) {
+            if (!host[k] || q.cap[k] >= m) continue;
+            dev_release(q.owned, q.d_buf[k]);
+            q.d_buf[k] = dev_alloc<char>(q.owned, m * kPixBytes[k]);
+            q.cap[k] = m;
+        }
+        HIP_CHECK(hipMemsetAsync(q.d_queue, 0, sizeof(uint32_t), d.stream));
+        for (int k = 0; k <= kPixState; k++)                    // (the states go up only where an entry can continue one: `first` is given)
+            if (host[k] && (k != kPixState || host[kPixFirst]))
+                HIP_CHECK(hipMemcpyAsync(q.d_buf[k], static_cast<const char*>(host[k]) + first * kPixBytes[k], m * kPixBytes[k], hipMemcpyHostToDevice, d.stream));
+        auto buf = [&](int k) { return host[k] ? q.d_buf[k] : nullptr; };
+        RtPixelBatch b;
+        b.ij = reinterpret_cast<const int32_t*>(buf(kPixIj)); b.ns = reinterpret_cast<const int32_t*>(buf(kPixNs));
+        b.first = reinterpret_cast<const int32_t*>(buf(kPixFirst)); b.state = reinterpret_cast<uint32_t*>(buf(kPixState));
+        b.out = reinterpret_cast<rt_vec3*>(buf(kPixOut)); b.rays = reinterpret_cast<uint32_t*>(buf(kPixRays));
+        b.queue = q.d_queue; b.n = (int32_t)m; b.ns_all = ns_all;
+        const bool fast = c.opt.fp == RT_FP_FAST;
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        if (c.is_spheres) {
+            RtSphereParams p = sphere_params(d, whole_image_partition());
+            p.max_depth = c.max_depth; p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
+            HIP_CHECK(fast ? rt_launch_pixels_spheres_fast(p, b, max_waves, d.stream) : rt_launch_pixels_spheres_parity(p, b, max_waves, d.stream));
+        } else {
+            RtMeshParams p = mesh_params(d, whole_image_partition());
+            p.max_depth = c.max_depth; p.nee = c.opt.nee; p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
+            p.light = c.opt.light; p.lightColor = c.opt.lightColor;
+            HIP_CHECK(fast ? rt_launch_pixels_mesh_fast(p, b, max_waves, d.stream) : rt_launch_pixels_mesh_parity(p, b, max_waves, d.stream));
+        }
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        for (int k = kPixState; k < kPixBuffers; k++)
+            if (host[k])
+                HIP_CHECK(hipMemcpyAsync(static_cast<char*>(host[k]) + first * kPixBytes[k], q.d_buf[k], m * kPixBytes[k], hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's arrays are complete on return; the events are read per chunk
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, q.ev_start, q.ev_stop));
+        ms_sum += (double)ms;
+    }
+    HIP_CHECK(hipSetDevice(current));
+    c.pixels_ms = ms_sum;
+}
+
+void renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, const int32_t* first, uint32_t* state, rt_vec3* out, uint32_t* rays) {
+    const RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("renderPixels before init");
+    if (n < 0) rt_fail("renderPixels: n is negative");
+    if (n == 0) return;
+    if (!ij) rt_fail("renderPixels: ij is null");
+    if (!out && !state && !rays) rt_fail("renderPixels: out, state and rays are all null");
+    if (first && !state) rt_fail("renderPixels: first needs state (the sums and stream words the pixels resume from)");
+    if (c.opt.rng != RT_RNG_REFERENCE_STREAM) rt_fail("renderPixels: only the reference RNG stream is one sequential stream per pixel (RT_RNG_COUNTER sums sample chunks)");
+    if (c.opt.variant != 0) rt_fail("renderPixels: only the default kernels' frame (variant 0) is defined per pixel");
+    if (c.is_spheres && c.opt.floor) rt_fail("renderPixels: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
+    if (c.is_spheres && c.opt.nee) rt_fail("renderPixels: next-event estimation is only defined for mesh scenes");
+    for (int k = 0; k < n; k++) {                           // every entry, before anything is uploaded
+        const long long cnt = ns ? ns[k] : ns_all, f = first ? first[k] : 0;
+        if (ij[2 * (size_t)k] < 0 || ij[2 * (size_t)k] >= c.nx || ij[2 * (size_t)k + 1] < 0 || ij[2 * (size_t)k + 1] >= c.ny)
+            rt_fail("renderPixels: a pixel lies outside [0, nx) x [0, ny)");
+        if (cnt < 1) rt_fail("renderPixels: a pixel's sample count is below 1");
+        if (f < 0) rt_fail("renderPixels: a pixel's first sample is negative");
+        if (f + cnt > RT_PROGRESSIVE_MAX_SAMPLES) rt_fail("renderPixels: first + count above RT_PROGRESSIVE_MAX_SAMPLES");
+        // (a pixel's seed is odd and xorshift32 never reaches 0 from it: a zero word is no state of any stream - and the one input on which the stream
+        // stands still, so that the rejection loops of the lens and the diffuse bounce would never end on the device)
+        if (f > 0 && state[4 * (size_t)k + 3] == 0u) rt_fail("renderPixels: a resumed pixel's stream word is 0 (not a state renderPixels returned)");
+    }
+    void* const host[kPixBuffers] = { const_cast<int32_t*>(ij), const_cast<int32_t*>(ns), const_cast<int32_t*>(first), state, out, rays };
+    run_pixels(n, ns_all, host);
+}
+
+double rtLastPixelsMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastPixelsMs before init");
+    return g_ctx.pixels_ms;
 }
 
 // Guide-driven preview denoiser (rt_api.h).  The filter needs neighbours across stripe boundaries, so it works on the whole image on the first

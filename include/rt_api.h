@@ -408,6 +408,35 @@ void   traceRays(int n, const float* org, const float* dir, const float* t_min, 
 void   occludedRays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, uint8_t* occluded);
 double rtLastRaysMs(void);   /* HIP-event time of the ray kernels of the last traceRays / occludedRays (not the copies), summed over its chunks; 0 before the first */
 
+/* --- path-tracing a list of pixels: a region after an edit, the pixel under the cursor, a caller-driven adaptive loop ------------------
+ * renderPixels path-traces n caller-chosen pixels of the image of init* with a caller-chosen number of samples each, and can continue a pixel's stream
+ * where an earlier call stopped.  Every pixel is defined by what runRenderer stores there:
+ *   Pixel k        (i, j) = (ij[2k], ij[2k+1]): column, then row with 0 = bottom - rtCentreRays' convention.  Duplicates and any order are allowed; every
+ *                  entry is answered independently, in the caller's order.
+ *   Sample range   c = ns ? ns[k] : ns_all samples are rendered for pixel k: samples f .. f+c-1 of that pixel's stream, f = first ? first[k] : 0.
+ *   f == 0         the reference's per-pixel loop (kernels.cu:541-568): the seed from the global pixel id j*nx + i, ONE sequential xorshift stream over
+ *                  the pixel's samples, sum += sample in sample order.
+ *   f > 0          state[4k .. 4k+2] are the bits of the fp32 colour sum after f samples, state[4k+3] is the stream's xorshift word: the pixel resumes from
+ *                  them (what a call with `state` returned for the same pixel after f samples; nothing else is checked).
+ *   Outputs        out, state and rays may each be NULL.  state (read for f > 0, written if non-NULL: in place) receives the sum and the word after sample
+ *                  f+c-1;  out[k] = sum / (float)(f + c);  rays[k] = the closest-hit queries of these c samples - the `rays` of getRenderStats with
+ *                  counters = 1, shadow rays not included.
+ * The frame's options hold: camera, max_depth, t_min, sky, nee, rr, light, floor.  In RT_FP_PARITY out[k] is bit-identical to the pixel runRenderer(f + c)
+ * stores at (i, j), for any split of f + c into calls; in RT_FP_FAST the FAST objects' arithmetic runs: the same estimate with no bit promise, as for
+ * runRenderer itself.  The result does not depend on stripe_rows, part_rank / part_world or the device list: all pixels run on the first in-process device,
+ * as the ray queries do, RT_PIXEL_CHUNK pixels at a time - upload, kernel, download -; the device buffers (48 bytes per pixel of the largest chunk seen,
+ * only for the arrays that were passed) are freed where the ray buffers are.  The call is blocking and follows setCamera, setRenderOptions and the scene
+ * edits.  It changes nothing an existing call observes: the framebuffer, getRenderStats, rtLastLaunches, rtLastSphereForm, the progressive frame and
+ * rtProgressiveSamples, the cost map of sphere frames, every history and every other rtLast*Ms stay as they were.  n == 0 returns at once: nothing is
+ * written and rtLastPixelsMs stays as it was.  Misuse (rt error, exit 99), checked on the host before anything is uploaded: before init (rtLastPixelsMs as
+ * well), n < 0, ij NULL, out, state and rays all NULL, a pixel outside [0, nx) x [0, ny), c < 1 or f < 0, f + c > RT_PROGRESSIVE_MAX_SAMPLES, first given
+ * without state, a resumed pixel (f > 0) whose stream word is 0 (no stream ever holds it: the xorshift would stand still), RT_RNG_COUNTER or variant != 0
+ * (as runRendererProgressive refuses them), rt_render_options.floor = 1 or nee = 1 on a sphere scene (as runRenderer refuses them). */
+#define RT_PIXEL_CHUNK (1 << 22)
+void   renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, const int32_t* first,
+                    uint32_t* state, rt_vec3* out, uint32_t* rays);
+double rtLastPixelsMs(void);   /* HIP-event time of the pixel kernels of the last renderPixels, summed over its chunks; 0 before the first */
+
 /* --- editing the scene: move, recolour, animate without a new init ---------------------------------------------------------------
  * The calls below change the scene the renderer holds, in place, on every in-process device: a picked object (traceRays) is moved or recoloured, an
  * animation is played, without cleanupRenderer + init*.  The contract they share: after ANY sequence of them everything the library computes - runRenderer
