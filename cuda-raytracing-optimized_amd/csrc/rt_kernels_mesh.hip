@@ -122,6 +122,159 @@ __device__ __forceinline__ float hit_mesh(const RtMeshParams& P, const Ray& r, f
     return hit_bvh(P, r, t_min, t_max, is_shadow, triId, hu, hv, st);
 }
 
+// ---- one shading step for the kernels that nest their traversals (tile, pixel list) and the first-hit kernels (guides, rays) ------------
+// The default kernel's PROCESS phase below is this code regrouped around its ray jobs; what it shares is named there.
+
+// Nearest-texel albedo, kernels.cu:452-480: the barycentric texture coordinates of (hu, hv) on a triangle whose six are `tc`, wrapped into [0, 1).
+__device__ __forceinline__ f3 mesh_texel(const RtMeshParams& P, int texId, const float* tc, float hu, float hv) {
+    const float w0 = 1 - hu - hv;
+    const float tcu = (hu * tc[2] + hv * tc[4] + w0 * tc[0]);
+    const float tcv = (hu * tc[3] + hv * tc[5] + w0 * tc[1]);
+    const int width = P.tex_width[texId];
+    const int height = P.tex_height[texId];
+    float tu = tcu; tu = tu - floorf(tu);
+    float tv = tcv; tv = tv - floorf(tv);
+    const int tx = (int)((float)(width - 1) * tu);
+    const int ty = (int)((float)(height - 1) * tv);
+    const int tIdx = ty * width + tx;
+    const float* d = P.tex_data[texId];
+    return F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
+}
+
+// What a ray met, the tail of hit() (kernels.cu:331-360) after hitMesh returned t for (t_min, t_max) - a hit iff t < t_max: the triangle (re-loaded,
+// kernels.cu:334) with its geometric normal; else the floor plane (FLOOR and rt_render_options.floor; kernels.cu:341-345) against the same t_max.  The
+// normal faces the ray (kernels.cu:354-355).  prim: the triangle's index in mesh.tris, RT_GUIDE_PRIM_FLOOR or RT_GUIDE_PRIM_NONE (rt_api.h).
+struct MeshGeom {
+    int prim;
+    float t;                    // FLT_MAX unless a triangle or the floor is hit
+    f3 normal;                  // (0, 0, 0) likewise
+    Tri tri;                    // the triangle hit (prim >= 0 only)
+};
+template <bool FLOOR>
+__device__ __forceinline__ MeshGeom mesh_geometry(const RtMeshParams& P, const Ray& r, float t_min, float t_max, float t, uint32_t triId) {
+    MeshGeom g;
+    g.t = t;
+    g.normal = F3(0, 0, 0);
+    g.prim = RT_GUIDE_PRIM_NONE;
+    if (g.t < t_max) {
+        g.tri = load_tri(P.tris, triId);
+        g.normal = unit(cross(g.tri.v1 - g.tri.v0, g.tri.v2 - g.tri.v0));
+        g.prim = (int)triId;
+    } else {
+        g.t = FLT_MAX;
+        if (FLOOR && P.floor_on) g.t = plane_hit(ld3(P.floor.norm), ld3(P.floor.point), r, t_min, t_max);
+        if (g.t < FLT_MAX) {
+            g.normal = ld3(P.floor.norm);
+            g.prim = RT_GUIDE_PRIM_FLOOR;
+        }
+    }
+    if (g.prim != RT_GUIDE_PRIM_NONE && dot(r.d, g.normal) > 0.0f) g.normal = -g.normal;
+    return g;
+}
+
+// ... for a path: a specular one that met nothing may see the light sphere (kernels.cu:346); and what the surface is made of (kernels.cu:452-482): the
+// triangle's material with its texture applied, floor_diffuse_scatter (scene_materials.h:30-33) for the plane.  FLOOR = false (the tile kernel: the host
+// refuses the floor with variant 1) compiles no plane test.
+constexpr int kMeshPrimLight = -3;      // beside RT_GUIDE_PRIM_NONE, RT_GUIDE_PRIM_FLOOR and a triangle's index (>= 0)
+struct MeshSurface {
+    int prim;                   // as MeshGeom's, or kMeshPrimLight
+    float t_hit;
+    f3 normal, albedo;
+    int mtype;
+    float mparam;
+};
+template <bool FLOOR>
+__device__ __forceinline__ MeshSurface mesh_surface(const RtMeshParams& P, const Ray& r, float t, uint32_t triId, float hu, float hv, bool specular) {
+    const MeshGeom g = mesh_geometry<FLOOR>(P, r, P.t_min, FLT_MAX, t, triId);
+    MeshSurface sf;
+    sf.prim = g.prim; sf.t_hit = g.t; sf.normal = g.normal;
+    if (g.prim == RT_GUIDE_PRIM_NONE && specular && sphere_hit(ld3(P.light.center), P.light.radius, r, P.t_min, FLT_MAX) < FLT_MAX) sf.prim = kMeshPrimLight;     // kernels.cu:346
+    sf.albedo = F3(0, 0, 0); sf.mtype = RT_FLOOR_DIFFUSE; sf.mparam = 0.0f;
+    if (g.prim >= 0) {
+        const rt_material mat = P.materials[g.tri.meshID];
+        sf.mtype = mat.type; sf.mparam = mat.param;
+        if (mat.texId != -1) sf.albedo = mesh_texel(P, mat.texId, g.tri.tc, hu, hv);
+        else sf.albedo = ld3(mat.color);
+    }
+    return sf;
+}
+
+// Per-lane path state of the kernels that nest their traversals (path, helper_structs.h:48-71).
+struct MeshLane {
+    uint32_t rng;
+    f3 col;                     // pixel accumulator (kernels.cu:547)
+    f3 org, dir, atten, pcolor;
+    int bounce;
+    bool inside, specular;
+    int s;                      // sample index within the pixel
+    int i, j;                   // global pixel coordinates
+};
+
+// kernels.cu:549-555 + the head of color() :397-398: starts sample L.s of the lane's pixel.  COUNTER = false: the caller knows the stream is the
+// reference's (renderPixels refuses RT_RNG_COUNTER).
+template <bool COUNTER>
+__device__ __forceinline__ void start_sample(const RtMeshParams& P, MeshLane& L) {
+    if (COUNTER && P.rng_mode == RT_RNG_COUNTER) L.rng = sample_seed((uint32_t)(L.j * P.nx + L.i), (uint32_t)L.s);
+    const float u = ((float)L.i + rnd(L.rng)) / (float)P.nx;
+    const float v = ((float)L.j + rnd(L.rng)) / (float)P.ny;
+    f3 d;
+    get_ray(P.cam, u, v, L.rng, L.org, d);
+    L.dir = unit(d);
+    L.atten = F3(1.0f, 1.0f, 1.0f);
+    L.pcolor = F3(0, 0, 0);
+    L.bounce = 0;
+    L.inside = false;
+    L.specular = false;
+}
+
+// One iteration of the loop of color(), kernels.cu:402-531, for the lane's path: closest hit, what was met, sky or light, else scatter, next-event
+// estimation with its shadow traversal nested, Russian roulette, the depth bound.  True = the sample's path has ended (L.pcolor is its colour).
+template <bool FLOOR>
+__device__ __forceinline__ bool mesh_bounce_step(const RtMeshParams& P, MeshLane& L, TravStats& st, uint32_t& nrays, uint32_t& nshadow) {
+    const float eps = P.t_min;
+    // ---- hit(context, p, FLT_MAX, false, inters), kernels.cu:325-360
+    const Ray r = make_ray(L.org, L.dir);
+    uint32_t triId = 0;
+    float hu = 0.0f, hv = 0.0f;
+    nrays++;
+    const float t = hit_mesh(P, r, eps, FLT_MAX, false, triId, hu, hv, st);
+    const MeshSurface sf = mesh_surface<FLOOR>(P, r, t, triId, hu, hv, L.specular);
+    if (sf.prim == RT_GUIDE_PRIM_NONE) {
+        L.pcolor = L.pcolor + L.atten * sky_color(P.sky, L.dir);     // kernels.cu:419-425
+        return true;
+    }
+    if (sf.prim == kMeshPrimLight) {
+        if (!P.nee) L.pcolor = L.pcolor + L.atten * ld3(P.lightColor);       // kernels.cu:440-446
+        return true;
+    }
+    Scatter sc;
+    material_scatter(sc, sf.t_hit, r.o + sf.t_hit * r.d, sf.normal, L.inside, L.dir, sf.mtype, sf.albedo, sf.mparam, L.rng);
+    L.org = L.org + sc.t * L.dir;                                    // kernels.cu:485-489
+    L.dir = sc.wi;
+    L.atten = L.atten * sc.throughput;
+    L.specular = sc.specular;
+    L.inside = sc.refracted ? !L.inside : L.inside;
+
+    if (P.nee && !L.specular) {                                      // generateShadowRay, kernels.cu:363-393 (rt_device.h)
+        ShadowSample sh;
+        if (generate_shadow_ray(ld3(P.light.center), P.light.radius, ld3(P.lightColor), L.org, L.atten, sf.normal, L.rng, sh)) {
+            const Ray sr = make_ray(L.org, sh.dir);
+            uint32_t tid2 = 0; float u2, v2;
+            nshadow++;
+            const float ts = hit_mesh(P, sr, eps, sh.dist, true, tid2, u2, v2, st);
+            if (!(ts < sh.dist)) L.pcolor = L.pcolor + sh.contrib;   // kernels.cu:504-510
+        }
+    }
+    if (P.rr && L.bounce > 3) {                                      // kernels.cu:512-527
+        const float mx = max3(L.atten);
+        if (rnd(L.rng) > mx) return true;
+        const float kk = 1.0f / mx;
+        L.atten = F3(L.atten.x * kk, L.atten.y * kk, L.atten.z * kk);
+    }
+    L.bounce++;
+    return L.bounce >= P.max_depth;                                  // loop bound, kernels.cu:402,529-531
+}
+
 template <int VARIANT>
 __global__ void __launch_bounds__(kThreads) k_render_mesh(const RtMeshParams P) {
     __shared__ float s_fb[kThreads * 3];
@@ -130,119 +283,30 @@ __global__ void __launch_bounds__(kThreads) k_render_mesh(const RtMeshParams P) 
     const int wave = threadIdx.x >> 6;
     const int i0 = (blockIdx.x * kWavesPerWg + wave) * 8;
     const int lr0 = blockIdx.y * 8;
-    const int i = i0 + (lane & 7);
     const int lr = lr0 + (lane >> 3);
-    const bool valid = (i < P.nx) && (lr < P.part.local_rows);
-    const int j = global_row(P.part, lr);
-    const uint32_t pixelId = (uint32_t)(j * P.nx + i);
 
-    const float eps = P.t_min;
-    const f3 lightC = ld3(P.light.center);
-    const float lightR = P.light.radius;
-
-    uint32_t rng = pixel_seed(pixelId);
-    f3 col = F3(0, 0, 0);
-    f3 org = F3(0, 0, 0), dir = F3(0, 0, 1), atten = F3(1, 1, 1), pcolor = F3(0, 0, 0);
-    int bounce = 0;
-    bool inside = false, specular = false;
-    int s = 0;
+    MeshLane L;
+    L.i = i0 + (lane & 7);
+    L.j = global_row(P.part, lr);
+    L.rng = pixel_seed((uint32_t)(L.j * P.nx + L.i));
+    L.col = F3(0, 0, 0);
+    L.s = 0;
     TravStats st = { 0, 0 };
     uint32_t nrays = 0, nshadow = 0;
 
-    auto start_sample = [&]() {                                      // kernels.cu:549-555, 397-398
-        if (P.rng_mode == RT_RNG_COUNTER) rng = sample_seed(pixelId, (uint32_t)s);
-        const float u = ((float)i + rnd(rng)) / (float)P.nx;
-        const float v = ((float)j + rnd(rng)) / (float)P.ny;
-        f3 d;
-        get_ray(P.cam, u, v, rng, org, d);
-        dir = unit(d);
-        atten = F3(1.0f, 1.0f, 1.0f);
-        pcolor = F3(0, 0, 0);
-        bounce = 0;
-        inside = false;
-        specular = false;
-    };
-
-    bool active = valid && (P.ns > 0);
-    if (active) start_sample();
+    bool active = (L.i < P.nx) && (lr < P.part.local_rows) && (P.ns > 0);
+    if (active) start_sample<true>(P, L);
 
     while (active) {
-        // ---- hit(context, p, FLT_MAX, false, inters), kernels.cu:325-360
-        const Ray r = make_ray(org, dir);
-        uint32_t triId = 0;
-        float hu = 0.0f, hv = 0.0f;
-        nrays++;
-        const float t = hit_mesh(P, r, eps, FLT_MAX, false, triId, hu, hv, st);
-        bool path_done = false;
-        if (t < FLT_MAX) {
-            const Tri tri = load_tri(P.tris, triId);                 // kernels.cu:334
-            f3 normal = unit(cross(tri.v1 - tri.v0, tri.v2 - tri.v0));
-            const float w0 = 1 - hu - hv;
-            const float tcu = (hu * tri.tc[2] + hv * tri.tc[4] + w0 * tri.tc[0]);
-            const float tcv = (hu * tri.tc[3] + hv * tri.tc[5] + w0 * tri.tc[1]);
-            if (dot(r.d, normal) > 0.0f) normal = -normal;           // kernels.cu:354-355
-
-            const rt_material mat = P.materials[tri.meshID];         // kernels.cu:452-480
-            f3 albedo;
-            if (mat.texId != -1) {
-                const int width = P.tex_width[mat.texId];
-                const int height = P.tex_height[mat.texId];
-                float tu = tcu; tu = tu - floorf(tu);
-                float tv = tcv; tv = tv - floorf(tv);
-                const int tx = (int)((float)(width - 1) * tu);
-                const int ty = (int)((float)(height - 1) * tv);
-                const int tIdx = ty * width + tx;
-                const float* d = P.tex_data[mat.texId];
-                albedo = F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
-            } else {
-                albedo = ld3(mat.color);
-            }
-            Scatter sc;
-            material_scatter(sc, t, r.o + t * r.d, normal, inside, dir, mat.type, albedo, mat.param, rng);
-            org = org + sc.t * dir;                                  // kernels.cu:485-489
-            dir = sc.wi;
-            atten = atten * sc.throughput;
-            specular = sc.specular;
-            inside = sc.refracted ? !inside : inside;
-
-            if (P.nee && !specular) {                                // generateShadowRay, kernels.cu:363-393 (rt_device.h)
-                ShadowSample sh;
-                if (generate_shadow_ray(lightC, lightR, ld3(P.lightColor), org, atten, normal, rng, sh)) {
-                    const Ray sr = make_ray(org, sh.dir);
-                    uint32_t tid2 = 0; float u2, v2;
-                    nshadow++;
-                    const float ts = hit_mesh(P, sr, eps, sh.dist, true, tid2, u2, v2, st);
-                    if (!(ts < sh.dist)) pcolor = pcolor + sh.contrib;       // kernels.cu:504-510
-                }
-            }
-            if (P.rr && bounce > 3) {                                // kernels.cu:512-527
-                const float mx = max3(atten);
-                if (rnd(rng) > mx) {
-                    path_done = true;
-                } else {
-                    const float kk = 1.0f / mx;
-                    atten = F3(atten.x * kk, atten.y * kk, atten.z * kk);
-                }
-            }
-            bounce++;
-            if (bounce >= P.max_depth) path_done = true;
-        } else if (specular && sphere_hit(lightC, lightR, r, eps, FLT_MAX) < FLT_MAX) {   // kernels.cu:346
-            if (!P.nee) pcolor = pcolor + atten * ld3(P.lightColor);                      // kernels.cu:440-446
-            path_done = true;
-        } else {
-            pcolor = pcolor + atten * sky_color(P.sky, dir);         // kernels.cu:419-425
-            path_done = true;
-        }
-
-        if (path_done) {
-            col = col + pcolor;
-            s++;
-            if (s < P.ns) start_sample();
+        if (mesh_bounce_step<false>(P, L, st, nrays, nshadow)) {
+            L.col = L.col + L.pcolor;
+            L.s++;
+            if (L.s < P.ns) start_sample<true>(P, L);
             else active = false;
         }
     }
 
-    const f3 out = col / (float)P.ns;                                // kernels.cu:568
+    const f3 out = L.col / (float)P.ns;                              // kernels.cu:568
     float* my = s_fb + threadIdx.x * 3;
     my[0] = out.x; my[1] = out.y; my[2] = out.z;
     __syncthreads();
@@ -268,43 +332,25 @@ __global__ void __launch_bounds__(kThreads) k_render_mesh(const RtMeshParams P) 
 // ---- a list of pixels (renderPixels, rt_api.h) -----------------------------------------------------------------------------
 // One lane = one entry of the caller's list in 256-thread workgroups of persistent waves: a lane whose pixel is finished takes the next unassigned entry -
 // per refill round a wave takes ONE atomicAdd of the number of its idle lanes on B.queue and the lanes take their positions by mbcnt (the entries' costs
-// differ by more than an order of magnitude).  One iteration of the wave-uniform loop is one iteration of the bounce loop of k_render_mesh above for every
-// lane that holds an entry - closest hit, textures, next-event estimation with its shadow traversal, Russian roulette, the light - with the floor plane of
-// rt_render_options.floor where the default kernel tests it (a ray that misses the mesh; kernels.cu:341-345).  Not the default kernel's ray-job state
+// differ by more than an order of magnitude).  One iteration of the wave-uniform loop is one mesh_bounce_step - the step of k_render_mesh above - for every
+// lane that holds an entry, with the floor plane of rt_render_options.floor where the default kernel tests it (a ray that misses the mesh;
+// kernels.cu:341-345); what is this kernel's own is the refill, the resume from B.state and the three result stores.  Not the default kernel's ray-job state
 // machine: the lanes of a wave wait for its slowest traversal.  An entry that continues a stream (first > 0) loads (colour sum, xorshift word) from
 // B.state instead of the pixel's seed; a finished entry stores state / out / rays from the lane that owns it.  No spin: the loop ends when the queue is
 // empty and the wave's lanes are done.
 constexpr int kPixelThreads = 256;
 __global__ void __launch_bounds__(kPixelThreads) k_pixels_mesh(const RtMeshParams P, const RtPixelBatch B) {
     const uint32_t n = (uint32_t)B.n;
-    const float eps = P.t_min;
-    const f3 lightC = ld3(P.light.center);
-    const float lightR = P.light.radius;
 
-    int pi = 0, pj = 0;
-    uint32_t rng = 0u;
-    f3 col = F3(0, 0, 0);
-    f3 org = F3(0, 0, 0), dir = F3(0, 0, 1), atten = F3(1, 1, 1), pcolor = F3(0, 0, 0);
-    int bounce = 0;
-    bool inside = false, specular = false;
-    int s = 0, s_end = 0;               // the lane's entry ends with sample s_end - 1
+    MeshLane L;
+    L.rng = 0u; L.i = 0; L.j = 0; L.s = 0; L.bounce = 0;
+    L.inside = false; L.specular = false;
+    L.col = F3(0, 0, 0); L.org = F3(0, 0, 0); L.dir = F3(0, 0, 1); L.atten = F3(1, 1, 1); L.pcolor = F3(0, 0, 0);
+    int s_end = 0;                      // the lane's entry ends with sample s_end - 1
     TravStats st = { 0, 0 };
-    uint32_t entry = 0, pix_rays = 0;
+    uint32_t entry = 0, pix_rays = 0, nshadow = 0;
     bool active = false;                // the lane owns an unfinished entry
     bool exhausted = false;             // wave-uniform: the queue is empty
-
-    auto start_sample = [&]() {                                      // kernels.cu:549-555, 397-398 (the reference stream: renderPixels refuses RT_RNG_COUNTER)
-        const float u = ((float)pi + rnd(rng)) / (float)P.nx;
-        const float v = ((float)pj + rnd(rng)) / (float)P.ny;
-        f3 d;
-        get_ray(P.cam, u, v, rng, org, d);
-        dir = unit(d);
-        atten = F3(1.0f, 1.0f, 1.0f);
-        pcolor = F3(0, 0, 0);
-        bounce = 0;
-        inside = false;
-        specular = false;
-    };
 
     while (true) {
         const unsigned long long idle = __ballot(!active);
@@ -317,116 +363,33 @@ __global__ void __launch_bounds__(kPixelThreads) k_pixels_mesh(const RtMeshParam
             const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
             if (!active && k < n) {
                 entry = k;
-                pi = B.ij[2 * (size_t)k]; pj = B.ij[2 * (size_t)k + 1];
-                s = B.first ? B.first[k] : 0;
-                s_end = s + (B.ns ? B.ns[k] : B.ns_all);
-                if (s > 0) {                                         // the stream continues where an earlier call stopped
+                L.i = B.ij[2 * (size_t)k]; L.j = B.ij[2 * (size_t)k + 1];
+                L.s = B.first ? B.first[k] : 0;
+                s_end = L.s + (B.ns ? B.ns[k] : B.ns_all);
+                if (L.s > 0) {                                       // the stream continues where an earlier call stopped
                     const uint4 st4 = reinterpret_cast<const uint4*>(B.state)[k];
-                    col = F3(__uint_as_float(st4.x), __uint_as_float(st4.y), __uint_as_float(st4.z));
-                    rng = st4.w;
+                    L.col = F3(__uint_as_float(st4.x), __uint_as_float(st4.y), __uint_as_float(st4.z));
+                    L.rng = st4.w;
                 } else {
-                    col = F3(0, 0, 0);
-                    rng = pixel_seed((uint32_t)(pj * P.nx + pi));    // kernels.cu:541 (global id -> seed)
+                    L.col = F3(0, 0, 0);
+                    L.rng = pixel_seed((uint32_t)(L.j * P.nx + L.i));        // kernels.cu:541 (global id -> seed)
                 }
-                start_sample();
+                start_sample<false>(P, L);
                 pix_rays = 0;
                 active = true;
             }
         }
         if (__ballot(active) == 0ull) break;
         if (active) {
-            bool path_done = false;
-            if (P.max_depth <= 0) {                                  // the loop of kernels.cu:402 never runs: no ray, a black sample
-                path_done = true;
-            } else {
-                // ---- hit(context, p, FLT_MAX, false, inters), kernels.cu:325-360
-                const Ray r = make_ray(org, dir);
-                uint32_t triId = 0;
-                float hu = 0.0f, hv = 0.0f;
-                pix_rays++;
-                const float t = hit_mesh(P, r, eps, FLT_MAX, false, triId, hu, hv, st);
-                int obj = 0;                                         // 0 none, 1 triangle mesh, 2 floor, 3 light
-                float t_hit = t;
-                f3 normal = F3(0, 1, 0);
-                f3 albedo = F3(0, 0, 0);
-                int mtype = RT_FLOOR_DIFFUSE;                        // floor_diffuse_scatter, scene_materials.h:30-33 (kernels.cu:481-482)
-                float mparam = 0.0f;
-                if (t < FLT_MAX) {
-                    obj = 1;
-                    const Tri tri = load_tri(P.tris, triId);         // kernels.cu:334
-                    normal = unit(cross(tri.v1 - tri.v0, tri.v2 - tri.v0));
-                    const float w0 = 1 - hu - hv;
-                    const float tcu = (hu * tri.tc[2] + hv * tri.tc[4] + w0 * tri.tc[0]);
-                    const float tcv = (hu * tri.tc[3] + hv * tri.tc[5] + w0 * tri.tc[1]);
-                    const rt_material mat = P.materials[tri.meshID]; // kernels.cu:452-480
-                    mtype = mat.type; mparam = mat.param;
-                    if (mat.texId != -1) {
-                        const int width = P.tex_width[mat.texId];
-                        const int height = P.tex_height[mat.texId];
-                        float tu = tcu; tu = tu - floorf(tu);
-                        float tv = tcv; tv = tv - floorf(tv);
-                        const int tx = (int)((float)(width - 1) * tu);
-                        const int ty = (int)((float)(height - 1) * tv);
-                        const int tIdx = ty * width + tx;
-                        const float* d = P.tex_data[mat.texId];
-                        albedo = F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
-                    } else {
-                        albedo = ld3(mat.color);
-                    }
+            // (max_depth <= 0: the loop of kernels.cu:402 never runs: no ray, a black sample)
+            if (P.max_depth <= 0 || mesh_bounce_step<true>(P, L, st, pix_rays, nshadow)) {
+                L.col = L.col + L.pcolor;                            // kernels.cu:558
+                L.s++;
+                if (L.s < s_end) {
+                    start_sample<false>(P, L);
                 } else {
-                    float tp = FLT_MAX;
-                    if (P.floor_on) tp = plane_hit(ld3(P.floor.norm), ld3(P.floor.point), r, eps, FLT_MAX);      // kernels.cu:341-345, re-enabled by rt_render_options.floor
-                    if (tp < FLT_MAX) {
-                        obj = 2; t_hit = tp; normal = ld3(P.floor.norm);
-                    } else if (specular && sphere_hit(lightC, lightR, r, eps, FLT_MAX) < FLT_MAX) {               // kernels.cu:346
-                        obj = 3;
-                    }
-                }
-                if (obj == 0) {
-                    pcolor = pcolor + atten * sky_color(P.sky, dir); // kernels.cu:419-425
-                    path_done = true;
-                } else if (obj == 3) {
-                    if (!P.nee) pcolor = pcolor + atten * ld3(P.lightColor);                                      // kernels.cu:440-446
-                    path_done = true;
-                } else {
-                    if (dot(r.d, normal) > 0.0f) normal = -normal;   // kernels.cu:354-355
-                    Scatter sc;
-                    material_scatter(sc, t_hit, r.o + t_hit * r.d, normal, inside, dir, mtype, albedo, mparam, rng);
-                    org = org + sc.t * dir;                          // kernels.cu:485-489
-                    dir = sc.wi;
-                    atten = atten * sc.throughput;
-                    specular = sc.specular;
-                    inside = sc.refracted ? !inside : inside;
-
-                    if (P.nee && !specular) {                        // generateShadowRay, kernels.cu:363-393 (rt_device.h)
-                        ShadowSample sh;
-                        if (generate_shadow_ray(lightC, lightR, ld3(P.lightColor), org, atten, normal, rng, sh)) {
-                            const Ray sr = make_ray(org, sh.dir);
-                            uint32_t tid2 = 0; float u2, v2;
-                            const float ts = hit_mesh(P, sr, eps, sh.dist, true, tid2, u2, v2, st);
-                            if (!(ts < sh.dist)) pcolor = pcolor + sh.contrib;       // kernels.cu:504-510
-                        }
-                    }
-                    if (P.rr && bounce > 3) {                        // kernels.cu:512-527
-                        const float mx = max3(atten);
-                        if (rnd(rng) > mx) {
-                            path_done = true;
-                        } else {
-                            const float kk = 1.0f / mx;
-                            atten = F3(atten.x * kk, atten.y * kk, atten.z * kk);
-                        }
-                    }
-                    bounce++;
-                    if (bounce >= P.max_depth) path_done = true;
-                }
-            }
-            if (path_done) {
-                col = col + pcolor;                                  // kernels.cu:558
-                s++;
-                if (s < s_end) {
-                    start_sample();
-                } else {
-                    if (B.state) reinterpret_cast<uint4*>(B.state)[entry] = make_uint4(__float_as_uint(col.x), __float_as_uint(col.y), __float_as_uint(col.z), rng);
+                    const f3 col = L.col;
+                    if (B.state) reinterpret_cast<uint4*>(B.state)[entry] = make_uint4(__float_as_uint(col.x), __float_as_uint(col.y), __float_as_uint(col.z), L.rng);
                     if (B.out) {
                         const f3 out = col / (float)s_end;           // kernels.cu:568
                         *reinterpret_cast<float3*>(reinterpret_cast<float*>(B.out) + (size_t)entry * 3) = make_float3(out.x, out.y, out.z);
@@ -460,23 +423,13 @@ __device__ __forceinline__ FirstHitMesh first_hit_mesh(const RtMeshParams& P, co
     FirstHitMesh h;
     h.st = { 0, 0 };
     h.hu = 0.0f; h.hv = 0.0f;
-    h.normal = F3(0, 0, 0);
-    h.prim = RT_GUIDE_PRIM_NONE;
     uint32_t triId = 0;
-    h.t = hit_mesh(P, r, t_min, t_max, false, triId, h.hu, h.hv, h.st);
-    if (h.t < t_max) {
-        h.tri = load_tri(P.tris, triId);                             // kernels.cu:334
-        h.normal = unit(cross(h.tri.v1 - h.tri.v0, h.tri.v2 - h.tri.v0));
-        h.prim = (int)triId;
-    } else {
-        h.t = FLT_MAX;
-        if (P.floor_on) h.t = plane_hit(ld3(P.floor.norm), ld3(P.floor.point), r, t_min, t_max);       // kernels.cu:341-345
-        if (h.t < FLT_MAX) {
-            h.normal = ld3(P.floor.norm);
-            h.prim = RT_GUIDE_PRIM_FLOOR;
-        }
-    }
-    if (h.prim != RT_GUIDE_PRIM_NONE && dot(r.d, h.normal) > 0.0f) h.normal = -h.normal;     // kernels.cu:354-355
+    const float t = hit_mesh(P, r, t_min, t_max, false, triId, h.hu, h.hv, h.st);
+    const MeshGeom g = mesh_geometry<true>(P, r, t_min, t_max, t, triId);
+    h.t = g.t;
+    h.prim = g.prim;
+    h.normal = g.normal;
+    h.tri = g.tri;
     return h;
 }
 
@@ -494,25 +447,10 @@ __global__ void __launch_bounds__(kThreads) k_guides_mesh(const RtMeshParams P, 
     const FirstHitMesh h = first_hit_mesh(P, r, P.t_min, FLT_MAX);
     f3 albedo;
     if (h.prim >= 0) {
-        const Tri& tri = h.tri;
-        const float hu = h.hu, hv = h.hv;
-        const rt_material mat = P.materials[tri.meshID];             // kernels.cu:452-480
+        const rt_material mat = P.materials[h.tri.meshID];           // kernels.cu:452-480
         const bool basic = mat.type == RT_DIFFUSE || mat.type == RT_METAL || mat.type == RT_GLASS;
         f3 color = ld3(mat.color);
-        if (basic && mat.texId != -1) {
-            const float w0 = 1 - hu - hv;
-            const float tcu = (hu * tri.tc[2] + hv * tri.tc[4] + w0 * tri.tc[0]);
-            const float tcv = (hu * tri.tc[3] + hv * tri.tc[5] + w0 * tri.tc[1]);
-            const int width = P.tex_width[mat.texId];
-            const int height = P.tex_height[mat.texId];
-            float tu = tcu; tu = tu - floorf(tu);
-            float tv = tcv; tv = tv - floorf(tv);
-            const int tx = (int)((float)(width - 1) * tu);
-            const int ty = (int)((float)(height - 1) * tv);
-            const int tIdx = ty * width + tx;
-            const float* d = P.tex_data[mat.texId];
-            color = F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
-        }
+        if (basic && mat.texId != -1) color = mesh_texel(P, mat.texId, h.tri.tc, h.hu, h.hv);
         albedo = guide_albedo(mat.type, color, r.o + h.t * r.d);
     } else if (h.prim == RT_GUIDE_PRIM_FLOOR) {
         albedo = guide_albedo(RT_FLOOR_DIFFUSE, F3(0, 0, 0), F3(0, 0, 0));          // kernels.cu:481-482
@@ -793,6 +731,9 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
 
     while (true) {
         // ================= PROCESS: lanes without a running traversal =======================================
+        // mesh_bounce_step (above) regrouped around the ray jobs; of its pieces mesh_texel is shared.
+        // kept inline: what the ray met (here from the compact leaf record the leaf test read, without texture and plane when LEAN), extraction changes the code object
+        // kept inline: Russian roulette, extraction changes the code object
         unsigned long long c0 = dbg ? __builtin_amdgcn_s_memtime() : 0ull;
         if (dbg) { const int n_ = (int)__popcll(__ballot(have_pixel && J.idx == 0)); g_act[0] += (unsigned long long)n_; g_it[0] += n_ ? 1ull : 0ull; }
         if (have_pixel && J.idx == 0) {
@@ -830,19 +771,7 @@ __global__ void __launch_bounds__(kThreads, LEAN ? RT_MESH_LEAN_WAVES : (TRAV ==
                     const rt_material mat = P.materials[mesh_id];    // kernels.cu:452-480
                     mtype = mat.type; mparam = mat.param;
                     if (!LEAN && mat.texId != -1) {
-                        const float* tc = P.tris[J.triId].texCoords;
-                        const float w0 = 1 - J.hu - J.hv;
-                        const float tcu = (J.hu * tc[2] + J.hv * tc[4] + w0 * tc[0]);
-                        const float tcv = (J.hu * tc[3] + J.hv * tc[5] + w0 * tc[1]);
-                        const int width = P.tex_width[mat.texId];
-                        const int height = P.tex_height[mat.texId];
-                        float tu = tcu; tu = tu - floorf(tu);
-                        float tv = tcv; tv = tv - floorf(tv);
-                        const int tx = (int)((float)(width - 1) * tu);
-                        const int ty = (int)((float)(height - 1) * tv);
-                        const int tIdx = ty * width + tx;
-                        const float* d = P.tex_data[mat.texId];
-                        albedo = F3(d[tIdx * 3 + 0], d[tIdx * 3 + 1], d[tIdx * 3 + 2]);
+                        albedo = mesh_texel(P, mat.texId, P.tris[J.triId].texCoords, J.hu, J.hv);
                     } else {
                         albedo = ld3(mat.color);
                     }

@@ -90,8 +90,9 @@ def test_mesh_variants_agree_bit_for_bit_with_nee(rt, stair):
         assert (sa.rays, sa.node_visits, sa.prim_tests) == (sb.rays, sb.node_visits, sb.prim_tests), variant
 
 
-def test_mesh_textures_bit_exact(rt, O, stair):
-    """Albedo textures: nearest texel with wrap (kernels.cu:456-476), NEE off so the comparison is exact."""
+@pytest.fixture(scope="module")
+def textured(rt, O, stair):
+    """The staircase with three textured materials, 72x90 at 2 spp and depth 12 with NEE off, and the oracle's frame of it (computed once)."""
     hm, mats = stair
     mats = mats.copy()
     rng = np.random.default_rng(3)
@@ -104,10 +105,17 @@ def test_mesh_textures_bit_exact(rt, O, stair):
     o = O.default_options(False)
     o.nee = 0
     ref, _ = O.render(O.mesh_scene(hm, mats, tex), cam, o, nx, ny, ns, 12)
+    return hm, mats, tex, cam, nx, ny, ns, ref
+
+
+@pytest.mark.parametrize("variant", [0, 1])     # 0 = persistent state machine, 1 = tile per wave: each has its own call of the texture lookup
+def test_mesh_textures_bit_exact(rt, textured, variant):
+    """Albedo textures: nearest texel with wrap (kernels.cu:456-476), NEE off so the comparison is exact."""
+    hm, mats, tex, cam, nx, ny, ns, ref = textured
     ks, keep = rt.make_kernel_scene(hm, mats, tex)
     fb = rt.initRenderer(ks, cam, nx, ny, 12, keepalive=keep)
     oo = rt.getDefaultRenderOptions(False)
-    rt.setRenderOptions(oo, nee=0)
+    rt.setRenderOptions(oo, nee=0, variant=variant)
     rt.runRenderer(ns, 8, 8)
     got = np.array(fb, copy=True)
     rt.cleanupRenderer()
