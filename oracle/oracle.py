@@ -8,6 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_LIB = os.path.join(_HERE, "liboracle.so")
+NUDGE_LIB = os.path.join(_HERE, "liboracle_nudge.so")       # rt_oracle.c with -DORC_LIBM_NUDGE (oracle/Makefile)
 REF_LIB = os.path.join(_HERE, "_ref", "libref.so")
 REF_MAIN_LIB = os.path.join(_HERE, "_ref", "libref_main.so")
 
@@ -72,6 +73,7 @@ def _bind_common(lib, pre):
 
 
 _oracle = None
+_nudge = None
 _ref = None
 
 
@@ -91,26 +93,41 @@ def _check_abi(lib, fn, path):
                           f"mirror's {mine}: library and oracle/oracle.py are of different generations - rebuild (make -C oracle)")
 
 
+def _load_orc(path):
+    rt = _pkg()
+    lib = C.CDLL(path)
+    _check_abi(lib, "orc_abi_sizes", path)
+    _bind_common(lib, "orc_")
+    lib.orc_render.argtypes = [C.POINTER(orc_scene), C.POINTER(rt.camera), C.POINTER(rt.render_options),
+                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.c_void_p, C.POINTER(orc_counters)]
+    lib.orc_render.restype = None
+    lib.orc_hit_bvh.argtypes = [C.POINTER(orc_scene), _fp, _fp, C.c_float, C.c_float, C.c_int, _u32p, _fp, _fp,
+                                C.POINTER(orc_counters)]
+    lib.orc_hit_bvh.restype = C.c_float
+    lib.orc_generate_shadow_ray.argtypes = [C.POINTER(rt.render_options), _fp, _fp, _fp, _u32p, _fp]
+    lib.orc_generate_shadow_ray.restype = C.c_int
+    lib.orc_rmse.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.orc_rmse.restype = C.c_double
+    return lib
+
+
 def load_oracle():
     global _oracle
     if _oracle is None:
-        rt = _pkg()
-        lib = C.CDLL(ORACLE_LIB)
-        _check_abi(lib, "orc_abi_sizes", ORACLE_LIB)
-        _bind_common(lib, "orc_")
-        lib.orc_render.argtypes = [C.POINTER(orc_scene), C.POINTER(rt.camera), C.POINTER(rt.render_options),
-                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_void_p, C.POINTER(orc_counters)]
-        lib.orc_render.restype = None
-        lib.orc_hit_bvh.argtypes = [C.POINTER(orc_scene), _fp, _fp, C.c_float, C.c_float, C.c_int, _u32p, _fp, _fp,
-                                    C.POINTER(orc_counters)]
-        lib.orc_hit_bvh.restype = C.c_float
-        lib.orc_generate_shadow_ray.argtypes = [C.POINTER(rt.render_options), _fp, _fp, _fp, _u32p, _fp]
-        lib.orc_generate_shadow_ray.restype = C.c_int
-        lib.orc_rmse.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        lib.orc_rmse.restype = C.c_double
-        _oracle = lib
+        _oracle = _load_orc(ORACLE_LIB)
     return _oracle
+
+
+def load_nudge():
+    """The oracle's twin whose preset libm is an ulp off (liboracle_nudge.so); built on first use where the library is not there."""
+    global _nudge
+    if _nudge is None:
+        if not os.path.exists(NUDGE_LIB):
+            import subprocess
+            subprocess.run(["make", "-C", _HERE, "liboracle_nudge.so"], check=True, stdout=subprocess.DEVNULL)
+        _nudge = _load_orc(NUDGE_LIB)
+    return _nudge
 
 
 def have_ref():
@@ -271,10 +288,10 @@ def mesh_scene(host_mesh, materials, textures=(), floor=None):
     return sc
 
 
-def render(scene, cam, opt, nx, ny, ns, max_depth, region=None, counters=False, fb=None):
-    """orc_render over the pixel rectangle region=(x0,y0,x1,y1) (default: whole image).
+def render(scene, cam, opt, nx, ny, ns, max_depth, region=None, counters=False, fb=None, lib=None):
+    """orc_render over the pixel rectangle region=(x0,y0,x1,y1) (default: whole image); lib: load_nudge() for the nudged twin.
     Returns (fb[ny,nx,3] float32, counters or None)."""
-    lib = load_oracle()
+    lib = lib or load_oracle()
     if fb is None:
         fb = np.zeros((ny, nx, 3), np.float32)
     x0, y0, x1, y1 = region if region else (0, 0, nx, ny)

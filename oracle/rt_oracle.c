@@ -37,6 +37,33 @@ static inline float len(v3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z);
 static inline v3 unit(v3 a) { return divs(a, len(a)); }                                    /* vec3.h:194-196 */
 static inline float max3(v3 a) { return fmaxf(a.x, fmaxf(a.y, a.z)); }                     /* vec3.h:113-115 */
 
+/* ---------------------------------------------------------------- the presets' libm ------- */
+
+/* The sinf / logf / expf of the three presets whose device arithmetic is NOT bit-exact (the checker's product of sines, the subsurface distance,
+ * the two exp(-absorption * t), the tinted glass's logf(model_base)) go through these names; nothing else does.  Plain build: the libm calls
+ * themselves.  -DORC_LIBM_NUDGE (liboracle_nudge.so): the result moved by -1, 0 or +1 ulp, chosen by a hash of the argument's bits, which is what
+ * another correct libm may return; an argument of +-0 and a zero or non-finite result stay as they are (exp(-0 * t) = 1 of the clear glasses). */
+#ifdef ORC_LIBM_NUDGE
+static float libm_nudge(float arg, float res) {
+    uint32_t a, r;
+    memcpy(&a, &arg, 4); memcpy(&r, &res, 4);
+    if ((a << 1) == 0 || (r << 1) == 0 || (r & 0x7F800000u) == 0x7F800000u) return res;
+    uint32_t h = a * 0x9E3779B1u;
+    h ^= h >> 15; h *= 0x85EBCA77u; h ^= h >> 13;
+    r += (uint32_t)((int)(h % 3u) - 1);            /* the neighbour in magnitude: bit patterns of one sign are ordered */
+    if ((r & 0x7F800000u) == 0x7F800000u) return res;
+    memcpy(&res, &r, 4);
+    return res;
+}
+static float preset_sinf(float x) { return libm_nudge(x, sinf(x)); }
+static float preset_logf(float x) { return libm_nudge(x, logf(x)); }
+static float preset_expf(float x) { return libm_nudge(x, expf(x)); }
+#else
+#define preset_sinf sinf
+#define preset_logf logf
+#define preset_expf expf
+#endif
+
 /* ---------------------------------------------------------------- rnd.h ------------------- */
 
 uint32_t orc_xor_shift_32(uint32_t* state) {    /* rnd.h:5-13 */
@@ -302,7 +329,7 @@ static void dielectric_bsdf(scat_t* out, const inters_t* i, v3 wo, float layer_i
                             v3 absorption, uint32_t* rng) {                              /* material.h:73-92 */
     if (i->inside) {
         v3 e = muls(i->t, neg(absorption));          /* -absorptionCoefficient * i.t */
-        out->throughput = V(expf(e.x), expf(e.y), expf(e.z));
+        out->throughput = V(preset_expf(e.x), preset_expf(e.y), preset_expf(e.z));
     }
     if (fresnel_layer(i, wo, layer_ior, rng)) {
         glossy_bsdf(out, i, wo, glossy_tint, glossy_fuzz, rng);
@@ -315,7 +342,7 @@ static void dielectric_bsdf(scat_t* out, const inters_t* i, v3 wo, float layer_i
 }
 
 static int checker_layer(const inters_t* i, float frequency) {     /* material.h:33-36 */
-    float sines = sinf(frequency * i->p.x) * sinf(frequency * i->p.y) * sinf(frequency * i->p.z);
+    float sines = preset_sinf(frequency * i->p.x) * preset_sinf(frequency * i->p.y) * preset_sinf(frequency * i->p.z);
     return sines < 0;
 }
 
@@ -329,10 +356,10 @@ static void subsurface_dielectric_bsdf(scat_t* out, const inters_t* i, v3 wo, fl
                                        v3 absorption, float scatteringDistance, uint32_t* rng) {    /* material.h:119-143 */
     int scattered = 0;
     if (i->inside) {
-        float d = -logf(rnd(rng)) / scatteringDistance;
+        float d = -preset_logf(rnd(rng)) / scatteringDistance;
         if (d < i->t) { scattered = 1; out->t = d; }
         v3 e = muls(out->t, neg(absorption));
-        out->throughput = V(expf(e.x), expf(e.y), expf(e.z));
+        out->throughput = V(preset_expf(e.x), preset_expf(e.y), preset_expf(e.z));
     }
     if (scattered) {
         out->wi = random_in_unit_sphere(rng);            /* not normalised in the reference (:128) */
@@ -372,7 +399,7 @@ static void preset_scatter(scat_t* out, const inters_t* i, v3 wo, int type, uint
     case RT_MODEL_GLASS:   dielectric_bsdf(out, i, wo, 1.1f, one, 0.0f, V(0, 0, 0), rng); break;
     case RT_MODEL_TINTEDGLASS: {
         const float absorptionDistance = 10;
-        const v3 absorption = divs(neg(V(logf(model_base.x), logf(model_base.y), logf(model_base.z))), absorptionDistance);
+        const v3 absorption = divs(neg(V(preset_logf(model_base.x), preset_logf(model_base.y), preset_logf(model_base.z))), absorptionDistance);
         dielectric_bsdf(out, i, wo, 1.1f, one, 0.0f, absorption, rng);
         break;
     }
