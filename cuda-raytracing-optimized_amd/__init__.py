@@ -138,6 +138,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs",
                     "traceRays", "occludedRays", "rtLastRaysMs",
                     "renderPixels", "rtLastPixelsMs",
+                    "refineFrame", "rtResetRefine", "rtRefineSamples", "rtRefineLastList", "rtLastRefineMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
                     "rtLastSphereForm"]
@@ -325,6 +326,16 @@ def load_renderer():
         r.renderPixels.restype = None
         r.rtLastPixelsMs.argtypes = []
         r.rtLastPixelsMs.restype = C.c_double
+        r.refineFrame.argtypes = [C.POINTER(vec3), ip, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]
+        r.refineFrame.restype = C.c_int
+        r.rtResetRefine.argtypes = []
+        r.rtResetRefine.restype = None
+        r.rtRefineSamples.argtypes = []
+        r.rtRefineSamples.restype = C.c_longlong
+        r.rtRefineLastList.argtypes = [ip, C.c_int]
+        r.rtRefineLastList.restype = C.c_int
+        r.rtLastRefineMs.argtypes = []
+        r.rtLastRefineMs.restype = C.c_double
         r.updateTriangles.argtypes = [C.c_int, C.c_int, C.c_void_p]
         r.updateTriangles.restype = None
         r.updateMaterials.argtypes = [C.c_void_p, C.c_int]
@@ -707,6 +718,62 @@ def render_region(x0, y0, x1, y1, ns):
 def last_pixels_ms():
     """HIP-event time of the pixel kernels of the last render_pixels / render_region (not the copies), summed over its chunks, in milliseconds."""
     return load_renderer().rtLastPixelsMs()
+
+
+# refineFrame (include/rt_api.h): adaptive sampling on the device over the pixel kernels
+RT_REFINE_DILATE = 1
+RT_REFINE_LUM_EPS = 1e-3
+REFINE_PLANES = ("out", "samples", "error")
+
+
+def refine_frame(batch, min_batches, max_samples, threshold, flags=0, want=REFINE_PLANES):
+    """One pass of the adaptive frame (refineFrame, include/rt_api.h): selects the pixels that are not converged under these parameters, traces `batch` more
+    samples for each and updates their statistics.  Returns (sampled, out, samples, error): the number of pixels sampled - 0 = the frame is finished under
+    these parameters - and the planes named in `want`, None for the others: out (ny, nx, 3) float32 = the mean, samples (ny, nx) int32, error (ny, nx)
+    float32; row 0 = bottom.  want=() downloads nothing.  Blocking."""
+    for name, v in (("batch", batch), ("min_batches", min_batches), ("max_samples", max_samples), ("flags", flags)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"refine_frame: {name} must be an int, got {v!r}")
+    if not isinstance(threshold, (int, float, np.floating, np.integer)) or isinstance(threshold, bool):
+        raise ValueError(f"refine_frame: threshold must be a number, got {threshold!r}")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in REFINE_PLANES]
+    if unknown:
+        raise ValueError(f"refine_frame: want names unknown planes {unknown}; the planes are {REFINE_PLANES}")
+    ny, nx = _state["ny"], _state["nx"]
+    out = np.zeros((ny, nx, 3), np.float32) if "out" in want else None
+    samples = np.zeros((ny, nx), np.int32) if "samples" in want else None
+    error = np.zeros((ny, nx), np.float32) if "error" in want else None
+    sampled = load_renderer().refineFrame(None if out is None else out.ctypes.data_as(C.POINTER(vec3)),
+                                          None if samples is None else samples.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          None if error is None else error.ctypes.data_as(C.POINTER(C.c_float)),
+                                          int(batch), int(min_batches), int(max_samples), float(threshold), int(flags))
+    return sampled, out, samples, error
+
+
+def reset_refine():
+    """The next refine_frame starts at sample 0 (rtResetRefine)."""
+    load_renderer().rtResetRefine()
+
+
+def refine_samples():
+    """Samples traced by refine_frame since the last reset, over all pixels (rtRefineSamples)."""
+    return load_renderer().rtRefineSamples()
+
+
+def refine_last_list():
+    """The list of the last refine_frame's pass in the order it was handed to the pixel kernel (rtRefineLastList): (n, 2) int32, column i then row j."""
+    r = load_renderer()
+    n = r.rtRefineLastList(None, 0)
+    ij = np.zeros((n, 2), np.int32)
+    if n > 0:
+        r.rtRefineLastList(ij.ctypes.data_as(C.POINTER(C.c_int32)), n)
+    return ij
+
+
+def last_refine_ms():
+    """HIP-event time of select + pixel kernel + update of the last refine_frame (not the deliver kernel or the copies), in milliseconds."""
+    return load_renderer().rtLastRefineMs()
 
 
 # updateTriangles / updateMaterials / updateSpheres (include/rt_api.h): edit the scene in place.  The wrappers take arrays of the exact record type and

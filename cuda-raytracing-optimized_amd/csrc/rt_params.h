@@ -247,8 +247,9 @@ struct RtSwitches {
     int cost_reuse = 1;                 // RT_COST_REUSE: sphere frames 0 = neither record nor reuse the per-pixel cost map (every frame measures), 1 = reuse it until
                                         // setCamera changes the camera, 2 = across setCamera too (A/B: tools/bench_orbit.py)
     int pixels_waves = 0;               // RT_PIXELS_WAVES=<w>: renderPixels launches at most w waves (0 = no cap; tests: the refill path with a few hundred pixels)
+    bool refine_order = true;           // RT_REFINE_ORDER=0: refineFrame hands its list to the pixel kernels in ascending pixel order, not dearest first (A/B: tools/bench_refine.py)
     // the sphere launcher
-    int top_thr = 384;                  // RT_TOP_THR: 16 x rays per sample from which a pixel goes to chain list 0 (24; below 320: the default)
+    int top_thr = 384;                 // RT_TOP_THR: 16 x rays per sample from which a pixel goes to chain list 0 (24; below 320: the default)
     bool basic = true;                  // RT_BASIC=0 / RT_ONEPASS=0: keep the general shading code / pass loop where the lean kinds would do
     bool onepass = true;
     long long lean6_pixels = 2600000;   // RT_LEAN6_PIXELS: pixels per device from which the lean kernel runs six waves per SIMD (0 = never)

@@ -34,6 +34,7 @@
 #include "rt_display.h"
 #include "rt_update.h"
 #include "rt_build.h"
+#include "rt_refine.h"
 
 namespace {
 
@@ -253,12 +254,38 @@ struct PixelState {
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
 
+// refineFrame: the adaptive frame's per-pixel state for the WHOLE image, the list of a pass and the batch arrays of one chunk of it (rt_refine.h), on the
+// first in-process device, with a queue word and an event pair of their own beside the pixel list's (setup_devices).  Allocated by the first call, released
+// by free_pass where the pixel buffers are.  The host keeps what the helpers report and what decides whether the next call starts a new frame.
+struct RefineState {
+    int device = -1;
+    std::vector<void*> owned;           // its device allocations (dev_alloc)
+    RtRefineParams planes = {};         // the device pointers (everything else of the block is filled per call)
+    uint32_t* d_queue = nullptr;        // RtPixelBatch::queue
+    size_t chunk_cap = 0;               // entries the batch arrays hold
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    int passes = 0;                     // sampling calls since the last reset; 0 = the next call starts at sample 0
+    int batch = 0;                      // the frame's batch (fixed by its first call)
+    long long samples = 0;              // rtRefineSamples
+    uint32_t last_len = 0;              // the length of the last call's list (rtRefineLastList)
+    double ms = 0.0;                    // rtLastRefineMs
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
 DisplayState g_display;
 RayState g_rays;
 PixelState g_pixels;
+RefineState g_refine;
+
+// The adaptive frame back to "the next refineFrame starts at sample 0" (rtResetRefine, setCamera, setRenderOptions, the scene edits); the buffers stay.
+void reset_refine() {
+    g_refine.passes = 0;
+    g_refine.batch = 0;
+    g_refine.samples = 0;
+    g_refine.last_len = 0;
+}
 
 // The state of displayFrame's auto exposure back to "adapt from nothing" (rtResetDisplay, setRenderOptions); the buffers stay.
 void reset_display() {
@@ -370,6 +397,7 @@ void setup_devices() {
     free_pass(g_display);
     free_pass(g_rays);
     free_pass(g_pixels);
+    free_pass(g_refine);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -430,6 +458,9 @@ void setup_devices() {
     g_pixels.device = c.devs[0].device;                     // ... and renderPixels'
     HIP_CHECK(hipEventCreate(&g_pixels.ev_start));
     HIP_CHECK(hipEventCreate(&g_pixels.ev_stop));
+    g_refine.device = c.devs[0].device;                     // ... and refineFrame's
+    HIP_CHECK(hipEventCreate(&g_refine.ev_start));
+    HIP_CHECK(hipEventCreate(&g_refine.ev_stop));
     HIP_CHECK(hipSetDevice(current));
 }
 
@@ -479,6 +510,7 @@ void cleanup_impl() {
     free_pass(g_display);
     free_pass(g_rays);
     free_pass(g_pixels);
+    free_pass(g_refine);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -579,6 +611,7 @@ void setRenderOptions(const rt_render_options* opt) {
     g_accumulate.frames = 0;                                // (likewise the history of accumulateFrame)
     g_preview.frames = 0;                                   // (and previewFrame's)
     reset_display();                                        // (and displayFrame's adapted exposure)
+    reset_refine();                                         // (and the adaptive frame)
 }
 
 }  // extern "C"
@@ -1013,6 +1046,7 @@ RtSwitches rt_read_switches() {
     const int cost_reuse = env_int("RT_COST_REUSE", s.cost_reuse);
     s.cost_reuse = (cost_reuse >= 0 && cost_reuse <= 2) ? cost_reuse : 1;
     s.pixels_waves = std::max(0, env_int("RT_PIXELS_WAVES", s.pixels_waves));
+    s.refine_order = env_flag("RT_REFINE_ORDER", s.refine_order);
 
     const int top_thr = env_int("RT_TOP_THR", s.top_thr);
     if (top_thr >= 320) s.top_thr = top_thr;
@@ -1090,6 +1124,7 @@ void setCamera(const rt_camera* cam) {
     if (memcmp(&c.cam, cam, sizeof(rt_camera)) != 0) c.camera_moves++;      // (the cost maps of sphere frames: cost_key_of)
     c.cam = *cam;                                           // read by every frame's parameter block; nothing of the scene depends on it
     c.prog_samples = 0;
+    reset_refine();
 }
 
 // Scene edits (rt_api.h, "editing the scene").  Each call leaves every in-process device and the host mirrors with what a fresh init* of the
@@ -1110,6 +1145,7 @@ static void launch_refit(const DeviceState& d) {
 
 static void scene_edited() {
     g_ctx.prog_samples = 0;                                 // as setCamera
+    reset_refine();
     g_ctx.scene_edits++;                                    // (the cost maps of sphere frames: cost_key_of)
 }
 
@@ -1486,6 +1522,147 @@ void renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, const
 double rtLastPixelsMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastPixelsMs before init");
     return g_ctx.pixels_ms;
+}
+
+// Adaptive sampling on the device (rt_api.h).  One call is one pass over the whole image on the first in-process device: select (rt_refine.h)
+// builds the list, the pixel kernels of renderPixels trace `batch` more samples of its entries over device-resident batch arrays, chunk by chunk, update
+// scatters the states back.  Of the pass only one word crosses the bus, and only downwards: the length of the list, which the launch of the pixel kernel
+// needs on the host.  The parameter block is run_pixels'; nothing of a frame's, a pass's or renderPixels' own state is read or written.
+static void check_refine(const char* fn) {
+    if (!g_ctx.initialised) rt_fail(" before init", fn);
+}
+
+int refineFrame(rt_vec3* out, int32_t* samples, float* error, int batch, int min_batches, int max_samples, float threshold, int flags) {
+    RenderContext& c = g_ctx;
+    RefineState& q = g_refine;
+    check_refine("refineFrame");
+    if (batch < 1) rt_fail("refineFrame: batch must be at least 1");
+    if (min_batches < 2) rt_fail("refineFrame: min_batches must be at least 2 (the error needs two batch means)");
+    if (max_samples < batch || max_samples > RT_PROGRESSIVE_MAX_SAMPLES) rt_fail("refineFrame: max_samples must be batch .. RT_PROGRESSIVE_MAX_SAMPLES");
+    if (!std::isfinite(threshold) || threshold < 0.0f) rt_fail("refineFrame: threshold must be finite and not negative");
+    if ((flags & ~RT_REFINE_DILATE) != 0) rt_fail("refineFrame: unknown flag bits");
+    if (q.passes > 0 && batch != q.batch) rt_fail("refineFrame: batch differs from the frame's (it is fixed by the first call after a reset)");
+    if (c.opt.rng != RT_RNG_REFERENCE_STREAM) rt_fail("refineFrame: only the reference RNG stream is one sequential stream per pixel (RT_RNG_COUNTER sums sample chunks)");
+    if (c.opt.variant != 0) rt_fail("refineFrame: only the default kernels' frame (variant 0) is defined per pixel");
+    if (c.is_spheres && c.opt.floor) rt_fail("refineFrame: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
+    if (c.is_spheres && c.opt.nee) rt_fail("refineFrame: next-event estimation is only defined for mesh scenes");
+    const DeviceState& d = c.devs[0];
+    const size_t npix = (size_t)c.nx * c.ny, chunk = std::min(npix, (size_t)kPixelChunk);
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(d.device));
+    RtRefineParams& r = q.planes;
+    if (!r.state) {
+        r.state = dev_alloc<uint4>(q.owned, npix);
+        r.n = dev_alloc<int32_t>(q.owned, npix);
+        r.mom = dev_alloc<float2>(q.owned, npix);
+        r.rays = dev_alloc<uint32_t>(q.owned, npix);
+        r.lum = dev_alloc<float>(q.owned, npix);
+        r.flag = dev_alloc<uint8_t>(q.owned, npix);
+        r.cls = dev_alloc<uint8_t>(q.owned, npix);
+        r.list = dev_alloc<uint32_t>(q.owned, npix);
+        r.words = dev_alloc<uint32_t>(q.owned, kRefineWords);
+        r.b_ij = dev_alloc<int32_t>(q.owned, 2 * chunk);
+        r.b_first = dev_alloc<int32_t>(q.owned, chunk);
+        r.b_state = dev_alloc<uint32_t>(q.owned, 4 * chunk);
+        r.b_rays = dev_alloc<uint32_t>(q.owned, chunk);
+        q.chunk_cap = chunk;
+        q.d_queue = dev_alloc<uint32_t>(q.owned, 1);
+    }
+    if (out && !r.out) r.out = dev_alloc<rt_vec3>(q.owned, npix);
+    if (error && !r.err) r.err = dev_alloc<float>(q.owned, npix);
+    if (q.passes == 0) {                                    // a new frame: no samples, no statistics (a pixel with n = 0 starts from its seed, not from `state`)
+        HIP_CHECK(hipMemsetAsync(r.n, 0, npix * sizeof(int32_t), d.stream));
+        HIP_CHECK(hipMemsetAsync(r.mom, 0, npix * sizeof(float2), d.stream));
+        HIP_CHECK(hipMemsetAsync(r.rays, 0, npix * sizeof(uint32_t), d.stream));
+        HIP_CHECK(hipMemsetAsync(r.lum, 0, npix * sizeof(float), d.stream));
+        q.batch = batch;
+        q.samples = 0;
+    }
+    RtRefineParams p = r;
+    p.out = out ? r.out : nullptr; p.err = error ? r.err : nullptr;
+    p.nx = c.nx; p.ny = c.ny;
+    p.batch = batch; p.min_batches = min_batches; p.max_samples = max_samples; p.flags = flags; p.threshold = threshold;
+    const RtSwitches sw = rt_read_switches();
+    p.cost_order = sw.refine_order ? 1 : 0;
+    uint32_t total = 0;
+    HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+    HIP_CHECK(hipMemsetAsync(r.words, 0, kRefineWords * sizeof(uint32_t), d.stream));
+    HIP_CHECK(rt_launch_refine_select(p, d.stream));
+    HIP_CHECK(hipMemcpyAsync(&total, r.words + kRefineTotal, sizeof total, hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));              // the one readback of a pass: RtPixelBatch::n and the grid of the pixel kernel come from it
+    if ((size_t)total > npix) rt_fail("refineFrame: the list is longer than the image");
+    const bool fast = c.opt.fp == RT_FP_FAST;
+    for (size_t first = 0; first < (size_t)total; first += q.chunk_cap) {
+        p.chunk_first = (uint32_t)first;
+        p.chunk_n = (uint32_t)std::min(q.chunk_cap, (size_t)total - first);
+        HIP_CHECK(rt_launch_refine_gather(p, d.stream));
+        HIP_CHECK(hipMemsetAsync(q.d_queue, 0, sizeof(uint32_t), d.stream));
+        RtPixelBatch b;
+        b.ij = p.b_ij; b.ns = nullptr; b.first = p.b_first; b.state = p.b_state; b.out = nullptr; b.rays = p.b_rays;
+        b.queue = q.d_queue; b.n = (int32_t)p.chunk_n; b.ns_all = batch;
+        if (c.is_spheres) {
+            RtSphereParams sp = sphere_params(d, whole_image_partition());
+            sp.max_depth = c.max_depth; sp.rr = c.opt.rr; sp.rng_mode = c.opt.rng;
+            HIP_CHECK(fast ? rt_launch_pixels_spheres_fast(sp, b, sw.pixels_waves, d.stream) : rt_launch_pixels_spheres_parity(sp, b, sw.pixels_waves, d.stream));
+        } else {
+            RtMeshParams mp = mesh_params(d, whole_image_partition());
+            mp.max_depth = c.max_depth; mp.nee = c.opt.nee; mp.rr = c.opt.rr; mp.rng_mode = c.opt.rng;
+            mp.light = c.opt.light; mp.lightColor = c.opt.lightColor;
+            HIP_CHECK(fast ? rt_launch_pixels_mesh_fast(mp, b, sw.pixels_waves, d.stream) : rt_launch_pixels_mesh_parity(mp, b, sw.pixels_waves, d.stream));
+        }
+        HIP_CHECK(rt_launch_refine_update(p, d.stream));
+    }
+    HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+    if (p.out || p.err) HIP_CHECK(rt_launch_refine_deliver(p, d.stream));
+    if (out) HIP_CHECK(hipMemcpyAsync(out, p.out, npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
+    if (samples) HIP_CHECK(hipMemcpyAsync(samples, r.n, npix * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
+    if (error) HIP_CHECK(hipMemcpyAsync(error, p.err, npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's planes are complete on return
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, q.ev_start, q.ev_stop));
+    HIP_CHECK(hipSetDevice(current));
+    q.ms = (double)ms;
+    q.last_len = total;
+    if (total > 0) {
+        q.passes = std::min(q.passes, INT_MAX - 1) + 1;
+        q.samples += (long long)total * batch;
+    }
+    return (int)total;
+}
+
+void rtResetRefine(void) {
+    check_refine("rtResetRefine");
+    reset_refine();
+}
+
+long long rtRefineSamples(void) {
+    check_refine("rtRefineSamples");
+    return g_refine.samples;
+}
+
+int rtRefineLastList(int32_t* ij, int cap) {
+    check_refine("rtRefineLastList");
+    const RefineState& q = g_refine;
+    const size_t n = std::min((size_t)std::max(cap, 0), (size_t)q.last_len);
+    if (ij && n > 0) {
+        std::vector<uint32_t> ids(n);
+        int current = 0;
+        HIP_CHECK(hipGetDevice(&current));
+        HIP_CHECK(hipSetDevice(q.device));
+        HIP_CHECK(hipMemcpy(ids.data(), q.planes.list, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipSetDevice(current));
+        for (size_t k = 0; k < n; k++) {
+            ij[2 * k] = (int32_t)(ids[k] % (uint32_t)g_ctx.nx);
+            ij[2 * k + 1] = (int32_t)(ids[k] / (uint32_t)g_ctx.nx);
+        }
+    }
+    return (int)q.last_len;
+}
+
+double rtLastRefineMs(void) {
+    check_refine("rtLastRefineMs");
+    return g_refine.ms;
 }
 
 // Guide-driven preview denoiser (rt_api.h).  The filter needs neighbours across stripe boundaries, so it works on the whole image on the first

@@ -437,6 +437,55 @@ void   renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, con
                     uint32_t* state, rt_vec3* out, uint32_t* rays);
 double rtLastPixelsMs(void);   /* HIP-event time of the pixel kernels of the last renderPixels, summed over its chunks; 0 before the first */
 
+/* --- adaptive sampling: the samples go where the image is still noisy ---------------------------------------------------------------
+ * refineFrame renders an adaptive frame: every pixel gets samples in batches until an estimate of its own error says it has enough.  The frame's state, the
+ * selection, the list of a pass and the statistics live on the device; the pixel kernels of renderPixels trace the samples.  One call is one pass: select,
+ * trace `batch` more samples for every selected pixel, update their statistics, deliver.  It returns the number of pixels it sampled; 0 means the frame is
+ * finished under the call's parameters - nothing was traced, the planes are still delivered.  The caller's loop is  while (refineFrame(...)) {}  with
+ * previewFrame / displayFrame in it as often as it likes.
+ * All arithmetic is fp32, every operation rounded on its own (no FMA), operands in the order written, a comparison with a NaN false; lum is previewFrame's;
+ * max(x, 0) = x < 0 ? 0 : x, so a NaN stays a NaN.  Counts are integers and enter as (float)count.  So every stored number is defined bit for bit
+ * (tests/refine_reference.py restates this in numpy).
+ * Per-pixel state:  sum(p) and the stream word (renderPixels' state), n(p) samples so far, M1(p), M2(p), l(p) = lum(mean(p)), rays(p) = the closest-hit
+ *     queries of p's last batch.  After a reset n = 0, M1 = M2 = 0, rays = 0.
+ * Update of a sampled pixel:  the pixel kernel continues p's stream by `batch` samples (renderPixels with first = n(p)).  n' = n + batch;
+ *     mean(p)[k] = sum[k] / (float)n';  l' = lum(mean);  K = n' / batch
+ *     y = l'  if n == 0,  else  y = (l' * (float)n' - l * (float)n) / (float)batch         (the luminance of the batch's own mean, recovered from the two means)
+ *     M1 += y;  M2 += y*y
+ * Error of a pixel, K = n / batch:
+ *     K < 2:  err = FLT_MAX
+ *     else:   a1 = M1 / (float)K;  a2 = M2 / (float)K;  v = max(a2 - a1*a1, 0) / (float)(K - 1);  r = max(l, 0) + RT_REFINE_LUM_EPS;  err = v / (r*r)
+ *     (the relative variance of the mean, from the batch means)
+ * Select, with the call's parameters:
+ *     unconverged(p) = K(p) < min_batches || !(err(p) <= threshold*threshold)
+ *     want(p) = unconverged(p);  with RT_REFINE_DILATE: some q of the 3 x 3 window around p, clipped to the image, is unconverged - one pixel's lucky early
+ *               estimate must not leave a hole next to noise
+ *     active(p) = want(p) && n(p) + batch <= max_samples
+ *     So the first pass after a reset samples every pixel, and a pixel whose mean is not finite (err is a NaN) never converges and stops at max_samples.
+ * List order:  cls(p) = 31 - clz(max(rays(p), 1)).  The pass hands the active pixels to the pixel kernel with cls descending - dearest first, so the long
+ *     pixels do not start last; the order inside a class is unspecified, and no result depends on the order.
+ * Outputs: three caller-owned host planes of nx*ny entries, row 0 = bottom, each may be NULL (with all three NULL nothing is downloaded): out = mean(p),
+ * samples = n(p), error = err(p).  In RT_FP_PARITY out(p) is bit-identical to the pixel runRenderer(samples(p)) stores at p, and samples, error and the
+ * return value are the same after any sequence of calls wherever the library runs; in RT_FP_FAST the same procedure runs on the FAST pixel kernels with no
+ * bit promise, as for renderPixels.  threshold, min_batches, max_samples and flags act at selection only and may change from call to call (a max_samples
+ * raised after a 0 return continues the frame); batch is fixed by the first call after a reset.
+ * The frame is reset - the next call starts at sample 0 - by every init*, cleanupRenderer, every setRenderOptions, setCamera, every scene edit and rebuildBvh,
+ * and rtResetRefine.  The call is blocking, works on the WHOLE image on the first in-process device whatever the partition is, and changes nothing another
+ * call observes: the framebuffer, getRenderStats, rtLastLaunches, rtLastSphereForm, the progressive frame, the cost maps, every history, rtLastPixelsMs and
+ * every other rtLast*Ms stay as they were.  Device memory: 42 bytes per pixel of state and list, 12 and 4 more for the out and error planes once asked for,
+ * and 32 bytes per entry of one chunk of the list - lists above RT_PIXEL_CHUNK entries run in chunks -; allocated by the first call, freed where the pixel
+ * buffers are.  Of a pass one word is read back before the pixel kernel is launched: the length of its list.
+ * Misuse (rt error, exit 99), checked before any device work: any of the five calls before init, batch < 1, min_batches < 2, max_samples < batch or above
+ * RT_PROGRESSIVE_MAX_SAMPLES, threshold not finite or < 0, unknown flag bits, a batch different from the frame's, and every frame condition renderPixels
+ * refuses: RT_RNG_COUNTER, variant != 0, rt_render_options.floor = 1 or nee = 1 on a sphere scene. */
+enum { RT_REFINE_DILATE = 1 };
+#define RT_REFINE_LUM_EPS 1e-3f
+int    refineFrame(rt_vec3* out, int32_t* samples, float* error, int batch, int min_batches, int max_samples, float threshold, int flags);
+void   rtResetRefine(void);                    /* the next refineFrame starts at sample 0 */
+long long rtRefineSamples(void);               /* samples traced since the last reset, all pixels */
+int    rtRefineLastList(int32_t* ij, int cap); /* the list of the last call's pass, in the order it was handed to the kernel: min(cap, length) (i, j) pairs; returns its length */
+double rtLastRefineMs(void);                   /* HIP-event time of select + pixel kernel + update of the last call, not the deliver kernel or the copies; 0 before the first */
+
 /* --- editing the scene: move, recolour, animate without a new init ---------------------------------------------------------------
  * The calls below change the scene the renderer holds, in place, on every in-process device: a picked object (traceRays) is moved or recoloured, an
  * animation is played, without cleanupRenderer + init*.  The contract they share: after ANY sequence of them everything the library computes - runRenderer
