@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -225,45 +226,41 @@ struct DisplayState : PassState {
     float last_exposure = 1.0f;         // rtLastExposure
 };
 
-// traceRays / occludedRays: the device buffers of one chunk of rays - four inputs, five closest-hit planes, the any-hit bytes - on the first in-process
-// device, each grown to the largest chunk that asked for it, and an event pair of their own (created with the device list, setup_devices): the timings of a
-// frame, the guides and the passes stay what they were.  Released by free_pass where the passes' buffers are.
+// What every query call (traceRays / occludedRays, renderPixels, refineFrame) holds: the first in-process device, its allocations there and an event pair of
+// its own, created with the device list (setup_devices) - the timings of a frame, the guides, the passes and the other queries stay what they were.
+// Released by free_pass where the passes' buffers are.
+struct QueryState {
+    int device = -1;
+    std::vector<void*> owned;           // its device allocations (dev_alloc)
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+};
+
+// traceRays / occludedRays and renderPixels: the device buffers of one chunk of the caller's items, each grown to the largest chunk that asked for it
+// (run_chunks), by a table of what a buffer holds per item and which way it crosses the bus.  Rays: four inputs, five closest-hit planes, the any-hit bytes.
+// Pixels: three inputs, the stream states (read and written), two outputs - and the queue word of the pixel kernels.
+enum { kUp = 1, kDown = 2 };
+struct ChunkBuffer {
+    size_t bytes;                       // per item
+    int dir;                            // kUp: uploaded in front of the launch, kDown: downloaded behind it
+};
 enum { kRayOrg = 0, kRayDir, kRayTMin, kRayTMax, kRayT, kRayPrim, kRayNormal, kRayUv, kRayNodes, kRayOccluded, kRayBuffers };
-constexpr size_t kRayBytes[kRayBuffers] = { 12, 12, 4, 4, 4, 4, 12, 8, 4, 1 };      // bytes per ray
-constexpr int kRayChunk = RT_RAY_CHUNK;     // rays per upload - kernel - download round: 65 bytes per ray, so at most ~273 MB of device memory whatever the batch
-struct RayState {
-    int device = -1;
-    std::vector<void*> owned;           // its device allocations (dev_alloc)
-    char* d_buf[kRayBuffers] = {};
-    size_t cap[kRayBuffers] = {};       // rays d_buf[k] holds
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-};
-
-// renderPixels: the device buffers of one chunk of the list - three inputs, the stream states (read and written), two outputs - and the queue word, on the
-// first in-process device, each grown to the largest chunk that asked for it, with an event pair of their own beside the ray queries' (setup_devices).
-// Released by free_pass where the ray buffers are.
 enum { kPixIj = 0, kPixNs, kPixFirst, kPixState, kPixOut, kPixRays, kPixBuffers };
-constexpr size_t kPixBytes[kPixBuffers] = { 8, 4, 4, 16, 12, 4 };      // bytes per pixel: 48 in all
-constexpr int kPixelChunk = RT_PIXEL_CHUNK; // pixels per upload - kernel - download round
-struct PixelState {
-    int device = -1;
-    std::vector<void*> owned;           // its device allocations (dev_alloc)
-    char* d_buf[kPixBuffers] = {};
-    size_t cap[kPixBuffers] = {};       // pixels d_buf[k] holds
-    uint32_t* d_queue = nullptr;        // RtPixelBatch::queue
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+constexpr int kChunkBuffers = kRayBuffers;
+constexpr size_t kRayChunk = RT_RAY_CHUNK;      // rays per upload - kernel - download round: 65 bytes per ray, so at most ~273 MB of device memory whatever the batch
+constexpr size_t kPixelChunk = RT_PIXEL_CHUNK;  // pixels per upload - kernel - download round: 48 bytes per pixel
+struct ChunkState : QueryState {
+    char* d_buf[kChunkBuffers] = {};
+    size_t cap[kChunkBuffers] = {};     // items d_buf[k] holds
+    uint32_t* d_queue = nullptr;        // RtPixelBatch::queue (renderPixels)
 };
 
-// refineFrame: the adaptive frame's per-pixel state for the WHOLE image, the list of a pass and the batch arrays of one chunk of it (rt_refine.h), on the
-// first in-process device, with a queue word and an event pair of their own beside the pixel list's (setup_devices).  Allocated by the first call, released
-// by free_pass where the pixel buffers are.  The host keeps what the helpers report and what decides whether the next call starts a new frame.
-struct RefineState {
-    int device = -1;
-    std::vector<void*> owned;           // its device allocations (dev_alloc)
+// refineFrame: the adaptive frame's per-pixel state for the WHOLE image, the list of a pass and the batch arrays of one chunk of it (rt_refine.h), with a
+// queue word of its own beside the pixel list's.  Allocated by the first call.  The host keeps what the helpers report and what decides whether the next
+// call starts a new frame.
+struct RefineState : QueryState {
     RtRefineParams planes = {};         // the device pointers (everything else of the block is filled per call)
     uint32_t* d_queue = nullptr;        // RtPixelBatch::queue
     size_t chunk_cap = 0;               // entries the batch arrays hold
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     int passes = 0;                     // sampling calls since the last reset; 0 = the next call starts at sample 0
     int batch = 0;                      // the frame's batch (fixed by its first call)
     long long samples = 0;              // rtRefineSamples
@@ -275,8 +272,7 @@ DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
 DisplayState g_display;
-RayState g_rays;
-PixelState g_pixels;
+ChunkState g_rays, g_pixels;
 RefineState g_refine;
 
 // The adaptive frame back to "the next refineFrame starts at sample 0" (rtResetRefine, setCamera, setRenderOptions, the scene edits); the buffers stay.
@@ -451,16 +447,12 @@ void setup_devices() {
         HIP_CHECK(hipMemset(d.d_queue, 0, sizeof(uint32_t) * kXcdQueues * kXcdQueueWords));
         c.devs.push_back(d);
     }
-    HIP_CHECK(hipSetDevice(c.devs[0].device));              // the ray queries' own event pair, on the device they run on
-    g_rays.device = c.devs[0].device;
-    HIP_CHECK(hipEventCreate(&g_rays.ev_start));
-    HIP_CHECK(hipEventCreate(&g_rays.ev_stop));
-    g_pixels.device = c.devs[0].device;                     // ... and renderPixels'
-    HIP_CHECK(hipEventCreate(&g_pixels.ev_start));
-    HIP_CHECK(hipEventCreate(&g_pixels.ev_stop));
-    g_refine.device = c.devs[0].device;                     // ... and refineFrame's
-    HIP_CHECK(hipEventCreate(&g_refine.ev_start));
-    HIP_CHECK(hipEventCreate(&g_refine.ev_stop));
+    HIP_CHECK(hipSetDevice(c.devs[0].device));              // the query calls' own event pairs, on the device they run on
+    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_refine }) {
+        q->device = c.devs[0].device;
+        HIP_CHECK(hipEventCreate(&q->ev_start));
+        HIP_CHECK(hipEventCreate(&q->ev_stop));
+    }
     HIP_CHECK(hipSetDevice(current));
 }
 
@@ -665,9 +657,110 @@ RtMeshParams mesh_params(const DeviceState& d, const RtPartition& part) {
     return p;
 }
 
+// ... plus what every path-tracing kernel takes from the options: what a path is.  The only place these fields are assigned: a frame (render_frame) and the
+// pixel kernels (launch_pixels), which are bit-equal to it by contract, cannot disagree about them.
+RtSphereParams sphere_path_params(const DeviceState& d, const RtPartition& part) {
+    RtSphereParams p = sphere_params(d, part);
+    p.max_depth = g_ctx.max_depth; p.rr = g_ctx.opt.rr; p.rng_mode = g_ctx.opt.rng;
+    return p;
+}
+
+RtMeshParams mesh_path_params(const DeviceState& d, const RtPartition& part) {
+    RtMeshParams p = mesh_params(d, part);
+    p.max_depth = g_ctx.max_depth; p.rr = g_ctx.opt.rr; p.rng_mode = g_ctx.opt.rng;
+    p.nee = g_ctx.opt.nee; p.light = g_ctx.opt.light; p.lightColor = g_ctx.opt.lightColor;
+    return p;
+}
+
 // The first-hit guide kernel of the scene kind over rows `part`, into the compact planes `g` (renderGuides, begin_pass).
 void launch_guides(const DeviceState& d, const RtPartition& part, const RtGuidePlanes& g) {
     HIP_CHECK(g_ctx.is_spheres ? rt_launch_guides_spheres(sphere_params(d, part), g, d.stream) : rt_launch_guides_mesh(mesh_params(d, part), g, d.stream));
+}
+
+// The pixel kernel of the scene kind and fp mode over the batch `b` (renderPixels, refineFrame): a frame's parameter block without anything a frame parks,
+// records or reports, over the whole image as one member's rows.  max_waves: RtSwitches::pixels_waves as the call read it.
+void launch_pixels(const DeviceState& d, const RtPixelBatch& b, int max_waves) {
+    const bool fast = g_ctx.opt.fp == RT_FP_FAST;
+    if (g_ctx.is_spheres) {
+        const RtSphereParams p = sphere_path_params(d, whole_image_partition());
+        HIP_CHECK(fast ? rt_launch_pixels_spheres_fast(p, b, max_waves, d.stream) : rt_launch_pixels_spheres_parity(p, b, max_waves, d.stream));
+    } else {
+        const RtMeshParams p = mesh_path_params(d, whole_image_partition());
+        HIP_CHECK(fast ? rt_launch_pixels_mesh_fast(p, b, max_waves, d.stream) : rt_launch_pixels_mesh_parity(p, b, max_waves, d.stream));
+    }
+}
+
+// The query calls (traceRays / occludedRays, renderPixels, refineFrame) differ in their arguments, buffers and kernels; the rest is here, once.
+
+// What "defined per pixel" asks of the options in force (renderPixels, refineFrame), under the function's name `fn`.
+void check_per_pixel(const char* fn) {
+    const RenderContext& c = g_ctx;
+    if (c.opt.rng != RT_RNG_REFERENCE_STREAM) rt_fail(": only the reference RNG stream is one sequential stream per pixel (RT_RNG_COUNTER sums sample chunks)", fn);
+    if (c.opt.variant != 0) rt_fail(": only the default kernels' frame (variant 0) is defined per pixel", fn);
+    if (c.is_spheres && c.opt.floor) rt_fail(": the floor plane is only defined for mesh scenes (kernel_scene.floor)", fn);
+    if (c.is_spheres && c.opt.nee) rt_fail(": next-event estimation is only defined for mesh scenes", fn);
+}
+
+// Onto the query's device (the first in-process one: every device holds the whole scene, setup_devices); returns the device to restore (end_query).
+int begin_query(const QueryState& q) {
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(q.device));
+    return current;
+}
+
+void end_query(int current) { HIP_CHECK(hipSetDevice(current)); }
+
+// The HIP-event time between the query's two events, in milliseconds, once the stream they were recorded on has drained.
+double query_ms(const QueryState& q) {
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, q.ev_start, q.ev_stop));
+    return (double)ms;
+}
+
+// body(first, m) for every chunk [first, first + m) of n items, `chunk` at a time.
+template <typename Body>
+void for_chunks(size_t n, size_t chunk, Body body) {
+    for (size_t first = 0; first < n; first += chunk) body(first, std::min(chunk, n - first));
+}
+
+// n items of the caller's arrays through a kernel on the query's device, chunk by chunk on that device's stream: the buffers of `table` whose host[k] is not
+// NULL grown to the chunk, the queue word (with_queue) zeroed, the kUp buffers uploaded from item `first` of host[k], launch(dev, m) between the state's two
+// events - dev[k] = the device buffer of host[k], NULL where host[k] is -, the kDown buffers downloaded to item `first`, and the stream drained: blocking, the
+// caller's arrays are complete on return.  Nothing of a frame's, the guides' or the passes' state is read or written.  Returns the HIP-event time of the
+// launches (not the copies), summed over the chunks, in milliseconds.
+template <typename Launch>
+double run_chunks(ChunkState& q, size_t n, size_t chunk, const ChunkBuffer* table, int buffers, void* const* host, bool with_queue, Launch launch) {
+    const hipStream_t stream = g_ctx.devs[0].stream;
+    const int current = begin_query(q);
+    if (with_queue && !q.d_queue) q.d_queue = dev_alloc<uint32_t>(q.owned, 1);
+    double ms_sum = 0.0;
+    for_chunks(n, chunk, [&](size_t first, size_t m) {
+        char* dev[kChunkBuffers] = {};
+        for (int k = 0; k < buffers; k++) {
+            if (!host[k]) continue;
+            if (q.cap[k] < m) {
+                dev_release(q.owned, q.d_buf[k]);
+                q.d_buf[k] = dev_alloc<char>(q.owned, m * table[k].bytes);
+                q.cap[k] = m;
+            }
+            dev[k] = q.d_buf[k];
+        }
+        if (with_queue) HIP_CHECK(hipMemsetAsync(q.d_queue, 0, sizeof(uint32_t), stream));
+        for (int k = 0; k < buffers; k++)
+            if (dev[k] && (table[k].dir & kUp))
+                HIP_CHECK(hipMemcpyAsync(dev[k], static_cast<const char*>(host[k]) + first * table[k].bytes, m * table[k].bytes, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipEventRecord(q.ev_start, stream));
+        launch(dev, m);
+        HIP_CHECK(hipEventRecord(q.ev_stop, stream));
+        for (int k = 0; k < buffers; k++)
+            if (dev[k] && (table[k].dir & kDown))
+                HIP_CHECK(hipMemcpyAsync(static_cast<char*>(host[k]) + first * table[k].bytes, dev[k], m * table[k].bytes, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));                // (the events are read per chunk)
+        ms_sum += query_ms(q);
+    });
+    end_query(current);
+    return ms_sum;
 }
 
 // The diagnostic buffer of RT_WAVE_DEBUG (8 words per wave, or the mesh kernel's phase counters): allocated on first use, cleared on the stream.
@@ -876,10 +969,9 @@ void render_frame(int ns, int first, bool progressive) {
         if (c.max_depth <= 0) {
             HIP_CHECK(hipMemsetAsync(d.d_fb, 0, d.fb_rows * row_bytes, d.stream));     // loop of kernels.cu:402 never runs
         } else if (c.is_spheres) {
-            RtSphereParams p = sphere_params(d, part);
-            p.ns = ns; p.max_depth = c.max_depth;
+            RtSphereParams p = sphere_path_params(d, part);
+            p.ns = ns;
             p.fb = d.d_fb;
-            p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
             p.counters = c.opt.counters ? d.d_counters : nullptr;
             p.queue = d.d_queue;
             p.order = d.d_order;
@@ -939,12 +1031,10 @@ void render_frame(int ns, int first, bool progressive) {
                                              : rt_launch_spheres_parity(p, c.opt.variant, sw, d.stream));
             launches++;
         } else {
-            RtMeshParams p = mesh_params(d, part);
-            p.ns = ns; p.max_depth = c.max_depth;
+            RtMeshParams p = mesh_path_params(d, part);
+            p.ns = ns;
             p.leaf_tri = sw.compact_leaves ? d.d_leaf_tri : nullptr; p.leaf_ofs = sw.compact_leaves ? d.d_leaf_ofs : nullptr;
             p.fb = d.d_fb;
-            p.nee = c.opt.nee; p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
-            p.light = c.opt.light; p.lightColor = c.opt.lightColor;
             if (c.opt.floor && (c.opt.variant & 0xFF) == 1) rt_fail("runRenderer: the floor plane is not built into the tile-per-wave A/B kernel (variant 1)");
             p.counters = c.opt.counters ? d.d_counters : nullptr;
             p.queue = d.d_queue;
@@ -1346,53 +1436,26 @@ void renderGuides(int mask, float* albedo, float* normal, float* depth, int32_t*
 
 double rtLastGuidesMs(void) { return g_ctx.guides_ms; }
 
-// Batched ray queries (rt_api.h).  All rays run on the first in-process device (every device holds the whole scene, setup_devices), chunk by chunk: upload,
-// kernel, download on that device's stream, with buffers and events of their own (RayState) - nothing of a frame's, the guides' or the passes' state is read
-// or written.  host[k] = the caller's array of buffer k, or NULL.
-static void run_rays(int n, const void* const host_in[4], void* const host_out[kRayBuffers], bool any) {
+// Batched ray queries (rt_api.h), through run_chunks: the four inputs (the bounds may be NULL) and the planes `out` names at kRayT.., the others NULL.
+static void run_rays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, void* const out[kRayBuffers], bool any) {
     RenderContext& c = g_ctx;
-    RayState& q = g_rays;
     const DeviceState& d = c.devs[0];
-    int current = 0;
-    HIP_CHECK(hipGetDevice(&current));
-    HIP_CHECK(hipSetDevice(d.device));
-    const void* host[kRayBuffers];
-    for (int k = 0; k < kRayBuffers; k++) host[k] = k < kRayT ? host_in[k] : host_out[k];
-    double ms_sum = 0.0;
-    for (size_t first = 0; first < (size_t)n; first += kRayChunk) {
-        const size_t m = std::min((size_t)kRayChunk, (size_t)n - first);
-        for (int k = 0; k < kRayBuffers; k++) {
-            if (!host[k] || q.cap[k] >= m) continue;
-            dev_release(q.owned, q.d_buf[k]);
-            q.d_buf[k] = dev_alloc<char>(q.owned, m * kRayBytes[k]);
-            q.cap[k] = m;
-        }
-        for (int k = 0; k < kRayT; k++)
-            if (host[k])
-                HIP_CHECK(hipMemcpyAsync(q.d_buf[k], static_cast<const char*>(host[k]) + first * kRayBytes[k], m * kRayBytes[k], hipMemcpyHostToDevice, d.stream));
-        auto in = [&](int k) { return host[k] ? reinterpret_cast<const float*>(q.d_buf[k]) : nullptr; };
-        auto out = [&](int k) { return host[k] ? q.d_buf[k] : nullptr; };
+    static const ChunkBuffer table[kRayBuffers] = { { 12, kUp }, { 12, kUp }, { 4, kUp }, { 4, kUp }, { 4, kDown }, { 4, kDown }, { 12, kDown }, { 8, kDown },
+                                                    { 4, kDown }, { 1, kDown } };
+    void* host[kRayBuffers] = { const_cast<float*>(org), const_cast<float*>(dir), const_cast<float*>(t_min), const_cast<float*>(t_max) };
+    std::copy(out + kRayT, out + kRayBuffers, host + kRayT);
+    c.rays_ms = run_chunks(g_rays, (size_t)n, kRayChunk, table, kRayBuffers, host, false, [&](char* const* dev, size_t m) {
+        auto in = [&](int k) { return reinterpret_cast<const float*>(dev[k]); };
         RtRayBatch b;
         b.org = in(kRayOrg); b.dir = in(kRayDir); b.t_min = in(kRayTMin); b.t_max = in(kRayTMax);
-        b.t = reinterpret_cast<float*>(out(kRayT)); b.prim = reinterpret_cast<int32_t*>(out(kRayPrim));
-        b.normal = reinterpret_cast<float*>(out(kRayNormal)); b.uv = reinterpret_cast<float*>(out(kRayUv));
-        b.nodes = reinterpret_cast<int32_t*>(out(kRayNodes)); b.occluded = reinterpret_cast<uint8_t*>(out(kRayOccluded));
+        b.t = reinterpret_cast<float*>(dev[kRayT]); b.prim = reinterpret_cast<int32_t*>(dev[kRayPrim]);
+        b.normal = reinterpret_cast<float*>(dev[kRayNormal]); b.uv = reinterpret_cast<float*>(dev[kRayUv]);
+        b.nodes = reinterpret_cast<int32_t*>(dev[kRayNodes]); b.occluded = reinterpret_cast<uint8_t*>(dev[kRayOccluded]);
         b.n = (int32_t)m;
         b.t_min_default = c.opt.t_min;
-        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
         HIP_CHECK(c.is_spheres ? rt_launch_rays_spheres(sphere_params(d, whole_image_partition()), b, any, d.stream)
                                : rt_launch_rays_mesh(mesh_params(d, whole_image_partition()), b, any, d.stream));
-        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
-        for (int k = kRayT; k < kRayBuffers; k++)
-            if (host[k])
-                HIP_CHECK(hipMemcpyAsync(static_cast<char*>(host_out[k]) + first * kRayBytes[k], q.d_buf[k], m * kRayBytes[k], hipMemcpyDeviceToHost, d.stream));
-        HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's arrays are complete on return; the events are read per chunk
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, q.ev_start, q.ev_stop));
-        ms_sum += (double)ms;
-    }
-    HIP_CHECK(hipSetDevice(current));
-    c.rays_ms = ms_sum;
+    });
 }
 
 // The checks the two calls share; returns false for the empty batch (nothing to do, nothing written).
@@ -1415,20 +1478,18 @@ void traceRays(int n, const float* org, const float* dir, const float* t_min, co
     for (int k = 0; k < 5; k++)
         if ((mask >> k & 1) && !planes[k]) rt_fail("traceRays: a requested plane has a null pointer");
     if ((mask & RT_RAY_NODES) && g_ctx.is_spheres) rt_fail("traceRays: RT_RAY_NODES is only defined for mesh scenes");
-    const void* const in[4] = { org, dir, t_min, t_max };
     void* out[kRayBuffers] = {};
     for (int k = 0; k < 5; k++) out[kRayT + k] = (mask >> k & 1) ? planes[k] : nullptr;
-    run_rays(n, in, out, false);
+    run_rays(n, org, dir, t_min, t_max, out, false);
 }
 
 void occludedRays(int n, const float* org, const float* dir, const float* t_min, const float* t_max, uint8_t* occluded) {
     if (!g_ctx.initialised) rt_fail("occludedRays before init");
     if (!occluded) rt_fail("occludedRays: occluded is null");
     if (!check_rays("occludedRays", n, org, dir)) return;
-    const void* const in[4] = { org, dir, t_min, t_max };
     void* out[kRayBuffers] = {};
     out[kRayOccluded] = occluded;
-    run_rays(n, in, out, true);
+    run_rays(n, org, dir, t_min, t_max, out, true);
 }
 
 double rtLastRaysMs(void) {
@@ -1436,60 +1497,19 @@ double rtLastRaysMs(void) {
     return g_ctx.rays_ms;
 }
 
-// A list of pixels (rt_api.h).  Like the ray queries: all entries run on the first in-process device, chunk by chunk - the queue word zeroed,
-// upload, kernel, download on that device's stream - with buffers and events of their own (PixelState); the parameter block is a frame's without
-// anything a frame parks, records or reports, over the whole image as one member's rows.  host[k] = the caller's array of buffer k, or NULL.
+// A list of pixels (rt_api.h), through run_chunks with the queue word of the pixel kernels.  host[k] = the caller's array of buffer k, or NULL.
 static void run_pixels(int n, int ns_all, void* const host[kPixBuffers]) {
-    RenderContext& c = g_ctx;
-    PixelState& q = g_pixels;
-    const DeviceState& d = c.devs[0];
-    int current = 0;
-    HIP_CHECK(hipGetDevice(&current));
-    HIP_CHECK(hipSetDevice(d.device));
-    if (!q.d_queue) q.d_queue = dev_alloc<uint32_t>(q.owned, 1);
+    const int state_dir = host[kPixFirst] ? kUp | kDown : kDown;    // (the states go up only where an entry can continue one: `first` is given)
+    const ChunkBuffer table[kPixBuffers] = { { 8, kUp }, { 4, kUp }, { 4, kUp }, { 16, state_dir }, { 12, kDown }, { 4, kDown } };
     const int max_waves = rt_read_switches().pixels_waves;
-    double ms_sum = 0.0;
-    for (size_t first = 0; first < (size_t)n; first += kPixelChunk) {
-        const size_t m = std::min((size_t)kPixelChunk, (size_t)n - first);
-        for (int k = 0; k < kPixBuffers; k++) {
-            if (!host[k] || q.cap[k] >= m) continue;
-            dev_release(q.owned, q.d_buf[k]);
-            q.d_buf[k] = dev_alloc<char>(q.owned, m * kPixBytes[k]);
-            q.cap[k] = m;
-        }
-        HIP_CHECK(hipMemsetAsync(q.d_queue, 0, sizeof(uint32_t), d.stream));
-        for (int k = 0; k <= kPixState; k++)                    // (the states go up only where an entry can continue one: `first` is given)
-            if (host[k] && (k != kPixState || host[kPixFirst]))
-                HIP_CHECK(hipMemcpyAsync(q.d_buf[k], static_cast<const char*>(host[k]) + first * kPixBytes[k], m * kPixBytes[k], hipMemcpyHostToDevice, d.stream));
-        auto buf = [&](int k) { return host[k] ? q.d_buf[k] : nullptr; };
+    g_ctx.pixels_ms = run_chunks(g_pixels, (size_t)n, kPixelChunk, table, kPixBuffers, host, true, [&](char* const* dev, size_t m) {
         RtPixelBatch b;
-        b.ij = reinterpret_cast<const int32_t*>(buf(kPixIj)); b.ns = reinterpret_cast<const int32_t*>(buf(kPixNs));
-        b.first = reinterpret_cast<const int32_t*>(buf(kPixFirst)); b.state = reinterpret_cast<uint32_t*>(buf(kPixState));
-        b.out = reinterpret_cast<rt_vec3*>(buf(kPixOut)); b.rays = reinterpret_cast<uint32_t*>(buf(kPixRays));
-        b.queue = q.d_queue; b.n = (int32_t)m; b.ns_all = ns_all;
-        const bool fast = c.opt.fp == RT_FP_FAST;
-        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
-        if (c.is_spheres) {
-            RtSphereParams p = sphere_params(d, whole_image_partition());
-            p.max_depth = c.max_depth; p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
-            HIP_CHECK(fast ? rt_launch_pixels_spheres_fast(p, b, max_waves, d.stream) : rt_launch_pixels_spheres_parity(p, b, max_waves, d.stream));
-        } else {
-            RtMeshParams p = mesh_params(d, whole_image_partition());
-            p.max_depth = c.max_depth; p.nee = c.opt.nee; p.rr = c.opt.rr; p.rng_mode = c.opt.rng;
-            p.light = c.opt.light; p.lightColor = c.opt.lightColor;
-            HIP_CHECK(fast ? rt_launch_pixels_mesh_fast(p, b, max_waves, d.stream) : rt_launch_pixels_mesh_parity(p, b, max_waves, d.stream));
-        }
-        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
-        for (int k = kPixState; k < kPixBuffers; k++)
-            if (host[k])
-                HIP_CHECK(hipMemcpyAsync(static_cast<char*>(host[k]) + first * kPixBytes[k], q.d_buf[k], m * kPixBytes[k], hipMemcpyDeviceToHost, d.stream));
-        HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's arrays are complete on return; the events are read per chunk
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, q.ev_start, q.ev_stop));
-        ms_sum += (double)ms;
-    }
-    HIP_CHECK(hipSetDevice(current));
-    c.pixels_ms = ms_sum;
+        b.ij = reinterpret_cast<const int32_t*>(dev[kPixIj]); b.ns = reinterpret_cast<const int32_t*>(dev[kPixNs]);
+        b.first = reinterpret_cast<const int32_t*>(dev[kPixFirst]); b.state = reinterpret_cast<uint32_t*>(dev[kPixState]);
+        b.out = reinterpret_cast<rt_vec3*>(dev[kPixOut]); b.rays = reinterpret_cast<uint32_t*>(dev[kPixRays]);
+        b.queue = g_pixels.d_queue; b.n = (int32_t)m; b.ns_all = ns_all;
+        launch_pixels(g_ctx.devs[0], b, max_waves);
+    });
 }
 
 void renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, const int32_t* first, uint32_t* state, rt_vec3* out, uint32_t* rays) {
@@ -1500,10 +1520,7 @@ void renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, const
     if (!ij) rt_fail("renderPixels: ij is null");
     if (!out && !state && !rays) rt_fail("renderPixels: out, state and rays are all null");
     if (first && !state) rt_fail("renderPixels: first needs state (the sums and stream words the pixels resume from)");
-    if (c.opt.rng != RT_RNG_REFERENCE_STREAM) rt_fail("renderPixels: only the reference RNG stream is one sequential stream per pixel (RT_RNG_COUNTER sums sample chunks)");
-    if (c.opt.variant != 0) rt_fail("renderPixels: only the default kernels' frame (variant 0) is defined per pixel");
-    if (c.is_spheres && c.opt.floor) rt_fail("renderPixels: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
-    if (c.is_spheres && c.opt.nee) rt_fail("renderPixels: next-event estimation is only defined for mesh scenes");
+    check_per_pixel("renderPixels");
     for (int k = 0; k < n; k++) {                           // every entry, before anything is uploaded
         const long long cnt = ns ? ns[k] : ns_all, f = first ? first[k] : 0;
         if (ij[2 * (size_t)k] < 0 || ij[2 * (size_t)k] >= c.nx || ij[2 * (size_t)k + 1] < 0 || ij[2 * (size_t)k + 1] >= c.ny)
@@ -1527,7 +1544,7 @@ double rtLastPixelsMs(void) {
 // Adaptive sampling on the device (rt_api.h).  One call is one pass over the whole image on the first in-process device: select (rt_refine.h)
 // builds the list, the pixel kernels of renderPixels trace `batch` more samples of its entries over device-resident batch arrays, chunk by chunk, update
 // scatters the states back.  Of the pass only one word crosses the bus, and only downwards: the length of the list, which the launch of the pixel kernel
-// needs on the host.  The parameter block is run_pixels'; nothing of a frame's, a pass's or renderPixels' own state is read or written.
+// needs on the host.  The launch is renderPixels' (launch_pixels); nothing of a frame's, a pass's or renderPixels' own state is read or written.
 static void check_refine(const char* fn) {
     if (!g_ctx.initialised) rt_fail(" before init", fn);
 }
@@ -1542,15 +1559,10 @@ int refineFrame(rt_vec3* out, int32_t* samples, float* error, int batch, int min
     if (!std::isfinite(threshold) || threshold < 0.0f) rt_fail("refineFrame: threshold must be finite and not negative");
     if ((flags & ~RT_REFINE_DILATE) != 0) rt_fail("refineFrame: unknown flag bits");
     if (q.passes > 0 && batch != q.batch) rt_fail("refineFrame: batch differs from the frame's (it is fixed by the first call after a reset)");
-    if (c.opt.rng != RT_RNG_REFERENCE_STREAM) rt_fail("refineFrame: only the reference RNG stream is one sequential stream per pixel (RT_RNG_COUNTER sums sample chunks)");
-    if (c.opt.variant != 0) rt_fail("refineFrame: only the default kernels' frame (variant 0) is defined per pixel");
-    if (c.is_spheres && c.opt.floor) rt_fail("refineFrame: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
-    if (c.is_spheres && c.opt.nee) rt_fail("refineFrame: next-event estimation is only defined for mesh scenes");
+    check_per_pixel("refineFrame");
     const DeviceState& d = c.devs[0];
-    const size_t npix = (size_t)c.nx * c.ny, chunk = std::min(npix, (size_t)kPixelChunk);
-    int current = 0;
-    HIP_CHECK(hipGetDevice(&current));
-    HIP_CHECK(hipSetDevice(d.device));
+    const size_t npix = (size_t)c.nx * c.ny, chunk = std::min(npix, kPixelChunk);
+    const int current = begin_query(q);
     RtRefineParams& r = q.planes;
     if (!r.state) {
         r.state = dev_alloc<uint4>(q.owned, npix);
@@ -1592,37 +1604,25 @@ int refineFrame(rt_vec3* out, int32_t* samples, float* error, int batch, int min
     HIP_CHECK(hipMemcpyAsync(&total, r.words + kRefineTotal, sizeof total, hipMemcpyDeviceToHost, d.stream));
     HIP_CHECK(hipStreamSynchronize(d.stream));              // the one readback of a pass: RtPixelBatch::n and the grid of the pixel kernel come from it
     if ((size_t)total > npix) rt_fail("refineFrame: the list is longer than the image");
-    const bool fast = c.opt.fp == RT_FP_FAST;
-    for (size_t first = 0; first < (size_t)total; first += q.chunk_cap) {
+    for_chunks(total, q.chunk_cap, [&](size_t first, size_t m) {
         p.chunk_first = (uint32_t)first;
-        p.chunk_n = (uint32_t)std::min(q.chunk_cap, (size_t)total - first);
+        p.chunk_n = (uint32_t)m;
         HIP_CHECK(rt_launch_refine_gather(p, d.stream));
         HIP_CHECK(hipMemsetAsync(q.d_queue, 0, sizeof(uint32_t), d.stream));
         RtPixelBatch b;
         b.ij = p.b_ij; b.ns = nullptr; b.first = p.b_first; b.state = p.b_state; b.out = nullptr; b.rays = p.b_rays;
-        b.queue = q.d_queue; b.n = (int32_t)p.chunk_n; b.ns_all = batch;
-        if (c.is_spheres) {
-            RtSphereParams sp = sphere_params(d, whole_image_partition());
-            sp.max_depth = c.max_depth; sp.rr = c.opt.rr; sp.rng_mode = c.opt.rng;
-            HIP_CHECK(fast ? rt_launch_pixels_spheres_fast(sp, b, sw.pixels_waves, d.stream) : rt_launch_pixels_spheres_parity(sp, b, sw.pixels_waves, d.stream));
-        } else {
-            RtMeshParams mp = mesh_params(d, whole_image_partition());
-            mp.max_depth = c.max_depth; mp.nee = c.opt.nee; mp.rr = c.opt.rr; mp.rng_mode = c.opt.rng;
-            mp.light = c.opt.light; mp.lightColor = c.opt.lightColor;
-            HIP_CHECK(fast ? rt_launch_pixels_mesh_fast(mp, b, sw.pixels_waves, d.stream) : rt_launch_pixels_mesh_parity(mp, b, sw.pixels_waves, d.stream));
-        }
+        b.queue = q.d_queue; b.n = (int32_t)m; b.ns_all = batch;
+        launch_pixels(d, b, sw.pixels_waves);
         HIP_CHECK(rt_launch_refine_update(p, d.stream));
-    }
+    });
     HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
     if (p.out || p.err) HIP_CHECK(rt_launch_refine_deliver(p, d.stream));
     if (out) HIP_CHECK(hipMemcpyAsync(out, p.out, npix * sizeof(rt_vec3), hipMemcpyDeviceToHost, d.stream));
     if (samples) HIP_CHECK(hipMemcpyAsync(samples, r.n, npix * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
     if (error) HIP_CHECK(hipMemcpyAsync(error, p.err, npix * sizeof(float), hipMemcpyDeviceToHost, d.stream));
     HIP_CHECK(hipStreamSynchronize(d.stream));              // blocking: the caller's planes are complete on return
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, q.ev_start, q.ev_stop));
-    HIP_CHECK(hipSetDevice(current));
-    q.ms = (double)ms;
+    q.ms = query_ms(q);
+    end_query(current);
     q.last_len = total;
     if (total > 0) {
         q.passes = std::min(q.passes, INT_MAX - 1) + 1;
@@ -1647,11 +1647,9 @@ int rtRefineLastList(int32_t* ij, int cap) {
     const size_t n = std::min((size_t)std::max(cap, 0), (size_t)q.last_len);
     if (ij && n > 0) {
         std::vector<uint32_t> ids(n);
-        int current = 0;
-        HIP_CHECK(hipGetDevice(&current));
-        HIP_CHECK(hipSetDevice(q.device));
+        const int current = begin_query(q);
         HIP_CHECK(hipMemcpy(ids.data(), q.planes.list, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipSetDevice(current));
+        end_query(current);
         for (size_t k = 0; k < n; k++) {
             ij[2 * k] = (int32_t)(ids[k] % (uint32_t)g_ctx.nx);
             ij[2 * k + 1] = (int32_t)(ids[k] / (uint32_t)g_ctx.nx);

@@ -1,6 +1,6 @@
 """GPU checks of renderPixels (include/rt_api.h) against the frame rendered in the same process and the CPU oracle's per-pixel region renders
 (tests/pixels_reference.py): bit for bit in PARITY mode - the frame's pixels, per-pixel sample counts, continuation across calls, the smallest lists and
-the refill path through one wave, independence of the partition, the camera and scene edits - nothing another call observes changes, the FAST objects
+the refill path through one wave, a list that crosses RT_PIXEL_CHUNK, independence of the partition, the camera and scene edits - nothing another call observes changes, the FAST objects
 within the tolerance the project states for the FAST frame, and misuse is the library's exit 99."""
 import ctypes as C
 import json
@@ -145,6 +145,39 @@ def test_smallest_shapes_and_the_refill_path(rt, O, tmp_path, case):
     same(got["out"], ref_out, f"{case}: out against the oracle")
     assert np.array_equal(got["rays"], ref_rays)
     assert float(got["ms"]) > 0.0
+
+
+def test_chunk_crossing(rt):
+    """RT_PIXEL_CHUNK + 65 entries on S1 - 257 distinct pixels of the standard list, repeated in order: the second chunk holds 65 entries and starts in the
+    middle of a repetition.  At one sample per entry out, state and rays equal, bit for bit, those of the 257 pixels alone, in the caller's order (the small
+    list is tied to the frame and the oracle by test_equals_the_frame_and_the_oracle); so does the same list continued by one more sample from the returned
+    states - the buffer that goes up and comes down at a chunk's offset.  Adjacent entries of the reference differ: an offset error cannot hide."""
+    n, m = rt.RT_PIXEL_CHUNK + 65, 257
+    assert n == (1 << 22) + 65
+    idx = np.arange(n) % m
+    every, first_seen = PR.standard_list("S1")
+    small = np.ascontiguousarray(every[first_seen][:m])
+    assert len(np.unique(small[:, 1] * 40 + small[:, 0])) == m
+    ij = np.ascontiguousarray(small[idx])
+    PR.init(rt, "S1")
+    try:
+        ref_out, ref_state, ref_rays = rt.render_pixels(small, 1, rays=True)
+        ref2_out, ref2_state, ref2_rays = rt.render_pixels(small, 1, first=np.ones(m, np.int32), state=ref_state, rays=True)
+        out, state, rays = rt.render_pixels(ij, 1, rays=True)
+        ms = rt.last_pixels_ms()
+        out2, state2, rays2 = rt.render_pixels(ij, 1, first=np.ones(n, np.int32), state=state, rays=True)
+        ms2 = rt.last_pixels_ms()
+    finally:
+        rt.cleanupRenderer()
+    print("entries", n, "kernel ms", ms, ms2)
+    for ref in (ref_out, ref2_out):                         # entry k against entry k + 1, the last against the first of the next repetition
+        assert (bits(ref) != bits(np.roll(ref, -1, axis=0))).any(axis=1).all()
+    assert ms > 0.0 and ms2 > 0.0
+    same(out, ref_out[idx], "one sample across the chunk boundary, out")
+    assert np.array_equal(state, ref_state[idx]) and np.array_equal(rays, ref_rays[idx])
+    same(out2, ref2_out[idx], "continued by one sample across the chunk boundary, out")
+    assert np.array_equal(state2, ref2_state[idx]) and np.array_equal(rays2, ref2_rays[idx])
+    assert not np.array_equal(ref2_state, ref_state) and (ref_rays > 0).all()
 
 
 # ---- 5. independence -------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,8 @@ kernel parameter block is assigned in exactly one place (sphere_params / mesh_pa
 the scene; RenderContext holds the scene as the two layout structs of rt_scene_layout.h, which keep the scene's constants in parameter-block form (their
 `scene` templates), not as a second set of members that is copied across field by field; and the whole-image preview passes (denoiseFrame,
 accumulateFrame) share one state struct (PassState), one release (free_pass) and one path around their kernels (begin_pass / end_pass), so a third pass
-is not a third copy of them."""
+is not a third copy of them; and the query calls (traceRays / occludedRays, renderPixels, refineFrame) share one state base, one chunked path, one launch
+of the pixel kernels and one statement of what a path is (sphere_path_params / mesh_path_params), which a frame takes too."""
 import os
 import re
 
@@ -24,6 +25,10 @@ MIRRORED = ["n_spheres", "n_padded", "n_groups", "n_big_groups", "n_big", "globa
 # what every whole-image pass holds on the device
 PASS_MEMBERS = ["device", "npix", "owned", "d_guide", "d_in", "d_out"]
 PASSES = {"denoiseFrame", "accumulateFrame"}
+# the query calls and their chunk functions: whichever of them the file defines
+QUERIES = {"traceRays", "occludedRays", "renderPixels", "refineFrame", "rtRefineLastList", "run_rays", "run_pixels"}
+QUERY_MEMBERS = ["device", "owned", "ev_start", "ev_stop"]
+QUERY_STATES = ["g_rays", "g_pixels", "g_refine"]
 
 
 def _source(path=RENDERER):
@@ -106,3 +111,75 @@ def test_pass_members_are_declared_in_one_struct():
     assert len(whole) == 1, holders
     for name in ("npix", "d_in", "d_out"):                      # (a DeviceState has a device, a record of its allocations and guide planes of its own rows)
         assert holders[name] == whole, (name, holders[name])
+
+
+# ---- the query calls (traceRays / occludedRays, renderPixels, refineFrame): one state base, one chunked path, one pixel launch, one statement of a path ----
+
+def _body(src, name):
+    bodies = [src[a:b] for n, a, b in _functions(src) if n == name]
+    assert len(bodies) == 1, (name, len(bodies))
+    return bodies[0]
+
+
+def _assigners(src, field):
+    """The functions that assign `.field` of a struct as a whole - `o->light.center.e[0] = ...` writes an element, not the field - in the file's order.
+    RenderContext's own max_depth (`c.max_depth = ...`, common_init) is what the parameter blocks copy, not one of them."""
+    funcs = _functions(src)
+    return [_enclosing(funcs, m.start()) for m in re.finditer(r"(?<!\bc)\.%s\b\s*=(?!=)" % field, src)]
+
+
+def test_the_query_calls_leave_memory_events_and_the_current_device_to_the_shared_path():
+    src = _source()
+    defined = {n for n, _, _ in _functions(src)}
+    assert {"traceRays", "occludedRays", "renderPixels", "refineFrame", "rtRefineLastList"} <= defined
+    for call in ("hipMalloc", "hipFree", "hipEventCreate", "hipGetDevice", "hipSetDevice", "hipEventElapsedTime"):
+        callers = set(_callers(src, call))
+        assert callers, call
+        assert not QUERIES & callers, (call, sorted(QUERIES & callers))
+    assert set(_callers(src, "hipEventCreate")) == {"setup_devices", "begin_pass"}
+
+
+def test_the_ray_and_pixel_kernels_are_launched_from_one_place_each():
+    src = _source()
+    for name in ("rt_launch_pixels_spheres_parity", "rt_launch_pixels_spheres_fast", "rt_launch_pixels_mesh_parity", "rt_launch_pixels_mesh_fast",
+                 "rt_launch_rays_spheres", "rt_launch_rays_mesh"):
+        n = len(re.findall(r"\b%s\b" % name, src))
+        assert n == 1, f"{name} occurs {n} times"
+    launchers = {c for name in ("parity", "fast") for kind in ("spheres", "mesh") for c in _callers(src, f"rt_launch_pixels_{kind}_{name}")}
+    assert launchers == {"launch_pixels"}, launchers
+    assert {"run_pixels", "refineFrame"} <= set(_callers(src, "launch_pixels"))
+
+
+def test_what_a_path_is_is_assigned_once_per_scene_kind():
+    src = _source()
+    for field in ("max_depth", "rr", "rng_mode"):
+        assert _assigners(src, field) == ["sphere_path_params", "mesh_path_params"], (field, _assigners(src, field))
+    for field in ("nee", "light", "lightColor"):
+        assert _assigners(src, field) == ["mesh_path_params"], (field, _assigners(src, field))
+    for fn in ("render_frame", "launch_pixels"):
+        assert "sphere_path_params" in _body(src, fn) and "mesh_path_params" in _body(src, fn), fn
+
+
+def test_the_query_states_share_one_base():
+    src = _source()
+    structs = {name: (base, body) for name, base, body in re.findall(r"^struct (\w+)(?:\s*:\s*(\w+))?\s*\{(.*?)^\};", src, re.M | re.S)}
+    declares = lambda struct, member: re.search(r"\b%s\b\s*(?:\[\d+\]\s*)?[=;,]" % member, structs[struct][1]) is not None
+    types = []
+    for var in QUERY_STATES:
+        m = re.search(r"^(\w+)\s+(?:\w+\s*,\s*)*%s\b[^;()]*;" % var, src, re.M)
+        assert m and m.group(1) in structs, var
+        types.append(m.group(1))
+    bases = {structs[t][0] for t in types}
+    assert len(bases) == 1 and bases != {""}, dict(zip(QUERY_STATES, [(t, structs[t][0]) for t in types]))
+    base = bases.pop()
+    assert base != "PassState" and structs[base][0] == ""
+    for member in QUERY_MEMBERS:
+        assert declares(base, member), (base, member)
+        assert not [t for t in types if declares(t, member)], (member, types)
+
+
+def test_every_query_state_is_released_where_the_passes_are():
+    src = _source()
+    for fn in ("setup_devices", "cleanup_impl"):
+        for var in QUERY_STATES:
+            assert re.search(r"\bfree_pass\(%s\)" % var, _body(src, fn)), (fn, var)
