@@ -122,11 +122,24 @@ def real_triangles(hm):
     return hm.tris[~np.isinf(hm.tris["v"][:, 0, 0])]
 
 
-def frame_options(rt, O, name, nee=1, floor=None):
-    """The oracle's options of a frame: mesh defaults with `nee`, and the floor plane on for the soups unless floor = 0."""
+def light_structs(rt, light):
+    """(rt.sphere, rt.vec3) of a light ((centre xyz), radius, (colour rgb)): the values of rt_render_options.light and .lightColor."""
+    (cx, cy, cz), radius, (r, g, b) = light
+    sp, col = rt.sphere(), rt.vec3()
+    sp.center.e[:] = (cx, cy, cz)
+    sp.radius = radius
+    col.e[:] = (r, g, b)
+    return sp, col
+
+
+def frame_options(rt, O, name, nee=1, floor=None, light=None):
+    """The oracle's options of a frame: mesh defaults with `nee`, and the floor plane on for the soups unless floor = 0.  light: None for the default light,
+    else ((centre xyz), radius, (colour rgb))."""
     o = O.default_options(False)
     o.nee = nee
     o.floor = (1 if is_soup(name) else 0) if floor is None else floor
+    if light is not None:
+        o.light, o.lightColor = light_structs(rt, light)
     return o
 
 
@@ -135,21 +148,22 @@ def device_options(name, nee=1, floor=None, **more):
     return dict(more, nee=nee, floor=(1 if is_soup(name) else 0) if floor is None else floor)
 
 
-def oracle_render(rt, O, name, ns, mats, nee=1, floor=None, lib=None):
+def oracle_render(rt, O, name, ns, mats, nee=1, floor=None, lib=None, light=None):
     """(frame, counters) of the oracle (lib: O.load_nudge() for the nudged twin) for the frame's scene with the table `mats`."""
     f = frame(rt, O, name)
-    fb, cnt = O.render(O.mesh_scene(f["hm"], mats, f["tex"], floor=f["floor"]), f["cam"], frame_options(rt, O, name, nee, floor), f["nx"], f["ny"], ns,
+    fb, cnt = O.render(O.mesh_scene(f["hm"], mats, f["tex"], floor=f["floor"]), f["cam"], frame_options(rt, O, name, nee, floor, light), f["nx"], f["ny"], ns,
                        f["depth"], counters=True, lib=lib)
     fb.setflags(write=False)
     return fb, cnt
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_frame(rt, O, name, ns, nee=1, floor=None, table="own", nudged=False):
-    """The oracle's frame and counters, computed once and read-only.  table: "own", "swapped" (swapped()), "plain" (stair frames: plain_stair_table())."""
+def oracle_frame(rt, O, name, ns, nee=1, floor=None, table="own", nudged=False, light=None):
+    """The oracle's frame and counters, computed once and read-only.  table: "own", "swapped" (swapped()), "plain" (stair frames: plain_stair_table());
+    light: as frame_options."""
     mats = frame(rt, O, name)["mats"]
     mats = {"own": mats, "swapped": swapped(rt, mats), "plain": plain_stair_table(rt) if not is_soup(name) else None}[table]
-    return oracle_render(rt, O, name, ns, mats, nee, floor, O.load_nudge() if nudged else None)
+    return oracle_render(rt, O, name, ns, mats, nee, floor, O.load_nudge() if nudged else None, light)
 
 
 @functools.lru_cache(maxsize=None)

@@ -352,6 +352,35 @@ def test_generate_shadow_ray(rt, probe, O):
     assert n_gen > 500 and n_nan > 100 and n_rej > 100, (n_gen, n_nan, n_rej)
 
 
+def test_generate_shadow_ray_light_regimes(rt, probe, O):
+    """The same, with a light and a colour per call: the regimes of tests/mesh_lights_support.py (shadow_regimes) - a near light (|org - c| / R in (1, 2]),
+    radii 1e-3, 1e-4 (cosAMax = 1, sinA = 0) and 0, origins a float above and below the sphere's surface and at its centre (0 / 0: NaN before any draw),
+    directions on both sides of the 0.01 switch of the tangent frame, and the colours (30, 12, 3), (0, 5, 0), (-1, 2, 3), (1e30, 1, 1e-40).  Every output
+    exact against O.generate_shadow_ray; each regime has the outcomes it is named for in at least the stated number of cases (held on the CPU by
+    tests/test_oracle_vs_ref.py)."""
+    import mesh_lights_support as L
+    for reg in L.shadow_regimes():
+        exp = L.regime_oracle(rt, O, reg)
+        counts = L.regime_outcomes(exp)
+        for outcome, least in reg["expect"].items():
+            assert counts[outcome] >= least, (reg["name"], outcome, counts)
+        for sel, light, colour in L.regime_lights(rt, reg):
+            ok, sdir, lcon, dist, cam, draws, sa = probe.shadow_ray(light, colour, reg["org"][sel], reg["att"][sel], reg["nrm"][sel], reg["seeds"][sel])
+            what = (reg["name"], float(light.radius))
+            # cosAMax: the bits; where it is NaN, a NaN (IEEE 754 leaves the sign of the NaN an invalid operation makes to the implementation: 0 / 0 of the
+            # `centre` regime is 0xFFC00000 on the oracle's x86 and 0x7FC00000 on the device; nothing but isnan() reads it)
+            e_cam = exp["cos_a_max"][sel]
+            nan = np.isnan(e_cam)
+            assert np.array_equal(np.isnan(cam), nan) and np.array_equal(_bits(cam)[~nan], _bits(e_cam)[~nan]), (what, "cosAMax")
+            assert np.array_equal(draws, exp["draws"][sel]) and np.array_equal(sa, exp["rng_after"][sel]), (what, "draws / stream position")
+            assert np.array_equal(ok != 0, exp["generated"][sel] != 0), (what, "the dotl > 0 decision")
+            gen = exp["generated"][sel] != 0
+            for name, got, want in (("lightDist", dist, exp["dist"]), ("shadowDir", sdir, exp["dir"]), ("lightContribution", lcon, exp["contribution"])):
+                bad = _bits(got[gen]) != _bits(want[sel][gen])
+                assert not bad.any(), (what, name, int(bad.sum()), got[gen][bad.reshape(len(bad), -1).any(axis=1)][:3].tolist(),
+                                       want[sel][gen][bad.reshape(len(bad), -1).any(axis=1)][:3].tolist())
+
+
 def test_plane_hit(rt, probe, lib):
     rng = np.random.default_rng(16)
     pl = np.zeros((N, 6), np.float32)

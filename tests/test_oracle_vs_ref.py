@@ -2,7 +2,9 @@
 frames.  The reference side comes from the reference compiled where its sources exist (oracle/_ref/libref.so, libref_main.so);
 elsewhere from tests/golden/vs_ref.npz: the same reference calls on the same seeded inputs, frozen.  Where the shims exist the live
 outputs must also equal the frozen ones, so the file cannot go stale.  To re-mint it where the shims exist:
-RT_MINT_VS_REF=tests/golden/vs_ref.npz python -m pytest tests/test_oracle_vs_ref.py"""
+RT_MINT_VS_REF=tests/golden/vs_ref.npz python -m pytest tests/test_oracle_vs_ref.py
+The keys of the lights of tests/mesh_lights_support.py live in a second file, tests/golden/vs_ref_lights.npz (one file would pass the size limit of a
+committed file); the same command writes it beside the first, as <the given name>_lights.npz."""
 import ctypes as C
 import hashlib
 import os
@@ -10,32 +12,37 @@ import os
 import numpy as np
 import pytest
 
+import mesh_lights_support as L
+import mesh_materials_support as M
 from oracle import oracle as O
 
 FLT_MAX = float(np.finfo(np.float32).max)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vs_ref.npz")
+GOLDEN_LIGHTS = GOLDEN[:-len(".npz")] + "_lights.npz"
 MINT = os.environ.get("RT_MINT_VS_REF")
 _minted = {}
-_golden = None
+_golden = {}
 
 
-def _reference(key, live, have=O.have_ref):
-    """The reference's outputs for `key` as a dict of arrays: live() where the shim was built (checked against the frozen copy,
+def _reference(key, live, have=O.have_ref, golden=GOLDEN):
+    """The reference's outputs for `key` as a dict of arrays: live() where the shim was built (checked against the frozen copy in `golden`,
     or recorded into RT_MINT_VS_REF), else the frozen copy."""
-    global _golden
-    if _golden is None and os.path.exists(GOLDEN):
-        with np.load(GOLDEN) as z:
-            _golden = {k: z[k] for k in z.files}
-    frozen = {k[len(key) + 1:]: v for k, v in (_golden or {}).items() if k.startswith(key + "/")}
+    if golden not in _golden:
+        _golden[golden] = {}
+        if os.path.exists(golden):
+            with np.load(golden) as z:
+                _golden[golden] = {k: z[k] for k in z.files}
+    frozen = {k[len(key) + 1:]: v for k, v in _golden[golden].items() if k.startswith(key + "/")}
     if not have():
-        assert frozen, f"{key}: no reference shim and no frozen outputs in {GOLDEN}"
+        assert frozen, f"{key}: no reference shim and no frozen outputs in {golden}"
         return frozen
     out = {k: np.asarray(v) for k, v in live().items()}
     if MINT:
-        _minted.update({f"{key}/{k}": v for k, v in out.items()})
-        np.savez_compressed(MINT, **_minted)
+        minted = _minted.setdefault(golden, {})
+        minted.update({f"{key}/{k}": v for k, v in out.items()})
+        np.savez_compressed(MINT if golden == GOLDEN else MINT[:-len(".npz")] + "_lights.npz", **minted)
     else:
-        assert set(out) == set(frozen) and all(out[k].tobytes() == frozen[k].tobytes() for k in out), f"{key}: {GOLDEN} is stale"
+        assert set(out) == set(frozen) and all(out[k].tobytes() == frozen[k].tobytes() for k in out), f"{key}: {golden} is stale"
     return out
 
 
@@ -269,10 +276,11 @@ def _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, depth):
 
 
 @pytest.mark.parametrize("kw", [{}, {"nee": 0}, {"nee": 0, "rr": 0}, {"sky": 1}, {"floor": 1}, {"floor": 1, "nee": 0}, {"rng": 1},
-                                {"light_radius": 900.0}])
+                                {"light_radius": 900.0}, {"light": "inside"}])
 def test_mesh_frames_oracle_equals_reference_twin_staircase(rt, kw):
     """Frames + every counter, NEE on and off, RR on and off, gradient sky, the floor call site re-enabled (kernels.cu:341-345),
-    counter RNG, and a light so big that cosAMax is NaN for part of the scene (kernels.cu:371-372)."""
+    counter RNG, a light so big that cosAMax is NaN for part of the scene (kernels.cu:371-372), and the coloured light `inside` of
+    tests/mesh_lights_support.py: in the middle of the scene, with occluders behind it."""
     tris, mats = rt.scene_staircase_procedural(1)
     hm = rt.HostMesh.build(tris, 5)
     nx, ny, ns = 64, 80, 2
@@ -282,13 +290,16 @@ def test_mesh_frames_oracle_equals_reference_twin_staircase(rt, kw):
     kw = dict(kw)
     if "light_radius" in kw:
         opt.light.radius = kw.pop("light_radius")
+    golden = GOLDEN_LIGHTS if "light" in kw else GOLDEN
+    if "light" in kw:
+        opt.light, opt.lightColor = M.light_structs(rt, L.light_of("stair_exact", kw.pop("light")))
     for k, v in kw.items():
         setattr(opt, k, v)
     lo = np.array(hm.view.bounds.min.e[:])
     floor = (0.0, 1.0, 0.0, 0.0, float(lo[1]) - 5.0, 0.0)                 # plane(point, norm): norm first (helper_structs.h:165-171)
     sc = O.mesh_scene(hm, mats, floor=floor)
     a, ca = O.render(sc, cam, opt, nx, ny, ns, 64, counters=True)
-    ref = _reference(key, lambda: _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, 64))
+    ref = _reference(key, lambda: _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, 64), golden=golden)
     assert np.array_equal(_bits(a), _bits(ref["frame"])), np.count_nonzero(_bits(a) != _bits(ref["frame"]))
     assert np.array_equal(_counters(ca), ref["counters"])
     assert ca.ref_stats[rt.RT_STAT_PRIMARY] == nx * ny * ns and ca.ref_stats[rt.RT_STAT_PRIMARY] + ca.ref_stats[rt.RT_STAT_SECONDARY] == ca.rays
@@ -298,6 +309,19 @@ def test_mesh_frames_oracle_equals_reference_twin_staircase(rt, kw):
 
 @pytest.mark.parametrize("n,nppl,nee,floor", [(1, 1, 1, 0), (7, 5, 1, 1), (65, 3, 0, 1), (1000, 5, 1, 0), (1000, 16, 0, 0), (300, 20, 1, 1)])
 def test_mesh_frames_oracle_equals_reference_twin_soups(rt, n, nppl, nee, floor):
+    _soup_frame_equals_reference_twin(rt, n, nppl, nee, floor, None)
+
+
+@pytest.mark.parametrize("n,nppl,nee,floor,light", [(1000, 5, 1, 1, "inside"), (300, 20, 1, 1, "inside"), (1000, 5, 1, 1, "low"), (1000, 16, 0, 1, "sky")])
+def test_mesh_frames_oracle_equals_reference_twin_soups_lights(rt, n, nppl, nee, floor, light):
+    """The same soups under a coloured light of tests/mesh_lights_support.py (they fill the same box over the same floor as its soup_exact): `inside`
+    among the triangles, `low` between the floor and the bounds (shadow rays from the floor end before they reach the bounds), `sky` with nee = 0 (seen
+    directly by specular paths that leave the scene)."""
+    _soup_frame_equals_reference_twin(rt, n, nppl, nee, floor, light)
+
+
+def _soup_frame_equals_reference_twin(rt, n, nppl, nee, floor, light):
+    """light: None = a light above the soup, outside its bounds; else the name of a light of tests/mesh_lights_support.py."""
     rng = np.random.default_rng(777 + 13 * n + nppl)
     tris, mats = _triangle_soup(rt, rng, n)
     tex = [rng.uniform(0, 1, (9, 13, 3)).astype(np.float32)]
@@ -309,15 +333,27 @@ def test_mesh_frames_oracle_equals_reference_twin_soups(rt, n, nppl, nee, floor)
     opt.nee = nee
     opt.light.center.e[:] = (3.0, 9.0, 2.0); opt.light.radius = 1.5       # a light the soup can actually shadow
     opt.floor = floor
+    key, golden = f"mesh_soup_{n}_{nppl}_{nee}_{floor}", GOLDEN
+    if light is not None:
+        opt.light, opt.lightColor = M.light_structs(rt, L.light_of("soup_exact", light))
+        key, golden = f"{key}_{light}", GOLDEN_LIGHTS
     sc = O.mesh_scene(hm, mats, tex, floor=(0.0, 1.0, 0.0, 0.0, -3.0, 0.0))   # plane {norm, point} (helper_structs.h:165-171)
     a, ca = O.render(sc, cam, opt, nx, ny, ns, 12, counters=True)
-    ref = _reference(f"mesh_soup_{n}_{nppl}_{nee}_{floor}", lambda: _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, 12))
+    ref = _reference(key, lambda: _mesh_frame_and_counters(sc, cam, opt, nx, ny, ns, 12), golden=golden)
     assert np.array_equal(_bits(a), _bits(ref["frame"])), np.count_nonzero(_bits(a) != _bits(ref["frame"]))
     assert np.array_equal(_counters(ca), ref["counters"])
     if floor:       # primary rays that hit only the floor count as "primary nohit" (kernels.cu:430); paths leaving the floor into the sky as "secondary no hit"
         assert ca.ref_stats[rt.RT_STAT_SECONDARY_NOHIT] > 0 and ca.ref_stats[rt.RT_STAT_PRIMARY_NOHITS] > 0
     else:
         assert ca.ref_stats[rt.RT_STAT_SECONDARY_NOHIT] == 0
+    if light == "low":
+        assert 0 < ca.ref_stats[rt.RT_STAT_SHADOWS_BBOX_NOHITS] < ca.ref_stats[rt.RT_STAT_SHADOWS]
+    if light == "inside":
+        assert 0 < ca.ref_stats[rt.RT_STAT_SHADOWS_NOHITS] < ca.ref_stats[rt.RT_STAT_SHADOWS] and ca.ref_stats[rt.RT_STAT_SHADOWS_BBOX_NOHITS] == 0
+    if light == "sky":
+        black = rt.vec3()
+        opt.lightColor = black
+        assert np.count_nonzero((_bits(O.render(sc, cam, opt, nx, ny, ns, 12)[0]) != _bits(a)).any(axis=2)) >= 20       # the light is seen directly
 
 
 def _shadow_rays(opt, cases, which):
@@ -364,6 +400,43 @@ def test_generate_shadow_ray_oracle_equals_reference_twin(rt):
             n_rej += 1
             assert ra["draws"][k] == 2
     assert n_gen > 500 and n_nan > 100 and n_rej > 100
+
+
+@pytest.mark.parametrize("regime", [r["name"] for r in L.shadow_regimes()])
+def test_generate_shadow_ray_regimes_oracle_equals_reference_twin(rt, regime):
+    """The same on the regimes of tests/mesh_lights_support.py (shadow_regimes: a light of its own per regime - near, cosAMax = 1 by a small and by a
+    zero radius, origins a float off the sphere's surface and at its centre, both sides of the tangent frame's switch, odd colours), and each regime
+    yields the outcomes it is named for: the counts tests/test_gpu_probe_functions.py relies on."""
+    reg = next(r for r in L.shadow_regimes() if r["name"] == regime)
+    ra = L.regime_oracle(rt, O, reg)
+    rb = _reference(f"shadow_regime_{regime}", lambda: L.regime_oracle(rt, O, reg, "ref"), golden=GOLDEN_LIGHTS)
+    for k in ("generated", "draws", "rng_after"):
+        assert np.array_equal(ra[k], rb[k]), k
+    assert np.array_equal(_bits(ra["cos_a_max"]), _bits(rb["cos_a_max"]))
+    gen = ra["generated"] != 0
+    for k in ("dir", "contribution", "dist"):
+        assert np.array_equal(_bits(ra[k][gen]), _bits(rb[k][gen])), k
+    got = L.regime_outcomes(ra)
+    print(regime, got, "cosAMax", float(np.nanmin(ra["cos_a_max"])) if not np.isnan(ra["cos_a_max"]).all() else None, "to",
+          float(np.nanmax(ra["cos_a_max"])) if not np.isnan(ra["cos_a_max"]).all() else None)
+    for outcome, least in reg["expect"].items():
+        assert got[outcome] >= least, (regime, outcome, got)
+    cam = ra["cos_a_max"]
+    if regime == "near":
+        assert cam.min() < 0.1 and cam.max() < 0.87
+    if regime in ("small", "zero"):
+        assert (cam == 1.0).all() and (ra["contribution"][gen] == 0).all() and not np.signbit(ra["contribution"][gen]).any()
+    if regime == "near_one":
+        assert (cam < 1.0).all() and (cam > 0.99999).all()
+    if regime == "surface":
+        assert gen[0::2].sum() >= 100 and gen[1::2].sum() >= 100 and (~gen)[0::2].sum() >= 100 and (~gen)[1::2].sum() >= 100
+    if regime == "switch":
+        sw = np.array(reg["centre"]) - reg["org"].astype(np.float64)
+        x = np.abs(sw[:, 0] / np.linalg.norm(sw, axis=1))
+        assert (gen & (x > 0.0101)).sum() >= 100 and (gen & (x < 0.0099)).sum() >= 100
+    if regime == "colour_3":
+        c = ra["contribution"][gen]
+        assert c[:, 0].max() > 1e28 and ((c[:, 2] != 0) & (np.abs(c[:, 2]) < 1.2e-38)).sum() >= 100       # subnormal results
 
 
 # ---- the host I/O either side of the path, against the reference's own code (SURVEY.md §8 f-1 / f-2) -----------------------------------------
