@@ -66,7 +66,12 @@ $(OBJ)/build.o: $(CSRC)/rt_kernels_build.hip $(CSRC)/rt_build.h include/rt_types
 # defined bit for bit as the passes above, so one object with the flags of display.o.  Its own TU and header: no other kernel object depends on it.
 $(OBJ)/refine.o: $(CSRC)/rt_kernels_refine.hip $(CSRC)/rt_refine.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The kernels of rtMarkPose / renderMotion (the motion planes the temporal passes read with a pose marked; the gather that carries the mark through a rebuild):
+# defined bit for bit as the passes above, so one object with the flags of accumulate.o; the launcher's host arithmetic is compiled under them too.  Its own
+# TU and header: no other kernel object depends on it.
+$(OBJ)/motion.o: $(CSRC)/rt_kernels_motion.hip $(CSRC)/rt_motion.h include/rt_types.h include/rt_api.h | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_motion.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o
@@ -75,9 +80,10 @@ DISPLAY_OBJS := $(OBJ)/display.o
 UPDATE_OBJS := $(OBJ)/update.o
 BUILD_OBJS := $(OBJ)/build.o
 REFINE_OBJS := $(OBJ)/refine.o
+MOTION_OBJS := $(OBJ)/motion.o
 
-$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) -o $@
+$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) -o $@
 
 $(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp include/rt_host.h include/rt_types.h include/rt_api.h
 	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp -o $@

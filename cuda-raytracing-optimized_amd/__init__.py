@@ -141,6 +141,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "refineFrame", "rtResetRefine", "rtRefineSamples", "rtRefineLastList", "rtLastRefineMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
+                    "rtMarkPose", "rtClearPose", "rtPoseMarked", "renderMotion", "rtLastMotionMs",
                     "rtLastSphereForm"]
 RT_API_VERSION = 1002       # include/rt_api.h: the version this mirror was written against
 # the structs that cross the C-ABI, in the order of the RT_SIZEOF_* indices of include/rt_api.h
@@ -350,6 +351,16 @@ def load_renderer():
         r.rebuildBvh.restype = None
         r.rtLastRebuildMs.argtypes = []
         r.rtLastRebuildMs.restype = C.c_double
+        r.rtMarkPose.argtypes = []
+        r.rtMarkPose.restype = None
+        r.rtClearPose.argtypes = []
+        r.rtClearPose.restype = None
+        r.rtPoseMarked.argtypes = []
+        r.rtPoseMarked.restype = C.c_int
+        r.renderMotion.argtypes = [C.c_int, C.POINTER(camera), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        r.renderMotion.restype = None
+        r.rtLastMotionMs.argtypes = []
+        r.rtLastMotionMs.restype = C.c_double
         _renderer = r
     return _renderer
 
@@ -1022,6 +1033,50 @@ def preview_frames():
 def last_preview_ms():
     """HIP-event time of the kernels of the last previewFrame (temporal, variance, iterations), in milliseconds; 0 before the first call."""
     return load_renderer().rtLastPreviewMs()
+
+
+# rtMarkPose / renderMotion (include/rt_api.h): the planes of the mask
+RT_MOTION_POS, RT_MOTION_NORMAL, RT_MOTION_SCREEN = 1, 2, 4
+MOTION_PLANES = (("prev_pos", RT_MOTION_POS, 3), ("prev_normal", RT_MOTION_NORMAL, 3), ("screen", RT_MOTION_SCREEN, 2))
+
+
+def mark_pose():
+    """Remembers the scene's geometry as it is now - "the previous frame's pose" (rtMarkPose): from now on accumulateFrame and previewFrame reproject every
+    pixel through the point its surface point had in that pose, so what an edit moves keeps its history.  The loop of an animated frame: mark_pose,
+    update_triangles / update_spheres (and rebuild_bvh), setCamera, runRenderer(1), previewFrame, display_frame."""
+    load_renderer().rtMarkPose()
+
+
+def clear_pose():
+    """Forgets the marked pose (rtClearPose): the passes reproject through the current hit points again."""
+    load_renderer().rtClearPose()
+
+
+def pose_marked():
+    """True while a pose is marked."""
+    return bool(load_renderer().rtPoseMarked())
+
+
+def renderMotion(prev_cam=None, mask=RT_MOTION_POS | RT_MOTION_NORMAL | RT_MOTION_SCREEN):
+    """The motion planes of the current camera against the marked pose (include/rt_api.h).  Returns a dict with the planes of `mask`: prev_pos, prev_normal
+    (ny, nx, 3) float32 - where every pixel's surface point was in the marked pose and the normal it had there - and screen (ny, nx, 2) float32 - where
+    prev_cam (None = the current camera) saw that point, relative to the pixel, in pixels.  Without a marked pose prev_pos and prev_normal are the current hit
+    point and normal.  Blocking; always the whole image on the first device."""
+    nx, ny = _state["nx"], _state["ny"]
+    res, ptrs = {}, []
+    for name, bit, comps in MOTION_PLANES:
+        if not (mask & bit):
+            ptrs.append(None)
+            continue
+        res[name] = np.zeros((ny, nx, comps), np.float32)
+        ptrs.append(res[name].ctypes.data_as(C.POINTER(C.c_float)))
+    load_renderer().renderMotion(mask, None if prev_cam is None else C.byref(prev_cam), *ptrs)
+    return res
+
+
+def last_motion_ms():
+    """HIP-event time of the motion kernel of the last renderMotion, in milliseconds; 0 before the first call."""
+    return load_renderer().rtLastMotionMs()
 
 
 # displayFrame (include/rt_api.h): the flags, the tone maps, the histogram's size, the key the median luminance is exposed to, the dither matrix

@@ -27,6 +27,7 @@ struct RtAccumulateParams {
     float4* next;               // 3 * npix: this call's
     int32_t flags, has_history;
     float max_history, sigma_z, normal_min;
+    const float4* motion;       // 2 * npix: (Pm, -), (nm, -) of rt_motion.h for this call's camera, with a pose marked and a history; null = P, n themselves
 };
 
 // One kernel: reprojection, the four taps, the blend, the records of the next call, out.  prev_cam is C' (ignored with has_history = 0).  Returns the

@@ -38,8 +38,9 @@ __device__ __forceinline__ void unit3(float& x, float& y, float& z) {
 }
 
 // Stage T.  k_accumulate's reprojection and taps with two more accumulated quantities, the moments of the luminance; a tap reads the 8-byte moment record
-// beside its three 16-byte ones.
-template <bool HIST>
+// beside its three 16-byte ones.  MOTION: a pose is marked (rtMarkPose) - the reprojection and the taps' plane and normal tests take Pm(p), nm(p) of the
+// motion planes (rt_motion.h) in the place of P(p), n(p), as k_accumulate's; MOTION = false is the kernel as it was.
+template <bool HIST, bool MOTION>
 __global__ void __launch_bounds__(kPreviewThreads) k_preview_temporal(const RtPreviewParams D) {
     int i, j;
     if (!tile_pixel(D.nx, D.ny, i, j)) return;
@@ -68,7 +69,13 @@ __global__ void __launch_bounds__(kPreviewThreads) k_preview_temporal(const RtPr
     if (HIST) {
         const float rz = 1.0f / (D.sigma_z * t);
         const bool same_prim = (D.flags & RT_DENOISE_SAME_PRIM) != 0;
-        const float e[3] = { P[0] - D.prev_origin.e[0], P[1] - D.prev_origin.e[1], P[2] - D.prev_origin.e[2] };
+        float Pm[3] = { P[0], P[1], P[2] }, nm[3] = { n[0], n[1], n[2] };
+        if (MOTION) {
+            const float4 mp = D.motion[px], mn = D.motion[npix + px];
+            Pm[0] = mp.x; Pm[1] = mp.y; Pm[2] = mp.z;
+            nm[0] = mn.x; nm[1] = mn.y; nm[2] = mn.z;
+        }
+        const float e[3] = { Pm[0] - D.prev_origin.e[0], Pm[1] - D.prev_origin.e[1], Pm[2] - D.prev_origin.e[2] };
         const float ea = dot3(e, D.prev_u.e), eb = dot3(e, D.prev_v.e), ec = dot3(e, D.prev_w.e);
         const float r = D.Lw / ec;
         const float s = (ea * r - D.Lu) / D.Hl, tt = (eb * r - D.Lv) / D.Vl;
@@ -95,9 +102,9 @@ __global__ void __launch_bounds__(kPreviewThreads) k_preview_temporal(const RtPr
 #pragma unroll
         for (int k = 0; k < 4; k++) {                           // dy = k >> 1 (outer), dx = k & 1 (inner)
             const float bw = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-            const float ex = pq[k].x - P[0], ey = pq[k].y - P[1], ez = pq[k].z - P[2];
-            const float pd = fabsf(n[0] * ex + n[1] * ey + n[2] * ez) * rz;
-            const float dn = n[0] * gq[k].x + n[1] * gq[k].y + n[2] * gq[k].z;
+            const float ex = pq[k].x - Pm[0], ey = pq[k].y - Pm[1], ez = pq[k].z - Pm[2];
+            const float pd = fabsf(nm[0] * ex + nm[1] * ey + nm[2] * ez) * rz;
+            const float dn = nm[0] * gq[k].x + nm[1] * gq[k].y + nm[2] * gq[k].z;
             const bool other_prim = same_prim & (prim != __float_as_int(gq[k].w));
             const bool ok = inside[k] & (pq[k].w > 0.0f) & (pd < 1.0f) & (dn >= D.normal_min) & !other_prim;
             sum[0] = ok ? sum[0] + bw * cq[k].x : sum[0];
@@ -279,8 +286,9 @@ hipError_t rt_launch_preview_temporal(RtPreviewParams p, const rt_camera& prev_c
         p.Vl = dot3(prev_cam.vertical.e, prev_cam.v.e);
     }
     const dim3 grid = tile_grid(p), block(kPreviewThreads);
-    if (p.has_history) hipLaunchKernelGGL(k_preview_temporal<true>, grid, block, 0, stream, p);
-    else hipLaunchKernelGGL(k_preview_temporal<false>, grid, block, 0, stream, p);
+    if (p.has_history && p.motion) hipLaunchKernelGGL((k_preview_temporal<true, true>), grid, block, 0, stream, p);
+    else if (p.has_history) hipLaunchKernelGGL((k_preview_temporal<true, false>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((k_preview_temporal<false, false>), grid, block, 0, stream, p);
     return hipGetLastError();
 }
 

@@ -36,6 +36,7 @@ struct RtPreviewParams {
     float4* col[2];             // npix each: (c.xyz, var) of the a-trous iterations
     int32_t flags, has_history, normal_squarings;
     float max_history, sigma_z, normal_min, sigma_l;
+    const float4* motion;       // 2 * npix: (Pm, -), (nm, -) of rt_motion.h for this call's camera, with a pose marked and a history; null = P, n themselves
 };
 
 // Stage T: reprojection, the four taps, the blend of colour and moments, the records of the next call; pixels without a first hit: out = in.  prev_cam is C'

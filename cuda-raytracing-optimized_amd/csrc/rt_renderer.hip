@@ -32,6 +32,7 @@
 #include "rt_denoise.h"
 #include "rt_accumulate.h"
 #include "rt_preview.h"
+#include "rt_motion.h"
 #include "rt_display.h"
 #include "rt_update.h"
 #include "rt_build.h"
@@ -174,6 +175,7 @@ struct RenderContext {
     double display_ms = 0.0;            // rtLastDisplayMs
     double rays_ms = 0.0;               // rtLastRaysMs
     double pixels_ms = 0.0;             // rtLastPixelsMs
+    double motion_ms = 0.0;             // rtLastMotionMs
 };
 
 // What the whole-image preview passes (denoiseFrame, accumulateFrame, previewFrame) each hold on the device: buffers for the whole image on ONE device, the first in-process
@@ -268,10 +270,33 @@ struct RefineState : QueryState {
     double ms = 0.0;                    // rtLastRefineMs
 };
 
+// rtMarkPose / renderMotion (rt_motion.h): the marked pose of the scene and the motion planes of the pass that runs, on the first in-process device.  Nothing is
+// allocated before the first rtMarkPose or renderMotion; released by free_pass where the passes' buffers are, which also drops the mark (the state back to its
+// initial values).  The planes are one set for all passes: a pass fills them in front of its own kernels, on the one stream every pass runs on.
+struct PoseState : QueryState {
+    bool marked = false;                // rtPoseMarked
+    size_t count = 0;                   // slots / spheres of the mark
+    rt_triangle* d_mark = nullptr;      // mesh scenes: the leaf-ordered slots as rtMarkPose saw them, in the layout of the live array, and
+    rt_triangle* d_mark_alt = nullptr;  // the second buffer a rebuild gathers them into (then the two are swapped); allocated by the first such rebuild
+    std::vector<float4> h_mark;         // sphere scenes: (center, radius) in the caller's order as rtMarkPose saw them, and
+    float4* d_mark_sph = nullptr;       // their device copy;
+    float4* d_live_sph = nullptr;       // the same for the spheres as they are now, uploaded when a pass finds it older than the last edit:
+    int live_edits = -1;                // RenderContext::scene_edits of that upload
+    float4* d_planes = nullptr;         // RtMotionParams::planes, 2 * npix
+    float2* d_screen = nullptr;         // RtMotionParams::screen, npix; allocated by the first renderMotion that asks for it
+};
+
+// renderMotion: a pass without input and output frames (begin_pass is told so): the guide planes and the events are what it takes from the shared path.
+struct MotionState : PassState {
+    std::vector<float4> h_planes;       // the staging copy of PoseState::d_planes the caller's 3-float planes are filled from
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
 DisplayState g_display;
+PoseState g_pose;
+MotionState g_motion;
 ChunkState g_rays, g_pixels;
 RefineState g_refine;
 
@@ -391,6 +416,8 @@ void setup_devices() {
     free_pass(g_accumulate);                                // (so do the history's)
     free_pass(g_preview);
     free_pass(g_display);
+    free_pass(g_motion);
+    free_pass(g_pose);                                      // (the marked pose goes with it)
     free_pass(g_rays);
     free_pass(g_pixels);
     free_pass(g_refine);
@@ -500,6 +527,8 @@ void cleanup_impl() {
     free_pass(g_accumulate);
     free_pass(g_preview);
     free_pass(g_display);
+    free_pass(g_motion);
+    free_pass(g_pose);                                      // (the marked pose goes with it)
     free_pass(g_rays);
     free_pass(g_pixels);
     free_pass(g_refine);
@@ -808,9 +837,61 @@ void check_pass_args(const char* fn, int which, const rt_vec3* out, int flags, f
 // before anything is written (out may be in); the guide planes of the camera and options in force.  Returns the device to restore (end_pass).  The pass
 // records n.ev_start in front of its kernels.  `without` names what a pass does not take (displayFrame): kPassNoGuides - no guide planes, no guide launch;
 // kPassOwnOutput - no rt_vec3 output buffer, the pass delivers buffers of its own type (end_pass); kPassNoUpload - this call's input is on the device already.
-enum { kPassNoGuides = 1, kPassOwnOutput = 2, kPassNoUpload = 4 };
+// kPassNoInput - no input frame either (renderMotion).  `motion`: the pass reads the motion planes when a pose is marked (accumulateFrame and previewFrame with a
+// history): the motion kernel runs behind the guide kernel; without a mark nothing is launched and nothing is allocated.
+enum { kPassNoGuides = 1, kPassOwnOutput = 2, kPassNoUpload = 4, kPassNoInput = 8 };
+
+// The caller's spheres (center, radius) in the caller's order, from the slot layout the kernels read (rt_scene_layout.h).
+std::vector<float4> caller_spheres() {
+    const SphereLayout& s = g_ctx.sphere;
+    std::vector<float4> out((size_t)s.scene.n);
+    for (size_t k = 0; k < out.size(); k++) {
+        const int slot = s.slot_of[k];
+        const float4 c = s.spheres[(size_t)(slot + slot / kSphereGroup)];
+        out[k] = make_float4(c.x, c.y, c.z, s.rad[(size_t)slot]);
+    }
+    return out;
+}
+
+// Sphere scenes with a pose marked: the device copy of the caller-order spheres as they are now, uploaded again when an edit has made it stale.  The first
+// in-process device is current.
+void refresh_live_spheres() {
+    const RenderContext& c = g_ctx;
+    PoseState& m = g_pose;
+    if (!m.marked || !c.is_spheres || m.live_edits == c.scene_edits) return;
+    const DeviceState& d = c.devs[0];
+    const std::vector<float4> live = caller_spheres();
+    if (!m.d_live_sph) m.d_live_sph = dev_alloc<float4>(m.owned, m.count);
+    HIP_CHECK(hipMemcpyAsync(m.d_live_sph, live.data(), m.count * sizeof(float4), hipMemcpyHostToDevice, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));              // (the source is a local; every pass is blocking: nothing on the stream still reads the old copy)
+    m.live_edits = c.scene_edits;
+}
+
+// The motion kernel (rt_motion.h) over the guide planes of pass `n`, on the first in-process device, which is current: Pm and nm of the marked pose - P and n
+// themselves without one - into the planes every pass shares, `screen` (with its camera C') on request.
+void launch_motion(const PassState& n, bool screen, const rt_camera& prev_cam) {
+    const RenderContext& c = g_ctx;
+    const DeviceState& d = c.devs[0];
+    PoseState& m = g_pose;
+    m.device = d.device;
+    if (!m.d_planes) m.d_planes = dev_alloc<float4>(m.owned, 2 * n.npix);
+    if (screen && !m.d_screen) m.d_screen = dev_alloc<float2>(m.owned, n.npix);
+    RtMotionParams q;
+    memset(&q, 0, sizeof q);
+    q.cam = c.cam; q.nx = c.nx; q.ny = c.ny;
+    q.normal = n.d_guide[1]; q.depth = n.d_guide[2]; q.prim = reinterpret_cast<const int32_t*>(n.d_guide[3]);
+    q.planes = m.d_planes; q.screen = screen ? m.d_screen : nullptr;
+    refresh_live_spheres();
+    if (m.marked && c.is_spheres) {
+        q.live_sph = m.d_live_sph; q.mark_sph = m.d_mark_sph; q.count = (uint32_t)m.count;
+    } else if (m.marked) {
+        q.live = d.d_tris; q.mark = m.d_mark; q.count = (uint32_t)m.count;
+    }
+    HIP_CHECK(rt_launch_motion(q, prev_cam, d.stream));
+}
+
 template <typename State, typename AllocOwn>
-int begin_pass(State& n, const rt_vec3* in, AllocOwn alloc_own, int without = 0) {
+int begin_pass(State& n, const rt_vec3* in, AllocOwn alloc_own, int without = 0, bool motion = false) {
     const RenderContext& c = g_ctx;
     if (!in) in = c.h_ext ? c.h_ext : c.h_fb;
     int current = 0;
@@ -824,15 +905,16 @@ int begin_pass(State& n, const rt_vec3* in, AllocOwn alloc_own, int without = 0)
         n.device = d.device; n.npix = npix;
         if (!(without & kPassNoGuides))
             for (int q = 0; q < 4; q++) n.d_guide[q] = dev_alloc<float>(n.owned, npix * kGuideBytes[q] / sizeof(float));
-        n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
+        if (!(without & kPassNoInput)) n.d_in = dev_alloc<rt_vec3>(n.owned, npix);
         if (!(without & kPassOwnOutput)) n.d_out = dev_alloc<rt_vec3>(n.owned, npix);
         alloc_own();
         HIP_CHECK(hipEventCreate(&n.ev_start));
         HIP_CHECK(hipEventCreate(&n.ev_stop));
     }
-    if (!(without & kPassNoUpload)) HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));
+    if (!(without & (kPassNoUpload | kPassNoInput))) HIP_CHECK(hipMemcpyAsync(n.d_in, in, npix * sizeof(rt_vec3), hipMemcpyHostToDevice, d.stream));
     if (!(without & kPassNoGuides))
         launch_guides(d, whole_image_partition(), { n.d_guide[0], n.d_guide[1], n.d_guide[2], reinterpret_cast<int32_t*>(n.d_guide[3]), nullptr });
+    if (motion && g_pose.marked) launch_motion(n, false, c.cam);
     return current;
 }
 
@@ -1371,6 +1453,12 @@ void rebuildBvh(int32_t* old_slot) {
         if (d.d_leaf_tri) HIP_CHECK(hipMemsetAsync(d.d_leaf_tri, 0, slots * 3 * sizeof(float4), d.stream));   // (the refit writes the real slots only)
         launch_refit(d);
         HIP_CHECK(hipEventRecord(d.ev_reb_stop, d.stream));
+        if (&d == &c.devs[0] && g_pose.marked) {            // the marked pose follows the permutation: one gather, behind the timed kernels
+            PoseState& m = g_pose;
+            if (!m.d_mark_alt) m.d_mark_alt = dev_alloc<rt_triangle>(m.owned, num_tris);
+            HIP_CHECK(rt_launch_motion_gather(m.d_mark, m.d_mark_alt, d.d_old_slot, (uint32_t)num_tris, d.stream));
+            std::swap(m.d_mark, m.d_mark_alt);
+        }
     }
     const DeviceState& d0 = c.devs[0];
     rt_bvh_node root;
@@ -1709,12 +1797,13 @@ void accumulateFrame(const rt_vec3* in, rt_vec3* out, float* history, int flags,
         n.d_history = dev_alloc<float>(n.owned, n.npix);
         n.d_rec[0] = dev_alloc<float4>(n.owned, 3 * n.npix);
         n.d_rec[1] = dev_alloc<float4>(n.owned, 3 * n.npix);
-    });
+    }, 0, n.frames > 0);
     RtAccumulateParams q = pass_params<RtAccumulateParams>(n);
     q.history = history ? n.d_history : nullptr;
     q.prev = n.d_rec[n.newest]; q.next = n.d_rec[n.newest ^ 1];
     q.flags = flags; q.has_history = n.frames > 0 ? 1 : 0;
     q.max_history = (float)max_history; q.sigma_z = sigma_z; q.normal_min = normal_min;
+    q.motion = n.frames > 0 && g_pose.marked ? g_pose.d_planes : nullptr;
     const hipStream_t stream = g_ctx.devs[0].stream;
     HIP_CHECK(hipEventRecord(n.ev_start, stream));
     HIP_CHECK(rt_launch_accumulate(q, n.prev_cam, stream));
@@ -1757,7 +1846,7 @@ void previewFrame(const rt_vec3* in, rt_vec3* out, float* history, float* varian
             n.d_mom[k] = dev_alloc<float2>(n.owned, n.npix);
             n.d_col[k] = dev_alloc<float4>(n.owned, n.npix);
         }
-    });
+    }, 0, n.frames > 0);
     RtPreviewParams q = pass_params<RtPreviewParams>(n);
     q.history = history ? n.d_history : nullptr;
     q.variance = variance ? n.d_variance : nullptr;
@@ -1766,6 +1855,7 @@ void previewFrame(const rt_vec3* in, rt_vec3* out, float* history, float* varian
     q.col[0] = n.d_col[0]; q.col[1] = n.d_col[1];
     q.flags = flags; q.has_history = n.frames > 0 ? 1 : 0; q.normal_squarings = normal_squarings;
     q.max_history = (float)max_history; q.sigma_z = sigma_z; q.normal_min = normal_min; q.sigma_l = sigma_l;
+    q.motion = n.frames > 0 && g_pose.marked ? g_pose.d_planes : nullptr;
     const hipStream_t stream = g_ctx.devs[0].stream;
     HIP_CHECK(hipEventRecord(n.ev_start, stream));
     HIP_CHECK(rt_launch_preview_temporal(q, n.prev_cam, stream));
@@ -1788,6 +1878,72 @@ int rtPreviewFrames(void) {
 }
 
 double rtLastPreviewMs(void) { return g_ctx.preview_ms; }
+
+// The marked pose and the motion planes (rt_api.h).  The mark is a copy of the scene's geometry on the first in-process device, where the
+// passes run: the triangle slots device to device, the spheres from the host's layout.  A second rtMarkPose overwrites it.
+void rtMarkPose(void) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("rtMarkPose before init");
+    const DeviceState& d = c.devs[0];
+    PoseState& m = g_pose;
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    HIP_CHECK(hipSetDevice(d.device));
+    m.device = d.device;
+    if (c.is_spheres) {
+        m.h_mark = caller_spheres();
+        m.count = m.h_mark.size();
+        if (!m.d_mark_sph) m.d_mark_sph = dev_alloc<float4>(m.owned, m.count);
+        HIP_CHECK(hipMemcpyAsync(m.d_mark_sph, m.h_mark.data(), m.count * sizeof(float4), hipMemcpyHostToDevice, d.stream));
+    } else {
+        m.count = c.mesh.tris.size();
+        if (!m.d_mark) m.d_mark = dev_alloc<rt_triangle>(m.owned, m.count);
+        HIP_CHECK(hipMemcpyAsync(m.d_mark, d.d_tris, m.count * sizeof(rt_triangle), hipMemcpyDeviceToDevice, d.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+    HIP_CHECK(hipSetDevice(current));
+    m.marked = true;
+}
+
+void rtClearPose(void) {
+    if (!g_ctx.initialised) rt_fail("rtClearPose before init");
+    g_pose.marked = false;                                  // (the buffers stay for the next mark)
+}
+
+int rtPoseMarked(void) {
+    if (!g_ctx.initialised) rt_fail("rtPoseMarked before init");
+    return g_pose.marked ? 1 : 0;
+}
+
+void renderMotion(int mask, const rt_camera* prev_cam, float* prev_pos, float* prev_normal, float* screen) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("renderMotion before init");
+    constexpr int kAll = RT_MOTION_POS | RT_MOTION_NORMAL | RT_MOTION_SCREEN;
+    if (mask == 0 || (mask & ~kAll) != 0) rt_fail("renderMotion: mask must name at least one RT_MOTION_* plane and no unknown bit");
+    float* const host[3] = { prev_pos, prev_normal, screen };
+    for (int k = 0; k < 3; k++)
+        if ((mask >> k & 1) && !host[k]) rt_fail("renderMotion: a requested plane has a null pointer");
+    if (c.is_spheres && c.opt.floor) rt_fail("renderMotion: the floor plane is only defined for mesh scenes (kernel_scene.floor)");
+    MotionState& n = g_motion;
+    const int current = begin_pass(n, nullptr, [] {}, kPassOwnOutput | kPassNoInput);
+    const bool with_screen = (mask & RT_MOTION_SCREEN) != 0;
+    refresh_live_spheres();                                 // (in front of the start event: the time is the kernel's alone)
+    HIP_CHECK(hipEventRecord(n.ev_start, c.devs[0].stream));
+    launch_motion(n, with_screen, prev_cam ? *prev_cam : c.cam);
+    n.h_planes.resize(2 * n.npix);
+    PassCopy own[2] = { { n.h_planes.data(), g_pose.d_planes, 2 * n.npix * sizeof(float4) }, { screen, g_pose.d_screen, n.npix * sizeof(float2) } };
+    c.motion_ms = end_pass(n, current, nullptr, nullptr, nullptr, nullptr, nullptr, own, with_screen ? 2 : 1);
+    for (int k = 0; k < 2; k++) {
+        if (!(mask >> k & 1)) continue;
+        const float4* src = n.h_planes.data() + (size_t)k * n.npix;
+        for (size_t p = 0; p < n.npix; p++) { host[k][3 * p] = src[p].x; host[k][3 * p + 1] = src[p].y; host[k][3 * p + 2] = src[p].z; }
+    }
+}
+
+double rtLastMotionMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastMotionMs before init");
+    return g_ctx.motion_ms;
+}
 
 // The display transform (rt_api.h).  Through the passes' shared path, without guide planes: the whole image on the first in-process device, the
 // RGBA words and the histogram its own buffers.  With RT_DISPLAY_FROM_PREVIEW the input is previewFrame's output buffer where that call left it.

@@ -233,7 +233,8 @@ double rtLastDenoiseMs(void);
  * frame and the blend returns it.  Accumulation pays off when the image moves by about a pixel or more per frame; a still camera is what
  * runRendererProgressive is for.  A scene edit (updateTriangles, updateMaterials, updateSpheres below) keeps this history and previewFrame's: what moved
  * is rejected pixel by pixel by the plane-distance, normal and (with SAME_PRIM) primitive tests above, what stayed keeps its history; rtResetHistory /
- * rtResetPreview are there for a caller who wants a clean start after an edit.
+ * rtResetPreview are there for a caller who wants a clean start after an edit.  rtMarkPose in front of the edit lets what moved keep its history too
+ * ("the marked pose" below).
  *
  * accumulateFrame: `in`, `out` as denoiseFrame's - `in` NULL = the framebuffer the renderer currently delivers into, `out` caller-owned and never NULL, `out`
  * may be `in`; blocking.  `history` = NULL, or nx*ny floats that receive N(p).  flags = the denoiser's bits with the same meaning, default
@@ -553,6 +554,62 @@ double rtLastUpdateMs(void);   /* HIP-event time of the refit kernels of the las
 #define RT_REBUILD_TILE 256
 void   rebuildBvh(int32_t* old_slot);
 double rtLastRebuildMs(void);  /* HIP-event time of the build + refit kernels of the last rebuildBvh, the largest over the in-process devices; 0 before the first */
+
+/* --- the marked pose: temporal passes that follow moving geometry, and the motion planes ---------------------------------------------
+ * accumulateFrame and previewFrame reproject a pixel through its CURRENT hit point.  When an edit moves geometry between two frames that point is not where
+ * the surface was when the history was stored: the taps are rejected, or - a small move - taken from the wrong surface point.  rtMarkPose remembers the
+ * scene's geometry as it is now, "the previous frame's pose"; from then on both passes reproject every pixel through the point Pm its surface point had in
+ * the marked pose and test their taps against (Pm, nm), so a moved object keeps its history.  The loop of an animated frame is rtMarkPose, updateTriangles /
+ * updateSpheres (and rebuildBvh), setCamera, runRenderer(1), previewFrame, displayFrame.  renderMotion returns the planes themselves - for
+ * a caller's own TAA, motion blur or a video encoder.  Without an rtMarkPose call nothing the library computes changes: no new kernel is launched, no new
+ * buffer is allocated, and the passes run the kernels they ran before.
+ * All arithmetic is fp32, every operation rounded on its own (no FMA), operands in the order written, dot evaluated left to right, a comparison with a NaN
+ * false; cross(a, b) = (a.y*b.z - a.z*b.y, -(a.x*b.z - a.z*b.x), a.x*b.y - a.y*b.x); unit(a) = a / sqrt(a.x*a.x + a.y*a.y + a.z*a.z), three divisions.  So
+ * the planes are defined bit for bit (tests/motion_reference.py restates this in numpy).  valid(p), t(p), n(p), prim(p) and P(p) = o + t*d
+ * are accumulateFrame's own.  Per pixel p:
+ *     !valid(p):                                       Pm = (0,0,0);  nm = (0,0,0)
+ *     the floor;  no pose marked;  the marked slot is a sentinel (isinf(a0.x)):      Pm = P;  nm = n
+ *     triangle slot s = prim(p), live vertices v0..v2, marked vertices a0..a2:
+ *         all nine marked coordinates equal the live ones bit for bit:               Pm = P;  nm = n      (what did not move behaves exactly as before)
+ *         otherwise:
+ *             e1 = v1 - v0;  e2 = v2 - v0;  w = P - v0
+ *             d11 = dot(e1,e1);  d12 = dot(e1,e2);  d22 = dot(e2,e2);  d1w = dot(e1,w);  d2w = dot(e2,w)
+ *             den = d11*d22 - d12*d12;  bu = (d22*d1w - d12*d2w) / den;  bv = (d11*d2w - d12*d1w) / den
+ *             Pm[k] = a0[k] + bu*(a1[k] - a0[k]) + bv*(a2[k] - a0[k])                 (left to right)
+ *             gm = unit(cross(a1 - a0, a2 - a0));  nm = dot(cross(e1, e2), n(p)) < 0 ? -gm : gm        (the turn hit() gave the live normal)
+ *         A degenerate live or marked triangle gives NaN planes: every comparison of the passes is then false and the pixel starts anew.
+ *     sphere s = prim(p), live (c, r), marked (c', r'):
+ *         the four words equal bit for bit:  Pm = P;  nm = n;      otherwise:  Pm[k] = c'[k] + ((P[k] - c[k]) / r) * r';  nm = n(p)
+ *     screen, with C' = *prev_cam or, with prev_cam NULL, the current camera:  accumulateFrame's r, x, y computed from e = Pm - o' (the constants Lu .. Vl of
+ *         C' as there);  screen(p) = (x - (float)i, y - (float)j) if valid(p) && r > 0, else (0, 0): where the previous camera saw the surface point, relative
+ *         to the pixel, in pixels.
+ * With a pose marked accumulateFrame and stage T of previewFrame take Pm(p), nm(p) in the place of P(p), n(p) in exactly three places: the reprojection
+ * e = Pm - o', the tap's plane test abs(dot(nm, P'(q) - Pm)) * rz(p) < 1 and the tap's normal test dot(nm, n'(q)) >= normal_min.  Everything else is as it
+ * was: rz(p) from t(p), the SAME_PRIM test, the blend, the records stored for the next call (the current P, n, prim, c, N, M1, M2), stages V and A.
+ *
+ * rtMarkPose     copies, on the first in-process device (where the passes run): mesh scenes - the leaf-ordered triangle slots, device to device, 64 bytes a
+ *                slot; sphere scenes - the caller-order (center, radius) array, kept on the host and uploaded, 16 bytes a sphere.  A second call overwrites
+ *                the mark.  The mark is dropped by every init*, cleanupRenderer, rtClearPose and a setRenderOptions that changes the device layout; setCamera,
+ *                the update* calls, runRenderer* and every pass keep it, and any other setRenderOptions resets the histories as before and keeps it.
+ *                rebuildBvh carries it along: slot s of the mark becomes the old mark of old_slot[s], a sentinel where old_slot[s] < 0 - one gather on the
+ *                device - so "the previous pose of the triangle now in slot s" stays right.
+ * renderMotion   fills the planes named in `mask`, caller-owned host arrays of nx*ny entries, row 0 = bottom: prev_pos = Pm (3 floats), prev_normal = nm
+ *                (3 floats), screen (2 floats); nothing is written through a pointer whose plane is not named.  Blocking.  Like the passes it works on the
+ *                WHOLE image on the first in-process device, whatever the partition is, follows setCamera, setRenderOptions and the edits, and changes
+ *                nothing another call observes: the framebuffer, getRenderStats, rtLastLaunches, both histories, the progressive frame and every other
+ *                rtLast*Ms stay as they were.
+ * Device memory, from the first rtMarkPose or renderMotion on: the mark (twice for a mesh once a rebuild has carried it, and the live spheres beside the
+ * marked ones), 32 bytes per pixel of motion planes shared by all passes, 8 more for `screen` once asked for, and renderMotion's guide planes (28 bytes per
+ * pixel); freed where the passes' buffers are.  The motion kernel of a pass runs behind its guide kernel and, like that one, is not part of
+ * rtLastAccumulateMs / rtLastPreviewMs.
+ * Misuse (rt error, exit 99), checked before any device work: any of the six calls before init; mask 0 or with unknown bits; a named plane whose pointer
+ * is NULL; rt_render_options.floor = 1 on a sphere scene. */
+void   rtMarkPose(void);    /* remember the scene's geometry as it is now: "the previous frame's pose" */
+void   rtClearPose(void);   /* forget it */
+int    rtPoseMarked(void);  /* 0 / 1 */
+enum { RT_MOTION_POS = 1, RT_MOTION_NORMAL = 2, RT_MOTION_SCREEN = 4 };
+void   renderMotion(int mask, const rt_camera* prev_cam, float* prev_pos, float* prev_normal, float* screen);
+double rtLastMotionMs(void); /* HIP-event time of the motion kernel of the last renderMotion alone (not its guide kernel, not the copies); 0 before the first */
 
 enum { RT_KERNEL_SPHERE_QUEUE = 1, RT_KERNEL_SPHERE_TILES = 2, RT_KERNEL_MESH_QUEUE = 3, RT_KERNEL_MESH_TILES = 4 };
 enum { RT_LAUNCH_FAMILY = 0, RT_LAUNCH_PHASE, RT_LAUNCH_CLS, RT_LAUNCH_CHUNKED, RT_LAUNCH_DBG, RT_LAUNCH_SCENE, RT_LAUNCH_LEAN,
