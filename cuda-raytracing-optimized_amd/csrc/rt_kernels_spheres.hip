@@ -1733,6 +1733,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
     uint32_t pix_rays = 0;              // rays traced so far for the lane's current pixel
     bool exhausted = false;             // wave-uniform: the global queue is empty
     uint32_t pool_next = 0, pool_end = 0;   // wave-uniform: the wave's reserved queue positions [pool_next, pool_end)
+    unsigned long long capped_live = 0ull;  // wave-uniform (folded kinds): the lanes that held a pixel when the refill last stopped at the wave's cap (0: never)
     float* fbf = reinterpret_cast<float*>(P.fb);
     // Parameters read once per sample are NOT kept in SGPRs for the life of the wave (the camera alone is 22 of them, spilled to VGPR lanes):
     // they are re-read from the device copy of the parameter block through a pointer the optimiser cannot see through (scalar loads, cached).
@@ -1818,7 +1819,12 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
         const bool dbg_timers = DBG && wdbg && (cfg & kCfgDbgLight) == 0;          // RT_WAVE_DEBUG_LIGHT=1: time stamps of waves and pixels only (the section timers
                                                                                  // stretch a sparse step by 40 %: the light form keeps the frame's real proportions)
         const unsigned long long t_refill = dbg_timers ? __builtin_amdgcn_s_memtime() : 0ull;
-        while (!exhausted) {
+        // (folded kinds, DESIGN 3.26: the cap below depends on the role and on which lanes hold which pixels.  A wave that left this loop at its cap and still
+        // holds exactly those lanes - no lane finished, so none fetched - would compute the same cap and leave again: 3699 of a chain wave's 3700 iterations,
+        // and every iteration of a dense wave in which no pixel ended.  Every way out of the loop but the queues' end goes through the cap - a lane that
+        // finishes changes the mask, the loop runs and records again - so the record is never stale.)
+        const bool at_cap = FOLDED && capped_live != 0ull && __ballot(have_pixel) == capped_live;
+        if (!at_cap) while (!exhausted) {
             // live-lane cap of this wave: by its role and by the tiers of the pixels it still holds
             const unsigned long long live_m = __ballot(have_pixel);
             int cap = 64;
@@ -1830,7 +1836,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
                 if (__ballot(have_pixel && ccls == 0) != 0ull) cap = min(cap, caps & caps_list(0).mask);
             }
             const int allowed = cap - (int)__popcll(live_m);
-            if (allowed <= 0) break;
+            if (allowed <= 0) { if (FOLDED) capped_live = live_m; break; }
             const unsigned long long idle_m = ~live_m;
             const uint32_t idle_rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
             const unsigned long long need = __ballot(!have_pixel && idle_rank < (uint32_t)allowed);
