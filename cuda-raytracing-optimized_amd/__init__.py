@@ -138,6 +138,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "displayFrame", "rtLastExposure", "rtDisplayHistogram", "rtResetDisplay", "rtLastDisplayMs",
                     "traceRays", "occludedRays", "rtLastRaysMs",
                     "renderPixels", "rtLastPixelsMs",
+                    "radianceRays", "rtLastRadianceMs",
                     "refineFrame", "rtResetRefine", "rtRefineSamples", "rtRefineLastList", "rtLastRefineMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
@@ -149,7 +150,7 @@ ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle,
 HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtSceneRandomSpheres", "rtStaircaseCamera",
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
-                "rtDisplayFrameHost", "rtCentreRays", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh"]
+                "rtDisplayFrameHost", "rtCentreRays", "rtPinholeCamera", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh"]
 
 _renderer = None
 _host = None
@@ -202,6 +203,8 @@ def load_host():
         h.rtDisplayFrameHost.restype = C.c_int
         h.rtCentreRays.argtypes = [C.POINTER(camera), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, fp, fp]
         h.rtCentreRays.restype = None
+        h.rtPinholeCamera.argtypes = [fp, fp, C.POINTER(camera)]
+        h.rtPinholeCamera.restype = None
         h.rtRefitBvhArrays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.POINTER(bbox)]
         h.rtRefitBvhArrays.restype = C.c_int
         h.rtRefitBvh.argtypes = [C.c_void_p]
@@ -327,6 +330,10 @@ def load_renderer():
         r.renderPixels.restype = None
         r.rtLastPixelsMs.argtypes = []
         r.rtLastPixelsMs.restype = C.c_double
+        r.radianceRays.argtypes = [C.c_int, fp, fp, up, C.c_int, ip, ip, up, C.POINTER(vec3), up]
+        r.radianceRays.restype = None
+        r.rtLastRadianceMs.argtypes = []
+        r.rtLastRadianceMs.restype = C.c_double
         r.refineFrame.argtypes = [C.POINTER(vec3), ip, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]
         r.refineFrame.restype = C.c_int
         r.rtResetRefine.argtypes = []
@@ -729,6 +736,67 @@ def render_region(x0, y0, x1, y1, ns):
 def last_pixels_ms():
     """HIP-event time of the pixel kernels of the last render_pixels / render_region (not the copies), summed over its chunks, in milliseconds."""
     return load_renderer().rtLastPixelsMs()
+
+
+# radianceRays (include/rt_api.h): path-trace the caller's own rays, resumable
+def radiance_rays(org, dir, ns, ids=None, first=None, state=None, rays=False):
+    """Path-traces the rays (org, dir), both (n, 3) float (dir raw, non-zero: normalised once on the device) (radianceRays, include/rt_api.h).  ns: an int -
+    samples for every ray - or an (n,) int array; ids: None (ray k is seeded by k) or an (n,) uint32 array of seed ids; first: None (every ray starts its
+    stream) or an (n,) int array of the first sample of each ray, which needs `state` = the (n, 4) uint32 array an earlier call returned for the same rays
+    after that many samples.  Returns (out, state, rays): out (n, 3) float32 = sum / (first + ns); state (n, 4) uint32 after the last sample (a new array:
+    the caller's is not written); rays (n,) uint32 closest-hit queries of these samples, or None unless rays=True.  Blocking."""
+    org = np.ascontiguousarray(org, dtype=np.float32)
+    d = np.ascontiguousarray(dir, dtype=np.float32)
+    if org.ndim != 2 or org.shape[1] != 3 or d.shape != org.shape:
+        raise ValueError(f"radiance_rays: org and dir must both have shape (n, 3), got {org.shape} and {d.shape}")
+    n = org.shape[0]
+    fp, ip, up = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+
+    def per_ray(name, a, dtype=np.int32):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != (n,):
+            raise ValueError(f"radiance_rays: {name} must have shape ({n},), got {a.shape}")
+        return a
+
+    ns_all, ns_arr = 0, None
+    if isinstance(ns, (int, np.integer)) and not isinstance(ns, bool):
+        ns_all = int(ns)
+    else:
+        ns_arr = per_ray("ns", ns)
+    ids_arr = None if ids is None else per_ray("ids", ids, np.uint32)
+    first_arr = None if first is None else per_ray("first", first)
+    if state is None:
+        if first_arr is not None:
+            raise ValueError("radiance_rays: first needs the state the rays resume from")
+        st = np.zeros((n, 4), np.uint32)
+    else:
+        st = np.array(state, dtype=np.uint32, order="C")            # (a copy: radianceRays updates the states in place)
+        if st.shape != (n, 4):
+            raise ValueError(f"radiance_rays: state must have shape ({n}, 4), got {st.shape}")
+    out = np.zeros((n, 3), np.float32)
+    nrays = np.zeros(n, np.uint32) if rays else None
+    load_renderer().radianceRays(n, org.ctypes.data_as(fp), d.ctypes.data_as(fp), None if ids_arr is None else ids_arr.ctypes.data_as(up), ns_all,
+                                 None if ns_arr is None else ns_arr.ctypes.data_as(ip), None if first_arr is None else first_arr.ctypes.data_as(ip),
+                                 st.ctypes.data_as(up), out.ctypes.data_as(C.POINTER(vec3)), None if nrays is None else nrays.ctypes.data_as(up))
+    return out, st, nrays
+
+
+def last_radiance_ms():
+    """HIP-event time of the radiance kernels of the last radiance_rays (not the copies), summed over its chunks, in milliseconds."""
+    return load_renderer().rtLastRadianceMs()
+
+
+def pinhole_camera(o, target):
+    """The camera under which every pixel of a frame is the ray from o towards target (rtPinholeCamera, librt_host.so; no GPU): origin = o,
+    lower_left_corner = target, every other field 0.  The pixel with global id `id` of runRenderer(ns) under it is radiance_rays of (o, target - o, id)."""
+    fp = C.POINTER(C.c_float)
+    o = np.ascontiguousarray(o, dtype=np.float32)
+    t = np.ascontiguousarray(target, dtype=np.float32)
+    if o.shape != (3,) or t.shape != (3,):
+        raise ValueError(f"pinhole_camera: o and target must have shape (3,), got {o.shape} and {t.shape}")
+    cam = camera()
+    load_host().rtPinholeCamera(o.ctypes.data_as(fp), t.ctypes.data_as(fp), C.byref(cam))
+    return cam
 
 
 # refineFrame (include/rt_api.h): adaptive sampling on the device over the pixel kernels

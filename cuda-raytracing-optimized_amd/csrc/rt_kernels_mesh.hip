@@ -33,9 +33,11 @@ using namespace rtd;
 #if defined(RT_MODE_PARITY)
 #define RT_LAUNCH_NAME rt_launch_mesh_parity
 #define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_mesh_parity
+#define RT_RADIANCE_LAUNCH_NAME rt_launch_radiance_mesh_parity
 #elif defined(RT_MODE_FAST)
 #define RT_LAUNCH_NAME rt_launch_mesh_fast
 #define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_mesh_fast
+#define RT_RADIANCE_LAUNCH_NAME rt_launch_radiance_mesh_fast
 #else
 #error "define RT_MODE_PARITY or RT_MODE_FAST"
 #endif
@@ -395,6 +397,92 @@ __global__ void __launch_bounds__(kPixelThreads) k_pixels_mesh(const RtMeshParam
                         *reinterpret_cast<float3*>(reinterpret_cast<float*>(B.out) + (size_t)entry * 3) = make_float3(out.x, out.y, out.z);
                     }
                     if (B.rays) B.rays[entry] = pix_rays;
+                    active = false;
+                }
+            }
+        }
+    }
+}
+
+// ---- a list of the caller's own rays (radianceRays, rt_api.h) ---------------------------------------------------------------
+// k_pixels_mesh above with another entry and another sample start: one lane = one ray (o, d, seed id) of the caller's list, the same persistent waves, the
+// same one-atomic refill round, one mesh_bounce_step per iteration of the wave-uniform loop, the same resume from B.state and the same three stores.  An
+// entry loads its origin and normalises its raw direction once (ray.h:9, the rule of traceRays); a sample starts by drawing what a camera sample draws in
+// front of its path - the two jitter words (kernels.cu:549-550) and the lens's rejection loop (camera.h) - and throwing it away, then takes (o, dn) as its
+// ray.  With those draws a ray is the pixel `id` of a frame through a pinhole at o that looks at o + d (rtPinholeCamera, rt_host.h), bit for bit: that frame
+// is this kernel's oracle.  Nothing of the camera, the image size or the partition is read.
+// kernels.cu:549-555 + the head of color() :397-398 for a caller's ray
+__device__ __forceinline__ void start_ray_sample(MeshLane& L, f3 org, f3 dn) {
+    (void)rnd(L.rng);                                                // the jitter of u
+    (void)rnd(L.rng);                                                // ... and of v
+    (void)random_in_unit_disk(L.rng);                                // the lens
+    L.org = org;
+    L.dir = dn;
+    L.atten = F3(1.0f, 1.0f, 1.0f);
+    L.pcolor = F3(0, 0, 0);
+    L.bounce = 0;
+    L.inside = false;
+    L.specular = false;
+}
+
+__global__ void __launch_bounds__(kPixelThreads) k_radiance_mesh(const RtMeshParams P, const RtRadianceBatch B) {
+    const uint32_t n = (uint32_t)B.n;
+
+    MeshLane L;
+    L.rng = 0u; L.i = 0; L.j = 0; L.s = 0; L.bounce = 0;
+    L.inside = false; L.specular = false;
+    L.col = F3(0, 0, 0); L.org = F3(0, 0, 0); L.dir = F3(0, 0, 1); L.atten = F3(1, 1, 1); L.pcolor = F3(0, 0, 0);
+    f3 ray_org = F3(0, 0, 0), ray_dn = F3(0, 0, 1);                  // the lane's entry: every sample starts here
+    int s_end = 0;                      // the lane's entry ends with sample s_end - 1
+    TravStats st = { 0, 0 };
+    uint32_t entry = 0, ray_rays = 0, nshadow = 0;
+    bool active = false;                // the lane owns an unfinished entry
+    bool exhausted = false;             // wave-uniform: the queue is empty
+
+    while (true) {
+        const unsigned long long idle = __ballot(!active);
+        if (!exhausted && idle != 0ull) {                            // one refill round
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            uint32_t base = 0;
+            if ((threadIdx.x & 63) == 0) base = atomicAdd(B.queue, cnt);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + cnt >= n) exhausted = true;
+            const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            if (!active && k < n) {
+                entry = k;
+                L.s = B.first ? B.first[k] : 0;
+                s_end = L.s + (B.ns ? B.ns[k] : B.ns_all);
+                ray_org = F3(B.org[3 * (size_t)k], B.org[3 * (size_t)k + 1], B.org[3 * (size_t)k + 2]);
+                ray_dn = unit(F3(B.dir[3 * (size_t)k], B.dir[3 * (size_t)k + 1], B.dir[3 * (size_t)k + 2]));     // ray.h:9
+                if (L.s > 0) {                                       // the stream continues where an earlier call stopped
+                    const uint4 st4 = reinterpret_cast<const uint4*>(B.state)[k];
+                    L.col = F3(__uint_as_float(st4.x), __uint_as_float(st4.y), __uint_as_float(st4.z));
+                    L.rng = st4.w;
+                } else {
+                    L.col = F3(0, 0, 0);
+                    L.rng = pixel_seed(B.ids ? B.ids[k] : B.id0 + k);        // kernels.cu:541 (the caller's id -> seed)
+                }
+                start_ray_sample(L, ray_org, ray_dn);
+                ray_rays = 0;
+                active = true;
+            }
+        }
+        if (__ballot(active) == 0ull) break;
+        if (active) {
+            // (max_depth <= 0: the loop of kernels.cu:402 never runs: no ray, a black sample)
+            if (P.max_depth <= 0 || mesh_bounce_step<true>(P, L, st, ray_rays, nshadow)) {
+                L.col = L.col + L.pcolor;                            // kernels.cu:558
+                L.s++;
+                if (L.s < s_end) {
+                    start_ray_sample(L, ray_org, ray_dn);
+                } else {
+                    const f3 col = L.col;
+                    if (B.state) reinterpret_cast<uint4*>(B.state)[entry] = make_uint4(__float_as_uint(col.x), __float_as_uint(col.y), __float_as_uint(col.z), L.rng);
+                    if (B.out) {
+                        const f3 out = col / (float)s_end;           // kernels.cu:568
+                        *reinterpret_cast<float3*>(reinterpret_cast<float*>(B.out) + (size_t)entry * 3) = make_float3(out.x, out.y, out.z);
+                    }
+                    if (B.rays) B.rays[entry] = ray_rays;
                     active = false;
                 }
             }
@@ -1313,17 +1401,27 @@ hipError_t rt_launch_rays_mesh(const RtMeshParams& p, const RtRayBatch& b, bool 
 
 // renderPixels (rt_api.h): k_pixels_mesh over one chunk of the list, in this object's arithmetic.  Waves: four per SIMD of every CU - what stays resident -
 // and never more than ceil(n / 64), so a one-pixel call is one wave; max_waves > 0 caps them.
-hipError_t RT_PIXELS_LAUNCH_NAME(const RtMeshParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream) {
-    if (b.n <= 0) return hipSuccess;
-    if (!b.queue || !b.ij) return hipErrorInvalidValue;
+// radianceRays takes the same launch with k_radiance_mesh: the two kernels have one structure and one launch bound.
+template <typename Batch>
+static hipError_t launch_list_mesh(void (*kern)(const RtMeshParams, const Batch), const RtMeshParams& p, const Batch& b, int max_waves, hipStream_t stream) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     constexpr unsigned wg_waves = kPixelThreads / 64;
     unsigned waves = std::min((unsigned)cus * 16u, ((unsigned)b.n + 63u) / 64u);
     if (max_waves > 0) waves = std::min(waves, (unsigned)max_waves);
     const dim3 grid((waves + wg_waves - 1) / wg_waves), block(64u * std::min(waves, wg_waves));
-    hipLaunchKernelGGL(k_pixels_mesh, grid, block, 0, stream, p, b);
+    hipLaunchKernelGGL(kern, grid, block, 0, stream, p, b);
     return hipGetLastError();
+}
+hipError_t RT_PIXELS_LAUNCH_NAME(const RtMeshParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    if (!b.queue || !b.ij) return hipErrorInvalidValue;
+    return launch_list_mesh(k_pixels_mesh, p, b, max_waves, stream);
+}
+hipError_t RT_RADIANCE_LAUNCH_NAME(const RtMeshParams& p, const RtRadianceBatch& b, int max_waves, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    if (!b.queue || !b.org || !b.dir) return hipErrorInvalidValue;
+    return launch_list_mesh(k_radiance_mesh, p, b, max_waves, stream);
 }
 
 #if RT_MESH_TAIL_DIAG

@@ -57,9 +57,11 @@ using namespace rtd;
 #if defined(RT_MODE_PARITY)
 #define RT_LAUNCH_NAME rt_launch_spheres_parity
 #define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_spheres_parity
+#define RT_RADIANCE_LAUNCH_NAME rt_launch_radiance_spheres_parity
 #elif defined(RT_MODE_FAST)
 #define RT_LAUNCH_NAME rt_launch_spheres_fast
 #define RT_PIXELS_LAUNCH_NAME rt_launch_pixels_spheres_fast
+#define RT_RADIANCE_LAUNCH_NAME rt_launch_radiance_spheres_fast
 #else
 #error "define RT_MODE_PARITY or RT_MODE_FAST"
 #endif
@@ -1247,6 +1249,94 @@ __global__ void __launch_bounds__(kThreads) k_pixels_spheres(const RtSphereParam
     }
 }
 
+// ---- a list of the caller's own rays (radianceRays, rt_api.h) ---------------------------------------------------------------
+// k_pixels_spheres above with another entry and another sample start: one lane = one ray (o, d, seed id) of the caller's list, the same persistent waves,
+// the same one-atomic refill round, the same wave-uniform loop around trace_rays, the same resume from B.state and the same three stores.  An entry loads its
+// origin and normalises its raw direction once (ray.h:9, the rule of traceRays); a sample starts by drawing what a camera sample draws in front of its
+// path - the two jitter words (kernels.cu:549-550) and the lens's rejection loop (camera.h) - and throwing it away, then takes (o, dn) as its ray.  With those
+// draws a ray is the pixel `id` of a frame through a pinhole at o that looks at o + d (rtPinholeCamera, rt_host.h), bit for bit: that frame is this kernel's
+// oracle.  Nothing of the camera, the image size or the partition is read.
+// kernels.cu:549-555 + the head of color() :397-398 for a caller's ray
+__device__ __forceinline__ void start_ray_sample(Lane& L, f3 org, f3 dn) {
+    (void)rnd(L.rng);                                                // the jitter of u
+    (void)rnd(L.rng);                                                // ... and of v
+    (void)random_in_unit_disk(L.rng);                                // the lens
+    L.org = org;
+    L.dir = dn;
+    L.atten = F3(1.0f, 1.0f, 1.0f);
+    L.bounce = 0;
+    L.inside = false;
+}
+
+template <int SCENE>
+__global__ void __launch_bounds__(kThreads) k_radiance_spheres(const RtSphereParams P, const RtRadianceBatch B) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* unused;
+    const SceneLds S = stage_scene<false, SCENE>(P, smem, &unused);
+    const uint32_t n = (uint32_t)B.n;
+
+    Lane L;
+    L.rng = 0u; L.col = F3(0, 0, 0);
+    L.org = F3(0, 0, 0); L.dir = F3(0, 0, 1); L.atten = F3(1, 1, 1);
+    L.bounce = 0; L.inside = false; L.s = 0; L.i = 0; L.j = 0; L.pixelId = 0u;
+    f3 ray_org = F3(0, 0, 0), ray_dn = F3(0, 0, 1);                  // the lane's entry: every sample starts here
+    uint32_t entry = 0, ray_rays = 0, groups_done = 0, boxes_done = 0;
+    int s_end = 0;                      // the lane's entry ends with sample s_end - 1
+    bool active = false;                // the lane owns an unfinished entry
+    bool exhausted = false;             // wave-uniform: the queue is empty
+    while (true) {
+        const unsigned long long idle = __ballot(!active);
+        if (!exhausted && idle != 0ull) {                            // one refill round
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            uint32_t base = 0;
+            if ((threadIdx.x & 63) == 0) base = atomicAdd(B.queue, cnt);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + cnt >= n) exhausted = true;
+            const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            if (!active && k < n) {
+                entry = k;
+                L.s = B.first ? B.first[k] : 0;
+                s_end = L.s + (B.ns ? B.ns[k] : B.ns_all);
+                ray_org = F3(B.org[3 * (size_t)k], B.org[3 * (size_t)k + 1], B.org[3 * (size_t)k + 2]);
+                ray_dn = unit(F3(B.dir[3 * (size_t)k], B.dir[3 * (size_t)k + 1], B.dir[3 * (size_t)k + 2]));     // ray.h:9
+                if (L.s > 0) {                                       // the stream continues where an earlier call stopped
+                    const uint4 st = reinterpret_cast<const uint4*>(B.state)[k];
+                    L.col = F3(__uint_as_float(st.x), __uint_as_float(st.y), __uint_as_float(st.z));
+                    L.rng = st.w;
+                } else {
+                    L.col = F3(0, 0, 0);
+                    L.rng = pixel_seed(B.ids ? B.ids[k] : B.id0 + k);        // kernels.cu:541 (the caller's id -> seed)
+                }
+                start_ray_sample(L, ray_org, ray_dn);
+                ray_rays = 0;
+                active = true;
+            }
+        }
+        if (__ballot(active) == 0ull) break;
+        f3 sample = F3(0, 0, 0);
+        bool done = true;                                            // (max_depth <= 0: the loop of kernels.cu:402 never runs - no ray, a black sample)
+        if (P.max_depth > 0) {
+            if (active) ray_rays++;
+            done = trace_rays<false>(P, S, L, active, -1, true, groups_done, boxes_done, sample, kSparseRays, nullptr, true);
+        }
+        if (active && done) {
+            L.col = L.col + sample;                                  // kernels.cu:558
+            L.s++;
+            if (L.s < s_end) {
+                start_ray_sample(L, ray_org, ray_dn);
+            } else {
+                if (B.state) reinterpret_cast<uint4*>(B.state)[entry] = make_uint4(__float_as_uint(L.col.x), __float_as_uint(L.col.y), __float_as_uint(L.col.z), L.rng);
+                if (B.out) {
+                    const f3 out = L.col / (float)s_end;             // kernels.cu:568
+                    *reinterpret_cast<float3*>(reinterpret_cast<float*>(B.out) + (size_t)entry * 3) = make_float3(out.x, out.y, out.z);
+                }
+                if (B.rays) B.rays[entry] = ray_rays;
+                active = false;
+            }
+        }
+    }
+}
+
 // ---- work-order pre-pass ------------------------------------------------------------------------------------------
 // The persistent kernel ends with a tail in which every lane finishes the pixel it happens to hold.  That tail is short
 // when the LAST pixels handed out are cheap and alike.  A pixel whose centre ray (no lens offset, no jitter) misses every
@@ -2136,9 +2226,9 @@ hipError_t rt_launch_rays_spheres(const RtSphereParams& p, const RtRayBatch& b, 
 // renderPixels (rt_api.h): k_pixels_spheres over one chunk of the list, in this object's arithmetic.  The scene form is the guide kernel's choice with the
 // render kernels' per-wave scratch (the hybrid copy in 8-wave workgroups where 16 do not fit, as the frame's plan does).  Waves: as many as stay resident
 // - one workgroup per CU, the launch bound's 4 waves per SIMD - and never more than ceil(n / 64), so a one-pixel call is one wave; max_waves > 0 caps them.
-hipError_t RT_PIXELS_LAUNCH_NAME(const RtSphereParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream) {
-    if (b.n <= 0) return hipSuccess;
-    if (!b.queue || !b.ij) return hipErrorInvalidValue;
+// radianceRays takes the same launch with k_radiance_spheres: the two kernels have one structure and one launch bound.
+template <typename Batch, typename Kern>
+static hipError_t launch_list_spheres(const RtSphereParams& p, const Batch& b, int max_waves, hipStream_t stream, Kern k0, Kern k1, Kern k2) {
     const int scene = scene_form(p, false);
     const unsigned wg_waves = (scene == 2 && lds_bytes(p.n_padded, p.n, false, 2, kWavesPerWg) > kLdsPerCu) ? 8u : (unsigned)kWavesPerWg;
     const size_t lds = lds_bytes(p.n_padded, p.n, false, scene, (int)wg_waves);
@@ -2147,8 +2237,19 @@ hipError_t RT_PIXELS_LAUNCH_NAME(const RtSphereParams& p, const RtPixelBatch& b,
     unsigned waves = std::min((unsigned)cus * wg_waves, ((unsigned)b.n + 63u) / 64u);
     if (max_waves > 0) waves = std::min(waves, (unsigned)max_waves);
     const dim3 grid((waves + wg_waves - 1) / wg_waves), block(64u * std::min(waves, wg_waves));
-    const auto kern = scene == 0 ? k_pixels_spheres<0> : (scene == 1 ? k_pixels_spheres<1> : k_pixels_spheres<2>);
-    return launch_with_lds(kern, grid, block, lds, stream, p, b);
+    return launch_with_lds(scene == 0 ? k0 : (scene == 1 ? k1 : k2), grid, block, lds, stream, p, b);
+}
+hipError_t RT_PIXELS_LAUNCH_NAME(const RtSphereParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    if (!b.queue || !b.ij) return hipErrorInvalidValue;
+    using Kern = void (*)(const RtSphereParams, const RtPixelBatch);
+    return launch_list_spheres<RtPixelBatch, Kern>(p, b, max_waves, stream, k_pixels_spheres<0>, k_pixels_spheres<1>, k_pixels_spheres<2>);
+}
+hipError_t RT_RADIANCE_LAUNCH_NAME(const RtSphereParams& p, const RtRadianceBatch& b, int max_waves, hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    if (!b.queue || !b.org || !b.dir) return hipErrorInvalidValue;
+    using Kern = void (*)(const RtSphereParams, const RtRadianceBatch);
+    return launch_list_spheres<RtRadianceBatch, Kern>(p, b, max_waves, stream, k_radiance_spheres<0>, k_radiance_spheres<1>, k_radiance_spheres<2>);
 }
 
 // The LEAN kinds of k_render_spheres_queue that are built beside the general kernel (LEAN 0), by scene form and chunking: the one statement of them.  The

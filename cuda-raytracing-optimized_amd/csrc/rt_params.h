@@ -246,7 +246,7 @@ struct RtSwitches {
     bool cleanup_device_reset = false;  // RT_CLEANUP_DEVICE_RESET=1: cleanupRenderer ends with hipDeviceReset
     int cost_reuse = 1;                 // RT_COST_REUSE: sphere frames 0 = neither record nor reuse the per-pixel cost map (every frame measures), 1 = reuse it until
                                         // setCamera changes the camera, 2 = across setCamera too (A/B: tools/bench_orbit.py)
-    int pixels_waves = 0;               // RT_PIXELS_WAVES=<w>: renderPixels launches at most w waves (0 = no cap; tests: the refill path with a few hundred pixels)
+    int pixels_waves = 0;               // RT_PIXELS_WAVES=<w>: renderPixels and radianceRays launch at most w waves (0 = no cap; tests: the refill path with a few hundred entries)
     bool refine_order = true;           // RT_REFINE_ORDER=0: refineFrame hands its list to the pixel kernels in ascending pixel order, not dearest first (A/B: tools/bench_refine.py)
     // the sphere launcher
     int top_thr = 384;                 // RT_TOP_THR: 16 x rays per sample from which a pixel goes to chain list 0 (24; below 320: the default)
@@ -357,3 +357,27 @@ hipError_t rt_launch_pixels_spheres_parity(const RtSphereParams& p, const RtPixe
 hipError_t rt_launch_pixels_spheres_fast(const RtSphereParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream);
 hipError_t rt_launch_pixels_mesh_parity(const RtMeshParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream);
 hipError_t rt_launch_pixels_mesh_fast(const RtMeshParams& p, const RtPixelBatch& b, int max_waves, hipStream_t stream);
+
+// A list of the caller's own rays (radianceRays, rt_api.h): one chunk of the list on the device.  org / dir hold n x 3 floats (dir raw: the kernel normalises
+// it once); ids n words - the seed id of each ray - or nullptr (= id0 + the entry's index in the chunk: id0 is the chunk's first index in the caller's list);
+// ns / first / state / out / rays / queue as in RtPixelBatch.  The radiance kernels (k_radiance_spheres / k_radiance_mesh) exist in both fp objects and read
+// of the scene's parameter block the scene, max_depth and the options of a path (sky, t_min, rr; mesh: nee, light, floor): no camera, no image size, no
+// partition.  max_waves: RT_PIXELS_WAVES, 0 = as many as stay resident.
+struct RtRadianceBatch {
+    const float* org;
+    const float* dir;
+    const uint32_t* ids;
+    const int32_t* ns;
+    const int32_t* first;
+    uint32_t* state;
+    rt_vec3* out;
+    uint32_t* rays;
+    uint32_t* queue;
+    int32_t n;
+    int32_t ns_all;
+    uint32_t id0;
+};
+hipError_t rt_launch_radiance_spheres_parity(const RtSphereParams& p, const RtRadianceBatch& b, int max_waves, hipStream_t stream);
+hipError_t rt_launch_radiance_spheres_fast(const RtSphereParams& p, const RtRadianceBatch& b, int max_waves, hipStream_t stream);
+hipError_t rt_launch_radiance_mesh_parity(const RtMeshParams& p, const RtRadianceBatch& b, int max_waves, hipStream_t stream);
+hipError_t rt_launch_radiance_mesh_fast(const RtMeshParams& p, const RtRadianceBatch& b, int max_waves, hipStream_t stream);

@@ -175,6 +175,7 @@ struct RenderContext {
     double display_ms = 0.0;            // rtLastDisplayMs
     double rays_ms = 0.0;               // rtLastRaysMs
     double pixels_ms = 0.0;             // rtLastPixelsMs
+    double radiance_ms = 0.0;           // rtLastRadianceMs
     double motion_ms = 0.0;             // rtLastMotionMs
 };
 
@@ -228,7 +229,7 @@ struct DisplayState : PassState {
     float last_exposure = 1.0f;         // rtLastExposure
 };
 
-// What every query call (traceRays / occludedRays, renderPixels, refineFrame) holds: the first in-process device, its allocations there and an event pair of
+// What every query call (traceRays / occludedRays, renderPixels, radianceRays, refineFrame) holds: the first in-process device, its allocations there and an event pair of
 // its own, created with the device list (setup_devices) - the timings of a frame, the guides, the passes and the other queries stay what they were.
 // Released by free_pass where the passes' buffers are.
 struct QueryState {
@@ -237,9 +238,9 @@ struct QueryState {
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
 
-// traceRays / occludedRays and renderPixels: the device buffers of one chunk of the caller's items, each grown to the largest chunk that asked for it
+// traceRays / occludedRays, renderPixels and radianceRays: the device buffers of one chunk of the caller's items, each grown to the largest chunk that asked for it
 // (run_chunks), by a table of what a buffer holds per item and which way it crosses the bus.  Rays: four inputs, five closest-hit planes, the any-hit bytes.
-// Pixels: three inputs, the stream states (read and written), two outputs - and the queue word of the pixel kernels.
+// Pixels: three inputs, the stream states (read and written), two outputs - and the queue word of the pixel kernels.  Radiance rays: five inputs, then as pixels.
 enum { kUp = 1, kDown = 2 };
 struct ChunkBuffer {
     size_t bytes;                       // per item
@@ -247,13 +248,14 @@ struct ChunkBuffer {
 };
 enum { kRayOrg = 0, kRayDir, kRayTMin, kRayTMax, kRayT, kRayPrim, kRayNormal, kRayUv, kRayNodes, kRayOccluded, kRayBuffers };
 enum { kPixIj = 0, kPixNs, kPixFirst, kPixState, kPixOut, kPixRays, kPixBuffers };
+enum { kRadOrg = 0, kRadDir, kRadIds, kRadNs, kRadFirst, kRadState, kRadOut, kRadRays, kRadBuffers };
 constexpr int kChunkBuffers = kRayBuffers;
 constexpr size_t kRayChunk = RT_RAY_CHUNK;      // rays per upload - kernel - download round: 65 bytes per ray, so at most ~273 MB of device memory whatever the batch
 constexpr size_t kPixelChunk = RT_PIXEL_CHUNK;  // pixels per upload - kernel - download round: 48 bytes per pixel
 struct ChunkState : QueryState {
     char* d_buf[kChunkBuffers] = {};
     size_t cap[kChunkBuffers] = {};     // items d_buf[k] holds
-    uint32_t* d_queue = nullptr;        // RtPixelBatch::queue (renderPixels)
+    uint32_t* d_queue = nullptr;        // RtPixelBatch::queue (renderPixels), RtRadianceBatch::queue (radianceRays)
 };
 
 // refineFrame: the adaptive frame's per-pixel state for the WHOLE image, the list of a pass and the batch arrays of one chunk of it (rt_refine.h), with a
@@ -297,7 +299,7 @@ PreviewState g_preview;
 DisplayState g_display;
 PoseState g_pose;
 MotionState g_motion;
-ChunkState g_rays, g_pixels;
+ChunkState g_rays, g_pixels, g_radiance;
 RefineState g_refine;
 
 // The adaptive frame back to "the next refineFrame starts at sample 0" (rtResetRefine, setCamera, setRenderOptions, the scene edits); the buffers stay.
@@ -420,6 +422,7 @@ void setup_devices() {
     free_pass(g_pose);                                      // (the marked pose goes with it)
     free_pass(g_rays);
     free_pass(g_pixels);
+    free_pass(g_radiance);
     free_pass(g_refine);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
@@ -475,7 +478,7 @@ void setup_devices() {
         c.devs.push_back(d);
     }
     HIP_CHECK(hipSetDevice(c.devs[0].device));              // the query calls' own event pairs, on the device they run on
-    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_refine }) {
+    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine }) {
         q->device = c.devs[0].device;
         HIP_CHECK(hipEventCreate(&q->ev_start));
         HIP_CHECK(hipEventCreate(&q->ev_stop));
@@ -531,6 +534,7 @@ void cleanup_impl() {
     free_pass(g_pose);                                      // (the marked pose goes with it)
     free_pass(g_rays);
     free_pass(g_pixels);
+    free_pass(g_radiance);
     free_pass(g_refine);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
@@ -719,9 +723,22 @@ void launch_pixels(const DeviceState& d, const RtPixelBatch& b, int max_waves) {
     }
 }
 
-// The query calls (traceRays / occludedRays, renderPixels, refineFrame) differ in their arguments, buffers and kernels; the rest is here, once.
+// The radiance kernel of the scene kind and fp mode over the batch `b` (radianceRays): the parameter block of launch_pixels - what a path is -, of which the
+// kernel reads neither camera, image size nor partition.  max_waves: RtSwitches::pixels_waves as the call read it.
+void launch_radiance(const DeviceState& d, const RtRadianceBatch& b, int max_waves) {
+    const bool fast = g_ctx.opt.fp == RT_FP_FAST;
+    if (g_ctx.is_spheres) {
+        const RtSphereParams p = sphere_path_params(d, whole_image_partition());
+        HIP_CHECK(fast ? rt_launch_radiance_spheres_fast(p, b, max_waves, d.stream) : rt_launch_radiance_spheres_parity(p, b, max_waves, d.stream));
+    } else {
+        const RtMeshParams p = mesh_path_params(d, whole_image_partition());
+        HIP_CHECK(fast ? rt_launch_radiance_mesh_fast(p, b, max_waves, d.stream) : rt_launch_radiance_mesh_parity(p, b, max_waves, d.stream));
+    }
+}
 
-// What "defined per pixel" asks of the options in force (renderPixels, refineFrame), under the function's name `fn`.
+// The query calls (traceRays / occludedRays, renderPixels, radianceRays, refineFrame) differ in their arguments, buffers and kernels; the rest is here, once.
+
+// What "defined per pixel" asks of the options in force (renderPixels, radianceRays, refineFrame), under the function's name `fn`.
 void check_per_pixel(const char* fn) {
     const RenderContext& c = g_ctx;
     if (c.opt.rng != RT_RNG_REFERENCE_STREAM) rt_fail(": only the reference RNG stream is one sequential stream per pixel (RT_RNG_COUNTER sums sample chunks)", fn);
@@ -1627,6 +1644,54 @@ void renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, const
 double rtLastPixelsMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastPixelsMs before init");
     return g_ctx.pixels_ms;
+}
+
+// A list of the caller's own rays (rt_api.h), through run_chunks with the queue word of the radiance kernels: RT_RAY_CHUNK rays at a time, 68
+// bytes per ray.  host[k] = the caller's array of buffer k, or NULL.  A ray without ids is seeded by its index in the caller's list: the chunk's first index
+// goes with the batch.
+static void run_radiance(int n, int ns_all, void* const host[kRadBuffers]) {
+    const int state_dir = host[kRadFirst] ? kUp | kDown : kDown;    // (the states go up only where an entry can continue one: `first` is given)
+    const ChunkBuffer table[kRadBuffers] = { { 12, kUp }, { 12, kUp }, { 4, kUp }, { 4, kUp }, { 4, kUp }, { 16, state_dir }, { 12, kDown }, { 4, kDown } };
+    const int max_waves = rt_read_switches().pixels_waves;
+    size_t done = 0;                                        // rays of the chunks launched so far
+    g_ctx.radiance_ms = run_chunks(g_radiance, (size_t)n, kRayChunk, table, kRadBuffers, host, true, [&](char* const* dev, size_t m) {
+        RtRadianceBatch b;
+        b.org = reinterpret_cast<const float*>(dev[kRadOrg]); b.dir = reinterpret_cast<const float*>(dev[kRadDir]);
+        b.ids = reinterpret_cast<const uint32_t*>(dev[kRadIds]); b.ns = reinterpret_cast<const int32_t*>(dev[kRadNs]);
+        b.first = reinterpret_cast<const int32_t*>(dev[kRadFirst]); b.state = reinterpret_cast<uint32_t*>(dev[kRadState]);
+        b.out = reinterpret_cast<rt_vec3*>(dev[kRadOut]); b.rays = reinterpret_cast<uint32_t*>(dev[kRadRays]);
+        b.queue = g_radiance.d_queue; b.n = (int32_t)m; b.ns_all = ns_all; b.id0 = (uint32_t)done;
+        launch_radiance(g_ctx.devs[0], b, max_waves);
+        done += m;
+    });
+}
+
+void radianceRays(int n, const float* org, const float* dir, const uint32_t* ids, int ns_all, const int32_t* ns, const int32_t* first, uint32_t* state,
+                  rt_vec3* out, uint32_t* rays) {
+    const RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("radianceRays before init");
+    if (n < 0) rt_fail("radianceRays: n is negative");
+    if (n == 0) return;
+    if (!org || !dir) rt_fail("radianceRays: org and dir must not be null");
+    if (!out && !state && !rays) rt_fail("radianceRays: out, state and rays are all null");
+    if (first && !state) rt_fail("radianceRays: first needs state (the sums and stream words the rays resume from)");
+    check_per_pixel("radianceRays");
+    for (int k = 0; k < n; k++) {                           // every entry, before anything is uploaded
+        const long long cnt = ns ? ns[k] : ns_all, f = first ? first[k] : 0;
+        if (cnt < 1) rt_fail("radianceRays: a ray's sample count is below 1");
+        if (f < 0) rt_fail("radianceRays: a ray's first sample is negative");
+        if (f + cnt > RT_PROGRESSIVE_MAX_SAMPLES) rt_fail("radianceRays: first + count above RT_PROGRESSIVE_MAX_SAMPLES");
+        // (a zero word is no state of any stream, and the one on which the rejection loops would never end on the device: renderPixels)
+        if (f > 0 && state[4 * (size_t)k + 3] == 0u) rt_fail("radianceRays: a resumed ray's stream word is 0 (not a state radianceRays returned)");
+    }
+    void* const host[kRadBuffers] = { const_cast<float*>(org), const_cast<float*>(dir), const_cast<uint32_t*>(ids), const_cast<int32_t*>(ns),
+                                      const_cast<int32_t*>(first), state, out, rays };
+    run_radiance(n, ns_all, host);
+}
+
+double rtLastRadianceMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastRadianceMs before init");
+    return g_ctx.radiance_ms;
 }
 
 // Adaptive sampling on the device (rt_api.h).  One call is one pass over the whole image on the first in-process device: select (rt_refine.h)

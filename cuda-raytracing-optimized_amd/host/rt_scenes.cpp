@@ -136,4 +136,13 @@ void rtCentreRays(const rt_camera* cam, int nx, int ny, const int32_t* ij, int n
     }
 }
 
+// The camera under which a frame's pixel is the caller's ray (rt_host.h, radianceRays): nothing but the two points is set.
+void rtPinholeCamera(const float o[3], const float target[3], rt_camera* out) {
+    memset(out, 0, sizeof *out);
+    for (int a = 0; a < 3; a++) {
+        out->origin.e[a] = o[a];
+        out->lower_left_corner.e[a] = target[a];
+    }
+}
+
 }  // extern "C"

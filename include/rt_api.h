@@ -438,6 +438,41 @@ void   renderPixels(int n, const int32_t* ij, int ns_all, const int32_t* ns, con
                     uint32_t* state, rt_vec3* out, uint32_t* rays);
 double rtLastPixelsMs(void);   /* HIP-event time of the pixel kernels of the last renderPixels, summed over its chunks; 0 before the first */
 
+/* --- path-tracing the caller's own rays: light probes, cube maps at a point, lightmap and vertex bakes, a camera model of the caller's own ---------
+ * radianceRays answers "how much light arrives at this point from this direction" for n caller-chosen rays: the whole path tracer of a frame behind a ray
+ * that does not come from the camera, with a caller-chosen number of samples each, resumable like renderPixels.
+ *   Ray k          o = org[3k .. 3k+2], d = dir[3k .. 3k+2].  d is raw and is normalised once: dn = d / sqrt(d.x*d.x + d.y*d.y + d.z*d.z), traceRays' rule.
+ *                  The caller owes a finite o and a finite, non-zero d; rays are not validated one by one.  Duplicates and any order are allowed; every
+ *                  entry is answered independently, in the caller's order.
+ *   Seed id        id = ids ? ids[k] : (uint32_t)k - k the index in the caller's list, whatever the chunking.  Two entries with one id and one ray are equal.
+ *   Sample range   c = ns ? ns[k] : ns_all samples are traced for ray k: samples f .. f+c-1 of that ray's stream, f = first ? first[k] : 0.
+ *   f == 0         the stream word starts at the reference's seed of `id` (kernels.cu:541-542), the sum at 0: ONE sequential xorshift stream over the ray's
+ *                  samples, sum += sample in sample order.
+ *   f > 0          state[4k .. 4k+2] are the bits of the fp32 colour sum after f samples, state[4k+3] is the stream's xorshift word: the ray resumes from
+ *                  them (what a call with `state` returned for the same ray after f samples; nothing else is checked).
+ *   Sample         in this order: two rnd() draws, discarded (the jitter draws of kernels.cu:549-550); one random_in_unit_disk, discarded (the lens draw of
+ *                  camera.h: its rejection loop as it stands, however many words it takes); then the loop of color() (kernels.cu:397-531) from origin o
+ *                  with direction dn, specular = false, inside = false, attenuation 1, under the options in force: max_depth, t_min, sky, rr, and for
+ *                  meshes nee, light, floor and the textures; sum += colour.  With max_depth <= 0 a sample draws its head and is black, without a ray.
+ *   Outputs        out, state and rays may each be NULL, not all three.  state (read for f > 0, written if non-NULL: in place) receives the sum and the word
+ *                  after sample f+c-1;  out[k] = sum / (float)(f + c);  rays[k] = the closest-hit queries of these c samples, shadow rays not included.
+ * The head of a sample burns the camera's draws so that a ray is exactly a one-pixel render through a pinhole at o: for o and T without negative-zero
+ * coordinates and d = fl(T - o), ray (o, d, id) at f + c samples is bit-identical in RT_FP_PARITY to the pixel with global id `id` that runRenderer(f + c)
+ * stores under rtPinholeCamera(o, T) (rt_host.h), for any split of f + c into calls.  That gives the call a CPU oracle and a check inside the library, for
+ * about five RNG words per sample against a path of rays.  In RT_FP_FAST the FAST objects' arithmetic runs: the same estimate with no bit promise.
+ * The result does not depend on the camera, nx, ny, setCamera, stripe_rows, part_rank / part_world or the device list: all rays run on the first in-process
+ * device, RT_RAY_CHUNK rays at a time - upload, kernel, download -; the device buffers (68 bytes per ray of the largest chunk seen - org 12, dir 12, ids 4,
+ * ns 4, first 4, state 16, out 12, rays 4 -, only for the arrays that were passed) are freed where the ray buffers are.  The call is blocking and follows
+ * setRenderOptions, the scene edits and rebuildBvh.  RT_PIXELS_WAVES caps its waves as it caps renderPixels'.  It changes nothing an existing call observes:
+ * the framebuffer, getRenderStats, rtLastLaunches, rtLastSphereForm, the progressive frame and rtProgressiveSamples, the cost map of sphere frames, every
+ * history and every other rtLast*Ms stay as they were.  n == 0 returns at once: nothing is written and rtLastRadianceMs stays as it was.  Misuse (rt error,
+ * exit 99), checked on the host before anything is uploaded: before init (rtLastRadianceMs as well), n < 0, org or dir NULL, out, state and rays all NULL,
+ * c < 1 or f < 0, f + c > RT_PROGRESSIVE_MAX_SAMPLES, first given without state, a resumed ray (f > 0) whose stream word is 0, RT_RNG_COUNTER or
+ * variant != 0, rt_render_options.floor = 1 or nee = 1 on a sphere scene (the frame conditions renderPixels refuses). */
+void   radianceRays(int n, const float* org, const float* dir, const uint32_t* ids, int ns_all, const int32_t* ns,
+                    const int32_t* first, uint32_t* state, rt_vec3* out, uint32_t* rays);
+double rtLastRadianceMs(void);   /* HIP-event time of the radiance kernels of the last radianceRays, summed over its chunks; 0 before the first */
+
 /* --- adaptive sampling: the samples go where the image is still noisy ---------------------------------------------------------------
  * refineFrame renders an adaptive frame: every pixel gets samples in batches until an estimate of its own error says it has enough.  The frame's state, the
  * selection, the list of a pass and the statistics live on the device; the pixel kernels of renderPixels trace the samples.  One call is one pass: select,

@@ -45,6 +45,14 @@ void rtStaircaseCamera(int nx, int ny, rt_camera* cam);
  * for traceRays without a GPU.  Pixels outside the image are computed like any other. */
 void rtCentreRays(const rt_camera* cam, int nx, int ny, const int32_t* ij, int n, float* org, float* dir);
 
+/* The camera that turns a frame's pixels into one ray: origin = o, lower_left_corner = target, every other field 0 (no extent, no lens).  Under it get_ray
+ * (camera.h:8-12) returns origin o and direction target - o for every pixel and every jitter, because the jitter and the lens sample multiply zero vectors.
+ * This is the equivalence radianceRays (rt_api.h) is defined by: for o and T without negative-zero coordinates and d = fl(T - o) per component, the ray
+ * (o, d, id) of radianceRays at f + c samples is bit-identical to the pixel with global id `id` (= j*nx + i) that runRenderer(f + c) stores under
+ * rtPinholeCamera(o, T) - whatever the image size, which only decides which ids exist.  A frame under this camera is a constant-direction image: useful as
+ * the reference of a ray, not as a picture. */
+void rtPinholeCamera(const float o[3], const float target[3], rt_camera* out);
+
 /* ---- mesh scenes: BVH in the layout hitBvh expects (kernels.cu:154-224) ---- */
 
 typedef struct rt_host_mesh rt_host_mesh;    /* opaque; owns tris + bvh */
