@@ -1321,7 +1321,7 @@ def rmse(f, g):
 # ---------------------------------------------------------------------------------------------
 
 PROBE_SYMBOLS = [f"rtProbe{n}_{m}" for n in ("Rng", "DiskSphere", "GetRay", "SphereHit", "TriangleHit", "Bbox", "Scatter", "Math", "ShadowRay", "PlaneHit", "SinCos", "Schlick")
-                 for m in ("parity", "fast")] + ["rtProbeRenorm_parity", "rtProbeExactDiv_parity"]
+                 for m in ("parity", "fast")] + ["rtProbeRenorm_parity", "rtProbeExactDiv_parity", "rtProbeExactDivStored_parity"]
 
 
 def _f32(a):
@@ -1441,6 +1441,15 @@ class Probe:
         v = _f32(xyzl).reshape(-1, 4); n = len(v)
         out = np.zeros((n, 14), np.float32)
         self._fn("ExactDiv")(_p(v), C.c_int(n), _p(out))
+        return out
+
+    def exactdiv_stored(self, xyzl):
+        """(x, y, z) / l by the divisor's stored reciprocal (csrc/rt_exactdiv.h rt_exdiv3_y: the reciprocal from one kernel launch, the quotients from a
+        second) beside the plain operator, per operand set (x, y, z, l): 7 floats each (include/rt_probe.h).  The parity build only."""
+        assert self.sfx == "_parity", "the fast build keeps the plain operators: it has no rtProbeExactDivStored"
+        v = _f32(xyzl).reshape(-1, 4); n = len(v)
+        out = np.zeros((n, 7), np.float32)
+        self._fn("ExactDivStored")(_p(v), C.c_int(n), _p(out))
         return out
 
     def math(self, a, b):

@@ -51,7 +51,9 @@
 // Where: the folded kinds of the sphere kernel's cost-ordered dispatch (rt_device.h, the template switch XD).  Every other kernel - the first dispatch, the
 // general form, the diagnostic kinds, the ray queries, the guides, the mesh kernels - keeps the plain operators and compiles to what it was.
 // rt_exdiv3 under rt_exdiv3_window, the form over a divisor of any size, was measured on the hit normal's (hp - c) / radius and did not pay on top of the
-// other two: no kernel uses it; the probe and the host check hold it.
+// other two: no kernel uses it; the probe and the host check hold it.  With the divisor's part taken out of the ray step altogether - rt_exdiv3_y: the
+// refined reciprocal of a sphere's radius is stored beside the radius when the scene is staged - the same quotients do pay: the four-wave
+// folded kinds use it for the hit normal.
 #pragma once
 
 #include <stdint.h>
@@ -90,6 +92,24 @@ RT_EXDIV_FN float rt_exdiv_component(float x, float l, float y) {
 RT_EXDIV_FN RtExdiv3 rt_exdiv3(float x, float y, float z, float l, float y0) {
     const float r = rt_exdiv_recip(l, y0);
     return { rt_exdiv_component(x, l, r), rt_exdiv_component(y, l, r), rt_exdiv_component(z, l, r) };
+}
+// rt_exdiv3 with the refined reciprocal given: y = rt_exdiv_recip(l, v_rcp_f32(l)) depends on the divisor alone, so a divisor that is a constant of the
+// scene (a sphere's radius under the hit normal, intersections.h:95) has it computed once, when the scene is staged, and each hit runs the fifteen
+// per-component instructions and no reciprocal.  Same bits as rt_exdiv3, hence as the plain operator inside the window: y is the same three instructions on
+// the same value, and v_rcp_f32 returns the same result for the same input on the same device whenever it runs.  The host check (`exactdiv_dump --shared`)
+// holds the transcription; the device is held by rtProbeExactDivStored, which computes y in one launch and the quotients in a second from the stored y.
+RT_EXDIV_FN RtExdiv3 rt_exdiv3_y(float x, float y, float z, float l, float yr) {
+    return { rt_exdiv_component(x, l, yr), rt_exdiv_component(y, l, yr), rt_exdiv_component(z, l, yr) };
+}
+// What is stored beside a divisor: its refined reciprocal, or - the divisor outside the window - a NaN, the marker that fails rt_exdiv3_window_y
+RT_EXDIV_FN float rt_exdiv_stored(float l, float y0) {
+    return (l >= kExdivLo && l <= kExdivHi) ? rt_exdiv_recip(l, y0) : rt_exdiv_float(0x7fc00000u);
+}
+// the guard of rt_exdiv3_y: rt_exdiv3_window on the numerators, the divisor's part of it read off the stored word (a NaN is not equal to itself)
+RT_EXDIV_FN bool rt_exdiv3_window_y(float x, float y, float z, float yr) {
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y), az = __builtin_fabsf(z);
+    const float sum = ax + ay + az, least = __builtin_fminf(ax, __builtin_fminf(ay, az));
+    return sum <= kExdivHi && least >= kExdivLo && yr == yr;
 }
 // the guard of vec3 / float: the sum of the magnitudes bounds each of them from above and is NaN / inf when one of them is; the minimum bounds them from below
 // (fminf drops a NaN, the sum does not)

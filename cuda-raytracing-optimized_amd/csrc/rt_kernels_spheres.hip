@@ -117,8 +117,36 @@ __global__ void __launch_bounds__(256) k_poison_fb(const RtSphereParams P) {
 // sphereHit, intersections.h:85-104, on a pre-normalised direction `dn` with a = dot(dn,dn) hoisted (same bits every
 // call) and r2 = radius*radius precomputed (same bits).  `t_max` is INCLUSIVE here: the caller applies the reference's
 // strict `t < closest` itself, extended by the first-index-wins tie rule (see accept()).
-// XD (the folded kinds of the cost-ordered dispatch): the two roots over a by rt_exactdiv.h form B
-template <bool XD = false>
+// XD (the folded kinds of the cost-ordered dispatch; 0 in every other kernel): bit 0 = the bounce's divisions by rt_exactdiv.h (the two roots over a by form
+// B, here), the bits above it the cuts of the ray step's loads, each compiled in by its bit of RT_STEP_CUTS so that one source gives every
+// contestant of a leave-one-out measurement:
+//   kXdBurst   scan_single: the eight rounds of the 512-slot scene read their slots in one burst, at immediate offsets, before the first pre-test
+//   kXdTail    scan_single: the exact tail reads orig[] together with the slot
+//   kXdShade   shade: the four hit records are read together, ahead of the hit point
+//   kXdRecip   shade: the hit normal by the radius' stored reciprocal (stage_scene<.., RCP>; rt_exactdiv.h rt_exdiv3_y)
+// Which kind takes which (RT_STEP_CUTS_*: bit 0 burst, 1 tail, 2 shade, 3 reciprocal) is decided by its registers, read off the code objects: the one-list
+// four-wave kinds (~100 VGPRs) take all four (113 VGPRs, no scratch); the kinds without the one-list scan fill their 128 - the burst's 32 registers are
+// out of the question and the tail's pinned pair doubles their scratch, so they take the shade reads and the reciprocal; the six-wave kinds (80 VGPRs,
+// spilling) take the shade reads alone - the tail adds a spilled register, and the reciprocals are 4 bytes per slot of an LDS budget that two workgroups
+// per CU share.
+#ifndef RT_STEP_CUTS
+#define RT_STEP_CUTS 15
+#endif
+#ifndef RT_STEP_CUTS_WIDE
+#define RT_STEP_CUTS_WIDE 12
+#endif
+#ifndef RT_STEP_CUTS_SIX
+#define RT_STEP_CUTS_SIX 4
+#endif
+constexpr int kXdOn = 1, kXdBurst = 2, kXdTail = 4, kXdShade = 8, kXdRecip = 16;
+constexpr int xd_of(bool folded, int lean) {
+#ifdef RT_MODE_PARITY
+    return !folded ? 0 : (kXdOn | (((lean & 4) ? (RT_STEP_CUTS & RT_STEP_CUTS_SIX & 6) : ((lean & 2) ? RT_STEP_CUTS : (RT_STEP_CUTS & RT_STEP_CUTS_WIDE))) << 1));
+#else
+    return folded ? kXdOn : 0;
+#endif
+}
+template <int XD = 0>
 __device__ __forceinline__ float sphere_hit_exact(float4 s, f3 org, f3 dn, float a, float t_min, float t_max) {
     const f3 oc = org - F3(s.x, s.y, s.z);
     const float b = dot(oc, dn);
@@ -170,7 +198,9 @@ struct SceneLds {
 //        2 = what every sphere TEST reads (centres, radii^2, group boxes, original indices: 21 bytes per sphere) in the LDS, what only a HIT
 //            reads (colour, type, radius, slot index: 32 bytes per sphere) left in global memory - scenes of 500..1700 spheres keep two
 //            workgroups per CU this way, scenes up to ~5500 spheres stay out of the all-global form.
-template <bool WITH_FB, int SCENE = 0>
+// RCP (SCENE 0): the rad array holds PAIRS (radius, rt_exdiv_stored(radius)) - the refined reciprocal computed here, once per workgroup, on the device that
+// divides by it; a hit reads both in one ds_read_b64 off the base it read the radius from (radius_and_recip), so the ray step carries no new address
+template <bool WITH_FB, int SCENE = 0, bool RCP = false>
 __device__ __forceinline__ SceneLds stage_scene(const RtSphereParams& P, unsigned char* smem, float** after) {
     if (SCENE == 1) {                                                // the scene does not fit the LDS: read it where it lies (L2-resident)
         *after = nullptr;
@@ -192,9 +222,12 @@ __device__ __forceinline__ SceneLds stage_scene(const RtSphereParams& P, unsigne
     int*    s_typ = reinterpret_cast<int*>(s_mat + P.n_padded);
     int*    s_org = s_typ + P.n_padded;
     float*  s_rad = reinterpret_cast<float*>(s_org + P.n_padded);
-    int*    s_sof = reinterpret_cast<int*>(s_rad + P.n_padded);
+    int*    s_sof = reinterpret_cast<int*>(s_rad + (RCP ? 2 : 1) * P.n_padded);
     for (int k = threadIdx.x; k < P.n_padded + P.n_groups; k += (int)blockDim.x) s_sph[k] = P.spheres[k];   // the image is laid out for the LDS on the host
     for (int k = threadIdx.x; k < P.n_padded; k += (int)blockDim.x) {
+#ifdef RT_MODE_PARITY
+        if (RCP) { const float r = P.rad[k]; reinterpret_cast<float2*>(s_rad)[k] = make_float2(r, rt_exdiv_stored(r, __builtin_amdgcn_rcpf(r))); } else
+#endif
         s_rad[k] = P.rad[k];
         s_mat[k] = P.mat_color[k];
         s_typ[k] = P.mat_type[k];
@@ -208,6 +241,9 @@ __device__ __forceinline__ SceneLds stage_scene(const RtSphereParams& P, unsigne
     __syncthreads();
     return { s_sph, s_grp, s_mat, s_typ, s_org, s_sof, s_rad, scratch };
 }
+
+// (radius, its stored reciprocal) of a slot of a scene staged with RCP: the hit normal of the folded kinds (XD & kXdRecip)
+__device__ __forceinline__ float2 radius_and_recip(const SceneLds& S, int slot) { return reinterpret_cast<const float2*>(S.rad)[slot]; }
 
 // Per-lane path state (path, helper_structs.h:48-71, minus what sphere scenes never use).
 struct Lane {
@@ -585,7 +621,7 @@ __device__ __forceinline__ int wave_inclusive_scan(int x) {
 // loop below runs exactly once with every pass-level decision known at compile time (no windows, no carry between passes, no choice of the box test).
 //   OP   words of the one-list form: 0 = the general pass loop; 1 / 2 = the scene has at most 32 / 64 small groups, which take ONE list per ray batch
 //   C3   (with OP > 0) the prefilter is the general 3-axis one (group_needs_cells) instead of the shared-vertical-axis one (group_needs_cells_shared<1>)
-template <int OP = 0, bool C3 = false, bool XD = false>
+template <int OP = 0, bool C3 = false, int XD = 0>
 __device__ __forceinline__ Hit scan_pairs(const RtSphereParams& P, const SceneLds& S, f3 org, f3 dn, float a, bool has_ray, bool cull,
                                           uint32_t& groups_done, uint32_t& boxes_done, unsigned long long* tm = nullptr) {
     // tm (diagnostic instantiation only): cycles in [1] big spheres, [2] group boxes + pair list, [3] pair rounds, [4] candidates
@@ -849,7 +885,7 @@ __device__ __forceinline__ Hit scan_pairs(const RtSphereParams& P, const SceneLd
 // boxes are tested one group per lane.  Same exact tests, same (t, original index) merge as scan_pairs.  WAVE-LEVEL.
 constexpr int kSparseRays = 4;
 
-template <bool XD = false>
+template <int XD = 0>
 __device__ __forceinline__ void sparse_test_slot(const RtSphereParams& P, const SceneLds& S, int slot, f3 O, f3 D, float A,
                                                  unsigned long long* best) {
     const float4 sph = S.sph[sidx(slot)];
@@ -871,7 +907,7 @@ __device__ __forceinline__ void sparse_test_slot(const RtSphereParams& P, const 
 // (reachable (ray, group) pair, sphere of the group) - are numbered across the rays and dealt to the 64 lanes, 64 at a time;
 // a lane fetches the ray of its item from the wave's LDS ray table.  Two rays therefore cost three lane passes like one
 // ray does (16 + 16 big slots, 31 + 31 boxes, ~2 x 16 spheres), where handling the rays one after the other cost six.
-template <bool ONEPASS = false, bool XD = false>
+template <bool ONEPASS = false, int XD = 0>
 __device__ __forceinline__ Hit scan_sparse(const RtSphereParams& P, const SceneLds& S, f3 org, f3 dn, float a, unsigned long long live,
                                            bool cull, unsigned long long* tm = nullptr) {
     // tm (diagnostic instantiation only): cycles in [10] ray table + box set-up, [11] big spheres, [12] group boxes, [13] sphere tests + read-back
@@ -978,7 +1014,7 @@ __device__ __forceinline__ Hit scan_sparse(const RtSphereParams& P, const SceneL
 // independent LDS reads for the 488-sphere scene), resolves its own candidates with the literal sphereHit tail, and the per-lane (t, original
 // index) keys are merged on the scalar unit.  Same pre-test and slack as sparse_test_slot, same exact tail, same tie rule.  WAVE-LEVEL; q is
 // wave-uniform; at most 32 rounds (2048 slots).
-template <bool XD = false>
+template <int XD = 0>
 __device__ __forceinline__ Hit scan_single(const RtSphereParams& P, const SceneLds& S, int q, f3 org, f3 dn, float a) {
     const int lane = threadIdx.x & 63;
     auto bc = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), q)); };
@@ -987,23 +1023,51 @@ __device__ __forceinline__ Hit scan_single(const RtSphereParams& P, const SceneL
     const float Ak = A - 3.814697265625e-6f;
     const int rounds = P.n_padded >> 6;
     uint32_t mask = 0;
+    // (`if constexpr`: the kinds without a cut keep the text, and with it the instruction stream, they had)
+    if constexpr ((XD & kXdBurst) != 0) {
+        auto pre_test = [&](float4 sph, int r) {
+            const f3 oc = O - F3(sph.x, sph.y, sph.z);
+            const float b = __builtin_fmaf(oc.z, D.z, __builtin_fmaf(oc.y, D.y, oc.x * D.x));
+            const float c = __builtin_fmaf(oc.z, oc.z, __builtin_fmaf(oc.y, oc.y, __builtin_fmaf(oc.x, oc.x, -sph.w)));
+            const float v = __builtin_fmaf(Ak, c, -__builtin_fmaf(b, b, 7.62939453125e-6f * sph.w));
+            mask |= (__float_as_uint(v) >> 31) << r;                 // flagged: see sparse_test_slot
+        };
+        if (rounds == 8) {                                           // the 512-slot scene: ONE LDS round trip - the eight reads issued before the first test
+            // sidx((r << 6) + lane) = 68 r + lane + (lane >> 4): round r is the lane's own float4 plus 68 r, an immediate offset of one address
+            const float4* const lp = S.sph + sidx(lane);
+            const float4 s0 = lp[0], s1 = lp[68], s2 = lp[136], s3 = lp[204], s4 = lp[272], s5 = lp[340], s6 = lp[408], s7 = lp[476];
+            pre_test(s0, 0); pre_test(s1, 1); pre_test(s2, 2); pre_test(s3, 3); pre_test(s4, 4); pre_test(s5, 5); pre_test(s6, 6); pre_test(s7, 7);
+        } else {
 #pragma unroll 4
-    for (int r = 0; r < rounds; r++) {
-        const float4 sph = S.sph[sidx((r << 6) + lane)];
-        const f3 oc = O - F3(sph.x, sph.y, sph.z);
-        const float b = __builtin_fmaf(oc.z, D.z, __builtin_fmaf(oc.y, D.y, oc.x * D.x));
-        const float c = __builtin_fmaf(oc.z, oc.z, __builtin_fmaf(oc.y, oc.y, __builtin_fmaf(oc.x, oc.x, -sph.w)));
-        const float v = __builtin_fmaf(Ak, c, -__builtin_fmaf(b, b, 7.62939453125e-6f * sph.w));
-        mask |= (__float_as_uint(v) >> 31) << r;                     // flagged: see sparse_test_slot
+            for (int r = 0; r < rounds; r++) pre_test(S.sph[sidx((r << 6) + lane)], r);
+        }
+    } else {
+#pragma unroll 4
+        for (int r = 0; r < rounds; r++) {
+            const float4 sph = S.sph[sidx((r << 6) + lane)];
+            const f3 oc = O - F3(sph.x, sph.y, sph.z);
+            const float b = __builtin_fmaf(oc.z, D.z, __builtin_fmaf(oc.y, D.y, oc.x * D.x));
+            const float c = __builtin_fmaf(oc.z, oc.z, __builtin_fmaf(oc.y, oc.y, __builtin_fmaf(oc.x, oc.x, -sph.w)));
+            const float v = __builtin_fmaf(Ak, c, -__builtin_fmaf(b, b, 7.62939453125e-6f * sph.w));
+            mask |= (__float_as_uint(v) >> 31) << r;                 // flagged: see sparse_test_slot
+        }
     }
     Hit h = { FLT_MAX, -1, 0x7fffffff };
     while (mask) {
         const int r = __builtin_ctz(mask);
         mask &= mask - 1u;
         const int k = (r << 6) + lane;
-        const float t = sphere_hit_exact<XD>(S.sph[sidx(k)], O, D, A, P.t_min, FLT_MAX);
-        const int o = S.orig[k];
-        if (o != 0x7fffffff && t < FLT_MAX) accept(h, t, k, o);
+        if constexpr ((XD & kXdTail) != 0) {                         // the slot and its original index in ONE round trip, ahead of the tail's arithmetic
+            float4 sp = (S.sph + sidx(lane))[68 * r];                // (= S.sph[sidx(k)]: one multiply-add for the address)
+            int o = S.orig[k];
+            asm volatile("" : "+v"(sp.x), "+v"(o));                  // (holds the read of orig[] here: the compiler sinks it behind sphereHit and waits for it there)
+            const float t = sphere_hit_exact<XD>(sp, O, D, A, P.t_min, FLT_MAX);
+            if (o != 0x7fffffff && t < FLT_MAX) accept(h, t, k, o);
+        } else {
+            const float t = sphere_hit_exact<XD>(S.sph[sidx(k)], O, D, A, P.t_min, FLT_MAX);
+            const int o = S.orig[k];
+            if (o != 0x7fffffff && t < FLT_MAX) accept(h, t, k, o);
+        }
     }
     // merge: lexicographic minimum of (t, orig) over the lanes that found something (t > t_min >= 0: the bit patterns order like the values)
     unsigned long long found = __ballot(h.closest < FLT_MAX);
@@ -1030,7 +1094,7 @@ __device__ __forceinline__ Hit scan_single(const RtSphereParams& P, const SceneL
 template <bool STATS>
 __device__ __forceinline__ void ray_stat(const RtSphereParams& P, int k) { if (STATS && P.counters) atomicAdd(&P.counters->ref_stats[k], 1ull); }
 
-template <bool STATS, bool BASIC = false, bool XD = false>
+template <bool STATS, bool BASIC = false, int XD = 0>
 __device__ __forceinline__ bool shade(const RtSphereParams& P, const SceneLds& S, Lane& L, f3 dn, Hit h, f3& sample) {
     sample = F3(0, 0, 0);                                            // kernels.cu:397
     const bool primary = L.bounce == 0;
@@ -1045,14 +1109,39 @@ __device__ __forceinline__ bool shade(const RtSphereParams& P, const SceneLds& S
         return true;
     }
     if (primary) ray_stat<STATS>(P, RT_STAT_PRIMARY_HIT_MESH);              // kernels.cu:428-432
-    const float4 sc4 = S.sph[sidx(h.sid)];
-    const float radius = S.rad[h.sid];                               // slot-indexed, like every scene array on the device
+    float4 sc4 = S.sph[sidx(h.sid)];
+    float radius, yr = 0.0f;
+    if (XD & kXdRecip) { const float2 ry = radius_and_recip(S, h.sid); radius = ry.x; yr = ry.y; }
+    else radius = S.rad[h.sid];                                      // slot-indexed, like every scene array on the device
+    float4 m;
+    int type;
+    if (XD & kXdShade) {                                             // the hit's records in ONE LDS round trip: their address has been known since the scan
+        m = S.mat[h.sid];
+        type = S.typ[h.sid];
+    }
     const f3 hp = L.org + h.closest * dn;                            // ray.h:12 point_at_parameter
-    f3 normal = (hp - F3(sc4.x, sc4.y, sc4.z)) / radius;             // intersections.h:95
+    // (the empty asm holds the reads above it: the compiler sinks the last two behind the normal's divisions and waits for them there)
+    if (XD & kXdShade) asm volatile("" : "+v"(sc4.x), "+v"(radius), "+v"(m.x), "+v"(type), "+v"(yr));
+    f3 normal;
+#ifdef RT_MODE_PARITY
+    if (XD & kXdRecip) {                                             // intersections.h:95 by the stored reciprocal (rt_exactdiv.h rt_exdiv3_y): the same bits
+        const f3 d = hp - F3(sc4.x, sc4.y, sc4.z);
+        const RtExdiv3 q = rt_exdiv3_y(d.x, d.y, d.z, radius, yr);
+        normal = F3(q.x, q.y, q.z);
+        if (!rt_exdiv3_window_y(d.x, d.y, d.z, yr)) {                // a zero, tiny or huge component, or the radius' marker: the plain division
+            asm volatile("");                                        // (a real branch, as in div_a2)
+            normal = d / radius;
+        }
+    } else
+#endif
+    normal = (hp - F3(sc4.x, sc4.y, sc4.z)) / radius;                // intersections.h:95
     if (dot(dn, normal) > 0.0f) normal = -normal;                    // kernels.cu:354-355
-    const float4 m = S.mat[h.sid];
+    if (!(XD & kXdShade)) {
+        m = S.mat[h.sid];
+        type = S.typ[h.sid];
+    }
     Scatter sc;
-    material_scatter<BASIC, XD>(sc, h.closest, hp, normal, L.inside, L.dir, S.typ[h.sid], F3(m.x, m.y, m.z), m.w, L.rng);
+    material_scatter<BASIC, (XD != 0)>(sc, h.closest, hp, normal, L.inside, L.dir, type, F3(m.x, m.y, m.z), m.w, L.rng);
     L.org = L.org + sc.t * L.dir;                                    // kernels.cu:485-489
     L.dir = sc.wi;
     L.atten = L.atten * sc.throughput;
@@ -1077,7 +1166,7 @@ __device__ __forceinline__ bool shade(const RtSphereParams& P, const SceneLds& S
 // lanes must call it together.  With many live lanes each lane scans the sphere list for its own ray; with few
 // (the tail of a tile / of the frame, where a handful of pixels in sphere / ground wedges need thousands of rays each) the
 // whole wave works on one ray at a time, which cuts the latency of a ray ~30x and with it the critical path.
-template <bool LEGACY, bool STATS = false, bool BASIC = false, int OP = 0, bool C3 = false, bool XD = false>
+template <bool LEGACY, bool STATS = false, bool BASIC = false, int OP = 0, bool C3 = false, int XD = 0>
 __device__ __forceinline__ bool trace_rays(const RtSphereParams& P, const SceneLds& S, Lane& L, bool has_ray, int coop_below, bool cull,
                                            uint32_t& groups_done, uint32_t& boxes_done, f3& sample, int sparse_max = kSparseRays, unsigned long long* tm = nullptr, bool single = false) {
     // tm (diagnostic instantiation only): cycles in [0] ray set-up, [1..4] scan_pairs, [5] shade, [6] sparse scan
@@ -1726,7 +1815,8 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
     if (FOLDED) { cfg = kDefaultCfg; chain_cfg = default_chain_cfg((LEAN & 4) != 0); caps = kDefaultCaps; }      // immediates, not SGPRs or spilled lanes
     extern __shared__ __align__(16) unsigned char smem[];
     float* unused;
-    const SceneLds S = stage_scene<false, SCENE>(P, smem, &unused);
+    constexpr int XD = xd_of(FOLDED, LEAN);
+    const SceneLds S = stage_scene<false, SCENE, (XD & kXdRecip) != 0>(P, smem, &unused);
 
     const bool cull = (cfg & kCfgCull) != 0;
     const int boost = (cfg >> kCfgBoost.shift) & kCfgBoost.mask;
@@ -2105,7 +2195,7 @@ __global__ void __launch_bounds__(kThreads, (LEAN & 4) ? 6 : 4) k_render_spheres
             if (sel) { nrays++; pix_rays++; }
             if (x > 0 || steps == 1) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
             f3 sample;
-            const bool done = trace_rays<false, DBG, (LEAN & 1) != 0, (LEAN & 2) ? ((LEAN & 32) ? 4 : ((LEAN & 16) ? 2 : 1)) : 0, (LEAN & 8) != 0, FOLDED>(P, S, L, sel, -1, cull, groups_done, boxes_done, sample, sparse_max, dbg_timers ? dbg_tm : nullptr, (cfg & kCfgSingleRay) != 0);
+            const bool done = trace_rays<false, DBG, (LEAN & 1) != 0, (LEAN & 2) ? ((LEAN & 32) ? 4 : ((LEAN & 16) ? 2 : 1)) : 0, (LEAN & 8) != 0, XD>(P, S, L, sel, -1, cull, groups_done, boxes_done, sample, sparse_max, dbg_timers ? dbg_tm : nullptr, (cfg & kCfgSingleRay) != 0);
             if (dbg_timers) { dbg_tm[x > 0 ? 9 : 8] += 1ull; }
             finish(done && sel, steps > 1, sample);
         }
@@ -2164,6 +2254,11 @@ static size_t lds_bytes(int n_padded, int n, bool with_fb, int scene = 0, int wa
     if (scene == 2) return test_data + (size_t)n_padded * 4 + scratch;
     return test_data + (size_t)n_padded * 16 + (size_t)n_padded * 12 +
            (size_t)((n + 3) & ~3) * 4 + (with_fb ? (size_t)kThreads * 3 * 4 : 0) + scratch;
+}
+
+// What the folded form of kind `lean` adds to lds_bytes: a float per slot, the radius' stored reciprocal (stage_scene's RCP; xd_of: not the six-wave kinds)
+static size_t stored_recip_bytes(const RtSphereParams& p, int lean) {
+    return (xd_of(true, lean) & kXdRecip) ? (size_t)p.n_padded * 4 : 0;
 }
 
 // Where a kernel reads the scene from (stage_scene's SCENE): global memory when the renderer says so (p.global_scene), else the full LDS copy if it fits
@@ -2455,7 +2550,9 @@ static SpherePlan plan_spheres(const RtSphereParams& p, int variant, const RtSwi
     pl.stride1 = p.p1_tile_major == 1 ? 1u : pl.stride;
     pl.cfg1 = pl.cfg;
     const bool default_constants = pl.cfg == kDefaultCfg && pl.chain_cfg == default_chain_cfg((pl.lean & kLeanSixWaves) != 0) && pl.caps == kDefaultCaps;
-    pl.form = sphere_frame_form(pl.frame, p, sw, folded_built(2, 2, pl.chunked, false, pl.scene, pl.lean), default_constants);
+    // (the four-wave folded kinds stage the radii's reciprocals behind the scene copy: a scene whose copy leaves no room for them takes the general form)
+    const bool recip_fits = pl.lds + stored_recip_bytes(p, pl.lean) <= kLdsPerCu;
+    pl.form = sphere_frame_form(pl.frame, p, sw, folded_built(2, 2, pl.chunked, false, pl.scene, pl.lean) && recip_fits, default_constants);
     if (p.p1_tile_major == 2 && total_px > 512) {
         pl.stride1 = rt_coprime_stride((unsigned long long)total_px >> 3);
         pl.cfg1 |= kCfgP1Segments;
@@ -2477,7 +2574,8 @@ static hipError_t launch_sphere_queue(SphereQueueForm<PHASE, CLS, CHUNKED, DBG, 
     const int form = (PHASE == 2 && CLS == 2) ? pl.form : kSphereFormGeneral;
     auto launch_form = [&](auto tag) -> hipError_t {         // (FORM: deduced from the tag's type)
         void (*kern)(const RtSphereParams, uint32_t, int, int, int, decltype(tag)) = k_render_spheres_queue<PHASE, CLS, CHUNKED, DBG, SCENE, LEAN>;
-        return launch_with_lds(kern, dim3(pl.blocks), dim3(pl.threads), pl.lds, stream, q, stride, cfg, pl.chain_cfg, caps, tag);
+        const size_t lds = pl.lds + (std::is_same<decltype(tag), FormTag<kSphereFormDefault>>::value ? stored_recip_bytes(q, LEAN) : 0);
+        return launch_with_lds(kern, dim3(pl.blocks), dim3(pl.threads), lds, stream, q, stride, cfg, pl.chain_cfg, caps, tag);
     };
     hipError_t e;
     if constexpr (folded_built(PHASE, CLS, CHUNKED, DBG, SCENE, LEAN)) {

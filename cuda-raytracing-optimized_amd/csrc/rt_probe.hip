@@ -166,6 +166,26 @@ __global__ void k_exactdiv(const float* in4, int n, float* out14) {
     o[12] = r0;
     o[13] = r1;
 }
+// The hit normal of the folded sphere kinds (rt_exdiv3_y): the divisor's refined reciprocal is computed in one launch, as stage_scene stores it ...
+__global__ void k_exactdiv_store(const float* in4, int n, float* yr) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const float l = in4[4 * k + 3];
+    yr[k] = rt_exdiv_stored(l, __builtin_amdgcn_rcpf(l));
+}
+// ... and the quotients in a second launch from the stored word, as shade computes them, beside the plain operator: (x, y, z, l) in, 7 floats out
+__global__ void k_exactdiv_stored(const float* in4, const float* yr, int n, float* out7) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const f3 v = F3(in4[4 * k], in4[4 * k + 1], in4[4 * k + 2]);
+    const float l = in4[4 * k + 3], y = yr[k];
+    float* o = out7 + (size_t)7 * k;
+    const RtExdiv3 e = rt_exdiv3_y(v.x, v.y, v.z, l, y);
+    f3 q = F3(e.x, e.y, e.z);
+    const f3 qp = v / l;                                             // intersections.h:95
+    if (!rt_exdiv3_window_y(v.x, v.y, v.z, y)) q = qp;
+    o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = qp.x; o[4] = qp.y; o[5] = qp.z; o[6] = y;
+}
 #endif
 
 __global__ void k_sincos(const float* y, int n, float* s_out, float* c_out) {
@@ -300,6 +320,16 @@ void rtProbeExactDiv_parity(const float* in4, int n, float* out14) {
     auto a = in(in4, (size_t)4 * n); auto b = outb(out14, (size_t)14 * n);
     hipLaunchKernelGGL(k_exactdiv, grid_for(n), dim3(256), 0, 0, a.d, n, b.d);
     sync();
+}
+void rtProbeExactDivStored_parity(const float* in4, int n, float* out7) {
+    auto a = in(in4, (size_t)4 * n); auto b = outb(out7, (size_t)7 * n);
+    float* yr = nullptr;                                             // lives on the device between the two launches
+    HIP_CHECK(hipMalloc((void**)&yr, sizeof(float) * (size_t)(n > 0 ? n : 1)));
+    hipLaunchKernelGGL(k_exactdiv_store, grid_for(n), dim3(256), 0, 0, a.d, n, yr);
+    sync();
+    hipLaunchKernelGGL(k_exactdiv_stored, grid_for(n), dim3(256), 0, 0, a.d, (const float*)yr, n, b.d);
+    sync();
+    HIP_CHECK(hipFree(yr));
 }
 #endif
 

@@ -24,6 +24,7 @@
  *   rtProbeSchlick      schlick (with its powf(x, 5))         material.h:9-13 (glibc's powf restated: csrc/rt_glibc_powf.h)
  *   rtProbeRenorm       unit_vector of a unit direction       vec3.h:194-196 via ray.h:9 (csrc/rt_renorm.h; _parity only)
  *   rtProbeExactDiv     vec3 / float, unit_vector, root / a   vec3.h:79,194; intersections.h:98,100 (csrc/rt_exactdiv.h; _parity only)
+ *   rtProbeExactDivStored  vec3 / float by a stored reciprocal   intersections.h:95 (csrc/rt_exactdiv.h rt_exdiv3_y; _parity only)
  */
 #ifndef RT_PROBE_H
 #define RT_PROBE_H
@@ -69,6 +70,11 @@ void rtProbeRenorm_parity(const float* v3, int n, float* out3);
  * material_scatter normalises the bounce vector in the folded sphere kernels [6..8] and as vec3.h:194 writes it [9..11]; x / l and y / l as
  * sphere_hit_exact divides its two roots by a = l [12..13].  The parity build only. */
 void rtProbeExactDiv_parity(const float* in4, int n, float* out14);
+
+/* The hit normal of the folded sphere kinds (csrc/rt_exactdiv.h rt_exdiv3_y), per operand set in4 = (x, y, z, l): a first kernel launch stores the
+ * divisor's refined reciprocal (or the marker of a divisor outside the window) as the kernels stage it beside a sphere's radius, a second launch computes
+ * out7 = (x, y, z) / l from the stored word under rt_exdiv3_window_y [0..2], vec3.h:79 as written [3..5] and the stored word [6].  The parity build only. */
+void rtProbeExactDivStored_parity(const float* in4, int n, float* out7);
 
 #ifdef __cplusplus
 }
