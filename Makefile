@@ -71,7 +71,12 @@ $(OBJ)/refine.o: $(CSRC)/rt_kernels_refine.hip $(CSRC)/rt_refine.h include/rt_ty
 # TU and header: no other kernel object depends on it.
 $(OBJ)/motion.o: $(CSRC)/rt_kernels_motion.hip $(CSRC)/rt_motion.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_motion.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The kernels of gatherRadiance around the radiance and any-hit kernels (the directions of a chunk of points, the per-point reduction): defined bit for bit as
+# the passes above, so one object with the flags of display.o.  The generator's arithmetic is rt_gather_dirs.h, which librt_host.so compiles too
+# (rtGatherDirectionsHost).  Its own TU and headers: no other kernel object depends on it.
+$(OBJ)/gather.o: $(CSRC)/rt_kernels_gather.hip $(CSRC)/rt_gather.h $(CSRC)/rt_gather_dirs.h include/rt_types.h include/rt_api.h | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_motion.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h $(CSRC)/rt_gather.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o
@@ -81,12 +86,13 @@ UPDATE_OBJS := $(OBJ)/update.o
 BUILD_OBJS := $(OBJ)/build.o
 REFINE_OBJS := $(OBJ)/refine.o
 MOTION_OBJS := $(OBJ)/motion.o
+GATHER_OBJS := $(OBJ)/gather.o
 
-$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) -o $@
+$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) -o $@
 
-$(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp include/rt_host.h include/rt_types.h include/rt_api.h
-	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp -o $@
+$(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(CSRC)/rt_gather_dirs.h include/rt_host.h include/rt_types.h include/rt_api.h
+	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp -o $@
 
 oracle: $(PKG)/librt_mi355x.so $(PKG)/librt_host.so
 	$(MAKE) -C oracle

@@ -139,6 +139,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "traceRays", "occludedRays", "rtLastRaysMs",
                     "renderPixels", "rtLastPixelsMs",
                     "radianceRays", "rtLastRadianceMs",
+                    "rtGatherWidth", "gatherRadiance", "rtGatherDirections", "rtLastGatherMs",
                     "refineFrame", "rtResetRefine", "rtRefineSamples", "rtRefineLastList", "rtLastRefineMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
@@ -150,7 +151,8 @@ ABI_STRUCTS = [render_options, render_stats, camera, sphere, material, triangle,
 HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtSceneRandomSpheres", "rtStaircaseCamera",
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
-                "rtDisplayFrameHost", "rtCentreRays", "rtPinholeCamera", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh"]
+                "rtDisplayFrameHost", "rtCentreRays", "rtPinholeCamera", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh",
+                "rtGatherDirectionsHost"]
 
 _renderer = None
 _host = None
@@ -213,6 +215,8 @@ def load_host():
         h.rtRebuildBvhArrays.restype = C.c_int
         h.rtRebuildBvh.argtypes = [C.c_void_p, C.c_void_p]
         h.rtRebuildBvh.restype = C.c_int
+        h.rtGatherDirectionsHost.argtypes = [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, fp, fp, C.POINTER(C.c_uint32)]
+        h.rtGatherDirectionsHost.restype = None
         _host = h
     return _host
 
@@ -334,6 +338,14 @@ def load_renderer():
         r.radianceRays.restype = None
         r.rtLastRadianceMs.argtypes = []
         r.rtLastRadianceMs.restype = C.c_double
+        r.rtGatherWidth.argtypes = [C.c_int]
+        r.rtGatherWidth.restype = C.c_int
+        r.gatherRadiance.argtypes = [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, C.c_float, fp, fp, up]
+        r.gatherRadiance.restype = None
+        r.rtGatherDirections.argtypes = [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, fp, fp, up]
+        r.rtGatherDirections.restype = None
+        r.rtLastGatherMs.argtypes = []
+        r.rtLastGatherMs.restype = C.c_double
         r.refineFrame.argtypes = [C.POINTER(vec3), ip, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]
         r.refineFrame.restype = C.c_int
         r.rtResetRefine.argtypes = []
@@ -784,6 +796,91 @@ def radiance_rays(org, dir, ns, ids=None, first=None, state=None, rays=False):
 def last_radiance_ms():
     """HIP-event time of the radiance kernels of the last radiance_rays (not the copies), summed over its chunks, in milliseconds."""
     return load_renderer().rtLastRadianceMs()
+
+
+# gatherRadiance (include/rt_api.h): irradiance, SH9 and visibility at points, on the device
+RT_GATHER_IRRADIANCE, RT_GATHER_SH9, RT_GATHER_VISIBILITY = 0, 1, 2
+RT_GATHER_MAX_DIRS = 65536
+_GATHER_WIDTH = {RT_GATHER_IRRADIANCE: 3, RT_GATHER_SH9: 27, RT_GATHER_VISIBILITY: 1}
+
+
+def gather_width(mode):
+    """Floats per point in acc / out of gather_radiance (rtGatherWidth): 3, 27, 1."""
+    return load_renderer().rtGatherWidth(mode)
+
+
+def _gather_points(fn, pos, nrm, mode):
+    """Contiguous float32 copies (or the arrays themselves) of the points and normals; a wrong shape or an unknown mode is a ValueError."""
+    if mode not in _GATHER_WIDTH:
+        raise ValueError(f"{fn}: unknown mode {mode!r}")
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"{fn}: pos must have shape (n, 3), got {pos.shape}")
+    if nrm is None:
+        if mode != RT_GATHER_SH9:
+            raise ValueError(f"{fn}: nrm may be None only in RT_GATHER_SH9")
+    else:
+        nrm = np.ascontiguousarray(nrm, dtype=np.float32)
+        if nrm.shape != pos.shape:
+            raise ValueError(f"{fn}: nrm must have shape {pos.shape}, got {nrm.shape}")
+    return pos, nrm
+
+
+def gather_radiance(pos, nrm, mode, dirs, ns=1, first=0, dirs_total=None, acc=None, base_id=0, bias=0.0, max_dist=0.0, rays=False):
+    """Gathers at the points pos (n, 3) with normals nrm (n, 3; None in RT_GATHER_SH9): directions first .. first+dirs-1 of dirs_total (default first + dirs)
+    per point, drawn, traced at ns samples and reduced on the device (gatherRadiance, include/rt_api.h).  acc: None, or the (n, W) float32 sums an earlier
+    call returned for the same points after `first` directions (needed for first > 0).  Returns (out (n, W) float32, acc (n, W) float32 - a new array: the
+    caller's is not written -, rays (n,) uint32 or None unless rays=True), W = gather_width(mode).  Blocking."""
+    pos, nrm = _gather_points("gather_radiance", pos, nrm, mode)
+    n, W = pos.shape[0], _GATHER_WIDTH[mode]
+    if dirs_total is None:
+        dirs_total = first + dirs
+    if acc is None:
+        if first > 0:
+            raise ValueError("gather_radiance: first > 0 needs the acc the points resume from")
+        a = np.zeros((n, W), np.float32)
+    else:
+        a = np.array(acc, dtype=np.float32, order="C")              # (a copy: gatherRadiance updates the sums in place)
+        if a.shape != (n, W):
+            raise ValueError(f"gather_radiance: acc must have shape ({n}, {W}), got {a.shape}")
+    out = np.zeros((n, W), np.float32)
+    nrays = np.zeros(n, np.uint32) if rays else None
+    fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    load_renderer().gatherRadiance(n, pos.ctypes.data_as(fp), None if nrm is None else nrm.ctypes.data_as(fp), mode, first, dirs, dirs_total, ns, base_id,
+                                   bias, max_dist, a.ctypes.data_as(fp), out.ctypes.data_as(fp), None if nrays is None else nrays.ctypes.data_as(up))
+    return out, a, nrays
+
+
+def _gather_directions(fn, call, pos, nrm, mode, dirs, first, dirs_total, base_id, bias):
+    pos, nrm = _gather_points(fn, pos, nrm, mode)
+    n = pos.shape[0]
+    if dirs_total is None:
+        dirs_total = first + dirs
+    if dirs < 1 or first < 0 or first + dirs > dirs_total or dirs_total > RT_GATHER_MAX_DIRS:
+        raise ValueError(f"{fn}: needs 1 <= dirs, 0 <= first and first + dirs <= dirs_total <= RT_GATHER_MAX_DIRS")
+    org, d, ids = np.zeros((n * dirs, 3), np.float32), np.zeros((n * dirs, 3), np.float32), np.zeros(n * dirs, np.uint32)
+    fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    call(n, pos.ctypes.data_as(fp), None if nrm is None else nrm.ctypes.data_as(fp), mode, first, dirs, dirs_total, base_id, bias,
+         org.ctypes.data_as(fp), d.ctypes.data_as(fp), ids.ctypes.data_as(up))
+    return org, d, ids
+
+
+def gather_directions(pos, nrm, mode, dirs, first=0, dirs_total=None, base_id=0, bias=0.0):
+    """The rays gather_radiance traces, from the generator kernel alone (rtGatherDirections): (org (n * dirs, 3), dir (n * dirs, 3) raw, ids (n * dirs,) uint32),
+    entry k * dirs + (m - first).  Blocking."""
+    return _gather_directions("gather_directions", load_renderer().rtGatherDirections, pos, nrm, mode, dirs, first, dirs_total, base_id, bias)
+
+
+def gather_directions_host(pos, nrm, mode, dirs, first=0, dirs_total=None, base_id=0, bias=0.0):
+    """gather_directions on the CPU (librt_host.so, rtGatherDirectionsHost; no GPU, no renderer state): the same bits."""
+    if not np.isfinite(bias):
+        raise ValueError("gather_directions_host: bias must be finite")
+    return _gather_directions("gather_directions_host", load_host().rtGatherDirectionsHost, pos, nrm, mode, dirs, first, dirs_total, base_id, bias)
+
+
+def last_gather_ms():
+    """HIP-event time of generator + trace + reduce of the last gather_radiance (not the copies), summed over its chunks, in milliseconds."""
+    return load_renderer().rtLastGatherMs()
 
 
 def pinhole_camera(o, target):

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cfloat>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -37,6 +38,7 @@
 #include "rt_update.h"
 #include "rt_build.h"
 #include "rt_refine.h"
+#include "rt_gather.h"
 
 namespace {
 
@@ -176,6 +178,7 @@ struct RenderContext {
     double rays_ms = 0.0;               // rtLastRaysMs
     double pixels_ms = 0.0;             // rtLastPixelsMs
     double radiance_ms = 0.0;           // rtLastRadianceMs
+    double gather_ms = 0.0;             // rtLastGatherMs
     double motion_ms = 0.0;             // rtLastMotionMs
 };
 
@@ -229,7 +232,7 @@ struct DisplayState : PassState {
     float last_exposure = 1.0f;         // rtLastExposure
 };
 
-// What every query call (traceRays / occludedRays, renderPixels, radianceRays, refineFrame) holds: the first in-process device, its allocations there and an event pair of
+// What every query call (traceRays / occludedRays, renderPixels, radianceRays, refineFrame, gatherRadiance) holds: the first in-process device, its allocations there and an event pair of
 // its own, created with the device list (setup_devices) - the timings of a frame, the guides, the passes and the other queries stay what they were.
 // Released by free_pass where the passes' buffers are.
 struct QueryState {
@@ -293,6 +296,15 @@ struct MotionState : PassState {
     std::vector<float4> h_planes;       // the staging copy of PoseState::d_planes the caller's 3-float planes are filled from
 };
 
+// gatherRadiance / rtGatherDirections (rt_gather.h): the device arrays of one chunk of the caller's points - five per point, seven per ray of the chunk -, each
+// grown to the largest chunk that asked for it, and the queue word of the radiance kernels.  Its own buffers: radianceRays' and the ray queries' stay theirs.
+enum { kGatPos = 0, kGatNrm, kGatAcc, kGatOut, kGatNrays, kGatOrg, kGatDir, kGatIds, kGatTMax, kGatL, kGatRays, kGatOccluded, kGatBuffers };
+struct GatherState : QueryState {
+    char* d_buf[kGatBuffers] = {};
+    size_t cap[kGatBuffers] = {};       // bytes d_buf[k] holds
+    uint32_t* d_queue = nullptr;        // RtRadianceBatch::queue
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
@@ -301,6 +313,7 @@ PoseState g_pose;
 MotionState g_motion;
 ChunkState g_rays, g_pixels, g_radiance;
 RefineState g_refine;
+GatherState g_gather;
 
 // The adaptive frame back to "the next refineFrame starts at sample 0" (rtResetRefine, setCamera, setRenderOptions, the scene edits); the buffers stay.
 void reset_refine() {
@@ -424,6 +437,7 @@ void setup_devices() {
     free_pass(g_pixels);
     free_pass(g_radiance);
     free_pass(g_refine);
+    free_pass(g_gather);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -478,7 +492,7 @@ void setup_devices() {
         c.devs.push_back(d);
     }
     HIP_CHECK(hipSetDevice(c.devs[0].device));              // the query calls' own event pairs, on the device they run on
-    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine }) {
+    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine, &g_gather }) {
         q->device = c.devs[0].device;
         HIP_CHECK(hipEventCreate(&q->ev_start));
         HIP_CHECK(hipEventCreate(&q->ev_stop));
@@ -536,6 +550,7 @@ void cleanup_impl() {
     free_pass(g_pixels);
     free_pass(g_radiance);
     free_pass(g_refine);
+    free_pass(g_gather);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -736,7 +751,13 @@ void launch_radiance(const DeviceState& d, const RtRadianceBatch& b, int max_wav
     }
 }
 
-// The query calls (traceRays / occludedRays, renderPixels, radianceRays, refineFrame) differ in their arguments, buffers and kernels; the rest is here, once.
+// The ray kernel of the scene kind over the batch `b` (traceRays / occludedRays, gatherRadiance's visibility): closest hit, or any hit.
+void launch_rays(const DeviceState& d, const RtRayBatch& b, bool any) {
+    HIP_CHECK(g_ctx.is_spheres ? rt_launch_rays_spheres(sphere_params(d, whole_image_partition()), b, any, d.stream)
+                               : rt_launch_rays_mesh(mesh_params(d, whole_image_partition()), b, any, d.stream));
+}
+
+// The query calls (traceRays / occludedRays, renderPixels, radianceRays, refineFrame, gatherRadiance) differ in their arguments, buffers and kernels; the rest is here, once.
 
 // What "defined per pixel" asks of the options in force (renderPixels, radianceRays, refineFrame), under the function's name `fn`.
 void check_per_pixel(const char* fn) {
@@ -1558,8 +1579,7 @@ static void run_rays(int n, const float* org, const float* dir, const float* t_m
         b.nodes = reinterpret_cast<int32_t*>(dev[kRayNodes]); b.occluded = reinterpret_cast<uint8_t*>(dev[kRayOccluded]);
         b.n = (int32_t)m;
         b.t_min_default = c.opt.t_min;
-        HIP_CHECK(c.is_spheres ? rt_launch_rays_spheres(sphere_params(d, whole_image_partition()), b, any, d.stream)
-                               : rt_launch_rays_mesh(mesh_params(d, whole_image_partition()), b, any, d.stream));
+        launch_rays(d, b, any);
     });
 }
 
@@ -1692,6 +1712,154 @@ void radianceRays(int n, const float* org, const float* dir, const uint32_t* ids
 double rtLastRadianceMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastRadianceMs before init");
     return g_ctx.radiance_ms;
+}
+
+// Gathering at points (rt_api.h).  Per chunk of max(1, RT_RAY_CHUNK / dirs) points: pos / nrm (and acc where first > 0) go up, k_gather_dirs
+// fills the batch arrays, the radiance kernels (launch_radiance) or the any-hit kernels (launch_rays) run over them, k_gather_reduce folds them per point, and
+// acc / out / rays come down.  No per-ray datum crosses the bus.  Nothing of a frame's, a pass's, radianceRays' or the ray queries' state is read or written.
+static int gather_width(int mode) {
+    return mode == RT_GATHER_IRRADIANCE ? 3 : mode == RT_GATHER_SH9 ? 27 : mode == RT_GATHER_VISIBILITY ? 1 : 0;
+}
+
+int rtGatherWidth(int mode) {
+    const int w = gather_width(mode);
+    if (w == 0) rt_fail("rtGatherWidth: unknown mode");
+    return w;
+}
+
+// The checks gatherRadiance and rtGatherDirections share, under the function's name `fn`; returns false for the empty list (nothing to do, nothing written).
+static bool check_gather(const char* fn, int n, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total, float bias) {
+    const RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail(" before init", fn);
+    if (n < 0) rt_fail(": n is negative", fn);
+    if (n == 0) return false;
+    if (!pos) rt_fail(": pos is null", fn);
+    if (gather_width(mode) == 0) rt_fail(": unknown mode", fn);
+    if (mode != RT_GATHER_SH9 && !nrm) rt_fail(": nrm is null (only RT_GATHER_SH9 ignores it)", fn);
+    if (dirs < 1 || first < 0) rt_fail(": dirs must be at least 1 and first not negative", fn);
+    if (dirs_total > RT_GATHER_MAX_DIRS) rt_fail(": dirs_total above RT_GATHER_MAX_DIRS", fn);
+    if ((long long)first + dirs > dirs_total) rt_fail(": first + dirs above dirs_total", fn);
+    if (!std::isfinite(bias)) rt_fail(": bias is not finite", fn);
+    if (c.is_spheres && c.opt.floor) rt_fail(": the floor plane is only defined for mesh scenes (kernel_scene.floor)", fn);
+    return true;
+}
+
+// Buffer k of the gather state, grown to `bytes`.
+static char* gather_buffer(int k, size_t bytes) {
+    GatherState& q = g_gather;
+    if (q.cap[k] < bytes) {
+        dev_release(q.owned, q.d_buf[k]);
+        q.d_buf[k] = dev_alloc<char>(q.owned, bytes);
+        q.cap[k] = bytes;
+    }
+    return q.d_buf[k];
+}
+
+// The parameter block of chunk [k0, k0 + pts) with the per-point inputs uploaded and the per-ray arrays `want` names (-1: none) allocated; the rest is nullptr.
+static RtGatherParams gather_chunk(size_t k0, size_t pts, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total, uint32_t base_id,
+                                   float bias, std::initializer_list<int> want, hipStream_t stream) {
+    const size_t nray = pts * (size_t)dirs;
+    static const size_t ray_bytes[kGatBuffers] = { 0, 0, 0, 0, 0, 12, 12, 4, 4, 12, 4, 1 };
+    char* dev[kGatBuffers] = {};
+    for (int k : want)
+        if (k >= 0) dev[k] = gather_buffer(k, nray * ray_bytes[k]);
+    RtGatherParams p = {};
+    float* d_pos = reinterpret_cast<float*>(gather_buffer(kGatPos, pts * 12));
+    HIP_CHECK(hipMemcpyAsync(d_pos, pos + 3 * k0, pts * 12, hipMemcpyHostToDevice, stream));
+    p.pos = d_pos;
+    if (mode != RT_GATHER_SH9) {
+        float* d_nrm = reinterpret_cast<float*>(gather_buffer(kGatNrm, pts * 12));
+        HIP_CHECK(hipMemcpyAsync(d_nrm, nrm + 3 * k0, pts * 12, hipMemcpyHostToDevice, stream));
+        p.nrm = d_nrm;
+    }
+    p.org = reinterpret_cast<float*>(dev[kGatOrg]); p.dir = reinterpret_cast<float*>(dev[kGatDir]);
+    p.ids = reinterpret_cast<uint32_t*>(dev[kGatIds]); p.t_max = reinterpret_cast<float*>(dev[kGatTMax]);
+    p.L = reinterpret_cast<rt_vec3*>(dev[kGatL]); p.rays = reinterpret_cast<uint32_t*>(dev[kGatRays]);
+    p.occluded = reinterpret_cast<uint8_t*>(dev[kGatOccluded]);
+    p.pts = (uint32_t)pts; p.dirs = (uint32_t)dirs; p.first = (uint32_t)first; p.dirs_total = (uint32_t)dirs_total;
+    p.k0 = (uint32_t)k0; p.base_id = base_id; p.mode = mode; p.bias = bias;
+    return p;
+}
+
+void gatherRadiance(int n, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total, int ns, uint32_t base_id, float bias, float max_dist,
+                    float* acc, float* out, uint32_t* rays) {
+    RenderContext& c = g_ctx;
+    if (!check_gather("gatherRadiance", n, pos, nrm, mode, first, dirs, dirs_total, bias)) return;
+    if (first > 0 && !acc) rt_fail("gatherRadiance: first > 0 needs acc (the sums the points resume from)");
+    if (!acc && !out && !rays) rt_fail("gatherRadiance: acc, out and rays are all null");
+    if (std::isnan(max_dist) || max_dist < 0.0f) rt_fail("gatherRadiance: max_dist must not be a NaN or negative");
+    const bool vis = mode == RT_GATHER_VISIBILITY;
+    if (!vis) {
+        if (ns < 1 || ns > RT_PROGRESSIVE_MAX_SAMPLES) rt_fail("gatherRadiance: ns must be 1 .. RT_PROGRESSIVE_MAX_SAMPLES");
+        check_per_pixel("gatherRadiance");
+    }
+    GatherState& q = g_gather;
+    const DeviceState& d = c.devs[0];
+    const size_t W = (size_t)gather_width(mode), chunk = std::max<size_t>(1, kRayChunk / (size_t)dirs);
+    const int max_waves = rt_read_switches().pixels_waves;
+    const int current = begin_query(q);
+    if (!q.d_queue) q.d_queue = dev_alloc<uint32_t>(q.owned, 1);
+    double ms_sum = 0.0;
+    for_chunks((size_t)n, chunk, [&](size_t k0, size_t pts) {
+        RtGatherParams p = vis ? gather_chunk(k0, pts, pos, nrm, mode, first, dirs, dirs_total, base_id, bias, { kGatOrg, kGatDir, kGatTMax, kGatOccluded }, d.stream)
+                               : gather_chunk(k0, pts, pos, nrm, mode, first, dirs, dirs_total, base_id, bias, { kGatOrg, kGatDir, kGatIds, kGatL, kGatRays }, d.stream);
+        p.t_max_value = max_dist > 0.0f ? max_dist : FLT_MAX;
+        if (acc || first > 0) p.acc = reinterpret_cast<float*>(gather_buffer(kGatAcc, pts * W * 4));
+        if (out) p.out = reinterpret_cast<float*>(gather_buffer(kGatOut, pts * W * 4));
+        if (rays) p.nrays = reinterpret_cast<uint32_t*>(gather_buffer(kGatNrays, pts * 4));
+        if (first > 0) HIP_CHECK(hipMemcpyAsync(p.acc, acc + k0 * W, pts * W * 4, hipMemcpyHostToDevice, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        HIP_CHECK(rt_launch_gather_dirs(p, d.stream));
+        if (vis) {
+            RtRayBatch b = {};
+            b.org = p.org; b.dir = p.dir; b.t_max = p.t_max; b.occluded = p.occluded;
+            b.n = (int32_t)(pts * (size_t)dirs);
+            b.t_min_default = c.opt.t_min;
+            launch_rays(d, b, true);
+        } else {
+            HIP_CHECK(hipMemsetAsync(q.d_queue, 0, sizeof(uint32_t), d.stream));
+            RtRadianceBatch b = {};
+            b.org = p.org; b.dir = p.dir; b.ids = p.ids;
+            b.out = p.L; b.rays = p.rays;
+            b.queue = q.d_queue; b.n = (int32_t)(pts * (size_t)dirs); b.ns_all = ns;
+            launch_radiance(d, b, max_waves);
+        }
+        HIP_CHECK(rt_launch_gather_reduce(p, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        if (acc) HIP_CHECK(hipMemcpyAsync(acc + k0 * W, p.acc, pts * W * 4, hipMemcpyDeviceToHost, d.stream));
+        if (out) HIP_CHECK(hipMemcpyAsync(out + k0 * W, p.out, pts * W * 4, hipMemcpyDeviceToHost, d.stream));
+        if (rays) HIP_CHECK(hipMemcpyAsync(rays + k0, p.nrays, pts * 4, hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));              // (the events are read per chunk; blocking: the caller's arrays are complete on return)
+        ms_sum += query_ms(q);
+    });
+    end_query(current);
+    c.gather_ms = ms_sum;
+}
+
+void rtGatherDirections(int n, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total, uint32_t base_id, float bias,
+                        float* org, float* dir, uint32_t* ids) {
+    if (!check_gather("rtGatherDirections", n, pos, nrm, mode, first, dirs, dirs_total, bias)) return;
+    if (!org && !dir && !ids) rt_fail("rtGatherDirections: org, dir and ids are all null");
+    GatherState& q = g_gather;
+    const DeviceState& d = g_ctx.devs[0];
+    const size_t chunk = std::max<size_t>(1, kRayChunk / (size_t)dirs);
+    const int current = begin_query(q);
+    for_chunks((size_t)n, chunk, [&](size_t k0, size_t pts) {
+        RtGatherParams p = gather_chunk(k0, pts, pos, nrm, mode, first, dirs, dirs_total, base_id, bias,
+                                              { org ? kGatOrg : -1, dir ? kGatDir : -1, ids ? kGatIds : -1 }, d.stream);
+        HIP_CHECK(rt_launch_gather_dirs(p, d.stream));
+        const size_t e0 = k0 * (size_t)dirs, m = pts * (size_t)dirs;
+        if (org) HIP_CHECK(hipMemcpyAsync(org + 3 * e0, p.org, m * 12, hipMemcpyDeviceToHost, d.stream));
+        if (dir) HIP_CHECK(hipMemcpyAsync(dir + 3 * e0, p.dir, m * 12, hipMemcpyDeviceToHost, d.stream));
+        if (ids) HIP_CHECK(hipMemcpyAsync(ids + e0, p.ids, m * 4, hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));
+    });
+    end_query(current);
+}
+
+double rtLastGatherMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastGatherMs before init");
+    return g_ctx.gather_ms;
 }
 
 // Adaptive sampling on the device (rt_api.h).  One call is one pass over the whole image on the first in-process device: select (rt_refine.h)

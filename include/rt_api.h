@@ -473,6 +473,60 @@ void   radianceRays(int n, const float* org, const float* dir, const uint32_t* i
                     const int32_t* first, uint32_t* state, rt_vec3* out, uint32_t* rays);
 double rtLastRadianceMs(void);   /* HIP-event time of the radiance kernels of the last radianceRays, summed over its chunks; 0 before the first */
 
+/* --- gathering at points: irradiance, SH9 and visibility per point - probes, lightmap and vertex bakes, an AO / indirect-light plane ---------
+ * gatherRadiance answers "what arrives at this point" for n caller-named points: the device draws the directions, traces them with the kernels of
+ * radianceRays (RT_GATHER_IRRADIANCE, RT_GATHER_SH9) or occludedRays (RT_GATHER_VISIBILITY), unchanged, and reduces them per point in a fixed order.  Only the
+ * points go up and only per-point results come back.  All arithmetic of the generator and of the reduction is fp32, every operation rounded on its own (no
+ * FMA), operands in the order written, sqrt and / correctly rounded, dot(a, b) = a.x*b.x + a.y*b.y + a.z*b.z from left to right - in both fp modes.
+ *   Point k        the index in the caller's list, whatever the chunking.  P = pos[3k .. 3k+2], N = nrm[3k .. 3k+2].  The caller owes finite P and, outside
+ *                  SH9, a finite, non-zero N; points are not validated one by one.
+ *   Origin         IRRADIANCE, VISIBILITY: Nn = N / sqrt(dot(N, N)) (three divisions), o[a] = P[a] + bias * Nn[a] - computed also when bias is 0.
+ *                  SH9: o = P; nrm and bias are ignored, nrm may be NULL.
+ *   Direction m    m = first .. first+dirs-1.  g = base_id + (uint32_t)((uint64_t)k * dirs_total + m), modulo 2^32.  The direction stream is the xorshift
+ *                  word wd = pixel_seed(~g) (kernels.cu:541-542); rnd is rnd.h:5-18.  Drawn as rnd.h:41-49 draws: repeat { x = 2*rnd(wd) - 1; y likewise;
+ *                  z likewise; l2 = x*x + y*y + z*z } while (!(l2 < 1) || l2 == 0) - the zero rejection is added to the reference's loop so that u is
+ *                  always defined -; u = (x, y, z) / sqrt(l2) (three divisions).
+ *                  IRRADIANCE, VISIBILITY: D = Nn + u, and D = Nn where all three components of that sum are zero: a cosine-distributed direction about Nn.
+ *                  SH9: D = u, uniform on the sphere.
+ *   Ray (k, m)     IRRADIANCE, SH9: exactly radianceRays' ray (o, D, id = g) at ns samples from sample 0: L = its out, r = its rays.  Its path stream is
+ *                  pixel_seed(g), the direction stream pixel_seed(~g): the two do not share words.  (Ids near 2^31 make ~g meet other rays' g: harmless, but
+ *                  that ray's directions are correlated with another ray's path.)
+ *                  VISIBILITY: exactly occludedRays' ray (o, D, tmin = rt_render_options.t_min, tmax = max_dist > 0 ? max_dist : FLT_MAX):
+ *                  v = occluded ? 0.0f : 1.0f, r = 0; ns is ignored.
+ *   Reduction      per point, m ascending.  A starts at 0 when first == 0 (acc is not read then), else at acc[k*W ..]; W = rtGatherWidth(mode).
+ *                  IRRADIANCE (W = 3)   A[c] += L[c].
+ *                  SH9 (W = 27)         A[3i + c] += L[c] * y_i (the product rounded, then added), i = 0 .. 8, with D = (X, Y, Z) raw:
+ *                                       y0 = 0.282095f             y1 = 0.488603f * Y          y2 = 0.488603f * Z            y3 = 0.488603f * X
+ *                                       y4 = 1.092548f * (X * Y)   y5 = 1.092548f * (Y * Z)    y6 = 0.315392f * (3.0f * (Z * Z) - 1.0f)
+ *                                       y7 = 1.092548f * (X * Z)   y8 = 0.546274f * (X * X - Y * Y)
+ *                  VISIBILITY (W = 1)   A[0] += v (exact: the counts stay below 2^24).
+ *   Outputs        acc, out (W floats per point) and rays (one word per point) may each be NULL, not all three.  acc receives A.  With M = (float)(first + dirs):
+ *                  out[k*W + j] = A[j] / M (IRRADIANCE, VISIBILITY), (A[j] * 12.566371f) / M (SH9).  rays[k] = the sum of this call's r.
+ * So first / acc resume a point the way `state` resumes a ray: any split of dirs_total into calls is bit-identical to one call.  IRRADIANCE is irradiance / pi -
+ * the radiance a white Lambertian surface at the point would reflect; SH9 the nine real spherical-harmonic coefficients of the incoming radiance per channel
+ * (coefficient i of channel c at 3i + c); VISIBILITY cosine-weighted openness, i.e. ambient occlusion within max_dist.  Over the planes of renderGuides (hit
+ * point = origin + depth * d, with the normal plane) the same call gives an ambient-occlusion or indirect-light plane.
+ * The call is blocking and runs on the first in-process device, max(1, RT_RAY_CHUNK / dirs) points at a time - upload, generate, trace, reduce, download -;
+ * the device buffers (per ray of the largest chunk seen: org 12, dir 12, and ids 4, out 12, rays 4 = 44 bytes in the radiance modes, t_max 4, occluded 1 = 29
+ * bytes in VISIBILITY; per point: pos 12, nrm 12, acc 4W, out 4W, rays 4) are its own and are freed where the ray buffers are.  It follows setRenderOptions,
+ * the scene edits and rebuildBvh; RT_PIXELS_WAVES caps its path waves as it caps radianceRays'.  It changes nothing another call observes: the framebuffer,
+ * getRenderStats, rtLastLaunches, the progressive frame, every history, the buffers of radianceRays and traceRays and every other rtLast*Ms (rtLastRadianceMs
+ * and rtLastRaysMs included) stay as they were.  n == 0 returns at once: nothing is written and rtLastGatherMs stays as it was.
+ * rtGatherDirections runs the generator kernel alone and downloads it: entry k*dirs + (m - first) of org (3 floats), dir (3 floats, raw D) and ids (g); each
+ * pointer may be NULL, not all three.  rtGatherDirectionsHost (rt_host.h) is its CPU twin.  rtGatherWidth needs no init and never exits for a known mode.
+ * Misuse (rt error, exit 99), checked on the host before any device work: before init (rtLastGatherMs as well), n < 0, pos NULL, nrm NULL outside SH9, an
+ * unknown mode, dirs < 1 or first < 0, first + dirs > dirs_total, dirs_total > RT_GATHER_MAX_DIRS, first > 0 without acc, acc, out and rays all NULL (org, dir
+ * and ids all NULL), bias not finite, max_dist a NaN or negative; in the radiance modes ns outside 1 .. RT_PROGRESSIVE_MAX_SAMPLES and every frame condition
+ * radianceRays refuses; in every mode rt_render_options.floor = 1 on a sphere scene. */
+enum { RT_GATHER_IRRADIANCE = 0, RT_GATHER_SH9 = 1, RT_GATHER_VISIBILITY = 2 };
+#define RT_GATHER_MAX_DIRS 65536
+int    rtGatherWidth(int mode);          /* floats per point in acc / out: 3, 27, 1; never exits for a known mode */
+void   gatherRadiance(int n, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total, int ns, uint32_t base_id,
+                      float bias, float max_dist, float* acc, float* out, uint32_t* rays);
+void   rtGatherDirections(int n, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total,
+                          uint32_t base_id, float bias, float* org, float* dir, uint32_t* ids);   /* the generator kernel alone, downloaded */
+double rtLastGatherMs(void);   /* HIP-event time of generator + trace + reduce of the last gatherRadiance, summed over its chunks; 0 before the first */
+
 /* --- adaptive sampling: the samples go where the image is still noisy ---------------------------------------------------------------
  * refineFrame renders an adaptive frame: every pixel gets samples in batches until an estimate of its own error says it has enough.  The frame's state, the
  * selection, the list of a pass and the statistics live on the device; the pixel kernels of renderPixels trace the samples.  One call is one pass: select,

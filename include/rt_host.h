@@ -116,6 +116,12 @@ double rtRmse(const rt_vec3* f, const rt_vec3* g, int nx, int ny);
 int rtDisplayFrameHost(const rt_vec3* in, uint8_t* out_rgba, int nx, int ny, int flags, int tonemap, float exposure, float adapt, float* E_state,
                        uint32_t* hist);
 
+/* The direction generator of gatherRadiance (rt_api.h, "gathering at points": the definition is stated there, once) on the CPU, in plain C++: what
+ * rtGatherDirections downloads from the device, bit for bit - entry k*dirs + (m - first) of org (3 floats), dir (3 floats, raw D) and ids (g); each pointer
+ * may be NULL.  No renderer state is read: for arguments rtGatherDirections would refuse (and for n == 0) nothing is written. */
+void rtGatherDirectionsHost(int n, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total,
+                            uint32_t base_id, float bias, float* org, float* dir, uint32_t* ids);
+
 #ifdef __cplusplus
 }
 #endif
