@@ -140,6 +140,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "renderPixels", "rtLastPixelsMs",
                     "radianceRays", "rtLastRadianceMs",
                     "rtGatherWidth", "gatherRadiance", "rtGatherDirections", "rtLastGatherMs",
+                    "rasterTexels", "bakeTexels", "rtLastTexelsMs", "rtLastBakeMs",
                     "refineFrame", "rtResetRefine", "rtRefineSamples", "rtRefineLastList", "rtLastRefineMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
@@ -152,7 +153,7 @@ HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtScene
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
                 "rtDisplayFrameHost", "rtCentreRays", "rtPinholeCamera", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh",
-                "rtGatherDirectionsHost"]
+                "rtGatherDirectionsHost", "rtRasterTexelsHost", "rtAtlasGrid"]
 
 _renderer = None
 _host = None
@@ -217,6 +218,11 @@ def load_host():
         h.rtRebuildBvh.restype = C.c_int
         h.rtGatherDirectionsHost.argtypes = [C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, fp, fp, C.POINTER(C.c_uint32)]
         h.rtGatherDirectionsHost.restype = None
+        i32p = C.POINTER(C.c_int32)
+        h.rtRasterTexelsHost.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, i32p, i32p, fp, fp, fp]
+        h.rtRasterTexelsHost.restype = C.c_int
+        h.rtAtlasGrid.argtypes = [C.c_void_p, C.c_int, C.c_float]
+        h.rtAtlasGrid.restype = C.c_int
         _host = h
     return _host
 
@@ -346,6 +352,14 @@ def load_renderer():
         r.rtGatherDirections.restype = None
         r.rtLastGatherMs.argtypes = []
         r.rtLastGatherMs.restype = C.c_double
+        r.rasterTexels.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, fp, fp, fp]
+        r.rasterTexels.restype = C.c_int
+        r.bakeTexels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, C.c_float, fp, fp, up, ip, ip]
+        r.bakeTexels.restype = C.c_int
+        r.rtLastTexelsMs.argtypes = []
+        r.rtLastTexelsMs.restype = C.c_double
+        r.rtLastBakeMs.argtypes = []
+        r.rtLastBakeMs.restype = C.c_double
         r.refineFrame.argtypes = [C.POINTER(vec3), ip, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]
         r.refineFrame.restype = C.c_int
         r.rtResetRefine.argtypes = []
@@ -881,6 +895,99 @@ def gather_directions_host(pos, nrm, mode, dirs, first=0, dirs_total=None, base_
 def last_gather_ms():
     """HIP-event time of generator + trace + reduce of the last gather_radiance (not the copies), summed over its chunks, in milliseconds."""
     return load_renderer().rtLastGatherMs()
+
+
+# rasterTexels / bakeTexels (include/rt_api.h): the mesh's UV atlas rasterised on the device, a gather per covered texel, texel planes back
+RT_TEXEL_MAX_SIZE, RT_TEXEL_MAX_DILATE = 8192, 16
+TEXEL_PLANES = ("prim", "src", "bary", "pos", "nrm")
+
+
+def _texel_planes(fn, W, H, dilate, want):
+    """The planes `want` names as zeroed arrays of an H x W atlas (None for the others); a size or a name out of range is a ValueError."""
+    if not (1 <= W <= RT_TEXEL_MAX_SIZE and 1 <= H <= RT_TEXEL_MAX_SIZE and 0 <= dilate <= RT_TEXEL_MAX_DILATE):
+        raise ValueError(f"{fn}: needs 1 <= W, H <= RT_TEXEL_MAX_SIZE and 0 <= dilate <= RT_TEXEL_MAX_DILATE")
+    if not want or set(want) - set(TEXEL_PLANES):
+        raise ValueError(f"{fn}: want must name at least one of {TEXEL_PLANES}")
+    shape = {"prim": (H, W), "src": (H, W), "bary": (H, W, 2), "pos": (H, W, 3), "nrm": (H, W, 3)}
+    return {k: (np.zeros(shape[k], np.int32 if k in ("prim", "src") else np.float32) if k in want else None) for k in TEXEL_PLANES}
+
+
+def _plane_ptr(a, t):
+    return None if a is None else a.ctypes.data_as(t)
+
+
+def raster_texels(W, H, dilate=0, want=TEXEL_PLANES):
+    """Rasterises the live triangles' UV atlas at W x H on the device (rasterTexels): returns (owned, planes) - the number of owned texels and a dict of the
+    planes `want` names: prim (H, W) int32, src (H, W) int32 after `dilate` iterations, bary (H, W, 2), pos (H, W, 3), nrm (H, W, 3) float32.  Blocking."""
+    pl = _texel_planes("raster_texels", W, H, dilate, want)
+    ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    owned = load_renderer().rasterTexels(W, H, dilate, _plane_ptr(pl["prim"], ip), _plane_ptr(pl["src"], ip), _plane_ptr(pl["bary"], fp),
+                                         _plane_ptr(pl["pos"], fp), _plane_ptr(pl["nrm"], fp))
+    return owned, {k: v for k, v in pl.items() if v is not None}
+
+
+def raster_texels_host(tris, W, H, dilate=0, want=TEXEL_PLANES):
+    """raster_texels on the CPU (librt_host.so, rtRasterTexelsHost; no GPU, no renderer state) over `tris`, a 1-D array of triangle_dtype in slot order:
+    the same bits."""
+    tris = _records("raster_texels_host", "triangle", tris, triangle_dtype)
+    pl = _texel_planes("raster_texels_host", W, H, dilate, want)
+    ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    owned = load_host().rtRasterTexelsHost(tris.ctypes.data if len(tris) else None, len(tris), W, H, dilate, _plane_ptr(pl["prim"], ip),
+                                           _plane_ptr(pl["src"], ip), _plane_ptr(pl["bary"], fp), _plane_ptr(pl["pos"], fp), _plane_ptr(pl["nrm"], fp))
+    return owned, {k: v for k, v in pl.items() if v is not None}
+
+
+def atlas_grid(tris, margin=0.05):
+    """Overwrites texCoords of `tris` (a writable 1-D array of triangle_dtype) with the trivial non-overlapping atlas of rtAtlasGrid (include/rt_host.h): two
+    triangles per square cell.  Returns the cells per side."""
+    tris = _records("atlas_grid", "triangle", tris, triangle_dtype)
+    if not tris.flags["WRITEABLE"] or len(tris) < 1 or not (0.0 <= margin < 0.25):
+        raise ValueError("atlas_grid: needs a writable, non-empty array and 0 <= margin < 0.25")
+    return load_host().rtAtlasGrid(tris.ctypes.data, len(tris), margin)
+
+
+def bake_texels(W, H, mode, dirs, ns=1, dilate=0, first=0, dirs_total=None, acc=None, base_id=0, bias=0.0, max_dist=0.0, rays=False, want=("prim", "src")):
+    """Rasterises the atlas at W x H and gathers at every owned texel (bakeTexels, include/rt_api.h): directions first .. first+dirs-1 of dirs_total (default
+    first + dirs), as gather_radiance over the points (pos(t), nrm(t)) with point index t.  acc: None, or the (H, W, Wd) float32 sums an earlier call returned
+    (needed for first > 0).  Returns (owned, planes): planes["out"] (H, W, Wd) float32 - dilated through src -, planes["acc"] (a new array), planes["rays"]
+    (H, W) uint32 with rays=True, and the prim / src planes `want` names; Wd = gather_width(mode).  Blocking."""
+    if mode not in _GATHER_WIDTH:
+        raise ValueError(f"bake_texels: unknown mode {mode!r}")
+    if set(want) - {"prim", "src"}:
+        raise ValueError("bake_texels: want names prim and src only")
+    pl = _texel_planes("bake_texels", W, H, dilate, tuple(want) or ("prim",))
+    Wd = _GATHER_WIDTH[mode]
+    if dirs_total is None:
+        dirs_total = first + dirs
+    if acc is None:
+        if first > 0:
+            raise ValueError("bake_texels: first > 0 needs the acc the texels resume from")
+        a = np.zeros((H, W, Wd), np.float32)
+    else:
+        a = np.array(acc, dtype=np.float32, order="C")              # (a copy: bakeTexels updates the sums in place)
+        if a.shape != (H, W, Wd):
+            raise ValueError(f"bake_texels: acc must have shape ({H}, {W}, {Wd}), got {a.shape}")
+    out = np.zeros((H, W, Wd), np.float32)
+    nrays = np.zeros((H, W), np.uint32) if rays else None
+    ip, fp, up = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    owned = load_renderer().bakeTexels(W, H, dilate, mode, first, dirs, dirs_total, ns, base_id, bias, max_dist, a.ctypes.data_as(fp), out.ctypes.data_as(fp),
+                                       _plane_ptr(nrays, up), _plane_ptr(pl["prim"] if "prim" in want else None, ip),
+                                       _plane_ptr(pl["src"] if "src" in want else None, ip))
+    planes = {"out": out, "acc": a}
+    if rays:
+        planes["rays"] = nrays
+    planes.update({k: pl[k] for k in want})
+    return owned, planes
+
+
+def last_texels_ms():
+    """HIP-event time of the raster, resolve, dilation and compaction kernels of the last raster_texels / bake_texels, in milliseconds."""
+    return load_renderer().rtLastTexelsMs()
+
+
+def last_bake_ms():
+    """HIP-event time of generator + trace + reduce + scatter of the last bake_texels (not the copies), summed over its chunks, in milliseconds."""
+    return load_renderer().rtLastBakeMs()
 
 
 def pinhole_camera(o, target):

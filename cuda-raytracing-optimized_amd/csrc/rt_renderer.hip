@@ -39,6 +39,7 @@
 #include "rt_build.h"
 #include "rt_refine.h"
 #include "rt_gather.h"
+#include "rt_texels.h"
 
 namespace {
 
@@ -179,6 +180,8 @@ struct RenderContext {
     double pixels_ms = 0.0;             // rtLastPixelsMs
     double radiance_ms = 0.0;           // rtLastRadianceMs
     double gather_ms = 0.0;             // rtLastGatherMs
+    double texels_ms = 0.0;             // rtLastTexelsMs
+    double bake_ms = 0.0;               // rtLastBakeMs
     double motion_ms = 0.0;             // rtLastMotionMs
 };
 
@@ -305,6 +308,19 @@ struct GatherState : QueryState {
     uint32_t* d_queue = nullptr;        // RtRadianceBatch::queue
 };
 
+// rasterTexels / bakeTexels (rt_texels.h): the raster's planes and work words, the compact list with its per-entry arrays, the planes a bake scatters into and
+// the seven per-ray arrays of one chunk of the list, each grown to the largest call that asked for it, and the queue word of the radiance kernels.  Its own
+// buffers: gatherRadiance's stay gatherRadiance's.
+enum { kTexOwner = 0, kTexPrim, kTexSrc0, kTexSrc1, kTexBary, kTexPos, kTexNrm, kTexCounts, kTexRank, kTexList, kTexListPos, kTexListNrm,
+       kTexAccPlane, kTexOutPlane, kTexRaysPlane, kTexAcc, kTexOut, kTexNrays,
+       kTexOrg, kTexDir, kTexIds, kTexTMax, kTexL, kTexRays, kTexOccluded, kTexBuffers };
+struct TexelState : QueryState {
+    char* d_buf[kTexBuffers] = {};
+    size_t cap[kTexBuffers] = {};       // bytes d_buf[k] holds
+    uint32_t* d_length = nullptr;       // RtTexelParams::length
+    uint32_t* d_queue = nullptr;        // RtRadianceBatch::queue
+};
+
 DenoiseState g_denoise;
 AccumulateState g_accumulate;
 PreviewState g_preview;
@@ -314,6 +330,7 @@ MotionState g_motion;
 ChunkState g_rays, g_pixels, g_radiance;
 RefineState g_refine;
 GatherState g_gather;
+TexelState g_texels;
 
 // The adaptive frame back to "the next refineFrame starts at sample 0" (rtResetRefine, setCamera, setRenderOptions, the scene edits); the buffers stay.
 void reset_refine() {
@@ -438,6 +455,7 @@ void setup_devices() {
     free_pass(g_radiance);
     free_pass(g_refine);
     free_pass(g_gather);
+    free_pass(g_texels);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -492,7 +510,7 @@ void setup_devices() {
         c.devs.push_back(d);
     }
     HIP_CHECK(hipSetDevice(c.devs[0].device));              // the query calls' own event pairs, on the device they run on
-    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine, &g_gather }) {
+    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine, &g_gather, &g_texels }) {
         q->device = c.devs[0].device;
         HIP_CHECK(hipEventCreate(&q->ev_start));
         HIP_CHECK(hipEventCreate(&q->ev_stop));
@@ -551,6 +569,7 @@ void cleanup_impl() {
     free_pass(g_radiance);
     free_pass(g_refine);
     free_pass(g_gather);
+    free_pass(g_texels);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -789,6 +808,17 @@ double query_ms(const QueryState& q) {
 template <typename Body>
 void for_chunks(size_t n, size_t chunk, Body body) {
     for (size_t first = 0; first < n; first += chunk) body(first, std::min(chunk, n - first));
+}
+
+// Buffer k of a state that keeps d_buf / cap in bytes (GatherState, TexelState), grown to `bytes`.
+template <typename State>
+char* grown_buffer(State& q, int k, size_t bytes) {
+    if (q.cap[k] < bytes) {
+        dev_release(q.owned, q.d_buf[k]);
+        q.d_buf[k] = dev_alloc<char>(q.owned, bytes);
+        q.cap[k] = bytes;
+    }
+    return q.d_buf[k];
 }
 
 // n items of the caller's arrays through a kernel on the query's device, chunk by chunk on that device's stream: the buffers of `table` whose host[k] is not
@@ -1746,13 +1776,7 @@ static bool check_gather(const char* fn, int n, const float* pos, const float* n
 
 // Buffer k of the gather state, grown to `bytes`.
 static char* gather_buffer(int k, size_t bytes) {
-    GatherState& q = g_gather;
-    if (q.cap[k] < bytes) {
-        dev_release(q.owned, q.d_buf[k]);
-        q.d_buf[k] = dev_alloc<char>(q.owned, bytes);
-        q.cap[k] = bytes;
-    }
-    return q.d_buf[k];
+    return grown_buffer(g_gather, k, bytes);
 }
 
 // The parameter block of chunk [k0, k0 + pts) with the per-point inputs uploaded and the per-ray arrays `want` names (-1: none) allocated; the rest is nullptr.
@@ -1860,6 +1884,196 @@ void rtGatherDirections(int n, const float* pos, const float* nrm, int mode, int
 double rtLastGatherMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastGatherMs before init");
     return g_ctx.gather_ms;
+}
+
+// Baking texels (rt_api.h).  The raster runs over the first device's live slots: coverage, resolve, `dilate` dilation launches, the scan of the
+// workgroup counts - then the one word that crosses the bus before the planes do, the length of the list - and, for a bake, the compaction.  A bake goes on
+// chunk by chunk over the compact list as gatherRadiance goes over the caller's: k_texel_dirs fills the batch arrays, the radiance kernels (launch_radiance) or
+// the any-hit kernels (launch_rays) run over them, k_gather_reduce folds them per list entry; the scatter writes the texel planes, which come down.  Nothing
+// of a frame's, a pass's, gatherRadiance's or the other queries' state is read or written.
+static char* texel_buffer(int k, size_t bytes) {
+    return grown_buffer(g_texels, k, std::max<size_t>(bytes, 4));
+}
+
+static void check_texels(const char* fn, int W, int H, int dilate) {
+    const RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail(" before init", fn);
+    if (c.is_spheres) rt_fail(": only a mesh scene has a UV atlas", fn);
+    if (W < 1 || H < 1 || W > RT_TEXEL_MAX_SIZE || H > RT_TEXEL_MAX_SIZE) rt_fail(": W and H must be 1 .. RT_TEXEL_MAX_SIZE", fn);
+    if (dilate < 0 || dilate > RT_TEXEL_MAX_DILATE) rt_fail(": dilate must be 0 .. RT_TEXEL_MAX_DILATE", fn);
+}
+
+// The raster's kernels on the query's device (begin_query has run): the planes `want_*` name, src after `dilate` iterations in src[dilate & 1], and with
+// `with_list` rank, list, list_pos and list_nrm.  *length = the owned texels.  Returns the block; sets rtLastTexelsMs.
+static RtTexelParams texel_raster(int W, int H, int dilate, bool want_prim, bool want_bary, bool want_pos, bool want_nrm, bool with_list, uint32_t* length) {
+    RenderContext& c = g_ctx;
+    TexelState& q = g_texels;
+    const DeviceState& d = c.devs[0];
+    const size_t n = (size_t)W * H;
+    RtTexelParams p = {};
+    p.slots = d.d_tris; p.num_slots = (uint32_t)c.mesh.tris.size();
+    p.W = W; p.H = H;
+    p.owner = reinterpret_cast<int32_t*>(texel_buffer(kTexOwner, n * 4));
+    p.src[0] = reinterpret_cast<int32_t*>(texel_buffer(kTexSrc0, n * 4));
+    if (dilate > 0) p.src[1] = reinterpret_cast<int32_t*>(texel_buffer(kTexSrc1, n * 4));
+    if (want_prim) p.prim = reinterpret_cast<int32_t*>(texel_buffer(kTexPrim, n * 4));
+    if (want_bary) p.bary = reinterpret_cast<float*>(texel_buffer(kTexBary, n * 8));
+    if (want_pos) p.pos = reinterpret_cast<float*>(texel_buffer(kTexPos, n * 12));
+    if (want_nrm) p.nrm = reinterpret_cast<float*>(texel_buffer(kTexNrm, n * 12));
+    p.blocks = (uint32_t)((n + kTexelBlock - 1) / kTexelBlock);
+    p.counts = reinterpret_cast<uint32_t*>(texel_buffer(kTexCounts, (size_t)p.blocks * 4));
+    if (!q.d_length) q.d_length = dev_alloc<uint32_t>(q.owned, 1);
+    p.length = q.d_length;
+    HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+    HIP_CHECK(rt_launch_texel_coverage(p, d.stream));
+    HIP_CHECK(rt_launch_texel_resolve(p, d.stream));
+    for (int i = 1; i <= dilate; i++) HIP_CHECK(rt_launch_texel_dilate(p, i, d.stream));
+    HIP_CHECK(rt_launch_texel_scan(p, d.stream));
+    HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+    HIP_CHECK(hipMemcpyAsync(length, q.d_length, sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+    double ms = query_ms(q);
+    if (with_list) {
+        p.rank = reinterpret_cast<int32_t*>(texel_buffer(kTexRank, n * 4));
+        p.list = reinterpret_cast<uint32_t*>(texel_buffer(kTexList, (size_t)*length * 4));
+        p.list_pos = reinterpret_cast<float*>(texel_buffer(kTexListPos, (size_t)*length * 12));
+        p.list_nrm = reinterpret_cast<float*>(texel_buffer(kTexListNrm, (size_t)*length * 12));
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        HIP_CHECK(rt_launch_texel_compact(p, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));
+        ms += query_ms(q);
+    }
+    c.texels_ms = ms;
+    return p;
+}
+
+int rasterTexels(int W, int H, int dilate, int32_t* prim, int32_t* src, float* bary, float* pos, float* nrm) {
+    check_texels("rasterTexels", W, H, dilate);
+    if (!prim && !src && !bary && !pos && !nrm) rt_fail("rasterTexels: prim, src, bary, pos and nrm are all null");
+    TexelState& q = g_texels;
+    const DeviceState& d = g_ctx.devs[0];
+    const size_t n = (size_t)W * H;
+    const int current = begin_query(q);
+    uint32_t length = 0;
+    const RtTexelParams p = texel_raster(W, H, dilate, prim != nullptr, bary != nullptr, pos != nullptr, nrm != nullptr, false, &length);
+    if (prim) HIP_CHECK(hipMemcpyAsync(prim, p.prim, n * 4, hipMemcpyDeviceToHost, d.stream));
+    if (src) HIP_CHECK(hipMemcpyAsync(src, p.src[dilate & 1], n * 4, hipMemcpyDeviceToHost, d.stream));
+    if (bary) HIP_CHECK(hipMemcpyAsync(bary, p.bary, n * 8, hipMemcpyDeviceToHost, d.stream));
+    if (pos) HIP_CHECK(hipMemcpyAsync(pos, p.pos, n * 12, hipMemcpyDeviceToHost, d.stream));
+    if (nrm) HIP_CHECK(hipMemcpyAsync(nrm, p.nrm, n * 12, hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));
+    end_query(current);
+    return (int)length;
+}
+
+int bakeTexels(int W, int H, int dilate, int mode, int first, int dirs, int dirs_total, int ns, uint32_t base_id, float bias, float max_dist,
+               float* acc, float* out, uint32_t* rays, int32_t* prim, int32_t* src) {
+    RenderContext& c = g_ctx;
+    check_texels("bakeTexels", W, H, dilate);
+    static const float unit_z[3] = { 0.0f, 0.0f, 1.0f };            // (the points are the raster's: what check_gather asks of a list holds)
+    check_gather("bakeTexels", 1, unit_z, unit_z, mode, first, dirs, dirs_total, bias);
+    if (first > 0 && !acc) rt_fail("bakeTexels: first > 0 needs acc (the sums the texels resume from)");
+    if (!acc && !out && !rays) rt_fail("bakeTexels: acc, out and rays are all null");
+    if (std::isnan(max_dist) || max_dist < 0.0f) rt_fail("bakeTexels: max_dist must not be a NaN or negative");
+    const bool vis = mode == RT_GATHER_VISIBILITY;
+    if (!vis) {
+        if (ns < 1 || ns > RT_PROGRESSIVE_MAX_SAMPLES) rt_fail("bakeTexels: ns must be 1 .. RT_PROGRESSIVE_MAX_SAMPLES");
+        check_per_pixel("bakeTexels");
+    }
+    TexelState& q = g_texels;
+    const DeviceState& d = c.devs[0];
+    const size_t n = (size_t)W * H, Wd = (size_t)gather_width(mode), chunk = std::max<size_t>(1, kRayChunk / (size_t)dirs);
+    const int max_waves = rt_read_switches().pixels_waves;
+    const int current = begin_query(q);
+    if (!q.d_queue) q.d_queue = dev_alloc<uint32_t>(q.owned, 1);
+    uint32_t length = 0;
+    const RtTexelParams p = texel_raster(W, H, dilate, prim != nullptr, false, false, false, true, &length);
+    RtTexelBakeParams b = {};
+    b.src = p.src[dilate & 1]; b.rank = p.rank; b.list = p.list;
+    b.length = length; b.texels = (uint32_t)n; b.Wd = (int32_t)Wd;
+    if (acc) {
+        b.acc_plane = reinterpret_cast<float*>(texel_buffer(kTexAccPlane, n * Wd * 4));
+        b.acc = reinterpret_cast<float*>(texel_buffer(kTexAcc, (size_t)length * Wd * 4));
+    }
+    if (out) {
+        b.out_plane = reinterpret_cast<float*>(texel_buffer(kTexOutPlane, n * Wd * 4));
+        b.out = reinterpret_cast<float*>(texel_buffer(kTexOut, (size_t)length * Wd * 4));
+    }
+    if (rays) {
+        b.rays_plane = reinterpret_cast<uint32_t*>(texel_buffer(kTexRaysPlane, n * 4));
+        b.nrays = reinterpret_cast<uint32_t*>(texel_buffer(kTexNrays, (size_t)length * 4));
+    }
+    double ms_sum = 0.0;
+    if (first > 0) {
+        HIP_CHECK(hipMemcpyAsync(b.acc_plane, acc, n * Wd * 4, hipMemcpyHostToDevice, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        HIP_CHECK(rt_launch_texel_fetch(b, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));
+        ms_sum += query_ms(q);
+    }
+    for_chunks((size_t)length, chunk, [&](size_t k0, size_t pts) {
+        const size_t nray = pts * (size_t)dirs;
+        RtGatherParams g = {};
+        g.pos = p.list_pos + 3 * k0; g.nrm = p.list_nrm + 3 * k0;
+        if (b.acc) g.acc = b.acc + k0 * Wd;
+        if (b.out) g.out = b.out + k0 * Wd;
+        if (b.nrays) g.nrays = b.nrays + k0;
+        g.org = reinterpret_cast<float*>(texel_buffer(kTexOrg, nray * 12)); g.dir = reinterpret_cast<float*>(texel_buffer(kTexDir, nray * 12));
+        if (vis) {
+            g.t_max = reinterpret_cast<float*>(texel_buffer(kTexTMax, nray * 4)); g.occluded = reinterpret_cast<uint8_t*>(texel_buffer(kTexOccluded, nray));
+        } else {
+            g.ids = reinterpret_cast<uint32_t*>(texel_buffer(kTexIds, nray * 4)); g.L = reinterpret_cast<rt_vec3*>(texel_buffer(kTexL, nray * 12));
+            g.rays = reinterpret_cast<uint32_t*>(texel_buffer(kTexRays, nray * 4));
+        }
+        g.pts = (uint32_t)pts; g.dirs = (uint32_t)dirs; g.first = (uint32_t)first; g.dirs_total = (uint32_t)dirs_total;
+        g.k0 = (uint32_t)k0; g.base_id = base_id; g.mode = mode; g.bias = bias;
+        g.t_max_value = max_dist > 0.0f ? max_dist : FLT_MAX;
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        HIP_CHECK(rt_launch_texel_dirs(g, p.list, d.stream));
+        if (vis) {
+            RtRayBatch r = {};
+            r.org = g.org; r.dir = g.dir; r.t_max = g.t_max; r.occluded = g.occluded;
+            r.n = (int32_t)nray;
+            r.t_min_default = c.opt.t_min;
+            launch_rays(d, r, true);
+        } else {
+            HIP_CHECK(hipMemsetAsync(q.d_queue, 0, sizeof(uint32_t), d.stream));
+            RtRadianceBatch r = {};
+            r.org = g.org; r.dir = g.dir; r.ids = g.ids;
+            r.out = g.L; r.rays = g.rays;
+            r.queue = q.d_queue; r.n = (int32_t)nray; r.ns_all = ns;
+            launch_radiance(d, r, max_waves);
+        }
+        HIP_CHECK(rt_launch_gather_reduce(g, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));              // (the events are read per chunk)
+        ms_sum += query_ms(q);
+    });
+    HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+    HIP_CHECK(rt_launch_texel_scatter(b, d.stream));
+    HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+    if (acc) HIP_CHECK(hipMemcpyAsync(acc, b.acc_plane, n * Wd * 4, hipMemcpyDeviceToHost, d.stream));
+    if (out) HIP_CHECK(hipMemcpyAsync(out, b.out_plane, n * Wd * 4, hipMemcpyDeviceToHost, d.stream));
+    if (rays) HIP_CHECK(hipMemcpyAsync(rays, b.rays_plane, n * 4, hipMemcpyDeviceToHost, d.stream));
+    if (prim) HIP_CHECK(hipMemcpyAsync(prim, p.prim, n * 4, hipMemcpyDeviceToHost, d.stream));
+    if (src) HIP_CHECK(hipMemcpyAsync(src, b.src, n * 4, hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));                  // blocking: the caller's planes are complete on return
+    ms_sum += query_ms(q);
+    end_query(current);
+    c.bake_ms = ms_sum;
+    return (int)length;
+}
+
+double rtLastTexelsMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastTexelsMs before init");
+    return g_ctx.texels_ms;
+}
+
+double rtLastBakeMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastBakeMs before init");
+    return g_ctx.bake_ms;
 }
 
 // Adaptive sampling on the device (rt_api.h).  One call is one pass over the whole image on the first in-process device: select (rt_refine.h)

@@ -527,6 +527,64 @@ void   rtGatherDirections(int n, const float* pos, const float* nrm, int mode, i
                           uint32_t base_id, float bias, float* org, float* dir, uint32_t* ids);   /* the generator kernel alone, downloaded */
 double rtLastGatherMs(void);   /* HIP-event time of generator + trace + reduce of the last gatherRadiance, summed over its chunks; 0 before the first */
 
+/* --- baking texels: the mesh's UV atlas rasterised on the device, a gather per covered texel, texel planes back ---------------------------------
+ * rasterTexels turns the live triangles' texCoords and an atlas size into texel points; bakeTexels does that and gathers at them with gatherRadiance's
+ * generator, kernels and reduction, scatters the results back into texel planes and dilates the chart borders.  Nothing goes up (but acc, to resume); only
+ * texel planes come back.  Mesh scenes only.  All arithmetic is fp32, in both fp modes: every operation is rounded on its own (no FMA), operands are in the
+ * order written, / and sqrt are correctly rounded, a comparison with a NaN is false.
+ * The raster.  Atlas W x H, with 1 <= W, H <= RT_TEXEL_MAX_SIZE (8192).
+ *   Texel          t = y*W + x.  Row 0 is v near 0, which is the row the renderer's own texture lookup addresses first.
+ *   Sample point   s = (((float)x + 0.5f) / (float)W, ((float)y + 0.5f) / (float)H).  UVs are not wrapped.  What lies outside [0,1]^2 is clipped.
+ *   Candidates     every slot k in [0, numTris) of the live leaf-ordered triangle array whose v[0].x is not +-inf.  This is the index RT_GUIDE_PRIM reports.
+ *                  It follows updateTriangles and rebuildBvh.
+ *   UV vertices    a = tc[0..1], b = tc[2..3], c = tc[4..5].  This is the order mesh_texel uses: weight hu on b, hv on c.
+ *   Box test       (part of the definition, so that a texel walk bounded by the triangle's UV box is exact, not merely conservative):
+ *                  umin <= s.x && s.x <= umax && vmin <= s.y && s.y <= vmax.  The bounds are the min / max of the three vertices by < / >: each starts at
+ *                  a's coordinate, then takes b's, then c's where that is smaller (larger).
+ *   Inside test    d = (b.x-a.x)*(c.y-a.y) - (b.y-a.y)*(c.x-a.x).  !(d != 0) covers nothing.
+ *                  w1 = (s.x-a.x)*(c.y-a.y) - (s.y-a.y)*(c.x-a.x)
+ *                  w2 = (b.x-a.x)*(s.y-a.y) - (b.y-a.y)*(s.x-a.x)
+ *                  hu = w1/d; hv = w2/d; w0 = 1 - hu - hv
+ *                  covered iff hu >= 0 && hv >= 0 && w0 >= 0.  Edges and vertices are inclusive.
+ *   Owner          prim(t) is the lowest covering slot.  No slot gives RT_GUIDE_PRIM_NONE.
+ *   Resolve        for an owned texel: bary = (hu, hv) of the owner, recomputed with the same lines.
+ *                  pos[k] = v0[k] + hu*(v1[k]-v0[k]) + hv*(v2[k]-v0[k]), left to right.
+ *                  nrm = unit(cross(v1-v0, v2-v0)), with renderMotion's cross and unit (three divisions).  The geometric normal is by winding and is not
+ *                  turned.  An unowned texel gets zeros.
+ *   Dilation       dilate in 0 .. RT_TEXEL_MAX_DILATE (16).  src_0(t) = t if owned, else -1.  Iteration i, for every t with src_{i-1}(t) == -1: scan
+ *                  dy = -1,0,1 (outer) and dx = -1,0,1 (inner) inside the image.  Take the first q with src_{i-1}(q) != -1 and set src_i(t) = src_{i-1}(q).
+ *                  If there is none, src_i(t) = -1.  Owned texels keep themselves.  The planes are ping-ponged, so the order of evaluation is free.
+ * Known: two triangles that share a UV edge each evaluate that edge with their own rounding.  A texel centre within an ulp of the edge can be claimed by
+ * neither.  Dilation fills it.
+ * Both calls return the number of owned texels.  Every plane pointer may be NULL.  For rasterTexels not all may be NULL; for bakeTexels not all of acc / out /
+ * rays.  Planes are caller-owned host arrays of W*H entries, row 0 first: prim and src one int32, bary 2 floats, pos and nrm 3 floats, acc and out
+ * rtGatherWidth(mode) floats, rays one word.  src is the plane after `dilate` iterations.
+ * bakeTexels.  Point k is the texel index t, whatever the compaction or chunking.  P = pos(t), N = nrm(t).  Everything else is gatherRadiance's definition
+ * word for word: origin and direction, g = base_id + (uint32_t)((uint64_t)t * dirs_total + m), the reduction, M, and W = rtGatherWidth(mode).
+ *   Bit promise    In RT_FP_PARITY the result at every owned texel is bit-identical to gatherRadiance over the W*H points (pos(t), nrm(t)) at entry t, with any
+ *                  finite filler at unowned entries, in every mode.  RT_GATHER_VISIBILITY is bit-identical in both fp modes.  The radiance modes in RT_FP_FAST
+ *                  are the same estimate with no bit promise, because the compacted batch puts other rays into a wave.
+ *   Outputs        acc and rays: written at owned texels, 0 elsewhere.  acc is read at owned texels when first > 0.  Any split of dirs_total into calls equals
+ *                  one call.  out(t) is the value of src(t), and zeros where src(t) == -1.
+ * Only owned texels are traced.  The call is blocking and runs on the first in-process device.  It chunks the compact list by max(1, RT_RAY_CHUNK / dirs)
+ * points.  It follows setRenderOptions, the scene edits and rebuildBvh; RT_PIXELS_WAVES caps its path waves as it caps gatherRadiance's.  It changes nothing
+ * another call observes: what gatherRadiance leaves alone, and gatherRadiance's own buffers and rtLastGatherMs.  The device buffers are its own and are freed
+ * where the query buffers are.  Per texel of the largest atlas seen: owner 4, src 4 (8 with dilate > 0), the work word of a workgroup of 256 texels, and
+ * where asked for prim 4, bary 8, pos 12, nrm 12 (rasterTexels); for a bake rank 4 and where asked for acc 4W, out 4W, rays 4.  Per owned texel of a bake:
+ * list 4, pos 12, nrm 12, and where asked for acc 4W, out 4W, rays 4.  Per ray of the largest chunk: gatherRadiance's 44 bytes in the radiance modes, 29 in
+ * VISIBILITY.  One word, the list's length, is read back between the raster and the bake.
+ * rtRasterTexelsHost (rt_host.h) is the raster's CPU twin; rtAtlasGrid there gives a mesh without unique UVs a trivial atlas.
+ * Misuse (rt error, exit 99), checked on the host before any device work: before init (rtLastTexelsMs and rtLastBakeMs as well), a sphere scene, W or H
+ * outside 1 .. RT_TEXEL_MAX_SIZE, dilate outside 0 .. RT_TEXEL_MAX_DILATE, all planes NULL (bakeTexels: acc, out and rays), and for bakeTexels everything
+ * gatherRadiance refuses for the same arguments. */
+#define RT_TEXEL_MAX_SIZE 8192
+#define RT_TEXEL_MAX_DILATE 16
+int    rasterTexels(int W, int H, int dilate, int32_t* prim, int32_t* src, float* bary, float* pos, float* nrm);
+int    bakeTexels(int W, int H, int dilate, int mode, int first, int dirs, int dirs_total, int ns, uint32_t base_id,
+                  float bias, float max_dist, float* acc, float* out, uint32_t* rays, int32_t* prim, int32_t* src);
+double rtLastTexelsMs(void);   /* raster + resolve + dilate + compact kernels of the last rasterTexels / bakeTexels */
+double rtLastBakeMs(void);     /* generator + trace + reduce + scatter of the last bakeTexels, summed over chunks */
+
 /* --- adaptive sampling: the samples go where the image is still noisy ---------------------------------------------------------------
  * refineFrame renders an adaptive frame: every pixel gets samples in batches until an estimate of its own error says it has enough.  The frame's state, the
  * selection, the list of a pass and the statistics live on the device; the pixel kernels of renderPixels trace the samples.  One call is one pass: select,

@@ -122,6 +122,22 @@ int rtDisplayFrameHost(const rt_vec3* in, uint8_t* out_rgba, int nx, int ny, int
 void rtGatherDirectionsHost(int n, const float* pos, const float* nrm, int mode, int first, int dirs, int dirs_total,
                             uint32_t base_id, float bias, float* org, float* dir, uint32_t* ids);
 
+/* The UV-atlas raster of rasterTexels / bakeTexels (rt_api.h, "baking texels": the definition is stated there, once) on the CPU, in plain C++, over the
+ * caller's leaf-ordered triangle array (HostMesh tris, or what rtRebuildBvh left): what rasterTexels downloads from the device, bit for bit - prim and src one
+ * int32 per texel, bary 2 floats, pos and nrm 3 floats, row 0 first; each pointer may be NULL, not all.  Returns the number of owned texels, or -1 for
+ * arguments rasterTexels would refuse (nothing is written then).  No renderer state is read. */
+int rtRasterTexelsHost(const rt_triangle* tris, uint32_t numTris, int W, int H, int dilate, int32_t* prim, int32_t* src, float* bary, float* pos, float* nrm);
+
+/* A trivial non-overlapping atlas: overwrites texCoords of tris[0 .. n-1]; nothing else is touched (sentinel slots get coordinates too; the raster skips them).
+ * fp32, every operation rounded on its own, operands in the order written:
+ *   pairs = (n + 1) / 2;  cells = the smallest integer with cells * cells >= pairs;  cs = 1.0f / (float)cells;  m = margin * cs;  m3 = 3.0f * m
+ *   triangle i lies in cell q = i / 2 at column q % cells, row q / cells:  u0 = (float)(q % cells) * cs;  v0 = (float)(q / cells) * cs;  u1 = u0 + cs;  v1 = v0 + cs
+ *   i even, the lower-left half:   a = (u0 + m, v0 + m)   b = (u1 - m3, v0 + m)   c = (u0 + m, v1 - m3)
+ *   i odd, the upper-right half:   a = (u1 - m, v1 - m)   b = (u0 + m3, v1 - m)   c = (u1 - m, v0 + m3)
+ * so each half keeps m from the cell's border and 2m (along an axis) from the cell's diagonal: with margin > 0 and a texel smaller than m no texel centre is
+ * covered twice.  Returns cells, or 0 (nothing written) for tris NULL, n < 1 or margin outside [0, 0.25). */
+int rtAtlasGrid(rt_triangle* tris, int n, float margin);
+
 #ifdef __cplusplus
 }
 #endif
