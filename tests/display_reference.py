@@ -1,7 +1,8 @@
 """The test reference of displayFrame (include/rt_api.h): the definition restated in numpy float32, one rounded operation per numpy operation, in the order
 written.  powf goes through ctypes to libm.so.6's powf, element by element: numpy's own float32 power may be a SIMD routine with other bits.  No test: a plain
 module, imported by tests/test_display_api.py (against rtDisplayFrameHost) and tests/test_gpu_display.py (against displayFrame); the frames and cases both use
-are here too, so the CPU twin and the device are held against the same inputs."""
+are here too, so the CPU twin and the device are held against the same inputs, and so is the one comparison of a displayFrame call every GPU test makes
+(check) and the frame of tests/test_gpu_capped_grids.py whose median depends on the pixels past the histogram kernel's first round (round_two_frame)."""
 import ctypes as C
 import functools
 import itertools
@@ -156,6 +157,58 @@ def synthetic(seed, nx, ny, scale=1.0):
     """A seeded (ny, nx, 3) frame: values over 2^-20 .. 2^20 (times `scale`), the edge pixels above at random places, 5 % negative channels.  Read-only and
     shared: computed once."""
     return _synthetic(seed, nx, ny, float(scale))
+
+
+@functools.lru_cache(maxsize=None)
+def round_two_frame(seed, nx, ny, first, share=0.65):
+    """synthetic(seed, nx, ny) rearranged so that the median bin hangs on the pixels with index >= `first` alone (the ones a grid capped at `first` lanes
+    reaches in its second round): returns (frame, (r1, r2)).  r1, r2 are the two bins around the synthetic frame's median.  Pixels below `first` that fall
+    in them move 16 bins up (times 4: exact), so that no pixel of the first round is counted there; the pixels from `first` on are given luminances in r1
+    (`share` of them) and in r2 (the rest); then pixels of the first round move from above r2 to 32 bins lower (times 2^-4: exact) until
+    D = (count above r2) - (count below r1) is 0.45 n.  With x pixels in r1 and n - x in r2 the median bin is
+        r2 for the frame as it is     (2 x < D + n and D <= n),
+        r1 with the n counted twice   (4 x >= D + 2 n),
+        another bin without them      (r1 and r2 are empty then, and the median bin is never an empty one),
+    which test_capped_grids_api.py asserts on the result.  Read-only and shared: computed once."""
+    a = np.array(synthetic(seed, nx, ny), copy=True)
+    flat = a.reshape(-1, 3)
+    n = len(flat) - first
+    assert 0 < n < first
+    b, counted = bins_of(flat)
+    cum = np.cumsum(np.bincount(np.minimum(b[counted], BINS - 1), minlength=BINS))
+    r1 = int(np.argmax(2 * cum >= cum[-1]))
+    r2 = r1 + 1
+    head = np.arange(len(flat)) < first
+    flat[head & counted & ((b == r1) | (b == r2))] *= F(4)
+    x = int(share * n)
+    lums = np.array([((r + BIAS) << 20) | (0x1000 + k * 1237 % 0xfe000) for k, r in enumerate([r1] * x + [r2] * (n - x))], np.uint32).view(F)
+    flat[first:] = 0                                            # a green pixel whose luminance is within an ulp of one well inside the bin
+    flat[first:, 1] = lums / _K[1]
+    b, counted = bins_of(flat)
+    D = int((counted & (b > r2)).sum()) - int((counted & (b < r1)).sum())
+    want = 9 * n // 20                                          # x = 0.65 n lies in [(D + 2 n) / 4, (D + n) / 2) for D in (0.3 n, 0.6 n]: aim at the middle
+    assert D >= want, (D, want)                                 # (the median bin itself was emptied upwards, so more lies above than below)
+    above = np.flatnonzero(head & counted & (b > r2) & (b <= r2 + 8))[:(D - want) // 2]
+    assert len(above) == (D - want) // 2
+    flat[above] *= F(2.0 ** -4)
+    a.setflags(write=False)
+    return a, (r1, r2)
+
+
+def check(rt, ref, frame, src, flags, tonemap, exposure=1.0, adapt=1.0, what=""):
+    """One displayFrame call on both sides, bit for bit: the bytes, rtLastExposure and (with AUTO_EXPOSURE) the histogram.  `ref` is a Display, `frame` is
+    what it sees, `src` what displayFrame is given (None: the framebuffer, which holds `frame`).  Returns the bytes."""
+    got = rt.display_frame(src, flags=flags, tonemap=tonemap, exposure=exposure, adapt=adapt)
+    want, E_used, hist = ref.step(frame, flags, tonemap, exposure, adapt)
+    diff = got != want
+    print(f"{what} flags {flags} tonemap {tonemap}: {int(diff.sum())} of {diff.size} bytes differ, E_used {rt.last_exposure()!r} / {float(E_used)!r}")
+    assert got.shape == want.shape and got.dtype == np.uint8
+    assert int(F(rt.last_exposure()).view(np.uint32)) == int(F(E_used).view(np.uint32)), (what, flags, tonemap, rt.last_exposure(), float(E_used))
+    if flags & AUTO_EXPOSURE:
+        assert np.array_equal(rt.display_histogram(), hist), (what, flags, tonemap)
+    assert np.array_equal(got, want), (what, flags, tonemap, int(diff.sum()), np.argwhere(diff)[:5].tolist())
+    assert rt.last_display_ms() > 0.0
+    return got
 
 
 SPECIAL_VALUES = (float("nan"), float("inf"), float("-inf"), 1e30, -1e30, 3.4028234e38, 2.0 ** 40, 1e-40, -1e-40, 0.0, -0.0, 1.0, 254.5 / 255.9)

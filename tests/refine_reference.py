@@ -3,7 +3,8 @@ samples per pixel - a pixel of the oracle's frame at n is the pixel of the list 
 module, imported by tests/test_refine_api.py and tests/test_gpu_refine.py.
 
 Scenes: the tags of tests/pixels_reference.py, and S1_13x5 = S1's three spheres re-initialised at 13 x 5 (65 pixels: one wave + 1, and the 3 x 3 window of
-every pixel but the 33 inner ones is clipped by the border).  CASES holds the parameters the tests run with; the thresholds are chosen and pinned by
+every pixel but the 33 inner ones is clipped by the border), and S1_523x503 = the same spheres at 523 x 503 (263 069 pixels = 1028 workgroups of 256: the
+counting and scattering kernels, capped at 1024 workgroups, go round twice, and the second round holds 925 pixels; tests/test_capped_grids_api.py).  CASES holds the parameters the tests run with; the thresholds are chosen and pinned by
 tests/test_refine_api.py.
 
 Every operation below is one float32 operation of the header's definition, in its order: numpy rounds each on its own.  max0(x) = x < 0 ? 0 : x keeps a
@@ -20,8 +21,8 @@ LUM_EPS = F(1e-3)
 FLT_MAX = np.finfo(np.float32).max
 
 #         tag: (batch, min_batches, max_samples, threshold)
-CASES = {"S2": (2, 2, 12, 0.1), "M1": (2, 2, 8, 0.8), "S1_13x5": (2, 2, 10, 0.1)}
-SMALL = {"S1_13x5": ("S1", 13, 5)}
+CASES = {"S2": (2, 2, 12, 0.1), "M1": (2, 2, 8, 0.8), "S1_13x5": (2, 2, 10, 0.1), "S1_523x503": (2, 2, 8, 0.0003)}
+SMALL = {"S1_13x5": ("S1", 13, 5), "S1_523x503": ("S1", 523, 503)}         # (a scene of pixels_reference at another size)
 
 
 def size(tag):
@@ -49,6 +50,28 @@ def oracle_frame(rt, O, tag, n):
     fb, _ = O.render(O.sphere_scene(sp, mt), cam, O.default_options(True), nx, ny, n, PR.SCENES[base][2])
     fb.setflags(write=False)
     return fb
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_rays(rt, O, tag, n):
+    """The oracle's rays of every pixel over its first n samples, (ny, nx) uint32, read-only: one region render per pixel, as PR.oracle_planes counts them
+    (which serves the tags that are not in SMALL)."""
+    if tag not in SMALL:
+        return PR.oracle_planes(rt, O, tag, n)[1]
+    base, nx, ny = SMALL[tag]
+    sp, mt, cam = rt.scene_three_spheres(nx, ny)
+    sc, opt, fb = O.sphere_scene(sp, mt), O.default_options(True), np.zeros((ny, nx, 3), np.float32)
+    rays = np.zeros((ny, nx), np.uint32)
+    for j in range(ny):
+        for i in range(nx):
+            rays[j, i] = O.render(sc, cam, opt, nx, ny, n, PR.SCENES[base][2], region=(i, j, i + 1, j + 1), counters=True, fb=fb)[1].rays
+    rays.setflags(write=False)
+    return rays
+
+
+def classes(rays):
+    """The cost class of a last batch's rays: 31 - clz(max(rays, 1)); exact below 2^53."""
+    return np.floor(np.log2(np.maximum(np.asarray(rays).astype(np.int64), 1))).astype(np.int64)
 
 
 def lum(c):
@@ -120,10 +143,10 @@ class Frame:
         return sampled, self.mean.copy(), self.n.copy(), self.error(), active
 
 
-def run(rt, O, tag, flags=0, params=None, limit=64):
-    """The calls of a frame to completion under CASES[tag] (or params): a list of call results, the last one with sampled == 0."""
+def run(rt, O, tag, flags=0, params=None, limit=64, frames=None):
+    """The calls of a frame to completion under CASES[tag] (or params): a list of call results, the last one with sampled == 0.  `frames`: as Frame's."""
     batch, min_batches, max_samples, threshold = params or CASES[tag]
-    f, calls = Frame(rt, O, tag, batch), []
+    f, calls = Frame(rt, O, tag, batch, frames=frames), []
     while len(calls) < limit:
         calls.append(f.call(min_batches, max_samples, threshold, flags))
         if calls[-1][0] == 0:

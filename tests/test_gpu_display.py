@@ -17,19 +17,7 @@ def _f32_bits(x):
     return int(np.float32(x).view(np.uint32))
 
 
-def _check(rt, ref, frame, src, flags, tonemap, exposure=1.0, adapt=1.0, what=""):
-    """One call on both sides: `frame` is what the reference sees, `src` what displayFrame is given (None: the framebuffer, which holds `frame`)."""
-    got = rt.display_frame(src, flags=flags, tonemap=tonemap, exposure=exposure, adapt=adapt)
-    want, E_used, hist = ref.step(frame, flags, tonemap, exposure, adapt)
-    diff = got != want
-    print(f"{what} flags {flags} tonemap {tonemap}: {int(diff.sum())} of {diff.size} bytes differ, E_used {rt.last_exposure()!r} / {float(E_used)!r}")
-    assert got.shape == want.shape and got.dtype == np.uint8
-    assert _f32_bits(rt.last_exposure()) == _f32_bits(E_used), (what, flags, tonemap, rt.last_exposure(), float(E_used))
-    if flags & A:
-        assert np.array_equal(rt.display_histogram(), hist), (what, flags, tonemap)
-    assert np.array_equal(got, want), (what, flags, tonemap, int(diff.sum()), np.argwhere(diff)[:5].tolist())
-    assert rt.last_display_ms() > 0.0
-    return got
+_check = D.check                # one call on both sides, bit for bit (shared with tests/test_gpu_capped_grids.py)
 
 
 def _spheres(rt, nx, ny):

@@ -100,8 +100,7 @@ def test_one_wave_gives_the_same_bits(rt, O, tmp_path, tag, flags):
 
 # ---- 3. the list and its order ---------------------------------------------------------------------------------------------------
 
-def _classes(rays):
-    return np.floor(np.log2(np.maximum(rays.astype(np.int64), 1))).astype(np.int64)          # 31 - clz(max(rays, 1)); exact below 2^53
+_classes = RR.classes           # 31 - clz(max(rays, 1))
 
 
 def test_the_list_is_the_active_set_in_cost_order(rt, O):

@@ -9,6 +9,7 @@ of the final samples plane, off / on; pixels whose final count differs between o
   S2       batch 2, min_batches 2, max 12, threshold 0.1:  0.334 / 0.681;  {4, 6, 8, 10, 12} both;    1358 of 3072
   M1       batch 2, min_batches 2, max 8,  threshold 0.8:  0.135 / 0.596;  {4, 6, 8} both;             783 of 1536
   S1_13x5  batch 2, min_batches 2, max 10, threshold 0.1:  0.108 / 0.631;  {4, 6, 8, 10} both;          34 of 65
+  S1_523x503  batch 2, min_batches 2, max 8, threshold 0.0003:  0.558 / 0.821;  {4, 6, 8} both;  73531 of 263069  (chosen by tests/test_capped_grids_api.py)
 A pass that stops early with dilation on starts again later (S2: 11 calls instead of 7): a neighbour's new samples can move its error above the threshold."""
 import ctypes as C
 import os

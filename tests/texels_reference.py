@@ -66,14 +66,20 @@ def dilate_once(cur):
     return new
 
 
-def raster(tris, W, H, dilate=0):
+def raster(tris, W, H, dilate=0, slots=None):
     """The planes of the definition: dict(prim, src, bary, pos, nrm, owned) plus what the tests assert on the inputs - covers (H, W): covering slots per
-    texel, on_edge (H, W): the owner's hu, hv or w0 is exactly 0."""
+    texel, on_edge (H, W): the owner's hu, hv or w0 is exactly 0.  `slots`: the ascending slots to evaluate, where the caller has parked every other one
+    (keep_slots; checked here) - a parked slot covers nothing, and evaluating it over a large atlas only costs time."""
     sx, sy = samples(W, H)
     prim = np.full((H, W), PRIM_NONE, np.int32)
     bary, pos, nrm = np.zeros((H, W, 2), F), np.zeros((H, W, 3), F), np.zeros((H, W, 3), F)
     covers, on_edge = np.zeros((H, W), np.int32), np.zeros((H, W), bool)
-    for k in range(len(tris)):
+    if slots is not None:
+        slots = np.asarray(slots)
+        rest = np.ones(len(tris), bool)
+        rest[slots] = False
+        assert (np.diff(slots) > 0).all() and (tris["texCoords"][rest] == np.asarray(PARKED, F)).all()
+    for k in (range(len(tris)) if slots is None else slots.tolist()):
         if np.isinf(tris[k]["v"][0, 0]):
             continue
         cov, hu, hv, w0 = cover(tris[k]["texCoords"], sx, sy)
@@ -147,6 +153,19 @@ def _place(tris, uvs, order=None):
     live = np.flatnonzero(~np.isinf(out["v"][:, 0, 0]))
     assert len(live) >= len(uvs), (len(live), len(uvs))
     out["texCoords"][live[:len(uvs)]] = np.asarray(uvs, F)
+    return out
+
+
+def live_slots(tris):
+    """The slots that are no sentinel, ascending."""
+    return np.flatnonzero(~np.isinf(tris["v"][:, 0, 0]))
+
+
+def keep_slots(tris, slots):
+    """A copy of tris with every slot but `slots` parked: the atlas of `slots` alone, which raster(..., slots=slots) evaluates in len(slots) steps."""
+    out = tris.copy()
+    out["texCoords"] = PARKED
+    out["texCoords"][slots] = tris["texCoords"][slots]
     return out
 
 
