@@ -81,7 +81,13 @@ $(OBJ)/gather.o: $(CSRC)/rt_kernels_gather.hip $(CSRC)/rt_gather.h $(CSRC)/rt_ga
 # generator's is rt_gather_dirs.h, unchanged.  Its own TU and headers: no other kernel object depends on it.
 $(OBJ)/texels.o: $(CSRC)/rt_kernels_texels.hip $(CSRC)/rt_texels.h $(CSRC)/rt_texel_raster.h $(CSRC)/rt_gather.h $(CSRC)/rt_gather_dirs.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_motion.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h $(CSRC)/rt_gather.h $(CSRC)/rt_texels.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The kernels of filterTexels (the prologue that packs a texel's position, normal and footprint into records, the a-trous iterations, the scatter through the
+# dilated source plane): defined bit for bit as the passes above, so one object with the flags of texels.o.  The filter's arithmetic is rt_texel_filter.h,
+# which librt_host.so compiles too (rtFilterTexelsHost); the raster's is rt_texel_raster.h, unchanged.  Its own TU and headers: no other kernel object depends
+# on it.
+$(OBJ)/texel_filter.o: $(CSRC)/rt_kernels_texel_filter.hip $(CSRC)/rt_texel_filter.h $(CSRC)/rt_texel_filter_launch.h $(CSRC)/rt_texel_raster.h include/rt_types.h include/rt_api.h | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_motion.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h $(CSRC)/rt_gather.h $(CSRC)/rt_texels.h $(CSRC)/rt_texel_filter_launch.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o
@@ -93,12 +99,13 @@ REFINE_OBJS := $(OBJ)/refine.o
 MOTION_OBJS := $(OBJ)/motion.o
 GATHER_OBJS := $(OBJ)/gather.o
 TEXELS_OBJS := $(OBJ)/texels.o
+FILTER_OBJS := $(OBJ)/texel_filter.o
 
-$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS) -o $@
+$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS) $(FILTER_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS) $(FILTER_OBJS) -o $@
 
-$(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp $(CSRC)/rt_gather_dirs.h $(CSRC)/rt_texel_raster.h include/rt_host.h include/rt_types.h include/rt_api.h
-	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp -o $@
+$(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp $(HOST)/rt_texel_filter_host.cpp $(CSRC)/rt_gather_dirs.h $(CSRC)/rt_texel_raster.h $(CSRC)/rt_texel_filter.h include/rt_host.h include/rt_types.h include/rt_api.h
+	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp $(HOST)/rt_texel_filter_host.cpp -o $@
 
 oracle: $(PKG)/librt_mi355x.so $(PKG)/librt_host.so
 	$(MAKE) -C oracle

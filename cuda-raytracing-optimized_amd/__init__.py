@@ -141,6 +141,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "radianceRays", "rtLastRadianceMs",
                     "rtGatherWidth", "gatherRadiance", "rtGatherDirections", "rtLastGatherMs",
                     "rasterTexels", "bakeTexels", "rtLastTexelsMs", "rtLastBakeMs",
+                    "filterTexels", "rtLastFilterMs",
                     "refineFrame", "rtResetRefine", "rtRefineSamples", "rtRefineLastList", "rtLastRefineMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
@@ -153,7 +154,7 @@ HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtScene
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
                 "rtDisplayFrameHost", "rtCentreRays", "rtPinholeCamera", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh",
-                "rtGatherDirectionsHost", "rtRasterTexelsHost", "rtAtlasGrid"]
+                "rtGatherDirectionsHost", "rtRasterTexelsHost", "rtAtlasGrid", "rtFilterTexelsHost"]
 
 _renderer = None
 _host = None
@@ -223,6 +224,8 @@ def load_host():
         h.rtRasterTexelsHost.restype = C.c_int
         h.rtAtlasGrid.argtypes = [C.c_void_p, C.c_int, C.c_float]
         h.rtAtlasGrid.restype = C.c_int
+        h.rtFilterTexelsHost.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
+        h.rtFilterTexelsHost.restype = C.c_int
         _host = h
     return _host
 
@@ -356,6 +359,10 @@ def load_renderer():
         r.rasterTexels.restype = C.c_int
         r.bakeTexels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, C.c_float, fp, fp, up, ip, ip]
         r.bakeTexels.restype = C.c_int
+        r.filterTexels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
+        r.filterTexels.restype = C.c_int
+        r.rtLastFilterMs.argtypes = []
+        r.rtLastFilterMs.restype = C.c_double
         r.rtLastTexelsMs.argtypes = []
         r.rtLastTexelsMs.restype = C.c_double
         r.rtLastBakeMs.argtypes = []
@@ -988,6 +995,63 @@ def last_texels_ms():
 def last_bake_ms():
     """HIP-event time of generator + trace + reduce + scatter of the last bake_texels (not the copies), summed over its chunks, in milliseconds."""
     return load_renderer().rtLastBakeMs()
+
+
+# filterTexels (include/rt_api.h, "filtering texels"): the edge-aware, chart-aware denoise of baked texel planes; the defaults are the header's RT_FILTER_*
+RT_FILTER_ITERATIONS, RT_FILTER_SQUARINGS, RT_FILTER_SIGMA_D, RT_FILTER_SIGMA_Z, RT_FILTER_SIGMA_C = 3, 5, 2.0, 2.0, 0.5
+
+
+def _filter_planes(fn, W, H, dilate, mode, plane, out, needs_plane):
+    """(in, out) of a filter call: `plane` as a C-contiguous float32 (H, W, Wd) array (None stays None where the call allows it), `out` the caller's array
+    or a new one; a size, mode or shape out of range is a ValueError."""
+    if mode not in _GATHER_WIDTH:
+        raise ValueError(f"{fn}: unknown mode {mode!r}")
+    if not (1 <= W <= RT_TEXEL_MAX_SIZE and 1 <= H <= RT_TEXEL_MAX_SIZE and 0 <= dilate <= RT_TEXEL_MAX_DILATE):
+        raise ValueError(f"{fn}: needs 1 <= W, H <= RT_TEXEL_MAX_SIZE and 0 <= dilate <= RT_TEXEL_MAX_DILATE")
+    shape = (H, W, _GATHER_WIDTH[mode])
+    if plane is None:
+        if needs_plane:
+            raise ValueError(f"{fn}: needs a plane")
+    else:
+        plane = np.ascontiguousarray(plane, dtype=np.float32)
+        if plane.shape != shape:
+            raise ValueError(f"{fn}: the plane must have shape {shape}, got {plane.shape}")
+    if out is None:
+        out = np.zeros(shape, np.float32)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
+        raise ValueError(f"{fn}: out must be a writable C-contiguous float32 array of shape {shape}")
+    return plane, out
+
+
+def filter_texels(W, H, mode, plane=None, dilate=0, iterations=RT_FILTER_ITERATIONS, normal_squarings=RT_FILTER_SQUARINGS, sigma_d=RT_FILTER_SIGMA_D,
+                  sigma_z=RT_FILTER_SIGMA_Z, sigma_c=RT_FILTER_SIGMA_C, out=None):
+    """Filters a texel plane of the live atlas at W x H on the device (filterTexels, include/rt_api.h): `plane` is an (H, W, Wd) float32 array, Wd =
+    gather_width(mode) - bake_texels' planes["out"] -, or None: the out plane of the last bake_texels, where it lies on the device.  `out`: None (a new
+    array) or the array to write, which may be `plane` itself.  Returns (owned, out).  Blocking."""
+    plane, out = _filter_planes("filter_texels", W, H, dilate, mode, plane, out, False)
+    fp = C.POINTER(C.c_float)
+    owned = load_renderer().filterTexels(W, H, dilate, mode, _plane_ptr(plane, fp), out.ctypes.data_as(fp), iterations, normal_squarings, sigma_d, sigma_z,
+                                         sigma_c)
+    return owned, out
+
+
+def filter_texels_host(tris, W, H, mode, plane, dilate=0, iterations=RT_FILTER_ITERATIONS, normal_squarings=RT_FILTER_SQUARINGS, sigma_d=RT_FILTER_SIGMA_D,
+                       sigma_z=RT_FILTER_SIGMA_Z, sigma_c=RT_FILTER_SIGMA_C, out=None):
+    """filter_texels on the CPU (librt_host.so, rtFilterTexelsHost; no GPU, no renderer state) over `tris`, a 1-D array of triangle_dtype in slot order: the
+    same bits.  Returns (owned, out); what the device call would refuse is a ValueError."""
+    tris = _records("filter_texels_host", "triangle", tris, triangle_dtype)
+    plane, out = _filter_planes("filter_texels_host", W, H, dilate, mode, plane, out, True)
+    fp = C.POINTER(C.c_float)
+    owned = load_host().rtFilterTexelsHost(tris.ctypes.data if len(tris) else None, len(tris), W, H, dilate, mode, plane.ctypes.data_as(fp),
+                                           out.ctypes.data_as(fp), iterations, normal_squarings, sigma_d, sigma_z, sigma_c)
+    if owned < 0:
+        raise ValueError("filter_texels_host: iterations, normal_squarings or a sigma is out of range")
+    return owned, out
+
+
+def last_filter_ms():
+    """HIP-event time of the raster, prologue, iteration and scatter kernels of the last filter_texels (not the copies), in milliseconds."""
+    return load_renderer().rtLastFilterMs()
 
 
 def pinhole_camera(o, target):

@@ -40,6 +40,7 @@
 #include "rt_refine.h"
 #include "rt_gather.h"
 #include "rt_texels.h"
+#include "rt_texel_filter_launch.h"
 
 namespace {
 
@@ -182,6 +183,7 @@ struct RenderContext {
     double gather_ms = 0.0;             // rtLastGatherMs
     double texels_ms = 0.0;             // rtLastTexelsMs
     double bake_ms = 0.0;               // rtLastBakeMs
+    double filter_ms = 0.0;             // rtLastFilterMs
     double motion_ms = 0.0;             // rtLastMotionMs
 };
 
@@ -313,12 +315,14 @@ struct GatherState : QueryState {
 // buffers: gatherRadiance's stay gatherRadiance's.
 enum { kTexOwner = 0, kTexPrim, kTexSrc0, kTexSrc1, kTexBary, kTexPos, kTexNrm, kTexCounts, kTexRank, kTexList, kTexListPos, kTexListNrm,
        kTexAccPlane, kTexOutPlane, kTexRaysPlane, kTexAcc, kTexOut, kTexNrays,
-       kTexOrg, kTexDir, kTexIds, kTexTMax, kTexL, kTexRays, kTexOccluded, kTexBuffers };
+       kTexOrg, kTexDir, kTexIds, kTexTMax, kTexL, kTexRays, kTexOccluded,
+       kFltRec, kFltCol0, kFltCol1, kFltIn, kFltOut, kTexBuffers };
 struct TexelState : QueryState {
     char* d_buf[kTexBuffers] = {};
     size_t cap[kTexBuffers] = {};       // bytes d_buf[k] holds
     uint32_t* d_length = nullptr;       // RtTexelParams::length
     uint32_t* d_queue = nullptr;        // RtRadianceBatch::queue
+    int out_W = 0, out_H = 0, out_mode = -1;    // what d_buf[kTexOutPlane] holds: the out plane of the last bakeTexels, if that asked for out (out_W > 0)
 };
 
 DenoiseState g_denoise;
@@ -331,6 +335,9 @@ ChunkState g_rays, g_pixels, g_radiance;
 RefineState g_refine;
 GatherState g_gather;
 TexelState g_texels;
+// filterTexels (rt_texel_filter_launch.h): a raster of its own (the raster's entries of a second TexelState), the two records per texel, the ping-pong pair of
+// the values and the caller's planes (kFlt*).  Its own buffers and events: rasterTexels' and bakeTexels' stay theirs.
+TexelState g_filter;
 
 // The adaptive frame back to "the next refineFrame starts at sample 0" (rtResetRefine, setCamera, setRenderOptions, the scene edits); the buffers stay.
 void reset_refine() {
@@ -456,6 +463,7 @@ void setup_devices() {
     free_pass(g_refine);
     free_pass(g_gather);
     free_pass(g_texels);
+    free_pass(g_filter);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -510,7 +518,7 @@ void setup_devices() {
         c.devs.push_back(d);
     }
     HIP_CHECK(hipSetDevice(c.devs[0].device));              // the query calls' own event pairs, on the device they run on
-    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine, &g_gather, &g_texels }) {
+    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine, &g_gather, &g_texels, &g_filter }) {
         q->device = c.devs[0].device;
         HIP_CHECK(hipEventCreate(&q->ev_start));
         HIP_CHECK(hipEventCreate(&q->ev_stop));
@@ -570,6 +578,7 @@ void cleanup_impl() {
     free_pass(g_refine);
     free_pass(g_gather);
     free_pass(g_texels);
+    free_pass(g_filter);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -1891,9 +1900,10 @@ double rtLastGatherMs(void) {
 // chunk by chunk over the compact list as gatherRadiance goes over the caller's: k_texel_dirs fills the batch arrays, the radiance kernels (launch_radiance) or
 // the any-hit kernels (launch_rays) run over them, k_gather_reduce folds them per list entry; the scatter writes the texel planes, which come down.  Nothing
 // of a frame's, a pass's, gatherRadiance's or the other queries' state is read or written.
-static char* texel_buffer(int k, size_t bytes) {
-    return grown_buffer(g_texels, k, std::max<size_t>(bytes, 4));
+static char* texel_buffer(TexelState& q, int k, size_t bytes) {
+    return grown_buffer(q, k, std::max<size_t>(bytes, 4));
 }
+static char* texel_buffer(int k, size_t bytes) { return texel_buffer(g_texels, k, bytes); }
 
 static void check_texels(const char* fn, int W, int H, int dilate) {
     const RenderContext& c = g_ctx;
@@ -1904,24 +1914,25 @@ static void check_texels(const char* fn, int W, int H, int dilate) {
 }
 
 // The raster's kernels on the query's device (begin_query has run): the planes `want_*` name, src after `dilate` iterations in src[dilate & 1], and with
-// `with_list` rank, list, list_pos and list_nrm.  *length = the owned texels.  Returns the block; sets rtLastTexelsMs.
-static RtTexelParams texel_raster(int W, int H, int dilate, bool want_prim, bool want_bary, bool want_pos, bool want_nrm, bool with_list, uint32_t* length) {
+// `with_list` rank, list, list_pos and list_nrm, in the buffers and between the events of `q`.  *length = the owned texels, *ms_out the HIP-event time of the
+// kernels.  Returns the block.
+static RtTexelParams texel_raster(TexelState& q, double* ms_out, int W, int H, int dilate, bool want_prim, bool want_bary, bool want_pos, bool want_nrm,
+                                  bool with_list, uint32_t* length) {
     RenderContext& c = g_ctx;
-    TexelState& q = g_texels;
     const DeviceState& d = c.devs[0];
     const size_t n = (size_t)W * H;
     RtTexelParams p = {};
     p.slots = d.d_tris; p.num_slots = (uint32_t)c.mesh.tris.size();
     p.W = W; p.H = H;
-    p.owner = reinterpret_cast<int32_t*>(texel_buffer(kTexOwner, n * 4));
-    p.src[0] = reinterpret_cast<int32_t*>(texel_buffer(kTexSrc0, n * 4));
-    if (dilate > 0) p.src[1] = reinterpret_cast<int32_t*>(texel_buffer(kTexSrc1, n * 4));
-    if (want_prim) p.prim = reinterpret_cast<int32_t*>(texel_buffer(kTexPrim, n * 4));
-    if (want_bary) p.bary = reinterpret_cast<float*>(texel_buffer(kTexBary, n * 8));
-    if (want_pos) p.pos = reinterpret_cast<float*>(texel_buffer(kTexPos, n * 12));
-    if (want_nrm) p.nrm = reinterpret_cast<float*>(texel_buffer(kTexNrm, n * 12));
+    p.owner = reinterpret_cast<int32_t*>(texel_buffer(q, kTexOwner, n * 4));
+    p.src[0] = reinterpret_cast<int32_t*>(texel_buffer(q, kTexSrc0, n * 4));
+    if (dilate > 0) p.src[1] = reinterpret_cast<int32_t*>(texel_buffer(q, kTexSrc1, n * 4));
+    if (want_prim) p.prim = reinterpret_cast<int32_t*>(texel_buffer(q, kTexPrim, n * 4));
+    if (want_bary) p.bary = reinterpret_cast<float*>(texel_buffer(q, kTexBary, n * 8));
+    if (want_pos) p.pos = reinterpret_cast<float*>(texel_buffer(q, kTexPos, n * 12));
+    if (want_nrm) p.nrm = reinterpret_cast<float*>(texel_buffer(q, kTexNrm, n * 12));
     p.blocks = (uint32_t)((n + kTexelBlock - 1) / kTexelBlock);
-    p.counts = reinterpret_cast<uint32_t*>(texel_buffer(kTexCounts, (size_t)p.blocks * 4));
+    p.counts = reinterpret_cast<uint32_t*>(texel_buffer(q, kTexCounts, (size_t)p.blocks * 4));
     if (!q.d_length) q.d_length = dev_alloc<uint32_t>(q.owned, 1);
     p.length = q.d_length;
     HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
@@ -1934,17 +1945,17 @@ static RtTexelParams texel_raster(int W, int H, int dilate, bool want_prim, bool
     HIP_CHECK(hipStreamSynchronize(d.stream));
     double ms = query_ms(q);
     if (with_list) {
-        p.rank = reinterpret_cast<int32_t*>(texel_buffer(kTexRank, n * 4));
-        p.list = reinterpret_cast<uint32_t*>(texel_buffer(kTexList, (size_t)*length * 4));
-        p.list_pos = reinterpret_cast<float*>(texel_buffer(kTexListPos, (size_t)*length * 12));
-        p.list_nrm = reinterpret_cast<float*>(texel_buffer(kTexListNrm, (size_t)*length * 12));
+        p.rank = reinterpret_cast<int32_t*>(texel_buffer(q, kTexRank, n * 4));
+        p.list = reinterpret_cast<uint32_t*>(texel_buffer(q, kTexList, (size_t)*length * 4));
+        p.list_pos = reinterpret_cast<float*>(texel_buffer(q, kTexListPos, (size_t)*length * 12));
+        p.list_nrm = reinterpret_cast<float*>(texel_buffer(q, kTexListNrm, (size_t)*length * 12));
         HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
         HIP_CHECK(rt_launch_texel_compact(p, d.stream));
         HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
         HIP_CHECK(hipStreamSynchronize(d.stream));
         ms += query_ms(q);
     }
-    c.texels_ms = ms;
+    *ms_out = ms;
     return p;
 }
 
@@ -1956,7 +1967,7 @@ int rasterTexels(int W, int H, int dilate, int32_t* prim, int32_t* src, float* b
     const size_t n = (size_t)W * H;
     const int current = begin_query(q);
     uint32_t length = 0;
-    const RtTexelParams p = texel_raster(W, H, dilate, prim != nullptr, bary != nullptr, pos != nullptr, nrm != nullptr, false, &length);
+    const RtTexelParams p = texel_raster(q, &g_ctx.texels_ms, W, H, dilate, prim != nullptr, bary != nullptr, pos != nullptr, nrm != nullptr, false, &length);
     if (prim) HIP_CHECK(hipMemcpyAsync(prim, p.prim, n * 4, hipMemcpyDeviceToHost, d.stream));
     if (src) HIP_CHECK(hipMemcpyAsync(src, p.src[dilate & 1], n * 4, hipMemcpyDeviceToHost, d.stream));
     if (bary) HIP_CHECK(hipMemcpyAsync(bary, p.bary, n * 8, hipMemcpyDeviceToHost, d.stream));
@@ -1988,7 +1999,7 @@ int bakeTexels(int W, int H, int dilate, int mode, int first, int dirs, int dirs
     const int current = begin_query(q);
     if (!q.d_queue) q.d_queue = dev_alloc<uint32_t>(q.owned, 1);
     uint32_t length = 0;
-    const RtTexelParams p = texel_raster(W, H, dilate, prim != nullptr, false, false, false, true, &length);
+    const RtTexelParams p = texel_raster(q, &c.texels_ms, W, H, dilate, prim != nullptr, false, false, false, true, &length);
     RtTexelBakeParams b = {};
     b.src = p.src[dilate & 1]; b.rank = p.rank; b.list = p.list;
     b.length = length; b.texels = (uint32_t)n; b.Wd = (int32_t)Wd;
@@ -2063,6 +2074,7 @@ int bakeTexels(int W, int H, int dilate, int mode, int first, int dirs, int dirs
     ms_sum += query_ms(q);
     end_query(current);
     c.bake_ms = ms_sum;
+    q.out_W = out ? W : 0; q.out_H = out ? H : 0; q.out_mode = out ? mode : -1;    // (what filterTexels with in == NULL reads where it lies)
     return (int)length;
 }
 
@@ -2074,6 +2086,64 @@ double rtLastTexelsMs(void) {
 double rtLastBakeMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastBakeMs before init");
     return g_ctx.bake_ms;
+}
+
+// Filtering texels (rt_api.h).  A raster of its own over the first device's live slots (texel_raster into g_filter: g_texels, its planes and
+// rtLastTexelsMs stay what they were), then the prologue, one launch per iteration and the scatter through the dilated source plane.  The values go up from
+// the caller's plane - or, with in == NULL, are read where the last bakeTexels left its out plane - and the filtered plane comes down.
+int filterTexels(int W, int H, int dilate, int mode, const float* in, float* out, int iterations, int normal_squarings, float sigma_d, float sigma_z,
+                 float sigma_c) {
+    RenderContext& c = g_ctx;
+    check_texels("filterTexels", W, H, dilate);
+    if (mode != RT_GATHER_IRRADIANCE && mode != RT_GATHER_SH9 && mode != RT_GATHER_VISIBILITY) rt_fail("filterTexels: unknown mode");
+    if (!out) rt_fail("filterTexels: out is null");
+    if (iterations < 1 || iterations > RT_DENOISE_MAX_ITERATIONS) rt_fail("filterTexels: iterations must be 1 .. RT_DENOISE_MAX_ITERATIONS");
+    if (normal_squarings < 0 || normal_squarings > RT_DENOISE_MAX_SQUARINGS) rt_fail("filterTexels: normal_squarings must be 0 .. RT_DENOISE_MAX_SQUARINGS");
+    if (!std::isfinite(sigma_d) || sigma_d <= 0.0f) rt_fail("filterTexels: sigma_d must be finite and > 0");
+    if (!std::isfinite(sigma_z) || sigma_z <= 0.0f) rt_fail("filterTexels: sigma_z must be finite and > 0");
+    if (!std::isfinite(sigma_c)) rt_fail("filterTexels: sigma_c must be finite");
+    const size_t n = (size_t)W * H, Wd = (size_t)gather_width(mode);
+    if (!in && (g_texels.out_W < 1 || g_texels.out_W != W || g_texels.out_H != H || gather_width(g_texels.out_mode) != (int)Wd))
+        rt_fail("filterTexels: in is null and the last bakeTexels left no out plane of this W, H and width");
+    TexelState& q = g_filter;
+    const DeviceState& d = c.devs[0];
+    const int current = begin_query(q);
+    uint32_t length = 0;
+    double ms = 0.0;
+    const RtTexelParams p = texel_raster(q, &ms, W, H, dilate, false, false, false, false, false, &length);
+    RtTexelFilterParams f = {};
+    f.slots = p.slots; f.owner = p.owner; f.src = p.src[dilate & 1];
+    f.W = W; f.H = H; f.C = (int32_t)Wd;
+    f.normal_squarings = normal_squarings;
+    f.sigma_d = sigma_d; f.sigma_z = sigma_z; f.sigma_c = sigma_c;
+    const size_t values = Wd == 1 ? n * 4 : n * (Wd / 3) * sizeof(float4);
+    f.rec = reinterpret_cast<float4*>(texel_buffer(q, kFltRec, 2 * n * sizeof(float4)));
+    f.col[0] = texel_buffer(q, kFltCol0, values);
+    f.col[1] = texel_buffer(q, kFltCol1, values);
+    f.out = reinterpret_cast<float*>(texel_buffer(q, kFltOut, n * Wd * 4));
+    if (in) {
+        float* d_in = reinterpret_cast<float*>(texel_buffer(q, kFltIn, n * Wd * 4));
+        HIP_CHECK(hipMemcpyAsync(d_in, in, n * Wd * 4, hipMemcpyHostToDevice, d.stream));
+        f.in = d_in;
+    } else {
+        f.in = reinterpret_cast<const float*>(g_texels.d_buf[kTexOutPlane]);
+    }
+    HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+    HIP_CHECK(rt_launch_texel_filter_prologue(f, d.stream));
+    for (int it = 0; it < iterations; it++) HIP_CHECK(rt_launch_texel_filter_iteration(f, it, d.stream));
+    HIP_CHECK(rt_launch_texel_filter_scatter(f, iterations, d.stream));
+    HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+    HIP_CHECK(hipMemcpyAsync(out, f.out, n * Wd * 4, hipMemcpyDeviceToHost, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));                  // blocking: the caller's plane is complete on return
+    ms += query_ms(q);
+    end_query(current);
+    c.filter_ms = ms;
+    return (int)length;
+}
+
+double rtLastFilterMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastFilterMs before init");
+    return g_ctx.filter_ms;
 }
 
 // Adaptive sampling on the device (rt_api.h).  One call is one pass over the whole image on the first in-process device: select (rt_refine.h)

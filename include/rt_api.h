@@ -585,6 +585,73 @@ int    bakeTexels(int W, int H, int dilate, int mode, int first, int dirs, int d
 double rtLastTexelsMs(void);   /* raster + resolve + dilate + compact kernels of the last rasterTexels / bakeTexels */
 double rtLastBakeMs(void);     /* generator + trace + reduce + scatter of the last bakeTexels, summed over chunks */
 
+/* --- filtering texels: an edge-aware, chart-aware denoise of baked texel planes, on the device ----------------------------------------------------
+ * filterTexels is the last stage of a bake: an a-trous filter (denoiseFrame's skeleton: 25 taps, stride 2^it, compact max(1 - x, 0)^2 weights) over the texel
+ * planes bakeTexels writes, steered by what the raster knows of every texel - position, geometric normal and the world length of a texel step - instead of a
+ * camera's guide planes.  Neighbours on the atlas grid are not neighbours on a surface: charts metres apart lie side by side, so a tap is accepted only within
+ * reach (below).  Mesh scenes only.  All arithmetic is fp32, in both fp modes: every operation is rounded on its own (no FMA), operands are in the order
+ * written, / and sqrt are correctly rounded, a comparison with a NaN is false, max(x, 0) = x > 0 ? x : 0, dot is evaluated left to right.
+ * Planes      C = rtGatherWidth(mode) floats per texel (1, 3 or 27), t = y*W + x, row 0 first: exactly bakeTexels' out planes.  A caller with an RGB plane of
+ *             their own passes RT_GATHER_IRRADIANCE.
+ * Raster      rasterTexels' definition word for word, over the live slots, recomputed by the call: owned(t), the owner slot, P(t) = pos(t), n(t) = nrm(t) (the
+ *             geometric normal by winding, not turned) and src(t) after `dilate` iterations.
+ * Footprint   of an owned texel p, whose owner has UV vertices a, b, c, world vertices v0, v1, v2 and the raster's d;  e1 = v1 - v0, e2 = v2 - v0:
+ *                 ux = (c.y-a.y)/d;  vx = (a.y-b.y)/d;  uy = (a.x-c.x)/d;  vy = (b.x-a.x)/d
+ *                 Gx[k] = (ux*e1[k] + vx*e2[k]) / (float)W        Gy[k] = (uy*e1[k] + vy*e2[k]) / (float)H
+ *                 f2 = 0.5f * (dot(Gx,Gx) + dot(Gy,Gy))           (the squared world length of one texel step)
+ *                 r2(p) = (sigma_d*sigma_d) * f2                   rz(p) = 1 / (sigma_z * sqrt(f2))
+ * Iteration   it = 0 .. iterations-1:  s = 1 << it;  K = {0.375, 0.25, 0.0625};  with sigma_c > 0: sc = sigma_c * 2^-it, rc = 1/(sc*sc);  c_0 = in.
+ *             For every owned p = (x, y):
+ *                 sum[0..C-1] = 0; wsum = 0
+ *                 for dy = -2..2 (outer), dx = -2..2 (inner):
+ *                     q = (x + dx*s, y + dy*s);  h = K[|dx|] * K[|dy|]
+ *                     dx == 0 && dy == 0:  w = h
+ *                     else the tap ADDS NOTHING (dropped, not weighted by zero) unless all hold:
+ *                             q inside the atlas;  owned(q);
+ *                             e = P(q) - P(p);  d2 = dot(e,e);  d2 <= r2(p) * (float)((dx*dx + dy*dy) * s * s)     (the reach test)
+ *                         dn = dot(n(p), n(q));  wn = max(dn, 0);  normal_squarings times: wn = wn*wn
+ *                         pd = abs(dot(n(p), e));  wz = max(1 - pd * rz(p), 0);  wz = wz*wz
+ *                         w = h * wn * wz                                                      (left to right)
+ *                         if sigma_c > 0:  L = min(C, 3);  dc[j] = c(p)[j] - c(q)[j], j < L;  dd = sum of dc[j]*dc[j] left to right;
+ *                                          wc = max(1 - dd * rc, 0);  wc = wc*wc;  w = w * wc
+ *                     sum[j] += w * c(q)[j] for every j < C;  wsum += w
+ *                 c'(p)[j] = sum[j] / wsum                                                     (wsum >= 9/64: the centre tap)
+ *             The colour weight looks at the leading min(C, 3) floats - the RGB of IRRADIANCE, the DC coefficient's RGB of SH9, the scalar of VISIBILITY -
+ *             and every channel is filtered with that one weight.  The reach test is what makes the filter chart-aware: a tap k texels away is accepted
+ *             only within sigma_d times the world distance k texels span at p, so two charts packed side by side fail it even where they are coplanar with
+ *             equal normals.  A degenerate footprint (f2 of 0, inf or NaN: a triangle without world or UV extent, or an overflow) is handled by the rules
+ *             above without a special case: f2 = NaN fails every reach test, f2 = 0 passes only taps at P(p) itself and gives them the plane weight 0
+ *             (1 - 0 * inf is a NaN), f2 = inf passes every tap whose d2 is no NaN, with the plane weight 1 where pd is finite.  The centre tap always counts.
+ * Output      out(t)[j] = c_final(src(t))[j], and zeros where src(t) == -1: bakeTexels' rule for out, so the chart borders are re-dilated from the filtered
+ *             values.  `in` is read at owned texels only: whatever it holds elsewhere (the old dilation, NaNs) has no influence.  Non-finite values at
+ *             owned texels are not treated specially: a NaN or an inf spreads to every texel that accepts it as a tap with a weight that is not 0 (inf * 0
+ *             is a NaN too: with a weight of exactly 0), by up to 2 * (2^iterations - 1) texels per axis, as in denoiseFrame.  Returns the owned texels.
+ * in          any host memory of W*H*C floats, or NULL: the out plane of the last bakeTexels call, where it lies on the device - nothing is uploaded (the
+ *             pattern of RT_DISPLAY_FROM_PREVIEW).  That call must have asked for out, with this W, H and a mode of this width; a bakeTexels without out
+ *             leaves nothing to take, and so does everything that frees the texel buffers (cleanupRenderer, setRenderOptions with another device list).
+ *             A NULL in is taken as it is, even if the scene was edited after the bake: the raster is the live one.  out is caller-owned, never NULL, and
+ *             may be in.
+ * The call is blocking and runs on the first in-process device.  It follows the scene edits and rebuildBvh.  It changes nothing another call observes:
+ * rtLastTexelsMs, rtLastBakeMs, rtLastGatherMs, the buffers of rasterTexels / bakeTexels / gatherRadiance and everything those calls leave alone stay as they
+ * were: buffers, events and the raster are its own, freed where the query buffers are.  Per texel of the largest atlas seen: owner 4, src 4 (8 with dilate >
+ * 0), the work word of a workgroup of 256 texels, two 16-byte records, the ping-pong pair of the values - 2 x 4 bytes for C = 1, 2 x 16 per three channels
+ * otherwise (the fourth float of a record is unused) -, out 4C and, unless in is NULL, in 4C.
+ * Defaults (DESIGN.md 3.32 has the measurement that chose them): iterations 3, normal_squarings 5, sigma_d 2.0f, sigma_z 2.0f, sigma_c 0.5f - sigma_c is in
+ * the units of the values and the caller's to follow, roughly 2 / sqrt(dirs * ns) (0.5 is that of 16 directions, one sample); <= 0 switches the colour
+ * weight off.
+ * rtFilterTexelsHost (rt_host.h) is the CPU twin.
+ * Misuse (rt error, exit 99), checked on the host before any device work: before init (rtLastFilterMs as well), a sphere scene, what rasterTexels refuses for
+ * W, H and dilate, an unknown mode, out NULL, iterations outside 1 .. RT_DENOISE_MAX_ITERATIONS, normal_squarings outside 0 .. RT_DENOISE_MAX_SQUARINGS,
+ * sigma_d or sigma_z not finite or <= 0, sigma_c not finite, in NULL without a recorded bake plane or with one of another W, H or width. */
+#define RT_FILTER_ITERATIONS 3
+#define RT_FILTER_SQUARINGS  5
+#define RT_FILTER_SIGMA_D    2.0f
+#define RT_FILTER_SIGMA_Z    2.0f
+#define RT_FILTER_SIGMA_C    0.5f
+int    filterTexels(int W, int H, int dilate, int mode, const float* in, float* out,
+                    int iterations, int normal_squarings, float sigma_d, float sigma_z, float sigma_c);
+double rtLastFilterMs(void);   /* raster + prologue + iterations + scatter kernels of the last filterTexels (not the copies); 0 before the first */
+
 /* --- adaptive sampling: the samples go where the image is still noisy ---------------------------------------------------------------
  * refineFrame renders an adaptive frame: every pixel gets samples in batches until an estimate of its own error says it has enough.  The frame's state, the
  * selection, the list of a pass and the statistics live on the device; the pixel kernels of renderPixels trace the samples.  One call is one pass: select,

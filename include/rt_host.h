@@ -128,6 +128,13 @@ void rtGatherDirectionsHost(int n, const float* pos, const float* nrm, int mode,
  * arguments rasterTexels would refuse (nothing is written then).  No renderer state is read. */
 int rtRasterTexelsHost(const rt_triangle* tris, uint32_t numTris, int W, int H, int dilate, int32_t* prim, int32_t* src, float* bary, float* pos, float* nrm);
 
+/* filterTexels (rt_api.h, "filtering texels": the definition is stated there, once) on the CPU, in plain C++, on top of rtRasterTexelsHost over the caller's
+ * leaf-ordered triangle array: what filterTexels downloads from the device, bit for bit - out, W*H*rtGatherWidth(mode) floats, row 0 first; it may be `in`.
+ * Returns the number of owned texels, or -1 for arguments filterTexels would refuse and for in NULL - the twin has no bake to take a plane from - (nothing is
+ * written then).  No renderer state is read. */
+int rtFilterTexelsHost(const rt_triangle* tris, uint32_t numTris, int W, int H, int dilate, int mode, const float* in, float* out, int iterations,
+                       int normal_squarings, float sigma_d, float sigma_z, float sigma_c);
+
 /* A trivial non-overlapping atlas: overwrites texCoords of tris[0 .. n-1]; nothing else is touched (sentinel slots get coordinates too; the raster skips them).
  * fp32, every operation rounded on its own, operands in the order written:
  *   pairs = (n + 1) / 2;  cells = the smallest integer with cells * cells >= pairs;  cs = 1.0f / (float)cells;  m = margin * cs;  m3 = 3.0f * m
