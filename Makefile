@@ -87,7 +87,13 @@ $(OBJ)/texels.o: $(CSRC)/rt_kernels_texels.hip $(CSRC)/rt_texels.h $(CSRC)/rt_te
 # on it.
 $(OBJ)/texel_filter.o: $(CSRC)/rt_kernels_texel_filter.hip $(CSRC)/rt_texel_filter.h $(CSRC)/rt_texel_filter_launch.h $(CSRC)/rt_texel_raster.h include/rt_types.h include/rt_api.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
-$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_motion.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h $(CSRC)/rt_gather.h $(CSRC)/rt_texels.h $(CSRC)/rt_texel_filter_launch.h include/rt_api.h include/rt_types.h | $(OBJ)
+# The kernels of sampleTexels / renderLightmap (the lookup of texel planes at hits; the generator of a chunk of centre rays and the shade kernel around the
+# unchanged closest-hit ray kernel): defined bit for bit as the passes above, so one object with the flags of texels.o - and RT_MODE_PARITY, which selects in
+# rt_device.h the forms of the centre ray, the albedo and the sky that the guide and ray kernels compile (they exist in the PARITY objects only).  The lookup's
+# arithmetic is rt_texel_sample.h, which librt_host.so compiles too (rtSampleTexelsHost).  Its own TU and headers: no other kernel object depends on it.
+$(OBJ)/lightmap.o: $(CSRC)/rt_kernels_lightmap.hip $(CSRC)/rt_lightmap.h $(CSRC)/rt_texel_sample.h $(KERNEL_HDRS) | $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -DRT_MODE_PARITY -ffp-contract=off -fno-slp-vectorize -fno-vectorize -c $< -o $@
+$(OBJ)/renderer.o: $(CSRC)/rt_renderer.hip $(CSRC)/rt_params.h $(CSRC)/rt_scene_layout.h $(CSRC)/rt_denoise.h $(CSRC)/rt_accumulate.h $(CSRC)/rt_preview.h $(CSRC)/rt_motion.h $(CSRC)/rt_display.h $(CSRC)/rt_update.h $(CSRC)/rt_build.h $(CSRC)/rt_refine.h $(CSRC)/rt_gather.h $(CSRC)/rt_texels.h $(CSRC)/rt_texel_filter_launch.h $(CSRC)/rt_lightmap.h include/rt_api.h include/rt_types.h | $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 RT_OBJS := $(OBJ)/renderer.o $(OBJ)/probe_parity.o $(OBJ)/probe_fast.o $(OBJ)/spheres_parity.o $(OBJ)/spheres_fast.o $(OBJ)/mesh_parity.o $(OBJ)/mesh_fast.o $(OBJ)/denoise.o $(OBJ)/accumulate.o
@@ -100,12 +106,13 @@ MOTION_OBJS := $(OBJ)/motion.o
 GATHER_OBJS := $(OBJ)/gather.o
 TEXELS_OBJS := $(OBJ)/texels.o
 FILTER_OBJS := $(OBJ)/texel_filter.o
+LIGHTMAP_OBJS := $(OBJ)/lightmap.o
 
-$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS) $(FILTER_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS) $(FILTER_OBJS) -o $@
+$(PKG)/librt_mi355x.so: $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS) $(FILTER_OBJS) $(LIGHTMAP_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(RT_OBJS) $(DISPLAY_OBJS) $(UPDATE_OBJS) $(BUILD_OBJS) $(REFINE_OBJS) $(MOTION_OBJS) $(GATHER_OBJS) $(TEXELS_OBJS) $(FILTER_OBJS) $(LIGHTMAP_OBJS) -o $@
 
-$(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp $(HOST)/rt_texel_filter_host.cpp $(CSRC)/rt_gather_dirs.h $(CSRC)/rt_texel_raster.h $(CSRC)/rt_texel_filter.h include/rt_host.h include/rt_types.h include/rt_api.h
-	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp $(HOST)/rt_texel_filter_host.cpp -o $@
+$(PKG)/librt_host.so: $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp $(HOST)/rt_texel_filter_host.cpp $(HOST)/rt_texel_sample_host.cpp $(CSRC)/rt_gather_dirs.h $(CSRC)/rt_texel_raster.h $(CSRC)/rt_texel_filter.h $(CSRC)/rt_texel_sample.h include/rt_host.h include/rt_types.h include/rt_api.h
+	$(CXX) -O2 -ffp-contract=off -std=c++14 -Wall -fPIC -shared $(HOST)/rt_scenes.cpp $(HOST)/rt_bvh.cpp $(HOST)/rt_harness.cpp $(HOST)/rt_display_host.cpp $(HOST)/rt_gather_host.cpp $(HOST)/rt_texels_host.cpp $(HOST)/rt_texel_filter_host.cpp $(HOST)/rt_texel_sample_host.cpp -o $@
 
 oracle: $(PKG)/librt_mi355x.so $(PKG)/librt_host.so
 	$(MAKE) -C oracle

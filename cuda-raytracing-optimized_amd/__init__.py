@@ -142,6 +142,7 @@ RENDERER_SYMBOLS = ["initRenderer", "runRenderer", "cleanupRenderer", "initRende
                     "rtGatherWidth", "gatherRadiance", "rtGatherDirections", "rtLastGatherMs",
                     "rasterTexels", "bakeTexels", "rtLastTexelsMs", "rtLastBakeMs",
                     "filterTexels", "rtLastFilterMs",
+                    "sampleTexels", "renderLightmap", "rtLastSampleMs", "rtLastLightmapMs",
                     "refineFrame", "rtResetRefine", "rtRefineSamples", "rtRefineLastList", "rtLastRefineMs",
                     "updateTriangles", "updateMaterials", "updateSpheres", "getMeshBvh", "rtLastUpdateMs",
                     "rebuildBvh", "rtLastRebuildMs",
@@ -154,7 +155,7 @@ HOST_SYMBOLS = ["rtMakeCamera", "rtRandomFloat", "rtSceneThreeSpheres", "rtScene
                 "rtBuildBvh", "rtBuildBvhLevels", "rtLoadBvhFile", "rtSaveBvhFile", "rtFreeMesh", "rtMeshView",
                 "rtSceneStaircaseProcedural", "rtLinearToSRGB", "rtWritePPM", "rtSaveReference", "rtLoadReference", "rtRmse",
                 "rtDisplayFrameHost", "rtCentreRays", "rtPinholeCamera", "rtRefitBvhArrays", "rtRefitBvh", "rtRebuildBvhArrays", "rtRebuildBvh",
-                "rtGatherDirectionsHost", "rtRasterTexelsHost", "rtAtlasGrid", "rtFilterTexelsHost"]
+                "rtGatherDirectionsHost", "rtRasterTexelsHost", "rtAtlasGrid", "rtFilterTexelsHost", "rtSampleTexelsHost"]
 
 _renderer = None
 _host = None
@@ -226,6 +227,9 @@ def load_host():
         h.rtAtlasGrid.restype = C.c_int
         h.rtFilterTexelsHost.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
         h.rtFilterTexelsHost.restype = C.c_int
+        h.rtSampleTexelsHost.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_int32), fp, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp,
+                                         C.POINTER(C.c_uint8)]
+        h.rtSampleTexelsHost.restype = C.c_int
         _host = h
     return _host
 
@@ -363,6 +367,14 @@ def load_renderer():
         r.filterTexels.restype = C.c_int
         r.rtLastFilterMs.argtypes = []
         r.rtLastFilterMs.restype = C.c_double
+        r.sampleTexels.argtypes = [C.c_int, ip, fp, fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, C.POINTER(C.c_uint8)]
+        r.sampleTexels.restype = C.c_int
+        r.renderLightmap.argtypes = [C.c_int, C.c_int, C.c_int, fp, C.c_int, fp, C.POINTER(vec3)]
+        r.renderLightmap.restype = None
+        r.rtLastSampleMs.argtypes = []
+        r.rtLastSampleMs.restype = C.c_double
+        r.rtLastLightmapMs.argtypes = []
+        r.rtLastLightmapMs.restype = C.c_double
         r.rtLastTexelsMs.argtypes = []
         r.rtLastTexelsMs.restype = C.c_double
         r.rtLastBakeMs.argtypes = []
@@ -1052,6 +1064,98 @@ def filter_texels_host(tris, W, H, mode, plane, dilate=0, iterations=RT_FILTER_I
 def last_filter_ms():
     """HIP-event time of the raster, prologue, iteration and scatter kernels of the last filter_texels (not the copies), in milliseconds."""
     return load_renderer().rtLastFilterMs()
+
+
+# sampleTexels / renderLightmap (include/rt_api.h, "sampling texels"): texel planes looked up at hits, and the frame lit by them
+RT_SAMPLE_BILINEAR, RT_LIGHTMAP_ALBEDO, RT_TEXELS_FROM_BAKE, RT_TEXELS_FROM_FILTER = 1, 2, 4, 8
+
+
+def _sample_hits(fn, prim, uv, normal, mode):
+    """The hits as C-contiguous arrays: prim (n,) int32, uv (n, 2) float32, normal (n, 3) float32 or None (RT_GATHER_SH9 needs it); a wrong shape is a
+    ValueError."""
+    if mode not in _GATHER_WIDTH:
+        raise ValueError(f"{fn}: unknown mode {mode!r}")
+    prim = np.ascontiguousarray(prim, dtype=np.int32)
+    uv = np.ascontiguousarray(uv, dtype=np.float32)
+    n = len(prim)
+    if prim.ndim != 1 or uv.shape != (n, 2):
+        raise ValueError(f"{fn}: prim must have shape (n,) and uv (n, 2), got {prim.shape} and {uv.shape}")
+    if normal is not None:
+        normal = np.ascontiguousarray(normal, dtype=np.float32)
+        if normal.shape != (n, 3):
+            raise ValueError(f"{fn}: normal must have shape ({n}, 3), got {normal.shape}")
+    elif mode == RT_GATHER_SH9:
+        raise ValueError(f"{fn}: RT_GATHER_SH9 needs the normals")
+    return n, prim, uv, normal
+
+
+def _sample_planes(fn, W, H, mode, planes):
+    """`planes` as a C-contiguous float32 (H, W, Wd) array (None stays None); a size, mode or shape out of range is a ValueError."""
+    if mode not in _GATHER_WIDTH:
+        raise ValueError(f"{fn}: unknown mode {mode!r}")
+    if not (1 <= W <= RT_TEXEL_MAX_SIZE and 1 <= H <= RT_TEXEL_MAX_SIZE):
+        raise ValueError(f"{fn}: needs 1 <= W, H <= RT_TEXEL_MAX_SIZE")
+    if planes is not None:
+        planes = np.ascontiguousarray(planes, dtype=np.float32)
+        if planes.shape != (H, W, _GATHER_WIDTH[mode]):
+            raise ValueError(f"{fn}: the planes must have shape {(H, W, _GATHER_WIDTH[mode])}, got {planes.shape}")
+    return planes
+
+
+def sample_texels(prim, uv, normal, W, H, mode, planes=None, flags=0):
+    """Looks texel planes up at hits on the device (sampleTexels, include/rt_api.h): prim (n,) and uv (n, 2) as trace_rays returns them, normal (n, 3) or
+    None (RT_GATHER_SH9 needs it); `planes` an (H, W, Wd) float32 array, Wd = gather_width(mode), or None with RT_TEXELS_FROM_BAKE / RT_TEXELS_FROM_FILTER in
+    `flags`: the out plane of the last bake_texels / filter_texels, where it lies on the device.  RT_SAMPLE_BILINEAR: four taps instead of the nearest texel.
+    Returns (valid hits, out (n, 3) float32, valid (n,) uint8).  Blocking."""
+    n, prim, uv, normal = _sample_hits("sample_texels", prim, uv, normal, mode)
+    planes = _sample_planes("sample_texels", W, H, mode, planes)
+    out, valid = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+    ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    count = load_renderer().sampleTexels(n, prim.ctypes.data_as(ip), uv.ctypes.data_as(fp), _plane_ptr(normal, fp), W, H, mode, _plane_ptr(planes, fp), flags,
+                                         out.ctypes.data_as(fp), valid.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return count, out, valid
+
+
+def sample_texels_host(tris, prim, uv, normal, W, H, mode, planes, flags=0):
+    """sample_texels on the CPU (librt_host.so, rtSampleTexelsHost; no GPU, no renderer state) over `tris`, a 1-D array of triangle_dtype in slot order: the
+    same bits.  Returns (valid hits, out, valid); what the device call would refuse, and planes None, is a ValueError."""
+    tris = _records("sample_texels_host", "triangle", tris, triangle_dtype)
+    n, prim, uv, normal = _sample_hits("sample_texels_host", prim, uv, normal, mode)
+    planes = _sample_planes("sample_texels_host", W, H, mode, planes)
+    out, valid = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+    ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    count = load_host().rtSampleTexelsHost(tris.ctypes.data if len(tris) else None, len(tris), n, prim.ctypes.data_as(ip), uv.ctypes.data_as(fp),
+                                           _plane_ptr(normal, fp), W, H, mode, _plane_ptr(planes, fp), flags, out.ctypes.data_as(fp),
+                                           valid.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if count < 0:
+        raise ValueError("sample_texels_host: needs planes and no flag but RT_SAMPLE_BILINEAR")
+    return count, out, valid
+
+
+def render_lightmap(W, H, mode, planes=None, flags=0, floor_value=None, out=None):
+    """The frame of the centre rays lit by texel planes (renderLightmap, include/rt_api.h): `planes` and the FROM flags as sample_texels takes them;
+    RT_LIGHTMAP_ALBEDO multiplies a hit by the RT_GUIDE_ALBEDO value of its pixel; floor_value: what a floor hit is lit with, None = (1, 1, 1).  `out`: None
+    (a new array) or a writable C-contiguous (ny, nx, 3) float32 array.  Returns the frame, row 0 at the bottom.  Blocking."""
+    planes = _sample_planes("render_lightmap", W, H, mode, planes)
+    shape = (_state["ny"], _state["nx"], 3)
+    if out is None:
+        out = np.zeros(shape, np.float32)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == shape and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
+        raise ValueError(f"render_lightmap: out must be a writable C-contiguous float32 array of shape {shape}")
+    fp = C.POINTER(C.c_float)
+    fv = None if floor_value is None else (C.c_float * 3)(*[float(v) for v in floor_value])
+    load_renderer().renderLightmap(W, H, mode, _plane_ptr(planes, fp), flags, None if fv is None else C.cast(fv, fp), out.ctypes.data_as(C.POINTER(vec3)))
+    return out
+
+
+def last_sample_ms():
+    """HIP-event time of the lookup kernels of the last sample_texels (not the copies), summed over its chunks, in milliseconds."""
+    return load_renderer().rtLastSampleMs()
+
+
+def last_lightmap_ms():
+    """HIP-event time of ray generator + trace + shade of the last render_lightmap (not the copies), summed over its chunks, in milliseconds."""
+    return load_renderer().rtLastLightmapMs()
 
 
 def pinhole_camera(o, target):

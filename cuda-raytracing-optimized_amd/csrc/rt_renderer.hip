@@ -41,6 +41,7 @@
 #include "rt_gather.h"
 #include "rt_texels.h"
 #include "rt_texel_filter_launch.h"
+#include "rt_lightmap.h"
 
 namespace {
 
@@ -184,6 +185,8 @@ struct RenderContext {
     double texels_ms = 0.0;             // rtLastTexelsMs
     double bake_ms = 0.0;               // rtLastBakeMs
     double filter_ms = 0.0;             // rtLastFilterMs
+    double sample_ms = 0.0;             // rtLastSampleMs
+    double lightmap_ms = 0.0;           // rtLastLightmapMs
     double motion_ms = 0.0;             // rtLastMotionMs
 };
 
@@ -322,7 +325,18 @@ struct TexelState : QueryState {
     size_t cap[kTexBuffers] = {};       // bytes d_buf[k] holds
     uint32_t* d_length = nullptr;       // RtTexelParams::length
     uint32_t* d_queue = nullptr;        // RtRadianceBatch::queue
-    int out_W = 0, out_H = 0, out_mode = -1;    // what d_buf[kTexOutPlane] holds: the out plane of the last bakeTexels, if that asked for out (out_W > 0)
+    int out_W = 0, out_H = 0, out_mode = -1;    // what d_buf[kTexOutPlane] holds: the out plane of the last bakeTexels, if that asked for out (out_W > 0);
+                                        // in g_filter: what d_buf[kFltOut] holds, the out plane of the last filterTexels
+};
+
+// sampleTexels / renderLightmap (rt_lightmap.h): the arrays of one chunk of hits (prim, uv, normal up; out, valid down), or of one chunk of pixels (the ray
+// buffers, the ray kernel's four planes, the frame's chunk), the uploaded texel planes and the word the valid hits are counted in.  One state per call:
+// neither shares buffers or events with the other or with any other query.
+enum { kLmPrim = 0, kLmUv, kLmNormal, kLmOut, kLmValid, kLmOrg, kLmDir, kLmT, kLmPlanes, kLmBuffers };
+struct LightmapState : QueryState {
+    char* d_buf[kLmBuffers] = {};
+    size_t cap[kLmBuffers] = {};        // bytes d_buf[k] holds
+    uint32_t* d_count = nullptr;        // RtSampleParams::count
 };
 
 DenoiseState g_denoise;
@@ -338,6 +352,7 @@ TexelState g_texels;
 // filterTexels (rt_texel_filter_launch.h): a raster of its own (the raster's entries of a second TexelState), the two records per texel, the ping-pong pair of
 // the values and the caller's planes (kFlt*).  Its own buffers and events: rasterTexels' and bakeTexels' stay theirs.
 TexelState g_filter;
+LightmapState g_sample, g_lightmap;
 
 // The adaptive frame back to "the next refineFrame starts at sample 0" (rtResetRefine, setCamera, setRenderOptions, the scene edits); the buffers stay.
 void reset_refine() {
@@ -464,6 +479,8 @@ void setup_devices() {
     free_pass(g_gather);
     free_pass(g_texels);
     free_pass(g_filter);
+    free_pass(g_sample);
+    free_pass(g_lightmap);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     int count = 0;
@@ -518,7 +535,7 @@ void setup_devices() {
         c.devs.push_back(d);
     }
     HIP_CHECK(hipSetDevice(c.devs[0].device));              // the query calls' own event pairs, on the device they run on
-    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine, &g_gather, &g_texels, &g_filter }) {
+    for (QueryState* q : std::initializer_list<QueryState*>{ &g_rays, &g_pixels, &g_radiance, &g_refine, &g_gather, &g_texels, &g_filter, &g_sample, &g_lightmap }) {
         q->device = c.devs[0].device;
         HIP_CHECK(hipEventCreate(&q->ev_start));
         HIP_CHECK(hipEventCreate(&q->ev_stop));
@@ -579,6 +596,8 @@ void cleanup_impl() {
     free_pass(g_gather);
     free_pass(g_texels);
     free_pass(g_filter);
+    free_pass(g_sample);
+    free_pass(g_lightmap);
     for (DeviceState& d : c.devs) free_device(d);
     c.devs.clear();
     if (c.h_ext) { if (c.ext_registered) HIP_CHECK(hipHostUnregister(c.h_ext)); c.h_ext = nullptr; c.ext_registered = false; }
@@ -2138,12 +2157,176 @@ int filterTexels(int W, int H, int dilate, int mode, const float* in, float* out
     ms += query_ms(q);
     end_query(current);
     c.filter_ms = ms;
+    q.out_W = W; q.out_H = H; q.out_mode = mode;                // (what sampleTexels / renderLightmap with RT_TEXELS_FROM_FILTER read where it lies)
     return (int)length;
 }
 
 double rtLastFilterMs(void) {
     if (!g_ctx.initialised) rt_fail("rtLastFilterMs before init");
     return g_ctx.filter_ms;
+}
+
+// Sampling texels (rt_api.h).  sampleTexels: chunk by chunk, the caller's hits go up, k_sample_texels looks the planes up over the first
+// device's live slots, out and valid come down; the valid hits are counted in one device word, read back at the end.  renderLightmap: chunk by chunk over the
+// pixels of the whole image, k_lightmap_rays fills the ray buffers, the closest-hit ray kernel (launch_rays) runs over them, k_lightmap_shade turns its planes
+// into the frame's chunk, which comes down.  The planes go up once per call - or are read where the last bakeTexels / filterTexels left them.  Nothing of a
+// frame's, a pass's or another query's state is read or written.
+constexpr int kSampleFlags = RT_SAMPLE_BILINEAR | RT_TEXELS_FROM_BAKE | RT_TEXELS_FROM_FILTER;
+
+// The checks the two calls share, under the function's name `fn`: `known` = the flag bits the call takes.
+static void check_texel_source(const char* fn, int W, int H, int mode, const float* planes, int flags, int known) {
+    const RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail(" before init", fn);
+    if (c.is_spheres) rt_fail(": only a mesh scene has a UV atlas", fn);
+    if (W < 1 || H < 1 || W > RT_TEXEL_MAX_SIZE || H > RT_TEXEL_MAX_SIZE) rt_fail(": W and H must be 1 .. RT_TEXEL_MAX_SIZE", fn);
+    if (gather_width(mode) == 0) rt_fail(": unknown mode", fn);
+    if ((flags & ~known) != 0) rt_fail(": unknown flag bits", fn);
+    const bool bake = (flags & RT_TEXELS_FROM_BAKE) != 0, filter = (flags & RT_TEXELS_FROM_FILTER) != 0;
+    if (planes && (bake || filter)) rt_fail(": RT_TEXELS_FROM_BAKE / RT_TEXELS_FROM_FILTER with planes given", fn);
+    if (!planes && bake == filter) rt_fail(": planes is null and not exactly one of RT_TEXELS_FROM_BAKE / RT_TEXELS_FROM_FILTER is set", fn);
+    if (!planes) {
+        const TexelState& t = bake ? g_texels : g_filter;
+        if (t.out_W < 1 || t.out_W != W || t.out_H != H || gather_width(t.out_mode) != gather_width(mode))
+            rt_fail(bake ? ": the last bakeTexels left no out plane of this W, H and width" : ": the last filterTexels left no out plane of this W, H and width", fn);
+    }
+}
+
+static char* lightmap_buffer(LightmapState& q, int k, size_t bytes) {
+    return grown_buffer(q, k, std::max<size_t>(bytes, 4));
+}
+
+// The planes of a call on the query's device (begin_query has run): uploaded into the state's own buffer, or where the named call left them.
+static RtTexelSource texel_source(LightmapState& q, int W, int H, int mode, const float* planes, int flags, hipStream_t stream) {
+    RtTexelSource s = {};
+    s.W = W; s.H = H; s.mode = mode;
+    s.bilinear = (flags & RT_SAMPLE_BILINEAR) ? 1 : 0;
+    if (planes) {
+        const size_t bytes = (size_t)W * H * (size_t)gather_width(mode) * 4;
+        float* d_planes = reinterpret_cast<float*>(lightmap_buffer(q, kLmPlanes, bytes));
+        HIP_CHECK(hipMemcpyAsync(d_planes, planes, bytes, hipMemcpyHostToDevice, stream));
+        s.planes = d_planes;
+    } else {
+        s.planes = reinterpret_cast<const float*>((flags & RT_TEXELS_FROM_BAKE) ? g_texels.d_buf[kTexOutPlane] : g_filter.d_buf[kFltOut]);
+    }
+    return s;
+}
+
+// The parameter block of chunk [first, first + m) of sampleTexels with its inputs uploaded.
+static RtSampleParams sample_chunk(LightmapState& q, const RtTexelSource& src, size_t first, size_t m, const int32_t* prim, const float* uv,
+                                   const float* normal, bool want_valid, hipStream_t stream) {
+    const RenderContext& c = g_ctx;
+    RtSampleParams p = {};
+    p.slots = c.devs[0].d_tris; p.num_slots = (uint32_t)c.mesh.tris.size();
+    p.src = src;
+    int32_t* d_prim = reinterpret_cast<int32_t*>(lightmap_buffer(q, kLmPrim, m * 4));
+    float* d_uv = reinterpret_cast<float*>(lightmap_buffer(q, kLmUv, m * 8));
+    HIP_CHECK(hipMemcpyAsync(d_prim, prim + first, m * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(d_uv, uv + 2 * first, m * 8, hipMemcpyHostToDevice, stream));
+    p.prim = d_prim; p.uv = d_uv;
+    if (src.mode == RT_GATHER_SH9) {
+        float* d_nrm = reinterpret_cast<float*>(lightmap_buffer(q, kLmNormal, m * 12));
+        HIP_CHECK(hipMemcpyAsync(d_nrm, normal + 3 * first, m * 12, hipMemcpyHostToDevice, stream));
+        p.normal = d_nrm;
+    }
+    p.out = reinterpret_cast<float*>(lightmap_buffer(q, kLmOut, m * 12));
+    if (want_valid) p.valid = reinterpret_cast<uint8_t*>(lightmap_buffer(q, kLmValid, m));
+    p.count = q.d_count;
+    p.n = (int32_t)m;
+    return p;
+}
+
+int sampleTexels(int n, const int32_t* prim, const float* uv, const float* normal, int W, int H, int mode, const float* planes, int flags, float* out,
+                 uint8_t* valid) {
+    RenderContext& c = g_ctx;
+    if (!c.initialised) rt_fail("sampleTexels before init");
+    if (c.is_spheres) rt_fail("sampleTexels: only a mesh scene has a UV atlas");
+    if (n < 0) rt_fail("sampleTexels: n is negative");
+    if (n == 0) return 0;
+    if (!prim || !uv || !out) rt_fail("sampleTexels: prim, uv and out must not be null");
+    if (flags & RT_LIGHTMAP_ALBEDO) rt_fail("sampleTexels: RT_LIGHTMAP_ALBEDO is renderLightmap's flag");
+    check_texel_source("sampleTexels", W, H, mode, planes, flags, kSampleFlags);
+    if (mode == RT_GATHER_SH9 && !normal) rt_fail("sampleTexels: normal is null (RT_GATHER_SH9 reads it)");
+    LightmapState& q = g_sample;
+    const DeviceState& d = c.devs[0];
+    const int current = begin_query(q);
+    if (!q.d_count) q.d_count = dev_alloc<uint32_t>(q.owned, 1);
+    HIP_CHECK(hipMemsetAsync(q.d_count, 0, sizeof(uint32_t), d.stream));
+    const RtTexelSource src = texel_source(q, W, H, mode, planes, flags, d.stream);
+    double ms_sum = 0.0;
+    for_chunks((size_t)n, kRayChunk, [&](size_t first, size_t m) {
+        const RtSampleParams p = sample_chunk(q, src, first, m, prim, uv, normal, valid != nullptr, d.stream);
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        HIP_CHECK(rt_launch_sample_texels(p, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        HIP_CHECK(hipMemcpyAsync(out + 3 * first, p.out, m * 12, hipMemcpyDeviceToHost, d.stream));
+        if (valid) HIP_CHECK(hipMemcpyAsync(valid + first, p.valid, m, hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));              // (the events are read per chunk; blocking: the caller's arrays are complete on return)
+        ms_sum += query_ms(q);
+    });
+    uint32_t count = 0;
+    HIP_CHECK(hipMemcpy(&count, q.d_count, sizeof count, hipMemcpyDeviceToHost));
+    end_query(current);
+    c.sample_ms = ms_sum;
+    return (int)count;
+}
+
+double rtLastSampleMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastSampleMs before init");
+    return g_ctx.sample_ms;
+}
+
+// The parameter block of chunk [first, first + m) of renderLightmap, its buffers grown to the chunk.
+static RtLightmapParams lightmap_chunk(LightmapState& q, const RtTexelSource& src, size_t first, size_t m, int flags, const float floor_value[3]) {
+    RtLightmapParams l = {};
+    l.org = reinterpret_cast<float*>(lightmap_buffer(q, kLmOrg, m * 12));
+    l.dir = reinterpret_cast<float*>(lightmap_buffer(q, kLmDir, m * 12));
+    l.t = reinterpret_cast<float*>(lightmap_buffer(q, kLmT, m * 4));
+    l.prim = reinterpret_cast<int32_t*>(lightmap_buffer(q, kLmPrim, m * 4));
+    l.normal = reinterpret_cast<float*>(lightmap_buffer(q, kLmNormal, m * 12));
+    l.uv = reinterpret_cast<float*>(lightmap_buffer(q, kLmUv, m * 8));
+    l.num_slots = (uint32_t)g_ctx.mesh.tris.size();
+    l.src = src;
+    l.albedo = (flags & RT_LIGHTMAP_ALBEDO) ? 1 : 0;
+    for (int a = 0; a < 3; a++) l.floor_value[a] = floor_value ? floor_value[a] : 1.0f;
+    l.out = reinterpret_cast<rt_vec3*>(lightmap_buffer(q, kLmOut, m * 12));
+    l.first = (uint32_t)first;
+    l.n = (int32_t)m;
+    return l;
+}
+
+void renderLightmap(int W, int H, int mode, const float* planes, int flags, const float floor_value[3], rt_vec3* out) {
+    RenderContext& c = g_ctx;
+    check_texel_source("renderLightmap", W, H, mode, planes, flags, kSampleFlags | RT_LIGHTMAP_ALBEDO);
+    if (!out) rt_fail("renderLightmap: out is null");
+    LightmapState& q = g_lightmap;
+    const DeviceState& d = c.devs[0];
+    const int current = begin_query(q);
+    const RtTexelSource src = texel_source(q, W, H, mode, planes, flags, d.stream);
+    const RtMeshParams scene = mesh_params(d, whole_image_partition());
+    double ms_sum = 0.0;
+    for_chunks((size_t)c.nx * c.ny, kRayChunk, [&](size_t first, size_t m) {
+        const RtLightmapParams l = lightmap_chunk(q, src, first, m, flags, floor_value);
+        RtRayBatch b = {};
+        b.org = l.org; b.dir = l.dir;
+        b.t = const_cast<float*>(l.t); b.prim = const_cast<int32_t*>(l.prim); b.normal = const_cast<float*>(l.normal); b.uv = const_cast<float*>(l.uv);
+        b.n = l.n;
+        b.t_min_default = c.opt.t_min;
+        HIP_CHECK(hipEventRecord(q.ev_start, d.stream));
+        HIP_CHECK(rt_launch_lightmap_rays(scene, l, d.stream));
+        launch_rays(d, b, false);
+        HIP_CHECK(rt_launch_lightmap_shade(scene, l, d.stream));
+        HIP_CHECK(hipEventRecord(q.ev_stop, d.stream));
+        HIP_CHECK(hipMemcpyAsync(out + first, l.out, m * 12, hipMemcpyDeviceToHost, d.stream));
+        HIP_CHECK(hipStreamSynchronize(d.stream));              // (the events are read per chunk; blocking: the caller's frame is complete on return)
+        ms_sum += query_ms(q);
+    });
+    end_query(current);
+    c.lightmap_ms = ms_sum;
+}
+
+double rtLastLightmapMs(void) {
+    if (!g_ctx.initialised) rt_fail("rtLastLightmapMs before init");
+    return g_ctx.lightmap_ms;
 }
 
 // Adaptive sampling on the device (rt_api.h).  One call is one pass over the whole image on the first in-process device: select (rt_refine.h)

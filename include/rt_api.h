@@ -652,6 +652,61 @@ int    filterTexels(int W, int H, int dilate, int mode, const float* in, float* 
                     int iterations, int normal_squarings, float sigma_d, float sigma_z, float sigma_c);
 double rtLastFilterMs(void);   /* raster + prologue + iterations + scatter kernels of the last filterTexels (not the copies); 0 before the first */
 
+/* --- sampling texels: the planes of a bake looked up at hits, and the frame lit by them ------------------------------------------------------------
+ * sampleTexels reads texel planes - bakeTexels' or filterTexels' out, or the caller's own - back onto the surface: at each hit of a list, the atlas point
+ * of the hit, the texel (nearest) or the four texels around it (bilinear), and the value the mode stores.  renderLightmap is the frame built on it: one
+ * centre ray and one first-hit traversal per pixel, the lookup, the albedo and the sky on the device; only the frame comes back.  Mesh scenes only.  All
+ * arithmetic is fp32, in both fp modes: every operation is rounded on its own (no FMA), operands are in the order written, a comparison with a NaN is false.
+ * Hit k       p = prim[k] with RT_RAY_PRIM's meaning: a slot of the live leaf-ordered triangle array;  (hu, hv) = uv[2k..] as RT_RAY_UV;  nrm = normal[3k..]
+ *             as RT_RAY_NORMAL, read in RT_GATHER_SH9 only (NULL otherwise is fine).
+ * Valid       iff 0 <= p < numTris and the slot's v[0].x is not +-inf.  An invalid hit (a miss, the floor, a prim past the array, a sentinel slot) writes
+ *             out = (0, 0, 0) and valid = 0.  sampleTexels returns the number of valid hits.
+ * Atlas point w0 = 1 - hu - hv;  tcu = hu*tc[2] + hv*tc[4] + w0*tc[0];  tcv = hu*tc[3] + hv*tc[5] + w0*tc[1]   (tc = the slot's texCoords: mesh_texel's two
+ *             lines).  Not wrapped: the raster does not wrap either.
+ * Nearest     (RT_SAMPLE_BILINEAR not set)  fx = tcu * (float)W;  fx = fx > 0 ? fx : 0   (a NaN gives 0);  fx = fx < (float)(W-1) ? fx : (float)(W-1);
+ *             x = (int)fx;  y likewise from tcv and H;  c[j] = planes[(y*W + x)*C + j], C = rtGatherWidth(mode).
+ * Bilinear    fx = tcu*(float)W - 0.5f;  fx = fx > -1 ? fx : -1   (a NaN gives -1);  fx = fx < (float)W ? fx : (float)W;  x0f = floorf(fx);  ax = fx - x0f;
+ *             x0 = clamp((int)x0f, 0, W-1);  x1 = clamp((int)x0f + 1, 0, W-1);  y likewise: ay, y0, y1.  For every j < C, left to right:
+ *                 c[j] = ((1-ax)*(1-ay))*c00[j] + (ax*(1-ay))*c10[j] + ((1-ax)*ay)*c01[j] + (ax*ay)*c11[j]        (cXY = the texel (xX, yY))
+ *             The planes are read as they are: clamp to edge, no owner test.  Limit: across a chart border a tap reads whatever the plane holds there -
+ *             the zeros of an unowned texel, or the neighbouring chart - unless the bake or filter that made the plane dilated it (dilate >= 1 covers the
+ *             one texel a bilinear tap reaches).  A non-finite plane value reaches every hit that taps it (0 * inf is a NaN).
+ * Value       3 floats.  RT_GATHER_IRRADIANCE: e = c.  RT_GATHER_VISIBILITY: e = (c0, c0, c0).  RT_GATHER_SH9: (X, Y, Z) = nrm, coefficient i of channel ch
+ *             at c[3i + ch], left to right:
+ *                 e[ch] = 0.282095f*c0 + 0.325735f*(c1*Y) + 0.325735f*(c2*Z) + 0.325735f*(c3*X)
+ *                       + 0.273137f*(c4*(X*Y)) + 0.273137f*(c5*(Y*Z)) + 0.078848f*(c6*(3.0f*(Z*Z) - 1.0f))
+ *                       + 0.273137f*(c7*(X*Z)) + 0.136568f*(c8*(X*X - Y*Y))
+ *             then e[ch] = e[ch] > 0 ? e[ch] : 0.  These literals are the definition: gatherRadiance's basis constants times the cosine-lobe factors 1, 2/3
+ *             and 1/4, so the SH9 value is "irradiance / pi at normal nrm", the quantity RT_GATHER_IRRADIANCE stores.  SH9 follows the turned shading normal
+ *             the caller passes, so it serves both sides of a triangle; IRRADIANCE and VISIBILITY planes hold what the bake gathered on the winding side,
+ *             whichever side the ray meets.
+ * planes      host memory of W*H*C floats, row 0 first, or NULL with exactly one of RT_TEXELS_FROM_BAKE - the out plane of the last bakeTexels - and
+ *             RT_TEXELS_FROM_FILTER - the out of the last filterTexels -, read where it lies on the device: filterTexels' in = NULL rules (the recorded W, H
+ *             and width must match; a bake without out, and everything that frees the buffers, leaves nothing to take).  Either flag with planes given is
+ *             misuse.
+ * renderLightmap.  For every pixel (i, j) of the whole nx x ny image, whatever the row partition (as traceRays ignores it), the ray is renderGuides' centre
+ * ray and its first hit exactly what traceRays returns for the ray rtCentreRays gives: tmin = rt_render_options.t_min, tmax = FLT_MAX, the floor with
+ * rt_render_options.floor.  Triangle hit: L = e of the lookup with the pixel's prim, uv and normal.  Floor hit: L = floor_value (the plane is not in the
+ * atlas; NULL = (1, 1, 1)).  Miss: out = RT_GUIDE_ALBEDO's miss value, the sky colour of the direction.  With RT_LIGHTMAP_ALBEDO a hit stores out[ch] = A[ch]
+ * * L[ch], A = RT_GUIDE_ALBEDO's value of the pixel; without it out = L.  out is a caller-owned nx*ny frame, row 0 at the bottom: what denoiseFrame and
+ * displayFrame take.
+ *   Bit promise    out is bit-identical to the composition of renderGuides' ALBEDO plane, traceRays' PRIM, UV and NORMAL planes over rtCentreRays and the
+ *                  lookup above.
+ * Both calls are blocking and run on the first in-process device, RT_RAY_CHUNK hits (pixels) at a time.  They follow updateTriangles and rebuildBvh.  They
+ * change nothing another call observes: buffers, events and timing slots are their own, freed where the query buffers are.  Per hit of the largest chunk:
+ * 37 bytes (prim 4, uv 8, normal 12, out 12, valid 1); per pixel of the largest chunk: 64 (org 12, dir 12, t 4, prim 4, normal 12, uv 8, out 12); and the
+ * planes, 4C bytes per texel, unless they are read where they lie.  n == 0 returns 0 at once.
+ * rtSampleTexelsHost (rt_host.h) is the lookup's CPU twin.
+ * Misuse (rt error, exit 99), checked on the host before any device work: before init (rtLastSampleMs and rtLastLightmapMs as well), a sphere scene, n < 0,
+ * prim, uv or out NULL with n > 0, normal NULL in RT_GATHER_SH9, W or H outside 1 .. RT_TEXEL_MAX_SIZE, an unknown mode, unknown flag bits,
+ * RT_LIGHTMAP_ALBEDO passed to sampleTexels, and the NULL / FROM rules above. */
+enum { RT_SAMPLE_BILINEAR = 1, RT_LIGHTMAP_ALBEDO = 2, RT_TEXELS_FROM_BAKE = 4, RT_TEXELS_FROM_FILTER = 8 };
+int    sampleTexels(int n, const int32_t* prim, const float* uv, const float* normal, int W, int H, int mode,
+                    const float* planes, int flags, float* out, uint8_t* valid);
+void   renderLightmap(int W, int H, int mode, const float* planes, int flags, const float floor_value[3], rt_vec3* out);
+double rtLastSampleMs(void);     /* lookup kernels of the last sampleTexels, summed over chunks; 0 before the first */
+double rtLastLightmapMs(void);   /* ray generator + trace + shade kernels of the last renderLightmap, summed over chunks; 0 before the first */
+
 /* --- adaptive sampling: the samples go where the image is still noisy ---------------------------------------------------------------
  * refineFrame renders an adaptive frame: every pixel gets samples in batches until an estimate of its own error says it has enough.  The frame's state, the
  * selection, the list of a pass and the statistics live on the device; the pixel kernels of renderPixels trace the samples.  One call is one pass: select,

@@ -135,6 +135,13 @@ int rtRasterTexelsHost(const rt_triangle* tris, uint32_t numTris, int W, int H, 
 int rtFilterTexelsHost(const rt_triangle* tris, uint32_t numTris, int W, int H, int dilate, int mode, const float* in, float* out, int iterations,
                        int normal_squarings, float sigma_d, float sigma_z, float sigma_c);
 
+/* sampleTexels (rt_api.h, "sampling texels": the definition is stated there, once) on the CPU, in plain C++, over the caller's leaf-ordered triangle array:
+ * what sampleTexels downloads from the device, bit for bit - out, 3 floats per hit, and valid (may be NULL).  flags: RT_SAMPLE_BILINEAR or 0.  Returns the
+ * number of valid hits, or -1 for arguments sampleTexels would refuse and for planes NULL - the twin has no bake or filter to take a plane from - (nothing is
+ * written then).  No renderer state is read. */
+int rtSampleTexelsHost(const rt_triangle* tris, uint32_t numTris, int n, const int32_t* prim, const float* uv, const float* normal, int W, int H, int mode,
+                       const float* planes, int flags, float* out, uint8_t* valid);
+
 /* A trivial non-overlapping atlas: overwrites texCoords of tris[0 .. n-1]; nothing else is touched (sentinel slots get coordinates too; the raster skips them).
  * fp32, every operation rounded on its own, operands in the order written:
  *   pairs = (n + 1) / 2;  cells = the smallest integer with cells * cells >= pairs;  cs = 1.0f / (float)cells;  m = margin * cs;  m3 = 3.0f * m
